@@ -14,26 +14,31 @@ timed region).  Weak scaling: every rank fits its own 32 bodies; the only data-p
 all-reduce per iteration of the loss normalisers (psi-release_amd/dist.py).
 
 Protocol (the metric's own: BASELINE configs[1] is quoted on the reference's 100-iteration loop): W untimed warm-up
-steps plus an untimed clock-ramp warm-up (>= 0.3 s of iterations), then timed blocks of EXACTLY K steps each, every block bracketed by a
-barrier + torch.cuda.synchronize() on both sides and timed as the MAX over ranks.  Consecutive blocks form 100-ITERATION FRESH-START LOOPS
-(fitting_proxe.py:177-189: a new batch starts from the initial body vector with a fresh Adam — an untimed psi_fit_set_problem(reset)
-before the first block of every loop); at least 5 loops and 0.5 s of timed GPU time.  `ms_per_step` / `value` = the MEDIAN LOOP's time
-per iteration (loop total / 100; min / max next to it); `steady_state` carries the median block of iterations 20 .. 100 of the loops
-(the number earlier rounds reported), `loop_as_one_call` the same loop issued as ONE psi_fit_iterate call.
+steps plus an untimed clock-ramp warm-up (>= 0.3 s of iterations), then EXACTLY K timed steps, as consecutive 100-ITERATION FRESH-START
+LOOPS (fitting_proxe.py:177-189: a new batch starts from the initial body vector with a fresh Adam — an untimed psi_fit_set_problem(reset)
+in front of every loop, the last loop cut at K), every loop bracketed by a barrier + torch.cuda.synchronize() on both sides and timed as
+the MAX over ranks.  `ms_per_step` = the K steps' total time / K, `value` = iterations per second over all ranks.
+
+    --dump-outputs DIR   after the timed steps, write what the last one computed (the fitted 72-D body vectors and the step's losses;
+                         train_s2: the losses and the updated model parameters) as DIR/<name>.npy in float32.  The inputs are seeded:
+                         two builds run with the same arguments can be compared output for output.
+    --full               after the headline, everything else the benchmark measures (below); a plain run does only the headline.
 
 Workloads:  --workload fitting (default, configs[1]; configs[3] at --gpus 8) | fitting_habitat (configs[4]: contact
 constant 1.0, Habitat camera flip, 64 bodies per GPU, a sweep over 7 synthetic rooms) | train_s2 (configs[2]).
-The default line also carries `secondary.train_s2` (a bounded train_s2 measurement, N=1 only) so configs[2] is measured
-by the same run, and `secondary.fitting_smplx_sparse_weights`: the headline workload on a body model whose skinning rows have the
-released SMPL-X model's 4 non-zeros (the headline keeps the dense random [V, 55] weight matrix of the earlier rounds).
 
-The JSON line also carries
+With --full the JSON line also carries
+  loop_statistics — the median / min / max of repeated 100-iteration fresh-start loops (>= 5 loops and 0.5 s of timed GPU time);
+  steady_state  — the same blocks without the restart, `loop_as_one_call` the same loop issued as ONE psi_fit_iterate call;
   roofline     — the dominant (longest) kernel of the iteration: the bytes the implementation has to MOVE per launch (DESIGN.md section 3;
                  SURVEY 8(d)'s per-unit figure next to it as survey_8d_*) / its average launch duration measured with HIP events on the
                  launch stream; peak = 8 TB/s HBM3E (MI355X guide); traffic = the PMC bytes of profiles/r06_pmc_traffic.json;
   cpu_baseline — the oracle (oracle/psi_oracle.py + oracle/chamfer_oracle.c, a CPU port of the reference path,
                  validated against the reference's golden vectors) timed on this box's host cores on a bounded
-                 sample of the same workload (rank 0, N=1 only).
+                 sample of the same workload (rank 0, N=1 only);
+  secondary    — (N=1) `train_s2` / `train_s2_fp32` (bounded train_s2 measurements, so configs[2] is measured by the same run), and
+                 `fitting_smplx_sparse_weights`: the headline workload on a body model whose skinning rows have the released SMPL-X
+                 model's 4 non-zeros (the headline keeps the dense random [V, 55] weight matrix of the earlier rounds).
 """
 from __future__ import annotations
 
@@ -73,14 +78,21 @@ def parse(argv=None):
     ap.add_argument('--engine', default=os.environ.get('PSI_ENGINE', 'auto'), choices=['auto', 'fused', 'modular'])
     ap.add_argument('--workload', default='fitting', choices=['fitting', 'fitting_habitat', 'train_s2'],
                     help="'fitting' = BASELINE metric (configs[1]/[3]); 'fitting_habitat' = configs[4]; 'train_s2' = configs[2]")
-    ap.add_argument('--repeats', type=int, default=5, help='minimum number of timed K-step blocks (the median is reported)')
-    ap.add_argument('--min-timed-s', type=float, default=0.5, help='timed GPU time is kept above this by adding blocks')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run every other measurement: repeated-loop statistics, steady state, per-kernel times and '
+                         'rooflines, the CPU baseline and the secondary workloads')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32)')
+    ap.add_argument('--repeats', type=int, default=5, help='--full: minimum number of K-step blocks of the repeated-loop statistics')
+    ap.add_argument('--min-timed-s', type=float, default=0.5, help='--full: GPU time of the repeated-loop statistics is kept above this')
     ap.add_argument('--graph', type=int, default=1, help='train_s2: replay the whole optimiser step as one HIP graph')
     ap.add_argument('--bf16', type=int, default=1, help='train_s2: bf16 autocast for the CVAE trunk')
-    ap.add_argument('--secondary', type=int, default=1, help='attach the bounded train_s2 measurement (configs[2]) to the default line')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='time budget of the CPU baseline sample')
+    ap.add_argument('--secondary', type=int, default=1, help='--full: attach the secondary measurements (train_s2 = configs[2], ...) to the line')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='--full: time budget of the CPU baseline sample')
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.batch is None:
         args.batch = 64 if args.workload == 'fitting_habitat' else (128 if args.workload == 'train_s2' else 32)
     return args
@@ -116,6 +128,63 @@ def spawn_ranks(args):
 # ----------------------------------------------------------------------------------------------------------------------
 # timing protocol
 # ----------------------------------------------------------------------------------------------------------------------
+def timed_steps(run_steps, barrier, N, W, world, device, restart=None, loop=LOOP_ITERS, ramp_s=0.3):
+    """The headline: W untimed warm-up steps, then EXACTLY N timed steps.  run_steps(n) enqueues n steps.
+    With `restart` the N steps are consecutive `loop`-step fitting loops from a fresh problem (restart issued untimed in front of every
+    loop, the last loop cut at N), after an untimed clock ramp (>= ramp_s of steps: the first milliseconds after idle run at a lower
+    clock, measured 10 % on a 4 ms region); the restarts make the last step's result independent of the ramp.  Without `restart` there
+    is no ramp and the N steps are one block, so that the last step's result depends on W and N alone.
+    Every loop (block) is bracketed by barrier() on both sides and timed as the max over ranks.
+    Returns (seconds of the N steps, max over ranks per loop; this rank's own seconds; number of loops)."""
+    import torch
+    run_steps(W)
+    barrier()
+    if restart is not None and ramp_s > 0:
+        # with more than one rank the steps contain a collective: rank 0's clock decides, the decision is broadcast after every round
+        t0 = time.perf_counter()
+        go = torch.ones(1, device=device, dtype=torch.int32)
+        for _ in range(max(1, 10000 // loop)):
+            run_steps(loop)
+            torch.cuda.synchronize()
+            more = time.perf_counter() - t0 < ramp_s
+            if world > 1:
+                go.fill_(1 if more else 0)
+                torch.distributed.broadcast(go, src=0)
+                more = bool(go.item())
+            if not more:
+                break
+    sizes = [min(loop, N - s) for s in range(0, N, loop)] if restart is not None else [N]
+    times = []
+    for k in sizes:
+        if restart is not None:
+            restart()
+        barrier()
+        t0 = time.perf_counter()
+        run_steps(k)
+        barrier()
+        times.append(time.perf_counter() - t0)
+    own = sum(times)
+    if world > 1:
+        t = torch.tensor(times, device=device, dtype=torch.float64)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        times = [float(x) for x in t.tolist()]
+    return sum(times), own, len(sizes)
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=64 << 20):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32.  An array larger than its even share of `limit_bytes` keeps a fixed
+    sample of its rows (seed 0, in row order), so that two runs with the same arguments write the same entries."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit_bytes // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            keep = np.sort(np.random.RandomState(0).choice(a.shape[0], max(1, share // a[0].nbytes), replace=False))
+            a = a[keep]
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+
+
 def timed_blocks(run_steps, barrier, K, W, world, device, min_repeats=5, min_total_s=0.5, ramp_s=0.3, max_repeats=400, restart=None,
                  restart_every=1):
     """run_steps(n) enqueues n steps.  Returns the per-block wall times (max over ranks) of R blocks of exactly K steps.
@@ -507,43 +576,59 @@ def bench_fitting(args):
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    # The metric is a fitting LOOP from generated bodies (fitting_proxe.py:177-189: 100 iterations per file), so every timed block starts
+    # The metric is a fitting LOOP from generated bodies (fitting_proxe.py:177-189: 100 iterations per file), so every timed loop starts
     # where that loop starts: psi_fit_set_problem(reset) — the generated bodies as initial parameters, zeroed Adam state, no NN warm-start
-    # hints, an unconverged penetration mask — issued UNTIMED in front of the block's barrier.  `steady_state` (extra key) keeps iterating
+    # hints, an unconverged penetration mask — issued UNTIMED in front of the loop's barrier.  `steady_state` (--full) keeps iterating
     # one problem, i.e. times the converged regime (rounds 1-4 reported that as the headline).
     can_restart = args.engine_resolved == 'fused' and all(hasattr(r, 'restart') for r in runners)
     restart = (lambda: [r.restart() for r in runners]) if can_restart else None
-    # blocks of exactly K steps; LOOP_ITERS / K consecutive blocks (rounded up) form one loop of the reference and share one restart
-    bpl = max(1, int(math.ceil(LOOP_ITERS / args.steps))) if restart else 1
-    times = timed_blocks(run_steps, barrier, args.steps, args.warmup, world, device, max(args.repeats, bpl), args.min_timed_s, restart=restart,
-                         restart_every=bpl)
-    summ, med = summarize(times, args.steps)
-    if restart and bpl > 1:
-        # headline = the median LOOP: its blocks' times added up / its iterations (a median over single blocks would pick a warm block and
-        # hide the loop's cold first one)
-        loops = [sum(times[i:i + bpl]) for i in range(0, len(times), bpl)]
-        lmed = statistics.median(loops)
-        summ = dict(summ, ms_per_step=round(lmed / (bpl * args.steps) * 1e3, 4), ms_per_step_min=round(min(loops) / (bpl * args.steps) * 1e3, 4),
-                    ms_per_step_max=round(max(loops) / (bpl * args.steps) * 1e3, 4), loops=len(loops), blocks_per_loop=bpl,
-                    per_block_ms_per_step={'first_block_of_a_loop': round(statistics.median(times[0::bpl]) / args.steps * 1e3, 4),
-                                           'later_blocks': round(statistics.median([t for i, t in enumerate(times) if i % bpl]) / args.steps * 1e3, 4)})
-        med = lmed / bpl                                      # seconds per block of K steps, loop average
-    steady = None
-    if restart is not None:
-        ts = timed_blocks(run_steps, barrier, args.steps, 0, world, device, 5, 0.2, ramp_s=0.05)
-        steady, _ = summarize(ts, args.steps)
-        steady['what'] = 'the same blocks WITHOUT the restart: one problem iterated on and on (converged regime, warm NN hints)'
-    fresh = None
-    if world == 1 and not habitat and args.engine_resolved == 'fused':
-        fresh = fresh_start_blocks(runner, LOOP_ITERS)     # the same loop as ONE call of 100 iterations (no per-block synchronisation)
+    # the headline: exactly --steps timed steps, as fresh-start loops of LOOP_ITERS iterations where the engine can restart
+    total, own, n_loops = timed_steps(run_steps, barrier, args.steps, args.warmup, world, device, restart=restart)
+    med = total                                               # seconds of args.steps steps (max over ranks)
     losses = runners[-1].last_losses() if habitat else runner.last_losses()
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        # what FittingOP.fitting hands its caller after the last timed step: the fitted 72-D body vectors, and the step's four losses
+        from psi_release_amd.geometry import GeometryTransformer
+        xs, ls = [], []
+        for o, r in zip(ops if habitat else [op], runners):
+            r.finish()
+            xs.append(GeometryTransformer.convert_to_3D_rot(o.xhr_rec).detach().cpu().numpy())
+            ls.append(r.last_losses())
+        outputs = {'body_params': xs if habitat else xs[0], 'losses': ls if habitat else ls[0]}
+
+    summ = {'ms_per_step': round(total / args.steps * 1e3, 4), 'timed_s': round(total, 4)}
+    loop_stats = steady = fresh = per_rank_ms = None
+    if args.full:
+        # repeated-loop statistics: blocks of exactly K steps; LOOP_ITERS / K consecutive blocks (rounded up) form one loop of the reference
+        # and share one restart
+        bpl = max(1, int(math.ceil(LOOP_ITERS / args.steps))) if restart else 1
+        times = timed_blocks(run_steps, barrier, args.steps, args.warmup, world, device, max(args.repeats, bpl), args.min_timed_s, restart=restart,
+                             restart_every=bpl)
+        loop_stats, _ = summarize(times, args.steps)
+        if restart and bpl > 1:
+            # the median LOOP: its blocks' times added up / its iterations (a median over single blocks would pick a warm block and hide the
+            # loop's cold first one)
+            loops = [sum(times[i:i + bpl]) for i in range(0, len(times), bpl)]
+            lmed = statistics.median(loops)
+            loop_stats = dict(loop_stats, ms_per_step=round(lmed / (bpl * args.steps) * 1e3, 4), ms_per_step_min=round(min(loops) / (bpl * args.steps) * 1e3, 4),
+                              ms_per_step_max=round(max(loops) / (bpl * args.steps) * 1e3, 4), loops=len(loops), blocks_per_loop=bpl,
+                              per_block_ms_per_step={'first_block_of_a_loop': round(statistics.median(times[0::bpl]) / args.steps * 1e3, 4),
+                                                     'later_blocks': round(statistics.median([t for i, t in enumerate(times) if i % bpl]) / args.steps * 1e3, 4)})
+        loop_stats['what'] = ('the median of repeated %s (ms_per_step = median / its steps; min / max next to it)'
+                              % ('%d-iteration fresh-start loops' % (bpl * args.steps) if restart else 'blocks of %d steps' % args.steps))
+        if restart is not None:
+            ts = timed_blocks(run_steps, barrier, args.steps, 0, world, device, 5, 0.2, ramp_s=0.05)
+            steady, _ = summarize(ts, args.steps)
+            steady['what'] = 'the same blocks WITHOUT the restart: one problem iterated on and on (converged regime, warm NN hints)'
+        if world == 1 and not habitat and args.engine_resolved == 'fused':
+            fresh = fresh_start_blocks(runner, LOOP_ITERS)     # the same loop as ONE call of 100 iterations (no per-block synchronisation)
+        if world > 1:                                         # per-rank local view of the headline steps (no max-reduction)
+            t = torch.zeros(world, device=device, dtype=torch.float64)
+            t[rank] = own / args.steps * 1e3
+            torch.distributed.all_reduce(t)
+            per_rank_ms = [round(float(x), 4) for x in t.tolist()]
     rccl_world = torch.distributed.get_world_size() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 1
-    per_rank_ms = None
-    if world > 1:                                             # per-rank local view of the median block (no max-reduction)
-        t = torch.zeros(world, device=device, dtype=torch.float64)
-        t[rank] = med / args.steps * 1e3
-        torch.distributed.all_reduce(t)
-        per_rank_ms = [round(float(x), 4) for x in t.tolist()]
     # what RCCL ITSELF reports on every rank (ncclCommCount / ncclGetVersion through psi_dp_comm_info, all-gathered) and how each rank's
     # loop was launched (psi_fit_dp_mode): a line produced on N GPUs shows N ranks that each saw N ranks, all on graphs — or says what else
     # happened.  Single process: one entry, RCCL not loaded.
@@ -584,13 +669,17 @@ def bench_fitting(args):
                        'rccl_world_size': rccl_world, 'rccl_ranks_seen': rccl_seen, 'rccl_version': rccl_version, 'dp_launch_mode': dp_modes,
                        'backend': backend if world > 1 else 'none (single process)',
                        'launcher': 'bench.py self-spawn' if os.environ.get('PSI_BENCH_SPAWNED') == '1' else ('torchrun' if world > 1 else 'direct'),
-                       'protocol': '%d blocks of %d steps (barrier + synchronize around each, max over ranks)%s' % (
-                           summ['repeats'], args.steps, ('; %d consecutive blocks = ONE %d-iteration fitting loop from a FRESH problem (untimed '
-                           'psi_fit_set_problem with reset in front of its first block: generated bodies, zeroed Adam state, cold NN hints); '
-                           'ms_per_step = median loop / its iterations' % (bpl, bpl * args.steps)) if restart else '; median block'),
+                       'protocol': ('%d timed steps after %d warm-up steps%s (barrier + synchronize around each loop, max over ranks); '
+                                    'ms_per_step = their total time / %d' % (
+                                        args.steps, args.warmup,
+                                        (' and a clock ramp, as %d fitting loop(s) of up to %d iterations from a FRESH problem (untimed '
+                                         'psi_fit_set_problem with reset in front of each loop: generated bodies, zeroed Adam state, cold NN hints)'
+                                         % (n_loops, LOOP_ITERS)) if restart else ', as one block on one problem', args.steps)),
                        'final_losses': [round(float(x), 6) for x in losses]},
         }
         out.update(summ)
+        if loop_stats:
+            out['loop_statistics'] = loop_stats
         if steady:
             out['steady_state'] = steady
         if fresh:
@@ -600,7 +689,7 @@ def bench_fitting(args):
         # ---- per-kernel times of one iteration: HIP events recorded on the launch stream after every kernel launch
         work = kernel_work(args)
         roof = None
-        if args.engine_resolved == 'fused' and world == 1:
+        if args.full and args.engine_resolved == 'fused' and world == 1:
             kernels = runner.eng.profile(30)
             agg = {}
             for nm, ms in kernels:
@@ -611,7 +700,7 @@ def bench_fitting(args):
             alg = 131.7e6 + args.batch * 1.76e6                    # algorithmic bytes of the whole iteration
             out['iteration_roofline'] = {'bound': 'hbm', 'algorithmic_bytes': alg, 'achieved': round(alg / (med / args.steps) * 1e-9, 1),
                                          'peak': PEAK_HBM_GBS, 'unit': 'GB/s', 'frac': round(alg / (med / args.steps) * 1e-9 / PEAK_HBM_GBS, 4)}
-        if world == 1 and not habitat:
+        if args.full and world == 1 and not habitat:
             t_ch = time_chamfer_kernel(op, args)
             flops = 8.0 * args.batch * args.nc * args.m
             out['roofline_bruteforce_nn'] = {
@@ -623,7 +712,7 @@ def bench_fitting(args):
                 roof = dict(out['roofline_bruteforce_nn'], traffic=None)
         if roof is not None:
             out['roofline'] = roof
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out['cpu_baseline'] = cpu_baseline(args, assets, args.cpu_seconds, habitat)
             except Exception as e:  # the oracle needs gcc; report rather than fail the GPU number
@@ -635,7 +724,7 @@ def bench_fitting(args):
         del ops
     torch.cuda.empty_cache()
     if rank == 0:
-        if world == 1 and not habitat and args.secondary and (args.batch, args.nc, args.m, args.D) == (32, 2048, 32768, 256):
+        if args.full and world == 1 and not habitat and args.secondary and (args.batch, args.nc, args.m, args.D) == (32, 2048, 32768, 256):
             out['secondary'] = {}
             try:
                 # the same workload on a body model with the RELEASED SMPL-X model's skinning sparsity (4 non-zero weights per vertex,
@@ -690,7 +779,8 @@ def bench_fitting(args):
                 import io
                 buf = io.StringIO()
                 with contextlib.redirect_stdout(buf):
-                    sec = bench_train_s2(argparse.Namespace(**dict(vars(args), batch=128, steps=10, warmup=3, repeats=5, min_timed_s=0.3)))
+                    sec = bench_train_s2(argparse.Namespace(**dict(vars(args), batch=128, steps=10, warmup=3, repeats=5, min_timed_s=0.3,
+                                                                      dump_outputs=None)))
                 sys.stderr.write(buf.getvalue())
                 out['secondary']['train_s2'] = sec
             except Exception as e:
@@ -703,11 +793,14 @@ def bench_fitting(args):
                 import io
                 buf = io.StringIO()
                 with contextlib.redirect_stdout(buf):
-                    sec = bench_train_s2(argparse.Namespace(**dict(vars(args), batch=128, steps=5, warmup=3, repeats=3, min_timed_s=0.2, bf16=0)))
+                    sec = bench_train_s2(argparse.Namespace(**dict(vars(args), batch=128, steps=5, warmup=3, repeats=3, min_timed_s=0.2, bf16=0,
+                                                                      dump_outputs=None)))
                 sys.stderr.write(buf.getvalue())
                 out['secondary']['train_s2_fp32'] = sec
             except Exception as e:
                 out['secondary']['train_s2_fp32'] = {'error': repr(e)}
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
         sys.stdout.flush()
     if torch.distributed.is_available() and torch.distributed.is_initialized():
@@ -721,12 +814,15 @@ def bench_fitting(args):
 # ----------------------------------------------------------------------------------------------------------------------
 def bench_train_s2(args):
     """train_s2.py optimiser steps at batch 128 on synthetic PROX-shaped data (two scenes with 256^3 SDFs held once in HBM,
-    indirect scene ids), CVAE trunk on the matrix cores.  Returns the result dict (same keys as the main line)."""
+    indirect scene ids), CVAE trunk on the matrix cores.  Returns the result dict (same keys as the main line).
+    Seeded: the model's initial weights, the batch order and the latent noise are the same in every run with the same arguments."""
     import tempfile
     import numpy as np
     import torch
     from psi_release_amd import batch_gen, synth, training
+    full = getattr(args, 'full', False)
     dev = torch.device('cuda', torch.cuda.current_device())
+    torch.manual_seed(0)
     B = args.batch
     names = ['SynA', 'SynB']
     sd = {n: synth.make_scene(i, args.m, args.D, args.nc) for i, n in enumerate(names)}
@@ -739,7 +835,7 @@ def bench_train_s2(args):
          'cam_ext': synth.make_cam_ext(0, n), 'cam_int': synth.make_bodies(0, n)['cam_int'], 'max_d': np.full(n, 6.0),
          'sceneid': rs.randint(0, 2, n).astype(np.float32)}
     table = {k: np.concatenate([np.zeros_like(np.asarray(v)[:1]), np.asarray(v)]).astype(np.float32) for k, v in t.items()}
-    bg = batch_gen.BatchGeneratorWithSceneMesh.from_arrays(table, scenes, dev, indirect_sdf=True)
+    bg = batch_gen.BatchGeneratorWithSceneMesh.from_arrays(table, scenes, dev, indirect_sdf=True, seed=0)
     with tempfile.TemporaryDirectory() as tmp:
         cfg = {'human_model_path': None, 'vposer_ckpt_path': None, 'scene_model_ckpt': None, 'init_lr_h': 1e-4, 'batch_size': B, 'epoch': 10,
                'loss_weight_anealing': True, 'device': dev, 'save_dir': tmp, 'contact_id_folder': None, 'contact_part': synth.CONTACT_PARTS,
@@ -757,46 +853,61 @@ def bench_train_s2(args):
         # matrix-core flops of one step (forward + backward of the PyTorch trunk; the HIP body/scene operators are not GEMMs)
         # (counted with the hand-written convolution / dense / BN ops switched off: the flop counter only sees aten operators, and the
         # arithmetic of the model is the same on either path)
+        # (--full; in a forked RNG, so that the timed steps draw the same latent noise with and without it)
         flops = None
-        import psi_release_amd.models as _models
-        routing = {k: getattr(_models, k) for k in ('_precise', '_use_hip_bn', '_use_hip_linear', '_conv')}
-        try:
-            from torch.utils.flop_counter import FlopCounterMode
-            # (for the count only: every layer as the aten operator it is, so that the counter sees it — the product path below is untouched)
-            _models._precise = lambda x: False
-            _models._use_hip_bn = lambda bn, x: False
-            _models._use_hip_linear = lambda m, x: False
-            _models._conv = lambda conv, x: conv(x)
-            running = {k: v.clone() for k, v in op.model_h.state_dict().items() if 'running_' in k or 'num_batches' in k}
-            with FlopCounterMode(display=False) as fc:
+        if full:
+            import psi_release_amd.models as _models
+            routing = {k: getattr(_models, k) for k in ('_precise', '_use_hip_bn', '_use_hip_linear', '_conv')}
+            try:
+                from torch.utils.flop_counter import FlopCounterMode
+                # (for the count only: every layer as the aten operator it is, so that the counter sees it — the product path below is untouched)
+                _models._precise = lambda x: False
+                _models._use_hip_bn = lambda bn, x: False
+                _models._use_hip_linear = lambda m, x: False
+                _models._conv = lambda conv, x: conv(x)
+                running = {k: v.clone() for k, v in op.model_h.state_dict().items() if 'running_' in k or 'num_batches' in k}
+                with torch.random.fork_rng(devices=[dev.index]), FlopCounterMode(display=False) as fc:
+                    op.optimizer_h.zero_grad(set_to_none=True)
+                    sum(op._losses_from_batch(batches[0], 9)).backward()
+                flops = float(fc.get_total_flops())
                 op.optimizer_h.zero_grad(set_to_none=True)
-                sum(op._losses_from_batch(batches[0], 9)).backward()
-            flops = float(fc.get_total_flops())
-            op.optimizer_h.zero_grad(set_to_none=True)
-            op.model_h.load_state_dict(running, strict=False)
-        except Exception:
-            pass
-        finally:
-            for k, v in routing.items():
-                setattr(_models, k, v)
+                op.model_h.load_state_dict(running, strict=False)
+            except Exception:
+                pass
+            finally:
+                for k, v in routing.items():
+                    setattr(_models, k, v)
         cnt = [0]
+        last = [None]
 
         def run_steps(k):
             for _ in range(k):
-                op.train_step(batches[cnt[0] % len(batches)], ep=9)       # ep > 0.75*epoch: scene losses active
+                last[0] = op.train_step(batches[cnt[0] % len(batches)], ep=9)       # ep > 0.75*epoch: scene losses active
                 cnt[0] += 1
 
-        times = timed_blocks(run_steps, torch.cuda.synchronize, args.steps, args.warmup, 1, dev, args.repeats, args.min_timed_s, ramp_s=0.2)
-        summ, med = summarize(times, args.steps)
-    spp = med / args.steps
+        total, _, _ = timed_steps(run_steps, torch.cuda.synchronize, args.steps, args.warmup, 1, dev)
+        summ = {'ms_per_step': round(total / args.steps * 1e3, 4), 'timed_s': round(total, 4)}
+        if getattr(args, 'dump_outputs', None):
+            # what the step hands its caller (the seven losses of cal_loss) and the parameters it has just updated
+            dump_outputs(args.dump_outputs, {'losses': [float(l) for l in last[0]],
+                                             'model_params': torch.cat([p.detach().reshape(-1) for p in op.model_h.parameters()]).cpu().numpy()})
+        if full:
+            times = timed_blocks(run_steps, torch.cuda.synchronize, args.steps, 0, 1, dev, args.repeats, args.min_timed_s, ramp_s=0.2)
+            blocks, _ = summarize(times, args.steps)
+            blocks['what'] = 'the median of repeated blocks of %d steps after a clock ramp (ms_per_step = median / its steps; min / max next to it)' % args.steps
+    spp = total / args.steps
     res = {'metric': 'train_s2 optimiser steps/sec (HumanCVAES2 + SMPL-X + Chamfer + SDF), batch=%d' % B,
            'value': round(1.0 / spp, 3), 'unit': 'steps/s', 'samples_per_s': round(B / spp, 1), 'n_gpus': 1,
            'steps': args.steps, 'warmup': args.warmup, 'higher_is_better': True,
            'scaling': 'weak', 'vs_baseline': None,
            'dtype': 'bf16 trunk / f32 losses' if args.bf16 else 'f32 storage, bf16x3 split products (2^-16 per product), f32 accumulate', 'data': 'synthetic',
            'config': {'workload': 'train_s2.py step, batch=%d, 2 scenes (m=%d, SDF %d^3, indirect scene ids), n_c=%d (BASELINE configs[2])'
-                                  % (B, args.m, args.D, args.nc), 'hip_graph': bool(args.graph)}}
+                                  % (B, args.m, args.D, args.nc), 'hip_graph': bool(args.graph),
+                      'protocol': '%d timed steps after %d warm-up steps, one block; ms_per_step = their total time / %d' % (args.steps, args.warmup, args.steps)}}
     res.update(summ)
+    if not full:
+        return res
+    res['block_statistics'] = blocks
     if flops:
         # the fp32 model issues THREE bf16 products per useful multiply-add (hi*hi + hi*lo + lo*hi) on the bf16 matrix pipe: the fraction is
         # quoted against the pipe the step runs on (2.5 PFLOP/s bf16), with the issued flops; the useful-flop rate is next to it

@@ -1,7 +1,7 @@
 """Fit 4 bodies for 5 iterations under torchrun and print the result checksum; with PSI_FORCE_DP_PATH=1 through the
 data-parallel sequence over a 1-rank nccl group (tests/test_dist_gpu.py::test_rccl_leg_at_world_size_one)."""
 import os, sys
-sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from psi_release_amd import dist as psi_dist, fitting, synth
 psi_dist.init_from_env()

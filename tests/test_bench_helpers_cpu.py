@@ -84,3 +84,38 @@ def test_rank_launch_command_for_an_eight_gpu_node():
     assert cmd[script + 1:] == argv                                             # bench.py then joins the job: RANK / WORLD_SIZE from the env
     assert env['HSA_ENABLE_IPC_MODE_LEGACY'] == '0' and env['PSI_BENCH_SPAWNED'] == '1' and int(env['OMP_NUM_THREADS']) >= 1
     assert env['PATH'] == '/usr/bin'
+
+
+def test_plain_run_is_lean_by_default_and_full_is_opt_in():
+    a = bench.parse(['--steps', '7', '--warmup', '2'])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    b = bench.parse(['--full', '--dump-outputs', 'out'])
+    assert b.full is True and b.dump_outputs == 'out'
+
+
+def test_timed_steps_times_exactly_the_requested_steps_as_fresh_start_loops():
+    """--steps N means N timed steps: W warm-up steps untimed, then loops of LOOP_ITERS steps (the last one cut at N), each behind an
+    untimed restart; without a restart, one block and no clock ramp."""
+    log = []
+    run = lambda n: log.append(('run', n))
+    restart = lambda: log.append(('restart',))
+    barrier = lambda: None
+    total, own, loops = bench.timed_steps(run, barrier, 250, 3, 1, None, restart=restart, ramp_s=0)
+    assert loops == 3 and total == own and total >= 0
+    assert log == [('run', 3), ('restart',), ('run', 100), ('restart',), ('run', 100), ('restart',), ('run', 50)]
+    log.clear()
+    total, own, loops = bench.timed_steps(run, barrier, 250, 0, 1, None)
+    assert loops == 1 and log == [('run', 0), ('run', 250)]
+
+
+def test_dump_outputs_writes_float32_within_the_size_cap(tmp_path):
+    import numpy as np
+    big = np.arange(40000 * 8, dtype=np.float64).reshape(40000, 8)
+    bench.dump_outputs(str(tmp_path), {'small': [1.5, 2.5], 'big': big}, limit_bytes=2 * 64 * 1024)
+    small, got = np.load(tmp_path / 'small.npy'), np.load(tmp_path / 'big.npy')
+    assert small.dtype == np.float32 and small.tolist() == [1.5, 2.5]
+    assert got.dtype == np.float32 and got.nbytes <= 64 * 1024 and got.shape[1] == 8
+    # a fixed sample of whole rows, in row order: the same entries in every run
+    assert np.all(np.diff(got[:, 0]) > 0) and np.all(got[:, 1] == got[:, 0] + 1)
+    bench.dump_outputs(str(tmp_path / 'again'), {'big': big}, limit_bytes=64 * 1024)
+    assert np.array_equal(np.load(tmp_path / 'again' / 'big.npy'), got)

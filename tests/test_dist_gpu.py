@@ -119,7 +119,7 @@ def test_rccl_leg_at_world_size_one(iters):
     import subprocess
     out = {}
     for force in ('0', '1'):
-        env = dict(os.environ, PSI_FORCE_DP_PATH=force, GRAFT_REPO_ROOT=ROOT, PSI_TEST_ITERS=str(iters))
+        env = dict(os.environ, PSI_FORCE_DP_PATH=force, PSI_TEST_ITERS=str(iters))
         for attempt in range(2):                               # one retry: a failed rendezvous is not what this test is about
             port = _free_port()
             r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',

@@ -10,10 +10,10 @@ bash tools/pmc.sh r04f > $O/pmc.log 2>&1; cp gpurun_out/pmc_r04f_*.txt $O/
 # the bench lines below cite profiles/r04_* (rocprofv3 averages, PMC traffic): refresh the box's copy from THIS pass first
 cp $O/kernel_stats.csv profiles/r04_kernel_stats.csv; python tools/mk_pmc_json.py r04f r04 > /dev/null; cp profiles/r04_pmc_traffic.json profiles/r04_pmc_fetch_size.csv profiles/r04_pmc_write_size.csv $O/
 bash tools/gpu_call.sh final4 timeline timeline:10 timeline2 > $O/timelines.log 2>&1
-( time timeout 500 python bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_default.json 2> $O/bench_default.err; grep real $O/bench_default.err
-( PSI_FORCE_DP_PATH=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29613 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 ) > $O/bench_dp1_nccl.json 2> $O/bench_dp1_nccl.err
-( PSI_DIST_BACKEND=gloo timeout 300 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 ) > $O/bench_n2_gloo.json 2> $O/bench_n2_gloo.err
-timeout 300 python bench.py --workload fitting_habitat --steps 21 --warmup 7 --cpu-seconds 6 > $O/bench_habitat.json 2> $O/bench_habitat.err
+( time timeout 500 python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $O/bench_default.json 2> $O/bench_default.err; grep real $O/bench_default.err
+( PSI_FORCE_DP_PATH=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29613 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 ) > $O/bench_dp1_nccl.json 2> $O/bench_dp1_nccl.err
+( PSI_DIST_BACKEND=gloo timeout 300 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --secondary 0 ) > $O/bench_n2_gloo.json 2> $O/bench_n2_gloo.err
+timeout 300 python bench.py --full --workload fitting_habitat --steps 21 --warmup 7 --cpu-seconds 6 > $O/bench_habitat.json 2> $O/bench_habitat.err
 timeout 900 python tools/sensitivity.py > $O/sens.log 2>&1; cp gpurun_out/sensitivity.json $O/
 [ -n "$SKIP_TRAIN" ] || bash tools/gpu_call.sh final4 proftrain > $O/proftrain_summary.log 2>&1
 python - <<'PY'

@@ -7,7 +7,7 @@ runs = [dict(), dict(m=8192), dict(m=131072), dict(nc=512), dict(nc=4096), dict(
         dict(batch=4096), {'batch': 512, 'weight-nnz': 4}, {'batch': 4096, 'weight-nnz': 4}]
 out = []
 for r in runs:
-    args = [sys.executable, os.path.join(R, 'bench.py'), '--no-cpu-baseline', '--secondary', '0', '--steps', '20' if r.get('batch', 32) >= 512 else '60', '--warmup', '5']
+    args = [sys.executable, os.path.join(R, 'bench.py'), '--full', '--no-cpu-baseline', '--secondary', '0', '--steps', '20' if r.get('batch', 32) >= 512 else '60', '--warmup', '5']
     for k, v in r.items():
         args += ['--' + k, str(v)]
     p = subprocess.run(args, capture_output=True, text=True)
