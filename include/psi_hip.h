@@ -132,8 +132,9 @@ int psi_sdf_penetration_stats(const float *sdf_vals, long n, float *stats, void 
  * matrix pipe as three split products of two fp16 parts per operand (22 mantissa bits, exact power-of-two scales, fp32 accumulation):
  * 2^-22 relative per product, the accuracy class of an fp32 product chain (tests/test_lbs_gpu.py holds it to fp64 with the margin an
  * fp32 evaluation needs).  |betas| beyond 4094 saturate (the feature rows' fixed scale).  The backward product g_feat = g_vposed . dirs^T
- * is formed the same way, the gradient rows scaled by their largest entry of the call (psi_lbs_backward: a row-maximum pass; the fitting
- * engine below: recorded by the kernels that write the rows).
+ * is formed the same way, each body's gradient rows scaled by that body's own largest entry (psi_lbs_backward: a row-maximum pass; the
+ * fitting engine below: recorded per body by the kernels that write the rows), so that a body's accuracy and bits do not depend on the
+ * other bodies of the batch — a body with Inf / NaN gradient entries gets non-finite gradients itself and leaves the others unchanged.
  * ------------------------------------------------------------------------------------------- */
 typedef struct psi_lbs_model psi_lbs_model;
 int psi_lbs_create(psi_lbs_model **out, const float *h_v_template, const float *h_shapedirs,

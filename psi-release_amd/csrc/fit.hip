@@ -135,9 +135,12 @@ struct FitDev {
 #ifndef PSI_GV_SLOTS
 #define PSI_GV_SLOTS 1024
 #endif
-    unsigned *gvbits;                     // [2][PSI_GV_SLOTS] bit patterns of max |g_vposed| over the penetration / the contact class of rows of this iteration, in
-                                          // slots per class (integer atomicMax by their producers, slot = workgroup % PSI_GV_SLOTS: no hot address; read and combined by
-                                          // fit_bwd_joint_kernel for the fp16 parts' scale; zeroed by fit_reduce_kernel)
+    static_assert(PSI_GV_SLOTS >= 128, "one slot per body and class at least: fused_bwd runs batches up to 128 (merged_scene)");
+    unsigned *gvbits;                     // [2][PSI_GV_SLOTS] bit patterns of max |g_vposed| over the penetration / the contact class of rows of this iteration, per
+                                          // body: class c, body b owns slots c * PSI_GV_SLOTS + b * gv_sps + [0, gv_sps) (integer atomicMax by the body's producers, slot =
+                                          // the producer's block of the body % gv_sps: no hot address); read and combined per body by fit_bwd_joint_kernel for the
+                                          // fp16 parts' scale (lbs_joint_device.h: blend_bwd_h_body); zeroed by fit_reduce_kernel
+    int gv_sps;                           // slots per body and class, a power of two, B * gv_sps <= PSI_GV_SLOTS
     const float *dirs_ch;                 // the contact slots' blend-shape columns, one copy per slot, as two fp16 parts per entry in LbsDev::dirs_bh's operand order (12.6 MB at n_c = 2048)
     const float *WTt_c;                   // [ncp/64][PSI_JP][64] skinning weights of the contact slots, tiled per wave like LbsDev::WTt
     float *gA_part, *gfeat_part;          // [nsv + nsv_c][B][JP][16], [nsn_m + nsn_c][B][Kpad] split-contraction partials of both classes
@@ -506,8 +509,9 @@ struct SdfPenEpilogue {
     float *gl, *gvp, *gtp;
     int Npad, B;
     float gm[2][3], gs[2][3];
-    float gvmax;                  // max |g_vposed entry| this lane has stored (-> gmaxp, one integer atomicMax per workgroup)
-    unsigned *gmaxp;
+    float gvmax[2];               // per body of the workgroup: max |g_vposed entry| this lane has stored (-> gmaxp, one integer atomicMax per workgroup and body)
+    unsigned *gmaxp;              // the penetration class's per-body slots (FitDev::gvbits)
+    int gv_sps;
     // the vertex store of the skinning kernel.  All vertices: [B][V][3] as always.  Contact vertices only (large batches, where the NN search is
     // a launch of its own and reads them): the rows go to their contact SLOT, not to their vertex — the slot list follows the vertex order
     // within a contact part, so the 12-byte pieces of neighbouring lanes are neighbours in memory again (scattered through [B][V][3] they
@@ -576,7 +580,7 @@ struct SdfPenEpilogue {
         const float vx = psi_dot3(T2[0].x, T2[2].x, T2[4].x, lx, ly, lz), vy = psi_dot3(T2[0].y, T2[2].y, T2[4].y, lx, ly, lz),
                     vz = psi_dot3(T2[1].x, T2[3].x, T2[5].x, lx, ly, lz);
         psi_st(gvp + (size_t)b * Npad, v12, psi_p3{vx, vy, vz});
-        gvmax = fmaxf(gvmax, fmaxf(fabsf(vx), fmaxf(fabsf(vy), fabsf(vz))));
+        gvmax[n] = fmaxf(gvmax[n], fmaxf(fabsf(vx), fmaxf(fabsf(vy), fabsf(vz))));
         gs[n][0] = lx; gs[n][1] = ly; gs[n][2] = lz;
     }
     __device__ __forceinline__ void finish(int n, int b, int vblock, int nvb)
@@ -590,7 +594,7 @@ struct SdfPenEpilogue {
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = (psi_f2){ws, wc};
         if (gl) {
             const float sx = psi_wave_sum(gs[n][0]), sy = psi_wave_sum(gs[n][1]), sz = psi_wave_sum(gs[n][2]);
-            float mx = gvmax;
+            float mx = gvmax[n];
 #pragma unroll
             for (int o2 = 32; o2 > 0; o2 >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o2, 64));
             if ((threadIdx.x & 63) == 0) {
@@ -606,7 +610,7 @@ struct SdfPenEpilogue {
 #pragma unroll
             for (int w = 1; w < PSI_SKIN_BLK / 64; w++) mx = fmaxf(mx, redm[w]);
 #ifndef PSI_NO_GVMAX_ATOMIC
-            if (mx > 0.0f) atomicMax(gmaxp + (blockIdx.x & (PSI_GV_SLOTS - 1)), __float_as_uint(mx));
+            if (mx > 0.0f) atomicMax(gmaxp + (size_t)b * gv_sps + (vblock & (gv_sps - 1)), __float_as_uint(mx));
 #endif       // (non-negative floats order like their bit patterns; max is order-independent)
         }
         if (threadIdx.x == 0) {
@@ -627,7 +631,7 @@ struct SdfPenEpilogue {
 static inline SdfPenEpilogue make_sdf_epilogue(const FitDev &f, const PsiSdfGrid &G, bool contact_vertices_only = false, const PsiLbsView *bwd = nullptr)
 {
     SdfPenEpilogue e = {G, f.sdf, f.gmin, f.gmax, f.og, f.penpart, f.D, f.align_corners, f.Vpad, contact_vertices_only ? f.cs_first : nullptr,
-                        {0.0f, 0.0f}, {false, false}, f.cverts, f.cs_ptr, f.cs_idx, f.n_c, nullptr, nullptr, nullptr, 0, f.B, {}, {}, 0.0f, f.gvbits};
+                        {0.0f, 0.0f}, {false, false}, f.cverts, f.cs_ptr, f.cs_idx, f.n_c, nullptr, nullptr, nullptr, 0, f.B, {}, {}, {0.0f, 0.0f}, f.gvbits, f.gv_sps};
     if (bwd) {
         e.gl = bwd->gl;
         e.gvp = bwd->g_vp;
@@ -781,7 +785,7 @@ struct ContactSkinSrc {
 #pragma unroll
             for (int w = 1; w < psikd::QBLK / 64; w++) m2 = fmaxf(m2, wmax[w]);
 #ifndef PSI_NO_GVMAX_ATOMIC
-            if (m2 > 0.0f) atomicMax(f.gvbits + PSI_GV_SLOTS + (blockIdx.x & (PSI_GV_SLOTS - 1)), __float_as_uint(m2));
+            if (m2 > 0.0f) atomicMax(f.gvbits + PSI_GV_SLOTS + (size_t)b * f.gv_sps + (bx & (f.gv_sps - 1)), __float_as_uint(m2));
 #endif
         }
         if (threadIdx.x < 3) {
@@ -984,21 +988,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         trace.kind = slice < f.nsn_m ? 2 : 3;
 #endif
         float *part = f.gfeat_part + (size_t)slice * f.B * m.Kpad;
-        // (the rows' fp16 scale from the class's largest entry of THIS iteration, recorded by fwd_scene_kernel; the matrix's own scale is static)
+        // (the rows' fp16 scales: per body, from the largest entry of the body's rows of the class in THIS iteration, recorded by
+        // fwd_scene_kernel; the matrix's own scale is static)
         const float dsc_inv = m.dirs_unscale * PSI_FEAT_SCALE;
-        unsigned cbits = 0u;
-#pragma unroll
-        for (int q = 0; q < PSI_GV_SLOTS / 64; q++) cbits = max(cbits, f.gvbits[(slice < f.nsn_m ? 0 : PSI_GV_SLOTS) + q * 64 + (threadIdx.x & 63)]);
-#pragma unroll
-        for (int o2 = 32; o2 > 0; o2 >>= 1) cbits = max(cbits, (unsigned)__shfl_xor((int)cbits, o2, 64));
         if (slice < f.nsn_m) {
-            const float gsc = psi_fp16_class_scale(cbits);
-            const PsiBlendBwdColsH o = {m.dirs_bh, g_vp, (size_t)m.Npad, m.Kpad, m.Npad / 16, gsc, dsc_inv / gsc};
+            const PsiBlendBwdColsH o = {m.dirs_bh, g_vp, (size_t)m.Npad, m.Kpad, m.Npad / 16, f.gvbits, f.gv_sps, dsc_inv};
             blend_bwd_h_body<(MT + 1) / 2>(o, f.B, slice * f.spm, (slice + 1) * f.spm, part, kg, bg, smem);
         } else {
             const int c = slice - f.nsn_m;
-            const float gsc = psi_fp16_class_scale(cbits);
-            const PsiBlendBwdColsH o = {f.dirs_ch, f.gvpc, (size_t)f.ncp3, m.Kpad, f.ncp3 / 16, gsc, dsc_inv / gsc};
+            const PsiBlendBwdColsH o = {f.dirs_ch, f.gvpc, (size_t)f.ncp3, m.Kpad, f.ncp3 / 16, f.gvbits + PSI_GV_SLOTS, f.gv_sps, dsc_inv};
             blend_bwd_h_body<(MT + 1) / 2>(o, f.B, c * f.spc, (c + 1) * f.spc, part, kg, bg, smem);
         }
     } else {
@@ -1849,6 +1847,10 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
     f.fused_bwd = e->fused_bwd ? 1 : 0;
     f.ncp = psi_cdiv(f.n_c, 256) * 256;
     f.ncp3 = 3 * f.ncp;
+    // per-body slots of the rows' maxima: up to 16 per body (a body's rows come from one skinning workgroup per 256 vertices and a few
+    // search workgroups: a few producers per address, where one address for a whole class cost 6 us), all inside the class's PSI_GV_SLOTS
+    f.gv_sps = 16;
+    while (f.gv_sps > 1 && (long)f.gv_sps * B > PSI_GV_SLOTS) f.gv_sps >>= 1;
     size_t o_glc = 0, o_gvpc = 0, o_vpc = 0, o_gtc = 0, o_gvb = 0, o_wttc = 0, o_dirsc = 0, o_gap = 0, o_gfp = 0, o_spb = 0;
     {
         // slice counts of the model's own rows: from the LBS workspace layout (offsets only: no memory is touched through this view)
@@ -2385,6 +2387,7 @@ extern "C" int psi_fit_copy_buffer(psi_fit_engine *e, const char *name, float *d
     else if (!strcmp(name, "glc") && e->fused_bwd) { src = f.glc; cap = (long)f.B * f.ncp3; }
     else if (!strcmp(name, "gvpc") && e->fused_bwd) { src = f.gvpc; cap = (long)f.B * f.ncp3; }
     else if (!strcmp(name, "vpc") && e->fused_bwd) { src = f.vpc; cap = (long)f.B * f.ncp3; }
+    else if (!strcmp(name, "spb") && e->fused_bwd) { src = f.spb; cap = f.B; }      // independent bodies: each body's penetration factor -w / N_b
     PSI_REQUIRE(src != nullptr, "unknown buffer name");
     PSI_REQUIRE(n_floats <= cap, "buffer is smaller than requested");
     PSI_CHECK_HIP(hipMemcpyAsync(d_out, src, (size_t)n_floats * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));

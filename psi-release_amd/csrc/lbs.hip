@@ -56,7 +56,14 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 // workspace layout (floats)
 // ------------------------------------------------------------------------------------------------
-constexpr int GV_SLOTS = 1024;
+// parts per body row of the g_vposed maxima (gv_rowmax_kernel): about 1024 workgroups for the pass, at most 16 slots for a blend workgroup
+// to combine per body
+static inline int gv_parts(int B)
+{
+    int p = 16;
+    while (p > 1 && (long)p * B > 1024) p >>= 1;
+    return p;
+}
 struct WsLayout {
     size_t feat, R, Jl, G, A, v_posed, gl, g_vp, gA_part, gfeat_part, gt_part, gA, gfeat, gvbits, total;
     int nsv, nsn, nvb;
@@ -85,7 +92,7 @@ WsLayout ws_layout(const LbsDev &m, int B)
     w.gt_part = take((size_t)w.nvb * B * 4);
     w.gA = take((size_t)B * JP * 16);
     w.gfeat = take((size_t)B * m.Kpad);
-    w.gvbits = take(GV_SLOTS);                  // per-workgroup maxima of |g_vposed| (bit patterns), gv_rowmax_kernel -> bwd_joint_kernel
+    w.gvbits = take((size_t)B * gv_parts(B));   // [B][gv_parts] maxima of |g_vposed| per body (bit patterns), gv_rowmax_kernel -> bwd_joint_kernel
     w.total = o;
     return w;
 }
@@ -257,30 +264,33 @@ extern "C" int psi_dbg_timeline2(unsigned long long *out, int nblocks)
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(psi_dbg_tl2), sizeof(unsigned long long) * 4 * (size_t)(nblocks < 2048 ? nblocks : 2048));
 }
 #endif
-// The largest |entry| of g_vposed [B][Npad] as GV_SLOTS per-workgroup maxima (bit patterns; plain stores: nothing to reset, nothing atomic) — the
-// scale of the rows' fp16 parts in blend_bwd_h_body (lbs_joint_device.h).  The fused fitting engine gets the same number from the kernels
-// that WRITE the rows (fit.hip); here the rows come from psi_skin_bwd_v kernels of several kinds, and one more pass over rows that were
-// written a moment ago costs 2-15 us against the 5-90 us the fp16 matrix pipe saves on the launch behind it.
-__global__ __launch_bounds__(256) void gv_rowmax_kernel(const float *__restrict__ g, size_t n4, unsigned *__restrict__ slots)
+// The largest |entry| of every body's row of g_vposed [B][Npad], as P per-workgroup maxima per body (bit patterns, [B][P]; plain stores:
+// nothing to reset, nothing atomic) — the scale of that body's fp16 parts in blend_bwd_h_body (lbs_joint_device.h).  The fused fitting
+// engine gets the same numbers from the kernels that WRITE the rows (fit.hip); here the rows come from psi_skin_bwd_v kernels of several
+// kinds, and one more pass over rows that were written a moment ago costs 2-15 us against the 5-90 us the fp16 matrix pipe saves on the
+// launch behind it.  Grid (P, B): workgroup (p, b) takes quads p, p + P, ... (in 256-quad blocks) of row b.
+__global__ __launch_bounds__(256) void gv_rowmax_kernel(const float *__restrict__ g, int npad4, unsigned *__restrict__ slots)
 {
     __shared__ float red[4];
+    const int P = (int)gridDim.x, p = (int)blockIdx.x, b = (int)blockIdx.y;
+    const f4 *row = (const f4 *)g + (size_t)b * npad4;
     float mx = 0.0f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)GV_SLOTS * 256) {
-        const f4 v = ((const f4 *)g)[i];
+    for (int i = p * 256 + (int)threadIdx.x; i < npad4; i += P * 256) {
+        const f4 v = row[i];
         mx = fmaxf(mx, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
     }
 #pragma unroll
     for (int o2 = 32; o2 > 0; o2 >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o2, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
     __syncthreads();
-    if (threadIdx.x == 0) slots[blockIdx.x] = __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
+    if (threadIdx.x == 0) slots[(size_t)b * P + p] = __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
 }
 
 template <int MT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void bwd_joint_kernel(
     LbsDev m, const float *__restrict__ g_vp, const float *__restrict__ gl, const float *__restrict__ v_posed, int B, int steps_per_slice,
     float *__restrict__ gfeat_part, float *__restrict__ gA_part, int n_blend, int kgroups, int nslices, int nsv, int nbody,
-    const unsigned *__restrict__ gvbits)
+    const unsigned *__restrict__ gvbits, int gvparts)
 {
     // blend_bwd: [4][2][MTB][4][64] f4; skin_bwd_A: SKA_NBODY bodies' staged operands (2 x 3 component rows each)
     constexpr int SMEM_B = psi_blend_bwd_h_smem_f4<(MT + 1) / 2>();
@@ -296,14 +306,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (bid < n_blend) {
         int kg, slice, bg;
         psi_blend_bwd_place(bid, kgroups, nslices, kg, slice, bg);
-        // the rows' fp16 scale: the largest |g_vposed| entry of this backward (gv_rowmax_kernel left one maximum per workgroup)
-        unsigned cbits = 0u;
-#pragma unroll
-        for (int q = 0; q < GV_SLOTS / 64; q++) cbits = max(cbits, gvbits[q * 64 + (threadIdx.x & 63)]);
-#pragma unroll
-        for (int o2 = 32; o2 > 0; o2 >>= 1) cbits = max(cbits, (unsigned)__shfl_xor((int)cbits, o2, 64));
-        const float gsc = psi_fp16_class_scale(cbits);
-        const PsiBlendBwdColsH cols = {m.dirs_bh, g_vp, (size_t)m.Npad, m.Kpad, m.Npad / 16, gsc, m.dirs_unscale * PSI_FEAT_SCALE / gsc};
+        // (the rows' fp16 scales: per body, from the gvparts maxima gv_rowmax_kernel left for each body)
+        const PsiBlendBwdColsH cols = {m.dirs_bh, g_vp, (size_t)m.Npad, m.Kpad, m.Npad / 16, gvbits, gvparts, m.dirs_unscale * PSI_FEAT_SCALE};
         blend_bwd_h_body<(MT + 1) / 2>(cols, B, slice * steps_per_slice, (slice + 1) * steps_per_slice, gfeat_part + (size_t)slice * B * m.Kpad, kg, bg, smem);
     } else {
         const int i = bid - n_blend, vslice = i % nsv;
@@ -680,11 +684,12 @@ static int lbs_launch_bwd_joint_parts(const LbsDev &m, const WsLayout &L, int B,
     // (Round 4 measured the two halves as two launches of this kernel — stream workgroups, then the skin_bwd_A workgroups: 18.4 us each by
     // rocprofv3 = 36.8 against 27.2 for the heterogeneous grid, profiles/r04_ab_blend_loop.txt.  One grid it stays.)
     const int grid = n_blend + L.nsv * psi_cdiv(B, nbody);
-    hipLaunchKernelGGL(gv_rowmax_kernel, dim3(GV_SLOTS), dim3(256), 0, st, ws + L.g_vp, (size_t)B * m.Npad / 4, (unsigned *)(ws + L.gvbits));
+    const int gvp = gv_parts(B);
+    hipLaunchKernelGGL(gv_rowmax_kernel, dim3(gvp, B), dim3(256), 0, st, ws + L.g_vp, m.Npad / 4, (unsigned *)(ws + L.gvbits));
     PSI_CHECK_LAUNCH("gv_rowmax_kernel");
 #define PSI_LAUNCH_JOINT(MT_)                                                                                                      \
     hipLaunchKernelGGL(bwd_joint_kernel<MT_>, dim3(grid), dim3(256), 0, st, m, ws + L.g_vp, ws + L.gl, ws + L.v_posed, B, steps,     \
-                       ws + L.gfeat_part, ws + L.gA_part, n_blend, kgroups, L.nsn, L.nsv, nbody, (const unsigned *)(ws + L.gvbits))
+                       ws + L.gfeat_part, ws + L.gA_part, n_blend, kgroups, L.nsn, L.nsv, nbody, (const unsigned *)(ws + L.gvbits), gvp)
     if (mt == 4) PSI_LAUNCH_JOINT(4);
     else if (mt == 2) PSI_LAUNCH_JOINT(2);
     else PSI_LAUNCH_JOINT(1);

@@ -191,10 +191,9 @@ __device__ __forceinline__ void psi_pose_fwd_chain(const LbsDev &m, const float 
         if (joints)
             for (int r = 0; r < 3; r++) joints[((size_t)b * m.J + j) * 3 + r] = G[r * 4 + 3] + (transl ? transl[(size_t)b * 3 + r] : 0.0f);
     }
-    // The pipelined dense blend pads J to whole groups of 12 joints and multiplies ZERO weights with the transform rows behind a body's
-    // block: the next body's rows (finite) — or, for the last body, whatever lies behind the A array.  Those PSI_A_TAIL rows belong to
-    // the array (ws_layout) and are written here on every forward, so that a recycled / caller-provided workspace cannot put a NaN
-    // bit pattern under a zero weight.
+    // The pipelined dense blend pads J to whole groups of 12 joints; its padding joints read a zero row of their own, but the last load
+    // of a group still reaches up to 2 rows past the padding: behind the last body's block those are PSI_A_TAIL rows that belong to the
+    // array (ws_layout), so the load stays inside it, and are written here on every forward.
     if (b == B - 1)
         for (int q = j; q < PSI_A_TAIL * 3; q += blockDim.x) ((psi_f4 *)(As + (size_t)B * m.J * 12))[q] = psi_f4{0.0f, 0.0f, 0.0f, 0.0f};
 }
@@ -588,11 +587,11 @@ __device__ __forceinline__ void psi_st(void *uniform_base, unsigned lane_off, co
 //                      itself (a few scalar registers spill).  The smallest instruction footprint and the fewest scalar round trips in
 //                      a row — what the latency-bound BASELINE batch wants (skin_bwd_v 14.0 us; with a fence every 4 joints 15.2, every
 //                      2 joints 16.3; round 3's loop 14.7).
-//   PsiBlendPipelined  groups of 12 joints (J padded: the extra joints have zero weights and read the finite rows behind the body's
-//                      transforms) in sets of PS joints whose transforms sit in TWO alternating sets of scalar registers: the scalar
-//                      loads of set i + 1 are issued BEFORE set i is accumulated, so a wave hides them behind its own packed FMAs
-//                      instead of draining the scalar-load counter (it cannot count out-of-order returns: every wait is "all of
-//                      them") in front of every set.  SMPL-X's five groups are straight-line code: at a loop header the compiler waits
+//   PsiBlendPipelined  groups of 12 joints (J padded: the extra joints have zero weights and read a zero row — not the rows behind the
+//                      body's transforms, the next body's, whose Inf / NaN times a zero weight would be NaN here) in sets of PS
+//                      joints whose transforms sit in TWO alternating sets of scalar registers: the scalar loads of set i + 1 are
+//                      issued BEFORE set i is accumulated, so a wave hides them behind its own packed FMAs instead of draining the
+//                      scalar-load counter (it cannot count out-of-order returns: every wait is "all of them") in front of every set.  SMPL-X's five groups are straight-line code: at a loop header the compiler waits
 //                      for EVERY outstanding weight load, i.e. for the two requested a few cycles earlier; in straight-line code its
 //                      waits are exact.  What the throughput-bound large batches want (skin_fwd_sdf at B = 512, dense rows: 136 us
 //                      against 150 for the same code as a loop and 158 for the compact form).
@@ -600,6 +599,7 @@ __device__ __forceinline__ void psi_st(void *uniform_base, unsigned lane_off, co
 #define PSI_DENSE_UNROLL 11
 #endif
 enum PsiBlendForm { PsiBlendCompact = 0, PsiBlendPipelined = 1 };
+static __device__ const psi_f2 psi_zero_row[6] = {};           // the transform row a padding joint of PsiBlendPipelined reads
 // LDS home of a workgroup's staged joint transforms ([body][joint][6 float pairs]): ONE array per kernel for every user — the skinning
 // workgroups (PsiBlendN::commit, compressed rows) and, in the fused fitting engine's shared launch, the search workgroups that skin their own
 // contact vertex (fit.hip: ContactSkinSrc) are never the same workgroup, and two separate 3 KB arrays put that launch over an occupancy step
@@ -718,13 +718,20 @@ struct PsiBlendN {
 #pragma unroll
             for (int k = 0; k < G2; k++) w[k] = wload(k, ro);
             psi_f2 P0[NB][PS][6], P1[NB][PS][6];
-            auto aload = [&](psi_f2 (&P)[NB][PS][6], int j) {
+            // (the last group's joints past J are padding: their weights are zero, but the rows behind the body's block are the NEXT body's
+            // transforms, and 0 * Inf / NaN would carry a non-finite body into this one — a padding joint reads a zero row instead.  jn = J:
+            // a compile-time 55 for SMPL-X, where the compiler makes the choice (skin_fwd 39.6 against 37.2 us before, rocprofv3 average over
+            // B = 5 .. 512); any other J selects the address at run time, for joints of the last group only (ts = its first joint) — as the
+            // SMPL-X path that measured 60 us, and a branch around the padding joints' FMAs 46: either drains the pipelined waits)
+            auto aload = [&](psi_f2 (&P)[NB][PS][6], int j, int ts, int jn) {
 #pragma unroll
                 for (int n = 0; n < NB; n++)
 #pragma unroll
-                    for (int q = 0; q < PS; q++)
+                    for (int q = 0; q < PS; q++) {
+                        const psi_f2 *row = j + q >= ts && j + q >= jn ? psi_zero_row : Ab[n] + (j + q) * 6;
 #pragma unroll
-                        for (int e = 0; e < 6; e++) P[n][q][e] = Ab[n][(j + q) * 6 + e];
+                        for (int e = 0; e < 6; e++) P[n][q][e] = row[e];
+                    }
             };
             auto fmas = [&](const psi_f2 (&P)[NB][PS][6], const float *wk) {
 #pragma unroll
@@ -736,20 +743,20 @@ struct PsiBlendN {
                         for (int e = 0; e < 6; e++) T2[n][e] = __builtin_elementwise_fma(w2, P[n][q][e], T2[n][e]);
                 }
             };
-            aload(P0, 0);
             const int ngroups = (m.J + G2 - 1) / G2;
-            auto group = [&](int g) {
+            aload(P0, 0, (ngroups - 1) * G2, m.J);
+            auto group = [&](int g, int ts, int jn) {
                 const int j0 = g * G2;
                 ro += g + 1 < ngroups ? G2 * 256 : 0;
 #pragma unroll
                 for (int k = 0; k < G2; k += 2 * PS) {
-                    aload(P1, j0 + k + PS);
+                    aload(P1, j0 + k + PS, ts, jn);
                     __builtin_amdgcn_sched_barrier(0);
                     fmas(P0, w + k);
 #pragma unroll
                     for (int q = 0; q < PS; q++) w[k + q] = wload(k + q, ro);
                     __builtin_amdgcn_sched_barrier(0);
-                    aload(P0, j0 + k + 2 * PS);                      // (the last one of the last group reads rows that are never used)
+                    aload(P0, j0 + k + 2 * PS, ts, jn);              // (the last one of the last group reads rows that are never used)
                     __builtin_amdgcn_sched_barrier(0);
                     fmas(P1, w + k + PS);
 #pragma unroll
@@ -757,12 +764,15 @@ struct PsiBlendN {
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
-            if (ngroups == 5) {                                      // SMPL-X
+            if (m.J == 55) {                                         // SMPL-X
 #pragma unroll
-                for (int g = 0; g < 5; g++) group(g);
+                for (int g = 0; g < 5; g++) group(g, 4 * G2, 55);
+            } else if (ngroups == 5) {
+#pragma unroll
+                for (int g = 0; g < 5; g++) group(g, 4 * G2, m.J);
             } else {
 #pragma nounroll
-                for (int g = 0; g < ngroups; g++) group(g);
+                for (int g = 0; g < ngroups; g++) group(g, (ngroups - 1) * G2, m.J);
             }
         }
     }

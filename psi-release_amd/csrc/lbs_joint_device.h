@@ -152,10 +152,15 @@ __device__ __forceinline__ void skin_bwd_A_dispatch(const PsiSkaSlice &o, int B,
 // skin_bwd_A waves (with a quarter of them: 25.3 -> 21.2 us, profiles/r06_ab_blend_fp16x3.txt).  The matrix arrives as TWO fp16 parts per
 // entry (hi = fp16(x), lo = fp16((x - hi) 2^11), x = value * a power of two: 22 mantissa bits in the same 4 bytes) in MFMA operand order
 //   dirs_bh [n-step of 16][Kpad/32 k-tiles][part][n half][32 k][8 n]        (a wave's load of one part of one (step, k-tile) is 1 KB contiguous);
-// the gradient rows stay fp32 in memory and are split by the wave that loads them, with the scale 2^s that puts the class's largest entry
-// (an integer atomicMax of its bit pattern by the rows' producers: exact, order-independent) into [2^13, 2^14) — fp16 cannot overflow,
-// entries down to 1e-9 of the largest keep 22 bits, smaller ones an absolute error below 1e-12 of the largest.  A product is
-// hi*hi + (hi*lo + lo*hi) 2^-11 in two fp32 accumulators: 3 MFMAs of 32 cycles per 32 x 32 x 16 block instead of 16.
+// the gradient rows stay fp32 in memory and are split by the wave that loads them, with the scale 2^s that puts the largest entry of THAT
+// BODY's rows into [2^13, 2^14) — fp16 cannot overflow, entries down to 1e-9 of the body's largest keep 22 bits, smaller ones an absolute
+// error below 1e-12 of it.  The B operand's column is the body, and the lane that supplies column li also holds output column li, so the
+// scale and its inverse are per-lane values, one per body tile: a body's accuracy does not depend on the other bodies of the batch, and a
+// body with an Inf entry (scale clamped to 2^-100) or one a trillion times larger than the rest leaves their products bit for bit as they
+// were (the first form of this product took one scale per call, and such a body underflowed every other body's rows to zero in fp16).  The
+// body's largest entry arrives as the bit patterns of its slots ([B][gv_slots], integer maxima of the producers: exact, order-independent),
+// combined here.  A product is hi*hi + (hi*lo + lo*hi) 2^-11 in two fp32 accumulators: 3 MFMAs of 32 cycles per 32 x 32 x 16 block
+// instead of 16.
 // Workgroup = 4 waves sharing a 64-row k group (two 32-row k-tiles) and an n-slice; wave w takes n-steps w, w + 4, ...; LDS reduce.
 // ------------------------------------------------------------------------------------------------
 typedef _Float16 psi_h8 __attribute__((ext_vector_type(8)));
@@ -166,11 +171,12 @@ struct PsiBlendBwdColsH {
     const float *g_vp;         // [B][row_stride] fp32
     size_t row_stride;
     int Kpad, total_steps;
-    float g_scale;             // 2^s for the rows' fp16 parts
-    float unscale;             // 1 / (matrix scale * g_scale)
+    const unsigned *gvbits;    // [B][gv_slots] bit patterns of maxima of |row entry|: the largest of a body's slots is the largest entry of its rows
+    int gv_slots;              // slots per body (>= 1)
+    float dsc_inv;             // 1 / matrix scale (the rows' own scale 2^s is applied per body)
 };
-// scale for a class whose largest |entry| has the bit pattern `bits` (0: nothing stored this iteration)
-__device__ __forceinline__ float psi_fp16_class_scale(unsigned bits)
+// scale for rows whose largest |entry| has the bit pattern `bits` (0: nothing stored this iteration)
+__device__ __forceinline__ float psi_fp16_row_scale(unsigned bits)
 {
     int E = (int)((bits >> 23) & 0xffu);                 // largest entry in [2^(E-127), 2^(E-126))
     if (bits == 0u) E = 140;                             // (any scale: every entry is zero)
@@ -205,7 +211,18 @@ __device__ __forceinline__ void blend_bwd_h_body(const PsiBlendBwdColsH &o, int 
 #pragma unroll
     for (int t = 0; t < MTB; t++) grow[t] = o.g_vp + (size_t)min(b0 + t * 32 + li, B - 1) * o.row_stride + 8 * kh;
     const char *dbase = (const char *)o.dirs_bh + ((size_t)(2 * kgroup) * 2) * 1024 + (size_t)(kh * 32 + li) * 16;
-    const float gsc = o.g_scale;
+    // the scale of body tile t's column li (body b0 + 32 t + li) and the inverse of both scales for the same output column: lanes li and
+    // li + 32 hold the same body and split its slots between them
+    float gsc[MTB], us[MTB];
+#pragma unroll
+    for (int t = 0; t < MTB; t++) {
+        const unsigned *sl = o.gvbits + (size_t)min(b0 + t * 32 + li, B - 1) * o.gv_slots;
+        unsigned cbits = 0u;
+        for (int p = kh; p < o.gv_slots; p += 2) cbits = max(cbits, sl[p]);
+        cbits = max(cbits, (unsigned)__shfl_xor((int)cbits, 32, 64));
+        gsc[t] = psi_fp16_row_scale(cbits);
+        us[t] = o.dsc_inv / gsc[t];
+    }
     // PF steps' operands (PF x (4 + 2 MTB) 16-byte loads per lane) are requested before the first of them is split and multiplied
 #ifndef PSI_BWH_PF
 #define PSI_BWH_PF 1
@@ -236,7 +253,7 @@ __device__ __forceinline__ void blend_bwd_h_body(const PsiBlendBwdColsH &o, int 
                     psi_h8 gh, gl;
 #pragma unroll
                     for (int e = 0; e < 8; e++) {
-                        const float x = g[p][t][e >> 2][e & 3] * gsc;
+                        const float x = g[p][t][e >> 2][e & 3] * gsc[t];
                         const _Float16 hi = (_Float16)x;
                         gh[e] = hi;
                         gl[e] = (_Float16)((x - (float)hi) * 2048.0f);
@@ -254,16 +271,16 @@ __device__ __forceinline__ void blend_bwd_h_body(const PsiBlendBwdColsH &o, int 
     }
     // D[row = 8 q + 4 kh + e -> k][col = li -> body]: the two accumulators combined, the four waves' sums through LDS, wave w finishes quad q = w
     f4 (*red)[2][MTB][4][64] = (f4 (*)[2][MTB][4][64])smem;      // [wave][k-tile][body tile][row quad][lane]
-    const float us = o.unscale, us2 = o.unscale * (1.0f / 2048.0f);
 #pragma unroll
     for (int kt = 0; kt < 2; kt++)
 #pragma unroll
         for (int t = 0; t < MTB; t++)
 #pragma unroll
             for (int q = 0; q < 4; q++) {
+                const float us2 = us[t] * (1.0f / 2048.0f);
                 f4 v;
 #pragma unroll
-                for (int e = 0; e < 4; e++) v[e] = __builtin_fmaf(acc[kt][t][1][4 * q + e], us2, acc[kt][t][0][4 * q + e] * us);
+                for (int e = 0; e < 4; e++) v[e] = __builtin_fmaf(acc[kt][t][1][4 * q + e], us2, acc[kt][t][0][4 * q + e] * us[t]);
                 red[w][kt][t][q][lane] = v;
             }
     __syncthreads();

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import arbiter
+import per_body
 import psi_oracle as O
 from conftest import golden, rel_err
 from psi_release_amd import fitting, synth
@@ -385,3 +386,107 @@ def test_fused_blend_backward_is_in_the_fp32_accuracy_class(smplx_data, vposer_s
     scale = np.abs(ref).max(1, keepdims=True)
     d_prod, d_f32 = (np.abs(gfeat - ref) / scale).max(), (np.abs(r32 - ref) / scale).max()
     assert d_prod <= 4.0 * d_f32 + 2e-7, (d_prod, d_f32)
+
+
+# ---- one steep body in a batch: the fp16 split products of the fused blend backward take a scale PER BODY -----------------------------
+STEEP_X0 = 1.0          # the room's SDF is multiplied by 1e10 at grid points with x > STEEP_X0 (all of them are inside the wall)
+
+
+def _steep_scene():
+    """synth's room with its SDF multiplied by 1e10 on the x > STEEP_X0 side: a body that reaches there has a penetration gradient 1e10
+    times everyone else's.  (D = 32, align_corners: grid points at linspace(-2, 2, 32); the volume is [x][y][z], psi_oracle.sdf_sample.)"""
+    scene = synth.make_scene(5, 3000, 32, 300, kind='room')
+    ax = np.linspace(-2.0, 2.0, scene.grid_dim, dtype=np.float32)
+    sdf = scene.sdf.copy()
+    sdf[ax > STEEP_X0] *= np.float32(1e10)
+    assert (sdf[ax > STEEP_X0] < -1e9).all()
+    return dataclasses.replace(scene, sdf=sdf)
+
+
+def _steep_bodies(B, j, where):
+    """B bodies on the x < 0 side of the room (each with vertices inside its wall), body j at `where`: 'normal' (with the others),
+    'steep' (reaching into the x > STEEP_X0 region) or 'outside' (two scene-cloud box sizes beyond the scene)."""
+    bodies = synth.make_bodies(71, B)
+    bodies['transl'][:, 0] = -1.0
+    bodies['transl'][j, 0] = {'normal': -1.0, 'steep': 1.2, 'outside': 6.0}[where]
+    return bodies
+
+
+def _run_one_iteration(smplx_data, vposer_sd, scene, bodies, indep, w_contact=0.1):
+    B = len(bodies['transl'])
+    cfg = {'scene_verts_path': None, 'scene_sdf_path': None, 'human_model_path': None, 'vposer_ckpt_path': None,
+           'init_lr_h': 0.05, 'num_iter': 1, 'batch_size': B, 'device': torch.device(DEV),
+           'contact_part': synth.CONTACT_PARTS, 'contact_id_folder': None, 'verbose': False,
+           'smplx_data': smplx_data, 'vposer_state': vposer_sd, 'scene': scene, 'engine': 'fused', 'align_corners': True}
+    torch.manual_seed(0)
+    op = fitting.FittingOP(cfg, dict(LOSS, weight_contact=w_contact))
+    op.independent_bodies = indep
+    op.fitting(dict(bodies))
+    return op
+
+
+@pytest.mark.parametrize('B,indep,w_contact', [(5, False, 0.1), (5, True, 0.1), (40, False, 0.1), (40, True, 0.1), (128, False, 0.1),
+                                               (128, True, 0.1), (40, False, 0.0)])
+def test_fused_blend_backward_per_body_with_one_steep_body(smplx_data, vposer_sd, B, indep, w_contact):
+    """fit_bwd_joint_kernel's fp16 split products with one body whose penetration rows are 1e10 times everyone else's (the SDF is steep
+    where only that body reaches): every body's reduced feature gradient, recomputed in fp64 / fp32 from the engine's own g_vposed rows
+    of both classes, must be in the fp32 accuracy class on the body's OWN scale (per_body.py).  Coupled (reference batch semantics: one
+    penetration count N) and independent bodies (per-body -w / N_b); weight_contact = 0: the penetration class alone."""
+    j = B - 2
+    scene = _steep_scene()
+    op = _run_one_iteration(smplx_data, vposer_sd, scene, _steep_bodies(B, j, 'steep'), indep, w_contact)
+    V, K = 10475, 506
+    ids = op.contact_vertex_ids().cpu().numpy()
+    n_c = len(ids)
+    ncp3 = 3 * ((n_c + 255) // 256 * 256)
+    Npad = 3 * ((V + 255) // 256 * 256)
+    eng = op._fused
+    verts = eng.buffer('verts', (B, V, 3)).cpu().numpy()
+    gvp = eng.buffer('g_vp', (B, Npad)).cpu().numpy()[:, :3 * V]
+    gvpc = eng.buffer('gvpc', (B, ncp3)).cpu().numpy()[:, :3 * n_c]
+    gfeat = eng.buffer('gfeat', (B, 512)).cpu().numpy()[:, :K]
+    stats = eng.buffer('stats', (8,)).cpu().numpy()
+    # preconditions: only body j reaches the steep region (no grid corner of another body's vertices lies there), and the bodies'
+    # penetration rows differ by at least 1e9
+    h = 4.0 / (scene.grid_dim - 1)
+    others = np.arange(B) != j
+    assert verts[others, :, 0].max() < STEEP_X0 - h, verts[others, :, 0].max()
+    assert (verts[j, :, 0] > STEEP_X0 + h).sum() > 100
+    gmax = np.abs(gvp).max(1)
+    assert gmax[others].min() > 0 and gmax[j] >= 1e9 * gmax[others].max(), gmax
+    if w_contact == 0:
+        assert not np.any(gvpc)
+    else:
+        assert np.abs(gvpc).max(1).min() > 0
+    if indep:
+        sp = eng.buffer('spb', (B,)).cpu().numpy()
+        assert (sp < 0).all()
+    else:
+        assert stats[4] > 0
+        sp = np.full(B, np.float32(-LOSS['weight_collision']) / np.float32(stats[4]), np.float32)
+    m = O.SMPLXOracle(smplx_data)
+    D = np.concatenate([m.shapedirs.numpy().reshape(3 * V, -1).T, m.posedirs.numpy()], 0)          # [506][3 V] fp32 values
+    cols = (3 * ids[:, None] + np.arange(3)[None]).reshape(-1)
+    D64 = D.astype(np.float64)
+    ref = sp.astype(np.float64)[:, None] * (gvp.astype(np.float64) @ D64.T) + gvpc.astype(np.float64) @ D64[:, cols].T
+    r32 = sp[:, None] * (gvp @ D.T) + gvpc @ D[:, cols].T
+    per_body.assert_per_body_accuracy_class(gfeat, ref, r32, 'gfeat (B=%d, %s, w_contact=%g)' % (B, 'indep' if indep else 'coupled', w_contact))
+
+
+@pytest.mark.parametrize('where', ['steep', 'outside'])
+def test_fused_independent_bodies_do_not_see_each_other(smplx_data, vposer_sd, where):
+    """independent_bodies: every body is its own problem, so moving ONE body — into the region where the SDF is 1e10 times steeper, or two
+    scene-box sizes out of the scene (large contact distances: the contact class's rows) — leaves every other body's reduced gradients
+    (gA, gfeat, g_transl) after one iteration bit for bit as they were."""
+    B, j = 40, 17
+    scene = _steep_scene()
+    out = {}
+    for w in ('normal', where):
+        op = _run_one_iteration(smplx_data, vposer_sd, scene, _steep_bodies(B, j, w), True)
+        out[w] = {k: op._fused.buffer(k, s).cpu().numpy() for k, s in (('gA', (B, 64, 16)), ('gfeat', (B, 512)), ('g_transl', (B, 3)))}
+    others = np.arange(B) != j
+    for k in out['normal']:
+        a, b = out['normal'][k], out[where][k]
+        assert np.isfinite(b).all(), k
+        assert not np.array_equal(a[j], b[j]), k                                     # (body j itself did change)
+        assert np.array_equal(a[others], b[others]), '%s of the other bodies changed when body %d moved (%s)' % (k, j, where)

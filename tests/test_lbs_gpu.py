@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import psi_oracle as O
+import per_body
 from conftest import golden, rel_err
 from psi_release_amd import body_model, synth
 
@@ -199,3 +200,109 @@ def test_multi_body_skinning_kernels_bit_identical_to_single_body(compressed):
     for k in (1, 2, 3):                                                            # gradients: the per-body contractions are the same code,
         ref = torch.cat([p[k] for p in parts])                                     # only the MFMA row-tile variant differs (B > 32 vs 32)
         assert rel_err(whole[k].cpu(), ref.cpu()) < 1e-5
+
+
+def _oracle_grads(m, betas, pose, transl, cam, G, dtype):
+    """(grad_betas, grad_pose, grad_transl) of sum(lbs(betas, pose) + transl, through cam) * G by autograd of the oracle in `dtype`."""
+    c = lambda a: torch.tensor(np.asarray(a)).to(dtype)
+    bo, po, to = c(betas).requires_grad_(), c(pose).requires_grad_(), c(transl).requires_grad_()
+    vo, _ = O.lbs(bo, po, m.v_template, m.shapedirs, m.posedirs, m.J_regressor, m.parents, m.lbs_weights)
+    vo = O.verts_transform(vo + to.unsqueeze(1), c(cam))
+    (vo * c(G)).sum().backward()
+    return [t.grad.numpy() for t in (bo, po, to)]
+
+
+def _hip_grads(layer, betas, pose, transl, cam, G):
+    bt, pt, tt = T(betas).requires_grad_(), T(pose).requires_grad_(), T(transl).requires_grad_()
+    v = body_model.lbs(layer.lbs_model, bt, pt, tt, T(cam))
+    v.backward(gradient=T(G))
+    return [t.grad.detach().cpu() for t in (bt, pt, tt)]
+
+
+def _spread_inputs(B, seed):
+    """Inputs of a batch whose upstream gradients span 14 decades: body b's is N(0, 1) r_b, r_b log-spaced from 1 down to 1e-14; the
+    two smallest bodies sit in the first body tile (body 0) and in the last, partial one (body B - 1)."""
+    rs = np.random.RandomState(seed)
+    betas = rs.standard_normal((B, 20)).astype(np.float32)
+    pose = (rs.standard_normal((B, 165)) * 0.5).astype(np.float32)
+    transl = rs.standard_normal((B, 3)).astype(np.float32)
+    cam = synth.make_cam_ext(B + 1, B)
+    r = 10.0 ** np.linspace(0.0, -14.0, B)
+    order = np.argsort(r)                                      # smallest first
+    perm = np.concatenate([[order[0]], rs.permutation(order[2:]), [order[1]]]) if B > 2 else order
+    r = r[perm]
+    G = (rs.standard_normal((B, 10475, 3)) * r[:, None, None]).astype(np.float32)
+    return betas, pose, transl, cam, G, r
+
+
+@pytest.mark.parametrize('B', [5, 32, 40, 70, 131])          # MT 1 / 2 / 4 blend variants, partial last tiles, 64-body tile pairs, >= 128: multi-body skinning
+def test_lbs_backward_per_body_under_a_magnitude_spread(layer, smplx_data, oracle_model, B):
+    """psi_lbs_backward over a batch whose bodies' upstream gradients differ by up to 1e14: every body's grad_betas / grad_pose /
+    grad_transl must be in the fp32 accuracy class ON ITS OWN SCALE (per_body.py) — the blend backward's fp16 split products take their
+    scale from the body's own rows, not from the batch's largest entry (which underflowed the small bodies' rows to zero in fp16)."""
+    betas, pose, transl, cam, G, r = _spread_inputs(B, 300 + B)
+    gmax = np.abs(G).reshape(B, -1).max(1)
+    assert gmax.max() / gmax.min() >= 1e12, gmax
+    assert r[0] == r.min() and (B < 3 or r[B - 1] == np.sort(r)[1])
+    got = _hip_grads(layer, betas, pose, transl, cam, G)
+    m64 = O.SMPLXOracle(smplx_data, dtype=torch.float64)
+    ref64 = _oracle_grads(m64, betas, pose, transl, cam, G, torch.float64)
+    ref32 = _oracle_grads(oracle_model, betas, pose, transl, cam, G, torch.float32)
+    for name, x, a, b in zip(('grad_betas', 'grad_pose', 'grad_transl'), got, ref64, ref32):
+        per_body.assert_per_body_accuracy_class(x.numpy(), a, b, '%s (B=%d)' % (name, B))
+
+
+@pytest.mark.parametrize('mode', ['x2^60', 'inf', 'nan'])
+def test_lbs_backward_bodies_are_isolated(layer, smplx_data, mode):
+    """Body isolation of psi_lbs_backward, bit for bit: changing ONE body's upstream rows (x 2^60, one entry +Inf, one entry NaN) leaves
+    every other body's grad_betas / grad_pose / grad_transl exactly as they were.  The changed body itself: non-finite gradients for an
+    Inf / NaN entry (never silently finite), and the per-body fp64 accuracy class for the x 2^60 rows."""
+    B = 40
+    rs = np.random.RandomState(41)
+    betas = rs.standard_normal((B, 20)).astype(np.float32)
+    pose = (rs.standard_normal((B, 165)) * 0.5).astype(np.float32)
+    transl = rs.standard_normal((B, 3)).astype(np.float32)
+    cam = synth.make_cam_ext(7, B)
+    G = rs.standard_normal((B, 10475, 3)).astype(np.float32)
+    base = _hip_grads(layer, betas, pose, transl, cam, G)
+    assert all(torch.isfinite(g).all() for g in base)
+    for j in (0, B // 2, B - 1):
+        G2 = G.copy()
+        if mode == 'x2^60':
+            G2[j] *= np.float32(2.0 ** 60)
+        else:
+            G2[j, 5000, 1] = np.inf if mode == 'inf' else np.nan
+        got = _hip_grads(layer, betas, pose, transl, cam, G2)
+        others = np.arange(B) != j
+        for name, a, b in zip(('grad_betas', 'grad_pose', 'grad_transl'), got, base):
+            assert torch.equal(a[others], b[others]), '%s of the other bodies changed with body %d (%s)' % (name, j, mode)
+        if mode == 'x2^60':
+            sl = slice(j, j + 1)
+            m64 = O.SMPLXOracle(smplx_data, dtype=torch.float64)
+            ref64 = _oracle_grads(m64, betas[sl], pose[sl], transl[sl], cam[sl], G2[sl], torch.float64)
+            ref32 = _oracle_grads(O.SMPLXOracle(smplx_data), betas[sl], pose[sl], transl[sl], cam[sl], G2[sl], torch.float32)
+            for name, x, a, b in zip(('grad_betas', 'grad_pose', 'grad_transl'), got, ref64, ref32):
+                per_body.assert_per_body_accuracy_class(x[sl].numpy(), a, b, '%s of body %d x 2^60' % (name, j))
+        else:
+            for name, a in zip(('grad_betas', 'grad_pose', 'grad_transl'), got):
+                assert not torch.isfinite(a[j]).all(), '%s of body %d is finite with a %s entry upstream' % (name, j, mode)
+
+
+@pytest.mark.parametrize('B', [40, 131])                     # >= 128: the multi-body skinning kernels
+@pytest.mark.parametrize('value', [float('nan'), 5000.0])
+def test_lbs_forward_bodies_are_isolated(layer, value, B):
+    """The forward half: one body's shape parameters set to NaN or to 5000 (the blend features saturate, lbs_device.h) leave every other
+    body's vertices bit for bit as they were.  (The dense skinning blend pads J to whole groups of 12 joints, and the rows under the padding
+    joints' zero weights are the next body's transforms: a NaN body used to turn its predecessor into NaN through 0 * NaN.)"""
+    rs = np.random.RandomState(43)
+    betas = rs.standard_normal((B, 20)).astype(np.float32)
+    pose = (rs.standard_normal((B, 165)) * 0.5).astype(np.float32)
+    transl = rs.standard_normal((B, 3)).astype(np.float32)
+    cam = synth.make_cam_ext(8, B)
+    base = body_model.lbs(layer.lbs_model, T(betas), T(pose), T(transl), T(cam)).clone()
+    for j in (0, B // 2, B - 1):
+        b2 = betas.copy()
+        b2[j] = value
+        v = body_model.lbs(layer.lbs_model, T(b2), T(pose), T(transl), T(cam))
+        others = torch.arange(B, device=DEV) != j
+        assert torch.equal(v[others], base[others]), 'body %d (betas = %g) changed the other bodies\' vertices' % (j, value)
