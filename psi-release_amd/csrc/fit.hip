@@ -64,7 +64,9 @@ extern "C" int psi_dbg_timeline(unsigned long long *out, int nblocks)
 #define PSI_SDF_CELLS 1      // the engine's copy of the SDF volume: 1 = cell-major records (two 16-byte gathers per sample), 0 = apron bricks (four 8-byte)
 #endif
 #include "nnindex_device.h"
+#include <initializer_list>
 #include <limits.h>
+#include <memory>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1521,6 +1523,158 @@ __global__ void adam_reset_kernel(float *m, float *v, int *step, int n)
 #endif
 constexpr int GRAPH_UNROLL = PSI_GRAPH_UNROLL;
 
+// ---- host-only state of an engine: development switches, launch plan, graph caches.  Plain data: the engine is zero-filled on allocation.
+// Every development switch of the engine, read ONCE per engine at psi_fit_create (README, "Environment knobs"); a value that is not
+// accepted leaves the default (0 in the int fields)
+struct FitKnobs {
+    bool split_scene, keep_verts, no_fused_bwd, sdf_linear, scene_skin_first, bwdv_mb;
+    int head_cluster, skin_nb, ska_nbody;
+#ifdef PSI_HEAD_STOPS
+    int head_stop, tail_stop, skin_stop;      // tools/head_stops.sh
+#endif
+};
+
+static FitKnobs fit_read_knobs()
+{
+    auto is = [](const char *name, char c) { const char *v = getenv(name); return v && v[0] == c; };
+    auto num = [](const char *name) { const char *v = getenv(name); return v ? atoi(v) : 0; };
+    FitKnobs k = {};
+    k.split_scene = is("PSI_SPLIT_SCENE", '1');
+    k.keep_verts = is("PSI_KEEP_VERTS", '1');
+    k.no_fused_bwd = is("PSI_FIT_FUSED_BWD", '0');
+    k.sdf_linear = is("PSI_SDF_LINEAR", '1');
+    k.scene_skin_first = is("PSI_SCENE_ORDER", '1');
+    k.bwdv_mb = is("PSI_BWDV_MB", '1');
+    const int hc = num("PSI_HEAD_CLUSTER");
+    if (hc == 1 || hc == 2 || hc == 4 || hc == 8) k.head_cluster = hc;
+    if (getenv("PSI_SKIN_NB")) k.skin_nb = num("PSI_SKIN_NB") == 2 ? 2 : 1;
+    k.ska_nbody = psi_ska_nbody_override(SKA_NBODY);
+#ifdef PSI_HEAD_STOPS
+    k.head_stop = num("PSI_HEAD_STOP");
+    k.tail_stop = num("PSI_TAIL_STOP");
+    k.skin_stop = num("PSI_SKIN_STOP");
+#endif
+    return k;
+}
+
+// Launch geometry of fit_bwd_joint_kernel: fixed by the model and the batch size, so derived once (fit_plan_make, at psi_fit_create)
+struct FitPlan {
+    int mt;                       // 16-body tiles per stream workgroup (the template instance)
+    int kgroups, n_blend;         // stream workgroups: kgroups x column slices of both row classes x body groups
+    int nbody, n_ska;             // bodies per skin_bwd_A workgroup; number of those workgroups
+};
+static FitPlan fit_plan_make(const FitDev &f, const LbsDev &m, int ska_nbody_override)
+{
+    FitPlan p;
+    p.kgroups = m.Kpad / 64;
+    p.mt = f.B > 32 ? 4 : (f.B > 16 ? 2 : 1);
+    p.n_blend = p.kgroups * (f.nsn_m + f.nsn_c) * psi_cdiv(f.B, 16 * p.mt);
+    // bodies per skin_bwd_A workgroup: about one such workgroup per CU beside its stream workgroup
+    const int nsl = f.nsv + f.nsv_c;
+    // (AT MOST one: the body groups are whole, so 32 bodies in groups of 6 are 6 groups, not 5.33 — 45 slices x 6 = 270 workgroups put two on
+    // 14 CUs and the launch waited for those: bwd_joint 37.6 us at n_c = 1024 against 28.4 at 2048)
+    int nbody = psi_cdiv((long)f.B * nsl, 256);
+    if (nbody < 1) nbody = 1;
+    while (nbody < SKA_NBODY && (long)nsl * psi_cdiv(f.B, nbody) > 256) nbody++;
+    p.nbody = psi_ska_nbody(nbody, SKA_NBODY, ska_nbody_override);
+    p.n_ska = nsl * psi_cdiv(f.B, p.nbody);
+    return p;
+}
+
+// One captured sequence of launches and its executable
+struct FitGraph { hipGraph_t g; hipGraphExec_t exec; bool ready; };
+
+// Refused: "cannot capture here" — the stream's capture was invalidated by a call that is illegal under capture (hipStreamEndCapture answers
+// in the hipErrorStreamCapture* range 900 .. 908), or RCCL declined the enqueue under capture without touching the stream (ncclInvalidArgument
+// / ncclInvalidUsage, returned synchronously by ncclAllReduce as 1000 + 4 / 1000 + 5: nothing was launched, the communicator is intact).  The
+// data-parallel loop answers it with eager launches.  Error: a genuine failure, with the message of the call that failed, to be PROPAGATED
+// (round 3 treated every failure as "cannot capture" and retried eagerly on a communicator that may already have been aborted, overwriting
+// the error).  A sequence without a collective is never refused for a reason other than a bug: psi_fit_iterate treats both as errors.
+struct FitCaptured {
+    enum Kind { Ok, Refused, Error } kind;
+    int rc;                       // the sequence's own error if it had one, otherwise the capture's
+};
+
+template <class Seq>
+static FitCaptured fit_graph_capture(FitGraph *G, hipStream_t st, Seq &&seq)
+{
+    auto failed = [](const char *what, hipError_t he) {
+        psi_set_error("%s failed: %s", what, hipGetErrorString(he));
+        return FitCaptured{FitCaptured::Error, (int)he};
+    };
+    if (!st) {
+        psi_set_error("invalid argument: graph capture needs a non-default stream");
+        return {FitCaptured::Error, PSI_EINVAL};
+    }
+    hipError_t he = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
+    if (he != hipSuccess) return failed("begin of the stream capture", he);
+    const int rc = seq();
+    hipGraph_t g = nullptr;
+    he = hipStreamEndCapture(st, &g);
+    if (!rc && he == hipSuccess) {
+        he = hipGraphInstantiate(&G->exec, g, nullptr, nullptr, 0);
+        if (he != hipSuccess) {
+            (void)hipGraphDestroy(g);
+            return failed("hipGraphInstantiate", he);
+        }
+        G->g = g;
+        G->ready = true;
+        return {FitCaptured::Ok, 0};
+    }
+    if (g) (void)hipGraphDestroy(g);
+    if (!rc) (void)failed("hipStreamEndCapture", he);
+    const bool refused = (he >= hipErrorStreamCaptureUnsupported && he <= hipErrorStreamCaptureWrongThread) || rc == 1000 + 4 || rc == 1000 + 5;
+    return {refused ? FitCaptured::Refused : FitCaptured::Error, rc ? rc : (int)he};
+}
+
+static int fit_graph_launch(const FitGraph &G, hipStream_t st)
+{
+    PSI_CHECK_HIP(hipGraphLaunch(G.exec, st));
+    return 0;
+}
+
+static void fit_graph_drop(FitGraph *G)
+{
+    if (G->ready) {
+        (void)hipGraphExecDestroy(G->exec);
+        (void)hipGraphDestroy(G->g);
+    }
+    *G = FitGraph{};
+}
+
+// Iterations done .. n_iter from graphs, the longest first: each tier is captured when first needed (tier.iters runs of `one`) and
+// replayed as often as it fits into what is left.  Launching a graph costs ~8 us on this stack (tools/ubench_graph.hip: 9.8 us for a
+// 1-kernel graph, +1.5-2.7 us per further kernel), i.e. 4 % of an iteration when every iteration is its own launch; the iteration has no
+// host-side state (step count, history and statistics live on the device), so a 100-iteration fit is a handful of launches of the
+// long graphs.  A capture that does not succeed ends the schedule with *done where it stood.
+struct FitGraphTier { int iters; FitGraph *graph; };
+
+template <class Seq>
+static FitCaptured fit_run_graphs(hipStream_t st, int n_iter, int *done, std::initializer_list<FitGraphTier> tiers, Seq &&one)
+{
+    for (const FitGraphTier &t : tiers) {
+        if (n_iter - *done < t.iters) continue;
+        if (!t.graph->ready) {
+            const FitCaptured c = fit_graph_capture(t.graph, st, [&]() {
+                int rc = 0;
+                for (int i = 0; i < t.iters && !rc; i++) rc = one();
+                return rc;
+            });
+            if (c.kind != FitCaptured::Ok) return c;
+        }
+        for (; *done + t.iters <= n_iter; *done += t.iters)
+            if (int rc = fit_graph_launch(*t.graph, st)) return {FitCaptured::Error, rc};
+    }
+    return {FitCaptured::Ok, 0};
+}
+
+enum {
+    FIT_G_ITER_1, FIT_G_ITER_N, FIT_G_ITER_2N,      // psi_fit_iterate: one iteration / GRAPH_UNROLL iterations / twice that
+    FIT_G_HALF_FWD, FIT_G_HALF_BWD,                 // psi_fit_forward / psi_fit_backward_step: the caller's all-reduce sits between the halves
+    FIT_G_DP_1, FIT_G_DP_N,                         // psi_fit_iterate_dp: whole iterations — forward, RCCL all-reduce, backward
+    FIT_N_GRAPHS
+};
+
 struct psi_fit_engine {
     FitDev d;
     PsiSdfGrid grid;              // sampling constants of the bricked SDF volume (sdf_device.h)
@@ -1531,25 +1685,16 @@ struct psi_fit_engine {
     void *nn_ws;
     char *blob;
     float *stats_local;           // engine-owned stats buffer (single-GPU path)
+    FitKnobs knobs;
+    FitPlan plan;
     bool merged_scene;            // skinning + SDF and the NN search in one launch (kd-tree mode, J <= 56, 4 lanes per query)
     bool self_skin;               // the NN search can skin its own contact vertices (ContactSkinSrc): it does not read `verts`
     bool keep_verts;              // the forward skinning kernel stores the camera-frame vertices (only needed when !self_skin)
-    bool scene_skin_first;        // block order inside that launch: skinning + SDF workgroups before the NN-search workgroups
     bool fused_bwd;               // the skinning backward rides on fwd_scene (see fit_bwd_joint_kernel): six launches per iteration, no per-vertex backward launch
     int skin_nb;                  // bodies per workgroup of the forward skinning + SDF kernel (1 or 2: lbs_device.h)
-    hipGraph_t graph, graphN, graph2N;     // one iteration / GRAPH_UNROLL iterations / twice that
-    hipGraphExec_t graph_exec, graphN_exec, graph2N_exec;
-    bool graph_ready, graphN_ready, graph2N_ready;
-    // data-parallel path: forward and backward halves captured separately (the all-reduce sits between them)
-    hipGraph_t g_half[2];
-    hipGraphExec_t ge_half[2];
-    bool half_ready[2];
+    FitGraph graphs[FIT_N_GRAPHS];
+    // the captured graphs bake the statistics pointer (and the data-parallel ones the communicator) in
     const float *half_stats[2];
-    // data-parallel path with the collective issued from C (psi_fit_iterate_dp): whole iterations — forward, RCCL all-reduce, backward —
-    // captured like the single-process graphs; the captured graphs bake the communicator and the statistics pointer in
-    hipGraph_t g_dp[2];           // [0] one iteration, [1] GRAPH_UNROLL iterations
-    hipGraphExec_t ge_dp[2];
-    bool dp_ready[2];
     const void *dp_comm;
     const float *dp_stats;
     bool dp_warm;                 // the communicator has run a collective for this engine outside capture
@@ -1580,18 +1725,40 @@ static void launch_head_bwd(const FitDev &f, const PsiLbsView &lv, float *g_out,
     }
 }
 
-// local: single-process iteration — the statistics are produced inside the backward's first kernel (no loss_finalize launch)
-// Single-process iterations fold the statistics into the first backward kernel (every workgroup re-derives the global
-// penetration count from the per-workgroup partials: no loss_finalize launch).  That re-derivation reads B * 41 partial pairs per
-// workgroup — O(B^2) in total — so from B = 128 on the separate one-workgroup statistics kernel is used instead.
-static inline bool fit_use_local_stats(const FitDev &f, bool local) { return local && f.B < PSI_SKIN_MB_MIN_B; }
+// Who turns the per-workgroup loss partials of the forward into the statistics (stats[0..5]) that the backward scales its gradients with:
+enum class FitStats {
+    Finalize,                     // loss_finalize_kernel, one workgroup launched at the end of the forward
+    Backward,                     // the first kernel of the backward: the statistics workgroup of fit_bwd_joint_kernel (fused_bwd), or every
+                                  // workgroup of the per-vertex backward re-deriving them from the partials (FitGradSource<true>)
+    Caller                        // neither: `stats` is complete when the backward starts (the caller all-reduced it between the two halves)
+};
 
-// finalize = false (fused_bwd only): the caller produces the statistics itself (the data-parallel loop does it on a side stream)
-static int fit_forward(psi_fit_engine *e, float *stats, hipStream_t st, bool local = false, bool finalize = true)
+// A call site asks; the engine decides.  The wish holds except for Backward on an engine without the fused backward at B >=
+// PSI_SKIN_MB_MIN_B: the per-vertex backward's re-derivation reads B * 41 partial pairs per workgroup — O(B^2) in total — so from B = 128 on
+// the separate one-workgroup kernel is used instead.
+//
+//   call site                                             wish       fused_bwd    !fused_bwd, B < 128    !fused_bwd, B >= 128
+//   psi_fit_iterate (eager, captured), psi_fit_profile    Backward   Backward     Backward               Finalize
+//   psi_fit_iterate_dp, fused sequence                    Backward   Backward     -                      -
+//   psi_fit_iterate_dp, unfused sequence                  Finalize   -            Finalize               Finalize
+//   psi_fit_forward                                       Finalize   Finalize     Finalize               Finalize
+//   psi_fit_backward_step                                 Caller     Caller       Caller                 Caller
+static inline FitStats fit_stats_source(const psi_fit_engine *e, FitStats wish)
+{
+    return wish == FitStats::Backward && !e->fused_bwd && e->d.B >= PSI_SKIN_MB_MIN_B ? FitStats::Finalize : wish;
+}
+
+static int fit_launch_stats(psi_fit_engine *e, float *stats, hipStream_t st)
+{
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1024), 0, st, e->d, stats);
+    PSI_CHECK_LAUNCH("loss_finalize_kernel");
+    psi_mark("loss_finalize_kernel", st);
+    return 0;
+}
+
+static int fit_forward(psi_fit_engine *e, float *stats, hipStream_t st, FitStats who)
 {
     FitDev &f = e->d;
-    // fused_bwd: a single-process iteration takes its statistics from the joint kernel's statistics workgroup at every batch size
-    local = e->fused_bwd ? (local || !finalize) : fit_use_local_stats(f, local);
     launch_head_fwd(f, e->lv, st);
     PSI_CHECK_LAUNCH("head_fwd_kernel");
     psi_mark("head_fwd_kernel", st);
@@ -1604,84 +1771,55 @@ static int fit_forward(psi_fit_engine *e, float *stats, hipStream_t st, bool loc
         const int nqb = f.nfp, n_kd = nqb * f.B;
         FitDev fk = f;
         if (!e->keep_verts) fk.verts = nullptr;
-        if (e->skin_nb == 2)
-            hipLaunchKernelGGL(fwd_scene_kernel<2>, dim3(n_kd + f.nsdfblk * psi_cdiv(f.B, 2)), dim3(256), psikd::kd_lds_bytes(T.rows), st, fk, e->lv.m,
-                               e->lv.A, e->lv.v_posed, T, n_kd, nqb, T.rows, gscale, e->scene_skin_first ? 1 : 0, make_sdf_epilogue(f, e->grid, false, e->fused_bwd ? &e->lv : nullptr));
-        else
-            hipLaunchKernelGGL(fwd_scene_kernel<1>, dim3(n_kd + f.nsdfblk * f.B), dim3(256), psikd::kd_lds_bytes(T.rows), st, fk, e->lv.m, e->lv.A,
-                               e->lv.v_posed, T, n_kd, nqb, T.rows, gscale, e->scene_skin_first ? 1 : 0, make_sdf_epilogue(f, e->grid, false, e->fused_bwd ? &e->lv : nullptr));
+#define PSI_LAUNCH_FWD_SCENE(NB_)                                                                                                              \
+    hipLaunchKernelGGL(fwd_scene_kernel<NB_>, dim3(n_kd + f.nsdfblk * psi_cdiv(f.B, NB_)), dim3(256), psikd::kd_lds_bytes(T.rows), st, fk, e->lv.m, \
+                       e->lv.A, e->lv.v_posed, T, n_kd, nqb, T.rows, gscale, e->knobs.scene_skin_first ? 1 : 0,                                \
+                       make_sdf_epilogue(f, e->grid, false, e->fused_bwd ? &e->lv : nullptr))
+        if (e->skin_nb == 2) PSI_LAUNCH_FWD_SCENE(2);
+        else PSI_LAUNCH_FWD_SCENE(1);
+#undef PSI_LAUNCH_FWD_SCENE
         PSI_CHECK_LAUNCH("fwd_scene_kernel");
         psi_mark("fwd_scene_kernel", st);
-        if (local) return 0;
-        hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1024), 0, st, f, stats);
-        PSI_CHECK_LAUNCH("loss_finalize_kernel");
-        psi_mark("loss_finalize_kernel", st);
-        return 0;
+    } else {
+        // (Round 3 tried the dense blend of this kernel on the matrix cores at large batches — v_mfma_f32_16x16x4_f32 tiles of 16 vertices with
+        // the weights as the register-resident B operand and a body's transforms as the LDS-staged A operand, bit-identical results — on the
+        // grounds that the kernel is vector-ALU bound at B = 512 (805 VALU instructions per wave, 660 of them the blend; profiles/
+        // r03_pmc_skin_fwd_sdf_b512.txt).  It measured 191 us against 165: the fp32 MFMA runs at the vector FLOP rate and, as far as these timings
+        // show, does not overlap the other waves' vector instructions, so the blend's cycles moved but did not disappear.)
+        // separate launches (large batches): the search reads its contact vertices from `verts` — letting its lane groups skin them
+        // themselves, as in the shared launch, measured 157 us against 113 for the search at B = 512 — so the skinning kernel stores those
+        // rows, and ONLY those (2048 of 10475: the rest of the 64 MB was written for nobody; PSI_KEEP_VERTS=1 stores all of them)
+        const bool all_verts = !e->nn_index || e->knobs.keep_verts;
+#define PSI_LAUNCH_SKIN_FWD(NB_)                                                                                                               \
+    hipLaunchKernelGGL((psi_skin_fwd_kernel<SdfPenEpilogue, NB_>), dim3(f.nsdfblk, psi_cdiv(f.B, NB_)), dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A, \
+                       e->lv.v_posed, f.transl, f.cam, f.B, f.verts, make_sdf_epilogue(f, e->grid, !all_verts))
+        if (e->skin_nb == 2) PSI_LAUNCH_SKIN_FWD(2);
+        else PSI_LAUNCH_SKIN_FWD(1);
+#undef PSI_LAUNCH_SKIN_FWD
+        PSI_CHECK_LAUNCH("skin_fwd_sdf_kernel");
+        psi_mark("skin_fwd_sdf_kernel", st);
+        if (e->nn_index && !all_verts)                               // the contact rows in slot order: query j is row j
+            rc = psi_nn_index_contact(e->nn_index, f.cverts, (long)f.n_c * 3, nullptr, f.B, f.n_c, f.cconst, gscale, f.gq, f.fpart, f.nn_hint, st);
+        else if (e->nn_index)
+            rc = psi_nn_index_contact(e->nn_index, f.verts, (long)f.V * 3, f.vid, f.B, f.n_c, f.cconst, gscale, f.gq, f.fpart, f.nn_hint, st);
+        else
+            rc = psi_nn_contact(f.verts, (long)f.V * 3, f.vid, f.scene, f.B, f.n_c, f.m, e->nn_ws, f.cconst, gscale, f.gq, f.fpart, nullptr, st);
+        if (rc) return rc;
     }
-    // (Round 3 tried the dense blend of this kernel on the matrix cores at large batches — v_mfma_f32_16x16x4_f32 tiles of 16 vertices with
-    // the weights as the register-resident B operand and a body's transforms as the LDS-staged A operand, bit-identical results — on the
-    // grounds that the kernel is vector-ALU bound at B = 512 (805 VALU instructions per wave, 660 of them the blend; profiles/
-    // r03_pmc_skin_fwd_sdf_b512.txt).  It measured 191 us against 165: the fp32 MFMA runs at the vector FLOP rate and, as far as these timings
-    // show, does not overlap the other waves' vector instructions, so the blend's cycles moved but did not disappear.)
-    // separate launches (large batches): the search reads its contact vertices from `verts` — letting its lane groups skin them
-    // themselves, as in the shared launch, measured 157 us against 113 for the search at B = 512 — so the skinning kernel stores those
-    // rows, and ONLY those (2048 of 10475: the rest of the 64 MB was written for nobody; PSI_KEEP_VERTS=1 stores all of them)
-    const bool all_verts = !e->nn_index || (getenv("PSI_KEEP_VERTS") && getenv("PSI_KEEP_VERTS")[0] == '1');
-    if (e->skin_nb == 2)
-        hipLaunchKernelGGL((psi_skin_fwd_kernel<SdfPenEpilogue, 2>), dim3(f.nsdfblk, psi_cdiv(f.B, 2)), dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A,
-                           e->lv.v_posed, f.transl, f.cam, f.B, f.verts, make_sdf_epilogue(f, e->grid, !all_verts));
-    else
-        hipLaunchKernelGGL((psi_skin_fwd_kernel<SdfPenEpilogue, 1>), dim3(f.nsdfblk, f.B), dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A,
-                           e->lv.v_posed, f.transl, f.cam, f.B, f.verts, make_sdf_epilogue(f, e->grid, !all_verts));
-    PSI_CHECK_LAUNCH("skin_fwd_sdf_kernel");
-    psi_mark("skin_fwd_sdf_kernel", st);
-    if (e->nn_index && !all_verts)                               // the contact rows in slot order: query j is row j
-        rc = psi_nn_index_contact(e->nn_index, f.cverts, (long)f.n_c * 3, nullptr, f.B, f.n_c, f.cconst, gscale, f.gq, f.fpart, f.nn_hint, st);
-    else if (e->nn_index)
-        rc = psi_nn_index_contact(e->nn_index, f.verts, (long)f.V * 3, f.vid, f.B, f.n_c, f.cconst, gscale, f.gq, f.fpart, f.nn_hint, st);
-    else
-        rc = psi_nn_contact(f.verts, (long)f.V * 3, f.vid, f.scene, f.B, f.n_c, f.m, e->nn_ws, f.cconst, gscale, f.gq, f.fpart, nullptr, st);
-    if (rc) return rc;
-    if (local) return 0;
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1024), 0, st, f, stats);
-    PSI_CHECK_LAUNCH("loss_finalize_kernel");
-    psi_mark("loss_finalize_kernel", st);
-    return 0;
+    return fit_stats_source(e, who) == FitStats::Finalize ? fit_launch_stats(e, stats, st) : 0;
 }
 
-static int fit_launch_stats(psi_fit_engine *e, float *stats, hipStream_t st)
-{
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1024), 0, st, e->d, stats);
-    PSI_CHECK_LAUNCH("loss_finalize_kernel");
-    psi_mark("loss_finalize_kernel", st);
-    return 0;
-}
-
-// fused_bwd: the joint-side contractions over both classes of rows (+ the statistics workgroup when `local`); the rest of the backward
-// (fit_backward_tail) needs the FINAL statistics
-static int fit_backward_joint(psi_fit_engine *e, float *stats, hipStream_t st, bool local)
+// fused_bwd: the joint-side contractions over both classes of rows (+ the statistics workgroup for FitStats::Backward); the rest of the
+// backward (fit_backward_tail) needs the FINAL statistics
+static int fit_backward_joint(psi_fit_engine *e, float *stats, hipStream_t st, FitStats who)
 {
     FitDev &f = e->d;
-    const LbsDev &m = e->lv.m;
-    const int kgroups = m.Kpad / 64;
-    const int mt = f.B > 32 ? 4 : (f.B > 16 ? 2 : 1);
-    const int bgroups = psi_cdiv(f.B, 16 * mt);
-    const int n_blend = kgroups * (f.nsn_m + f.nsn_c) * bgroups;
-    // bodies per skin_bwd_A workgroup: about one such workgroup per CU beside its stream workgroup
-    const int nsl = f.nsv + f.nsv_c;
-    // (AT MOST one: the body groups are whole, so 32 bodies in groups of 6 are 6 groups, not 5.33 — 45 slices x 6 = 270 workgroups put two on
-    // 14 CUs and the launch waited for those: bwd_joint 37.6 us at n_c = 1024 against 28.4 at 2048)
-    int nbody = psi_cdiv((long)f.B * nsl, 256);
-    if (nbody < 1) nbody = 1;
-    while (nbody < SKA_NBODY && (long)nsl * psi_cdiv(f.B, nbody) > 256) nbody++;
-    if (nbody > SKA_NBODY) nbody = SKA_NBODY;
-    if (const char *ev = getenv("PSI_SKA_NBODY")) { int v = atoi(ev); if (v >= 1 && v <= SKA_NBODY) nbody = v; }
-    const int n_ska = nsl * psi_cdiv(f.B, nbody);
-    const dim3 grid(n_ska + n_blend + (local ? 1 : 0));
+    const FitPlan &p = e->plan;
+    const dim3 grid(p.n_ska + p.n_blend + (fit_stats_source(e, who) == FitStats::Backward ? 1 : 0));
 #define PSI_LAUNCH_FIT_JOINT(MT_)                                                                                                  \
-    hipLaunchKernelGGL(fit_bwd_joint_kernel<MT_>, grid, dim3(256), 0, st, f, m, e->lv.g_vp, e->lv.gl, e->lv.v_posed, n_ska, n_blend, kgroups, nbody, stats)
-    if (mt == 4) PSI_LAUNCH_FIT_JOINT(4);
-    else if (mt == 2) PSI_LAUNCH_FIT_JOINT(2);
+    hipLaunchKernelGGL(fit_bwd_joint_kernel<MT_>, grid, dim3(256), 0, st, f, e->lv.m, e->lv.g_vp, e->lv.gl, e->lv.v_posed, p.n_ska, p.n_blend, p.kgroups, p.nbody, stats)
+    if (p.mt == 4) PSI_LAUNCH_FIT_JOINT(4);
+    else if (p.mt == 2) PSI_LAUNCH_FIT_JOINT(2);
     else PSI_LAUNCH_FIT_JOINT(1);
 #undef PSI_LAUNCH_FIT_JOINT
     PSI_CHECK_LAUNCH("fit_bwd_joint_kernel");
@@ -1702,34 +1840,32 @@ static int fit_backward_tail(psi_fit_engine *e, float *stats, hipStream_t st)
     return 0;
 }
 
-static int fit_backward(psi_fit_engine *e, float *stats, hipStream_t st, bool local = false)
+static int fit_backward(psi_fit_engine *e, float *stats, hipStream_t st, FitStats who)
 {
     FitDev &f = e->d;
     if (e->fused_bwd) {
-        int rc = fit_backward_joint(e, stats, st, local);
+        int rc = fit_backward_joint(e, stats, st, who);
         return rc ? rc : fit_backward_tail(e, stats, st);
     }
-    local = fit_use_local_stats(f, local);
     // large batches: compressed rows keep the multi-body kernel (a lane's weights in registers, eight bodies per workgroup); DENSE rows
     // take one body per workgroup with the pipelined scalar-cache blend — the multi-body kernel reads the transforms as LDS broadcasts
     // and is bound by the LDS return path with 55-joint rows (PSI_BWDV_MB=1: the multi-body kernel for dense rows too)
-    static const bool dense_mb = getenv("PSI_BWDV_MB") && getenv("PSI_BWDV_MB")[0] == '1';
     const bool big = f.B >= PSI_SKIN_MB_MIN_B;
-    const bool mb = big && (e->lv.m.Wc || dense_mb);
+    const bool mb = big && (e->lv.m.Wc || e->knobs.bwdv_mb);
     const dim3 bgrid(f.nsdfblk, mb ? psi_cdiv(f.B, PSI_SKIN_MB) : f.B);
-    if (local && mb)
-        psi_launch_skin_bwd_v_mb(e->lv.m, e->lv.A, FitGradSource<true>{f, stats, 0.0f, nullptr, 0, {}, false}, f.cam, f.B, e->lv.gl, e->lv.g_vp, e->lv.gt_part_w, st);
-    else if (local)
-        hipLaunchKernelGGL(psi_skin_bwd_v_kernel<FitGradSource<true>>, bgrid, dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A,
-                           FitGradSource<true>{f, stats, 0.0f, nullptr, 0, {}, false}, f.cam, f.B, e->lv.gl, e->lv.g_vp, e->lv.gt_part_w);
-    else if (mb)
-        psi_launch_skin_bwd_v_mb(e->lv.m, e->lv.A, FitGradSource<false>{f, stats, 0.0f, nullptr, 0, {}, false}, f.cam, f.B, e->lv.gl, e->lv.g_vp, e->lv.gt_part_w, st);
-    else if (big)
-        hipLaunchKernelGGL((psi_skin_bwd_v_kernel<FitGradSource<false>, PsiBlendPipelined>), bgrid, dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A,
-                           FitGradSource<false>{f, stats, 0.0f, nullptr, 0, {}, false}, f.cam, f.B, e->lv.gl, e->lv.g_vp, e->lv.gt_part_w);
-    else
-        hipLaunchKernelGGL(psi_skin_bwd_v_kernel<FitGradSource<false>>, bgrid, dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A,
-                           FitGradSource<false>{f, stats, 0.0f, nullptr, 0, {}, false}, f.cam, f.B, e->lv.gl, e->lv.g_vp, e->lv.gt_part_w);
+#define PSI_LAUNCH_BWD_V(...)                                                                                                      \
+    hipLaunchKernelGGL((psi_skin_bwd_v_kernel<__VA_ARGS__>), bgrid, dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A, src, f.cam, f.B, e->lv.gl, e->lv.g_vp, e->lv.gt_part_w)
+    if (fit_stats_source(e, who) == FitStats::Backward) {
+        const FitGradSource<true> src{f, stats, 0.0f, nullptr, 0, {}, false};
+        if (mb) psi_launch_skin_bwd_v_mb(e->lv.m, e->lv.A, src, f.cam, f.B, e->lv.gl, e->lv.g_vp, e->lv.gt_part_w, st);
+        else PSI_LAUNCH_BWD_V(FitGradSource<true>);
+    } else {
+        const FitGradSource<false> src{f, stats, 0.0f, nullptr, 0, {}, false};
+        if (mb) psi_launch_skin_bwd_v_mb(e->lv.m, e->lv.A, src, f.cam, f.B, e->lv.gl, e->lv.g_vp, e->lv.gt_part_w, st);
+        else if (big) PSI_LAUNCH_BWD_V(FitGradSource<false>, PsiBlendPipelined);
+        else PSI_LAUNCH_BWD_V(FitGradSource<false>);
+    }
+#undef PSI_LAUNCH_BWD_V
     PSI_CHECK_LAUNCH("skin_bwd_v_grad_kernel");
     psi_mark("skin_bwd_v_grad_kernel", st);
     int rc = psi_lbs_backward_joint_parts(e->lbs, f.B, e->lbs_ws, f.g_transl, st);
@@ -1753,16 +1889,20 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
     PSI_REQUIRE(J == 55 && NB >= 10 && NB <= 32, "the fused engine is SMPL-X shaped (J=55, 10..32 betas)");
     PSI_REQUIRE(cfg->B > 0 && cfg->n_contact > 0 && cfg->n_contact < (1 << 24) && cfg->m_scene > 0 && cfg->D >= 2 && cfg->world_size >= 1, "bad sizes");
     PSI_REQUIRE(cfg->num_pca_comps > 0 && cfg->num_pca_comps <= 12, "1..12 hand PCA components");
+    PSI_REQUIRE(!(cfg->independent_bodies && cfg->world_size > 1), "independent bodies have no cross-rank coupling: use world_size 1");
     for (int i = 0; i < 66; i++) PSI_REQUIRE(h_pose_mean[i] == 0.0f, "pose_mean must be zero for global_orient/body joints");
     for (int i = 0; i < cfg->n_contact; i++) PSI_REQUIRE(h_contact_ids[i] >= 0 && h_contact_ids[i] < V, "contact id out of range");
     psi_fit_engine *e = new psi_fit_engine;
     memset(e, 0, sizeof(*e));
+    // the one way out of every failure below: psi_fit_destroy copes with each partially built engine (no blob yet; blob but no NN index)
+    // and sets no error message of its own, so the caller reads the failing call's
+    std::unique_ptr<psi_fit_engine, void (*)(psi_fit_engine *)> owner(e, psi_fit_destroy);
+    const FitKnobs &knobs = e->knobs = fit_read_knobs();
     e->lbs = lbs;
     FitDev &f = e->d;
     f.B = cfg->B; f.V = V; f.J = J; f.NB = NB; f.n_c = cfg->n_contact; f.m = cfg->m_scene; f.D = cfg->D;
     f.align_corners = cfg->align_corners; f.world = cfg->world_size; f.ncomp = cfg->num_pca_comps;
     f.indep = cfg->independent_bodies ? 1 : 0;
-    PSI_REQUIRE(!(f.indep && cfg->world_size > 1), "independent bodies have no cross-rank coupling: use world_size 1");
     f.w_rec = cfg->w_rec; f.w_vp = cfg->w_vposer; f.w_contact = cfg->w_contact; f.w_col = cfg->w_collision; f.cconst = cfg->contact_const;
     f.lr = cfg->lr; f.beta1 = cfg->beta1; f.beta2 = cfg->beta2; f.eps = cfg->eps;
     // the hyper-parameters as the doubles the caller's optimiser holds (0: only the fp32 fields were filled in)
@@ -1777,11 +1917,11 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
     // its own 256 vertices from LDS after the SDF lookup: 1312 workgroups = one occupancy round instead of two, no second skinning of the
     // query vertices.  It measured 42 us against 33: the search became a serial tail of every workgroup instead of running beside them.)
     e->self_skin = cfg->nn_mode == 1 && J <= PSI_JP - 8 && psikd::LPQ == 4;      // the search lanes can skin their own contact vertex
-    e->merged_scene = e->self_skin && cfg->B <= 128 && !(getenv("PSI_SPLIT_SCENE") && getenv("PSI_SPLIT_SCENE")[0] == '1');
+    e->merged_scene = e->self_skin && cfg->B <= 128 && !knobs.split_scene;
     // the vertices themselves are an output nobody reads when the search skins its own queries (the shared launch): not stored there
     // (psi_fit_copy_buffer("verts") produces them on demand); with separate launches the search reads its contact rows, which are the
     // only ones stored (fit_forward); PSI_KEEP_VERTS=1 stores all of them in every iteration
-    e->keep_verts = !e->merged_scene || (getenv("PSI_KEEP_VERTS") && getenv("PSI_KEEP_VERTS")[0] == '1');
+    e->keep_verts = !e->merged_scene || knobs.keep_verts;
     f.nsdfblk = psi_cdiv(V, 256);
     f.Vpad = f.nsdfblk * 256;
     f.nfp = cfg->nn_mode == 1 ? psi_nn_index_fparts(f.n_c) : psi_nn_contact_fparts(f.n_c);
@@ -1792,18 +1932,12 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
         f.hc = bodies <= 32 ? 8 : bodies <= 64 ? 4 : bodies <= 128 ? 2 : 1;
     }
 #ifdef PSI_HEAD_STOPS
-    f.stop_h = getenv("PSI_HEAD_STOP") ? atoi(getenv("PSI_HEAD_STOP")) : 0;
-    f.stop_t = getenv("PSI_TAIL_STOP") ? atoi(getenv("PSI_TAIL_STOP")) : 0;
-    {
-        int sst = getenv("PSI_SKIN_STOP") ? atoi(getenv("PSI_SKIN_STOP")) : 0;
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(psi_dbg_sstop), &sst, sizeof(int));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(psi_dbg_pstop), &f.stop_t, sizeof(int));
-    }
+    f.stop_h = knobs.head_stop;
+    f.stop_t = knobs.tail_stop;
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(psi_dbg_sstop), &knobs.skin_stop, sizeof(int));
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(psi_dbg_pstop), &f.stop_t, sizeof(int));
 #endif
-    if (const char *hcv = getenv("PSI_HEAD_CLUSTER")) {
-        const int v = atoi(hcv);
-        if (v == 1 || v == 2 || v == 4 || v == 8) f.hc = v;
-    }
+    if (knobs.head_cluster) f.hc = knobs.head_cluster;
     f.scene = d_scene_verts;
     f.sdf = d_sdf;
     const int B = f.B;
@@ -1843,7 +1977,7 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
     size_t o_hxo = take((size_t)B * f.hc * 128 * 8), o_hxg = take((size_t)B * f.hc * NH * 8), o_hxc = take((size_t)2 * B * 4);
     size_t o_wct = take((size_t)f.n_c * PSI_JP * 4);
     // the contact slots as a second class of rows of the joint-side contractions (fused_bwd)
-    e->fused_bwd = e->merged_scene && !(getenv("PSI_FIT_FUSED_BWD") && getenv("PSI_FIT_FUSED_BWD")[0] == '0');
+    e->fused_bwd = e->merged_scene && !knobs.no_fused_bwd;
     f.fused_bwd = e->fused_bwd ? 1 : 0;
     f.ncp = psi_cdiv(f.n_c, 256) * 256;
     f.ncp3 = 3 * f.ncp;
@@ -1855,7 +1989,7 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
     {
         // slice counts of the model's own rows: from the LBS workspace layout (offsets only: no memory is touched through this view)
         PsiLbsView lv0;
-        if (int rcv = psi_lbs_view(lbs, B, reinterpret_cast<float *>((uintptr_t)4096), &lv0)) { delete e; return rcv; }
+        if (int rcv = psi_lbs_view(lbs, B, reinterpret_cast<float *>((uintptr_t)4096), &lv0)) return rcv;
         const int Kpad = lv0.m.Kpad, Npad = lv0.m.Npad, nsn = lv0.nsn;
         const int SM = Npad / 16, SC = f.ncp3 / 16;
         f.nsv = lv0.nsv;
@@ -1879,7 +2013,7 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
         }
     }
     // (the bricked copy is addressed with 32-bit byte offsets: 512 bytes x (D / 4)^3 must stay below 4 GB, D <= 800)
-    const bool bricks = (cfg->D % 4 == 0) && cfg->D <= (PSI_SDF_CELLS ? 480 : 800) && !(getenv("PSI_SDF_LINEAR") && getenv("PSI_SDF_LINEAR")[0] == '1');
+    const bool bricks = (cfg->D % 4 == 0) && cfg->D <= (PSI_SDF_CELLS ? 480 : 800) && !knobs.sdf_linear;
 #if PSI_SDF_CELLS
     size_t o_brick = bricks ? take((size_t)f.D * f.D * f.D * 32) : 0;             // D <= 480 keeps the byte offsets below 4 GB
 #else
@@ -1889,7 +2023,6 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
     size_t o_lws = take(lbs_floats * 4), o_nws = take(psi_nn_ws_bytes(B, f.n_c, f.m));
     hipError_t err = hipMalloc((void **)&e->blob, o);
     if (err != hipSuccess) {
-        delete e;
         psi_set_error("psi_fit_create: hipMalloc(%zu) failed: %s", o, hipGetErrorString(err));
         return (int)err;
     }
@@ -1898,8 +2031,6 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
     for (auto &it : items)
         if (err == hipSuccess) err = hipMemcpy(e->blob + it.off, it.src, it.bytes, hipMemcpyHostToDevice);
     if (err != hipSuccess) {
-        (void)hipFree(e->blob);
-        delete e;
         psi_set_error("psi_fit_create: upload failed: %s", hipGetErrorString(err));
         return (int)err;
     }
@@ -1918,21 +2049,18 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
     f.hx_o6 = (unsigned long long *)(bl + o_hxo); f.hx_gh1 = (unsigned long long *)(bl + o_hxg); f.hx_epoch = (unsigned *)(bl + o_hxc);
     e->stats_local = F(o_stats);
     e->lbs_ws = F(o_lws);
-    {
-        int rcv = psi_lbs_view(lbs, B, e->lbs_ws, &e->lv);
-        if (rcv) { (void)hipFree(e->blob); delete e; return rcv; }
-    }
+    if (int rcv = psi_lbs_view(lbs, B, e->lbs_ws, &e->lv)) return rcv;
+    e->plan = fit_plan_make(f, e->lv.m, knobs.ska_nbody);
     f.Wct = F(o_wct);
     if (e->fused_bwd) {
         f.glc = F(o_glc); f.gvpc = F(o_gvpc); f.vpc = F(o_vpc); f.gtc_part = F(o_gtc); f.WTt_c = F(o_wttc); f.dirs_ch = F(o_dirsc); f.gvbits = (unsigned *)(bl + o_gvb);
         f.gA_part = F(o_gap); f.gfeat_part = F(o_gfp); f.spb = F(o_spb);
     }
-    e->scene_skin_first = getenv("PSI_SCENE_ORDER") && getenv("PSI_SCENE_ORDER")[0] == '1';
     // two bodies per skinning workgroup share one pass over the vertex's weight row: from the batch size at which the kernel is
     // throughput-bound (its own launch, B > 128); PSI_SKIN_NB=1|2 overrides
     // (compressed rows are read once per lane either way and measured 2-3 % slower with two bodies: 114.7 vs 112.3 us at B = 512)
     e->skin_nb = cfg->B > 128 && !e->lv.m.Wc ? 2 : 1;
-    if (const char *nbv = getenv("PSI_SKIN_NB")) e->skin_nb = atoi(nbv) == 2 ? 2 : 1;
+    if (knobs.skin_nb) e->skin_nb = knobs.skin_nb;
     hipLaunchKernelGGL(contact_weight_table_kernel, dim3(psi_cdiv((long)f.n_c * PSI_JP, 256)), dim3(256), 0, 0, e->lv.m.WT, e->lv.m.Vpad, f.vid,
                        f.n_c, J, (float *)f.Wct);
     if (e->fused_bwd) {
@@ -1955,8 +2083,6 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
     err = hipDeviceSynchronize();                                // the two one-off layout kernels above ran on the NULL stream
     if (err == hipSuccess) err = hipGetLastError();
     if (err != hipSuccess) {
-        (void)hipFree(e->blob);
-        delete e;
         psi_set_error("psi_fit_create: layout kernels failed: %s", hipGetErrorString(err));
         return (int)err;
     }
@@ -1964,13 +2090,9 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
     if (cfg->nn_mode == 1) {
         std::vector<float> hs((size_t)f.m * 3);
         err = hipMemcpy(hs.data(), d_scene_verts, hs.size() * 4, hipMemcpyDeviceToHost);
-        int rc = err == hipSuccess ? psi_nn_index_create(&e->nn_index, hs.data(), f.m) : (int)err;
-        if (rc) {
-            (void)hipFree(e->blob);
-            delete e;
-            return rc;
-        }
+        if (int rc = err == hipSuccess ? psi_nn_index_create(&e->nn_index, hs.data(), f.m) : (int)err) return rc;
     }
+    owner.release();
     *out = e;
     return 0;
 }
@@ -1979,28 +2101,7 @@ extern "C" void psi_fit_destroy(psi_fit_engine *e)
 {
     if (!e) return;
     if (e->nn_index) psi_nn_index_destroy(e->nn_index);
-    if (e->graph_ready) {
-        (void)hipGraphExecDestroy(e->graph_exec);
-        (void)hipGraphDestroy(e->graph);
-    }
-    if (e->graphN_ready) {
-        (void)hipGraphExecDestroy(e->graphN_exec);
-        (void)hipGraphDestroy(e->graphN);
-    }
-    if (e->graph2N_ready) {
-        (void)hipGraphExecDestroy(e->graph2N_exec);
-        (void)hipGraphDestroy(e->graph2N);
-    }
-    for (int i = 0; i < 2; i++) {
-        if (e->half_ready[i]) {
-            (void)hipGraphExecDestroy(e->ge_half[i]);
-            (void)hipGraphDestroy(e->g_half[i]);
-        }
-        if (e->dp_ready[i]) {
-            (void)hipGraphExecDestroy(e->ge_dp[i]);
-            (void)hipGraphDestroy(e->g_dp[i]);
-        }
-    }
+    for (FitGraph &G : e->graphs) fit_graph_drop(&G);
     (void)hipFree(e->blob);
     delete e;
 }
@@ -2024,27 +2125,25 @@ extern "C" int psi_fit_set_problem(psi_fit_engine *e, const float *d_xhr, const 
     return 0;
 }
 
+// one single-process iteration (psi_fit_iterate, psi_fit_profile)
+static int fit_iteration(psi_fit_engine *e, hipStream_t st)
+{
+    int rc = fit_forward(e, e->stats_local, st, FitStats::Backward);
+    return rc ? rc : fit_backward(e, e->stats_local, st, FitStats::Backward);
+}
+
 static int fit_half(psi_fit_engine *e, int which, float *stats, int use_graph, hipStream_t st)
 {
-    if (!use_graph) return which == 0 ? fit_forward(e, stats, st) : fit_backward(e, stats, st);
-    if (e->half_ready[which] && e->half_stats[which] != stats) {       // the captured graph bakes the stats pointer in
-        (void)hipGraphExecDestroy(e->ge_half[which]);
-        (void)hipGraphDestroy(e->g_half[which]);
-        e->half_ready[which] = false;
-    }
-    if (!e->half_ready[which]) {
-        PSI_REQUIRE(st != nullptr, "graph capture needs a non-default stream");
-        PSI_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-        int rc = which == 0 ? fit_forward(e, stats, st) : fit_backward(e, stats, st);
-        hipError_t ce = hipStreamEndCapture(st, &e->g_half[which]);
-        if (rc) return rc;
-        PSI_CHECK_HIP(ce);
-        PSI_CHECK_HIP(hipGraphInstantiate(&e->ge_half[which], e->g_half[which], nullptr, nullptr, 0));
-        e->half_ready[which] = true;
+    auto half = [&]() { return which == 0 ? fit_forward(e, stats, st, FitStats::Finalize) : fit_backward(e, stats, st, FitStats::Caller); };
+    if (!use_graph) return half();
+    FitGraph *G = &e->graphs[FIT_G_HALF_FWD + which];
+    if (G->ready && e->half_stats[which] != stats) fit_graph_drop(G);       // the captured graph bakes the stats pointer in
+    if (!G->ready) {
+        const FitCaptured c = fit_graph_capture(G, st, half);
+        if (c.kind != FitCaptured::Ok) return c.rc;
         e->half_stats[which] = stats;
     }
-    PSI_CHECK_HIP(hipGraphLaunch(e->ge_half[which], st));
-    return 0;
+    return fit_graph_launch(*G, st);
 }
 
 extern "C" int psi_fit_forward(psi_fit_engine *e, float *d_stats, int use_graph, void *stream)
@@ -2064,59 +2163,16 @@ extern "C" int psi_fit_iterate(psi_fit_engine *e, int n_iter, int use_graph, voi
     PSI_REQUIRE(e && n_iter >= 0, "bad arguments");
     PSI_REQUIRE(e->d.world == 1, "psi_fit_iterate is the single-process path; data-parallel runs call forward / all-reduce / backward_step");
     hipStream_t st = (hipStream_t)stream;
+    auto one = [&]() { return fit_iteration(e, st); };
+    int done = 0, rc = 0;
     if (!use_graph) {
-        for (int i = 0; i < n_iter; i++) {
-            int rc = fit_forward(e, e->stats_local, st, true);
-            if (rc) return rc;
-            rc = fit_backward(e, e->stats_local, st, true);
-            if (rc) return rc;
-        }
-        return 0;
+        for (; done < n_iter && !rc; done++) rc = one();
+        return rc;
     }
-    // Two graphs: one iteration, and GRAPH_UNROLL iterations back to back.  Launching a graph costs ~8 us on this stack
-    // (tools/ubench_graph.hip: 9.8 us for a 1-kernel graph, +1.5-2.7 us per further kernel), i.e. 4 % of an iteration when every
-    // iteration is its own launch; the iteration has no host-side state (step count, history and statistics live on the
-    // device), so a 100-iteration fit is 10 launches of the long graph.
-    auto capture = [&](int iters, hipGraph_t *g, hipGraphExec_t *ge) -> int {
-        PSI_REQUIRE(st != nullptr, "graph capture needs a non-default stream");
-        PSI_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-        int rc = 0;
-        for (int i = 0; i < iters && !rc; i++) {
-            rc = fit_forward(e, e->stats_local, st, true);
-            if (!rc) rc = fit_backward(e, e->stats_local, st, true);
-        }
-        hipError_t ce = hipStreamEndCapture(st, g);
-        if (rc) return rc;
-        PSI_CHECK_HIP(ce);
-        PSI_CHECK_HIP(hipGraphInstantiate(ge, *g, nullptr, nullptr, 0));
-        return 0;
-    };
-    int done = 0;
     // (a call of 2 GRAPH_UNROLL iterations or more — the reference's 100-iteration loop, the bench's 20-step blocks — takes the long graph
     // first: one launch per 20 iterations instead of two, 0.1115 -> 0.1111 ms per iteration, A/B on one box)
-    if (n_iter >= 2 * GRAPH_UNROLL) {
-        if (!e->graph2N_ready) {
-            int rc = capture(2 * GRAPH_UNROLL, &e->graph2N, &e->graph2N_exec);
-            if (rc) return rc;
-            e->graph2N_ready = true;
-        }
-        for (; done + 2 * GRAPH_UNROLL <= n_iter; done += 2 * GRAPH_UNROLL) PSI_CHECK_HIP(hipGraphLaunch(e->graph2N_exec, st));
-    }
-    if (n_iter - done >= GRAPH_UNROLL) {
-        if (!e->graphN_ready) {
-            int rc = capture(GRAPH_UNROLL, &e->graphN, &e->graphN_exec);
-            if (rc) return rc;
-            e->graphN_ready = true;
-        }
-        for (; done + GRAPH_UNROLL <= n_iter; done += GRAPH_UNROLL) PSI_CHECK_HIP(hipGraphLaunch(e->graphN_exec, st));
-    }
-    if (done < n_iter && !e->graph_ready) {
-        int rc = capture(1, &e->graph, &e->graph_exec);
-        if (rc) return rc;
-        e->graph_ready = true;
-    }
-    for (; done < n_iter; done++) PSI_CHECK_HIP(hipGraphLaunch(e->graph_exec, st));
-    return 0;
+    return fit_run_graphs(st, n_iter, &done,
+                          {{2 * GRAPH_UNROLL, &e->graphs[FIT_G_ITER_2N]}, {GRAPH_UNROLL, &e->graphs[FIT_G_ITER_N]}, {1, &e->graphs[FIT_G_ITER_1]}}, one).rc;
 }
 
 // Data-parallel iterations with the collective issued from C: forward half -> ncclAllReduce(stats[0..5], sum) -> backward half, n_iter
@@ -2139,102 +2195,43 @@ extern "C" int psi_fit_iterate_dp(psi_fit_engine *e, psi_dp_comm *comm, int n_it
             // the captured graph: 0.1237 ms per iteration over a 1-rank RCCL group against 0.1102 for the serial chain and 0.1041 single-process
             // on the same box, profiles/r06_ab_dp_overlap.txt: a cross-stream dependency inside a hipGraph costs ~6 us on this stack, twice,
             // which is more than the 6-float collective it hides until the all-reduce itself takes longer than that.)
-            int rc = fit_forward(e, stats, st, false, false);
-            if (!rc) rc = fit_backward_joint(e, stats, st, true);
+            int rc = fit_forward(e, stats, st, FitStats::Backward);
+            if (!rc) rc = fit_backward_joint(e, stats, st, FitStats::Backward);
             if (!rc) rc = psi_dp_allreduce_sum(comm, stats, 6, st);
             return rc ? rc : fit_backward_tail(e, stats, st);
         }
-        int rc = fit_forward(e, stats, st);
+        int rc = fit_forward(e, stats, st, FitStats::Finalize);
         if (!rc) rc = psi_dp_allreduce_sum(comm, stats, 6, st);
-        if (!rc) rc = fit_backward(e, stats, st);
+        if (!rc) rc = fit_backward(e, stats, st, FitStats::Finalize);
         return rc;
     };
-    if (e->dp_comm != comm || e->dp_stats != stats) {
-        for (int i = 0; i < 2; i++)
-            if (e->dp_ready[i]) {
-                (void)hipGraphExecDestroy(e->ge_dp[i]);
-                (void)hipGraphDestroy(e->g_dp[i]);
-                e->dp_ready[i] = false;
-            }
+    if (e->dp_comm != comm || e->dp_stats != stats) {         // the captured graphs bake both in
+        fit_graph_drop(&e->graphs[FIT_G_DP_1]);
+        fit_graph_drop(&e->graphs[FIT_G_DP_N]);
         e->dp_warm = e->dp_warm && e->dp_comm == comm;
         e->dp_comm = comm;
         e->dp_stats = stats;
     }
     int done = 0;
+    auto eager = [&](int upto) {
+        int rc = 0;
+        for (; done < upto && !rc; done++) rc = one();
+        return rc;
+    };
     if (!use_graph || (!e->dp_warm && n_iter > 0)) {
-        const int n_eager = use_graph ? 1 : n_iter;
-        for (; done < n_eager; done++) {
-            int rc = one();
-            if (rc) return rc;
-        }
+        if (int rc = eager(use_graph ? 1 : n_iter)) return rc;
         e->dp_warm = true;
         if (!use_graph) return 0;
     }
-    // capture() = 0: graph ready; 1: the capture itself was refused (the stream's capture was invalidated by a call that is illegal under
-    // capture — an RCCL build / transport that needs host work per collective); anything else: a genuine error of the sequence, with the
-    // message of the call that failed, to be PROPAGATED (round 3 treated every failure as "cannot capture" and retried eagerly on a
-    // communicator that may already have been aborted, overwriting the error)
-    bool capture_refused = false;
-    auto capture = [&](int iters, int slot) -> int {
-        PSI_REQUIRE(st != nullptr, "graph capture needs a non-default stream");
-        PSI_CHECK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-        int rc = 0;
-        for (int i = 0; i < iters && !rc; i++) rc = one();
-        hipGraph_t g = nullptr;
-        const hipError_t ce = hipStreamEndCapture(st, &g);
-        const bool invalidated = ce >= hipErrorStreamCaptureUnsupported && ce <= hipErrorStreamCaptureWrongThread;   // 900 .. 908
-        // ... or RCCL itself declined the enqueue under capture without touching the stream (ncclInvalidArgument / ncclInvalidUsage, returned
-        // synchronously by ncclAllReduce: nothing was launched, the communicator is intact) — the same "cannot capture here" answer
-        const bool declined = rc == 1000 + 4 || rc == 1000 + 5;
-        if (rc || ce != hipSuccess) {
-            if (g) (void)hipGraphDestroy(g);
-            if (invalidated || declined) {
-                (void)hipGetLastError();
-                capture_refused = true;
-                return 1;
-            }
-            if (!rc) {
-                psi_set_error("hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-                rc = (int)ce;
-            }
-            return rc;
-        }
-        e->g_dp[slot] = g;
-        PSI_CHECK_HIP(hipGraphInstantiate(&e->ge_dp[slot], e->g_dp[slot], nullptr, nullptr, 0));
-        e->dp_ready[slot] = true;
-        return 0;
-    };
-    // A collective that cannot be captured must not cost the run: the first refused capture switches this engine to eager launches of
-    // the same sequence — every rank takes the same decision at the same iteration, because they run the same code on the same communicator
-    auto eager_rest = [&]() -> int {
-        for (; done < n_iter; done++) {
-            int rc = one();
-            if (rc) return rc;
-        }
-        return 0;
-    };
-    if (e->dp_no_graph) return eager_rest();
-    if (n_iter - done >= GRAPH_UNROLL) {
-        if (!e->dp_ready[1]) {
-            const int rc = capture(GRAPH_UNROLL, 1);
-            if (rc && !capture_refused) return rc;
-            if (rc) {
-                e->dp_no_graph = true;
-                return eager_rest();
-            }
-        }
-        for (; done + GRAPH_UNROLL <= n_iter; done += GRAPH_UNROLL) PSI_CHECK_HIP(hipGraphLaunch(e->ge_dp[1], st));
+    if (!e->dp_no_graph) {
+        const FitCaptured c = fit_run_graphs(st, n_iter, &done, {{GRAPH_UNROLL, &e->graphs[FIT_G_DP_N]}, {1, &e->graphs[FIT_G_DP_1]}}, one);
+        if (c.kind != FitCaptured::Refused) return c.rc;
+        // A collective that cannot be captured must not cost the run: the first refused capture switches this engine to eager launches of
+        // the same sequence — every rank takes the same decision at the same iteration, because they run the same code on the same communicator
+        (void)hipGetLastError();
+        e->dp_no_graph = true;
     }
-    if (done < n_iter && !e->dp_ready[0]) {
-        const int rc = capture(1, 0);
-        if (rc && !capture_refused) return rc;
-        if (rc) {
-            e->dp_no_graph = true;
-            return eager_rest();
-        }
-    }
-    for (; done < n_iter; done++) PSI_CHECK_HIP(hipGraphLaunch(e->ge_dp[0], st));
-    return 0;
+    return eager(n_iter);
 }
 
 extern "C" int psi_fit_dp_mode(const psi_fit_engine *e)
@@ -2299,8 +2296,7 @@ extern "C" int psi_fit_profile(psi_fit_engine *e, int n_rep, char *h_names, int 
         tm.name[0] = "start";
         tm.n = 1;
         g_psi_timer = &tm;
-        rc = fit_forward(e, e->stats_local, st, true);
-        if (!rc) rc = fit_backward(e, e->stats_local, st, true);
+        rc = fit_iteration(e, st);
         g_psi_timer = nullptr;
         if (rc) break;
         PSI_CHECK_HIP(hipStreamSynchronize(st));

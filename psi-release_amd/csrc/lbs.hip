@@ -431,10 +431,13 @@ extern "C" int psi_lbs_create(psi_lbs_model **out, const float *h_v_template, co
     }
     // host staging
     // tile stride of the forward copy: a tile's 32 x Kpad floats + a skew (PSI_DIRS_SKEW floats, default 1088 = 4352 bytes), so that the
-    // 984 waves that walk their tiles at the same pace do not sit on the same memory channels (tiles exactly 64 KB apart do)
+    // 984 waves that walk their tiles at the same pace do not sit on the same memory channels (tiles exactly 64 KB apart do).  Accepted: 0 ..
+    // Kpad * 32 floats, one whole tile: a negative skew makes the tiles overlap in the fill below, and since a stride of 64 KB — SMPL-X's tile —
+    // meets the same channels again, a skew beyond the tile places nothing that a smaller one does not; it only grows the copy.  Else: ignored.
     {
         const char *sk = getenv("PSI_DIRS_SKEW");
-        d.dirs_tile = d.Kpad * 32 + (sk ? atoi(sk) / 4 * 4 : 1088);
+        const int skew = sk ? atoi(sk) / 4 * 4 : -1;
+        d.dirs_tile = d.Kpad * 32 + (skew >= 0 && skew <= d.Kpad * 32 ? skew : 1088);
     }
     std::vector<float> dirs_bh;
     std::vector<float> dense((size_t)d.Kpad * d.Npad, 0.0f), dirs((size_t)(d.Npad / 32) * d.dirs_tile, 0.0f), vt(d.Npad, 0.0f),
@@ -678,9 +681,8 @@ static int lbs_launch_bwd_joint_parts(const LbsDev &m, const WsLayout &L, int B,
     const int bgroups = psi_cdiv(B, 16 * mt);
     const int n_blend = kgroups * L.nsn * bgroups;
     // bodies per skin_bwd_A workgroup: about one such workgroup per CU beside its stream workgroup
-    int nbody = psi_cdiv(B, 256 / L.nsv > 0 ? 256 / L.nsv : 1);
-    if (nbody > SKA_NBODY) nbody = SKA_NBODY;
-    if (const char *ev = getenv("PSI_SKA_NBODY")) { int v = atoi(ev); if (v >= 1 && v <= SKA_NBODY) nbody = v; }
+    static const int nbody_override = psi_ska_nbody_override(SKA_NBODY);      // read once per process
+    const int nbody = psi_ska_nbody(psi_cdiv(B, 256 / L.nsv > 0 ? 256 / L.nsv : 1), SKA_NBODY, nbody_override);
     // (Round 4 measured the two halves as two launches of this kernel — stream workgroups, then the skin_bwd_A workgroups: 18.4 us each by
     // rocprofv3 = 36.8 against 27.2 for the heterogeneous grid, profiles/r04_ab_blend_loop.txt.  One grid it stays.)
     const int grid = n_blend + L.nsv * psi_cdiv(B, nbody);

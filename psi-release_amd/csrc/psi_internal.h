@@ -1,6 +1,7 @@
 // Host-side launchers shared between translation units of libpsi_hip.so (not part of the C ABI).
 #pragma once
 #include "psi_common.h"
+#include <stdlib.h>
 
 struct psi_lbs_model;
 
@@ -44,6 +45,15 @@ struct PsiLbsGradOut {
 int psi_lbs_backward_ex(const psi_lbs_model *mdl, const float *grad_verts, const float *betas, const float *pose,
                         const float *cam_ext, int B, float *ws, PsiLbsGradOut out, hipStream_t st);
 void psi_lbs_dims(const psi_lbs_model *mdl, int *V, int *J, int *NB);
+// bodies per skin_bwd_A workgroup (bwd_joint_kernel in lbs.hip, fit_bwd_joint_kernel in fit.hip): what the two launchers' rules have in
+// common — the kernel's limit, and PSI_SKA_NBODY=1..limit in the rule's place (0: not set, or not accepted)
+static inline int psi_ska_nbody_override(int limit)
+{
+    const char *v = getenv("PSI_SKA_NBODY");
+    const int n = v ? atoi(v) : 0;
+    return n >= 1 && n <= limit ? n : 0;
+}
+static inline int psi_ska_nbody(int rule, int limit, int override_) { return override_ ? override_ : (rule < limit ? rule : limit); }
 // the fused fitting engine runs the per-body pose stages inside its own kernels (lbs_device.h) and calls these for the rest
 struct PsiLbsView;
 int psi_lbs_view(const psi_lbs_model *mdl, int B, float *ws, PsiLbsView *out);
