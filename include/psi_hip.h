@@ -442,6 +442,37 @@ int psi_scene_losses_backward(const float *g_losses2, const float *stats2, const
  * chain[n_c + j] = 1 when no earlier slot lists it.  A constant of the list: build it once, pass it to every backward. */
 int psi_contact_slot_chain(const int32_t *vid, int n_c, int32_t *chain, void *stream);
 
+/* ---- evaluation: physical plausibility (utils/utils_eval_collision_habitat.py:91-175) ---------------------------------------------
+ * counts[b] = { #(sdf < 0), #(sdf > 0) } over the V vertices of body b, sampled in sdf[scene_id[b]] — the two integers
+ * utils_eval_collision_habitat.py:126-139 derives per body from smplx(...).vertices and F.grid_sample.  Inputs as psi_lbs_forward (betas, pose,
+ * transl, cam_ext, ws of psi_lbs_workspace_floats(model, B)) and as psi_sdf_sample_forward (sdf [S,D,D,D], scene_id [B] or NULL, gmin / gmax
+ * [S,3], align_corners; a scene_id outside [0,S) is clamped).  counts: device int32 [B,2], OVERWRITTEN.  No vertex, SDF value or gradient is
+ * written to memory: the sign test is the epilogue of the skinning kernel.  A vertex goes through the arithmetic of psi_lbs_forward and
+ * psi_sdf_sample_forward; the counters are integers, so the result is run-to-run identical. */
+int psi_lbs_sdf_counts(const psi_lbs_model *model, const float *betas, const float *pose, const float *transl,
+                       const float *cam_ext, int B, const float *sdf, const int32_t *scene_id, const float *gmin,
+                       const float *gmax, int D, int S, int align_corners, int32_t *counts, float *ws, void *stream);
+
+/* ---- evaluation: diversity (utils/utils_eval_diversity.py:93-104) -------------------------------------------------------------------
+ * scipy.cluster.vq.kmeans(obs, k) in its own protocol, all R restarts in one launch per stage: per restart
+ *   prev = +inf; repeat { code, dist = vq(obs, book) (first minimum wins); avg = mean(dist) (EUCLIDEAN, not squared); book = centroids of the
+ *   members, codes without members REMOVED, order of the others kept; diff = |prev - avg|; prev = avg } until not (diff > thresh)
+ * result: the book after the last update and the avg of the last vq.  Squared distances sum_f (x_f - c_f)^2 in fp32, features in index
+ * order; centroid sums, counts and avg in fp64 / integers, combined in a fixed order: bit-identical from run to run and independent of how
+ * the iterations are split into calls.
+ * obs [N,d] fp32 (device, borrowed: must outlive the object); guess [R,k,d] fp32 (device, copied): R initial codebooks.
+ * d <= 128, k <= 64, R <= 64, N >= k; otherwise PSI_EINVAL. */
+typedef struct psi_kmeans psi_kmeans;
+int psi_kmeans_create(psi_kmeans **out, const float *obs, int N, int d, const float *guess, int k, int R, float thresh);
+void psi_kmeans_destroy(psi_kmeans *km);
+/* Enqueue n_iter Lloyd iterations of every restart that has not converged; converged restarts are left untouched.  No host sync. */
+int psi_kmeans_iterate(psi_kmeans *km, int n_iter, void *stream);
+/* book [R,k,d] (first k_eff[r] rows of restart r valid), k_eff [R] int32, avg_dist [R] fp64, iters [R] int32: device outputs, each
+ * nullable.  h_converged (host, nullable): number of converged restarts; passing it synchronises the stream (like psi_fit_read). */
+int psi_kmeans_read(psi_kmeans *km, float *book, int32_t *k_eff, double *avg_dist, int32_t *iters, int *h_converged, void *stream);
+/* scipy.cluster.vq.vq: code[i] = lowest index of the nearest row of book [k,d], dist[i] = its Euclidean distance (nullable). */
+int psi_vq(const float *obs, int N, int d, const float *book, int k, int32_t *code, float *dist, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

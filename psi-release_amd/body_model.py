@@ -147,9 +147,9 @@ class SMPLXLayer(nn.Module):
         z = lambda n: nn.Parameter(torch.zeros(batch_size, n, device=dev), requires_grad=True)
         self.expression, self.jaw_pose, self.leye_pose, self.reye_pose = z(num_expression_coeffs), z(3), z(3), z(3)
 
-    def forward(self, betas=None, global_orient=None, body_pose=None, left_hand_pose=None, right_hand_pose=None,
-                transl=None, expression=None, jaw_pose=None, leye_pose=None, reye_pose=None, return_verts=True,
-                return_full_pose=False, cam_ext=None, **unused):
+    def _assemble(self, betas, global_orient, body_pose, left_hand_pose, right_hand_pose, expression=None, jaw_pose=None,
+                  leye_pose=None, reye_pose=None):
+        """(shape [B,NB], full axis-angle pose [B,J*3]) of the kernels from the smplx keyword arguments."""
         B = betas.shape[0]
         dev = betas.device
         zeros3 = torch.zeros(B, 3, device=dev)
@@ -160,10 +160,59 @@ class SMPLXLayer(nn.Module):
         rh = right_hand_pose @ self.right_hand_components
         full_pose = torch.cat([global_orient, body_pose, jaw, le, re, lh, rh], dim=1) + self.pose_mean
         expr = torch.zeros(B, self.num_expr, device=dev) if expression is None else expression
-        shape = torch.cat([betas, expr], dim=-1)
+        return torch.cat([betas, expr], dim=-1), full_pose
+
+    def forward(self, betas=None, global_orient=None, body_pose=None, left_hand_pose=None, right_hand_pose=None,
+                transl=None, expression=None, jaw_pose=None, leye_pose=None, reye_pose=None, return_verts=True,
+                return_full_pose=False, cam_ext=None, **unused):
+        shape, full_pose = self._assemble(betas, global_orient, body_pose, left_hand_pose, right_hand_pose, expression, jaw_pose,
+                                          leye_pose, reye_pose)
         verts, joints = lbs(self.lbs_model, shape, full_pose, transl, cam_ext, return_joints=True)
         return SimpleNamespace(vertices=verts, joints=joints, full_pose=full_pose if return_full_pose else None,
                                betas=betas, global_orient=global_orient, body_pose=body_pose)
+
+    @torch.no_grad()
+    def sdf_counts(self, sdf, grid_min, grid_max, scene_id=None, align_corners=True, cam_ext=None, betas=None, global_orient=None,
+                   body_pose=None, left_hand_pose=None, right_hand_pose=None, transl=None, expression=None, jaw_pose=None,
+                   leye_pose=None, reye_pose=None, **unused):
+        """int32 [B,2] = (#(sdf < 0), #(sdf > 0)) over each body's vertices, sampled in ``sdf[scene_id[b]]`` — what
+        ``ops.sdf_sample(self(...).vertices, ...)`` followed by two sign sums gives, in one skinning launch that stores no vertex
+        (psi_lbs_sdf_counts; utils_eval_collision_habitat.py:126-139).  Arguments as ``forward`` and ``ops.sdf_sample``.  No autograd."""
+        shape, full_pose = self._assemble(betas, global_orient, body_pose, left_hand_pose, right_hand_pose, expression, jaw_pose,
+                                          leye_pose, reye_pose)
+        model = self.lbs_model
+        shape, full_pose = shape.contiguous().float(), full_pose.contiguous().float()
+        B = shape.shape[0]
+        if tuple(shape.shape) != (B, model.NB) or tuple(full_pose.shape) != (B, model.J * 3):
+            raise ValueError('sdf_counts: betas must be [B,%d] and pose [B,%d]' % (model.NB, model.J * 3))
+        if transl is not None:
+            if tuple(transl.shape) != (B, 3):
+                raise ValueError('sdf_counts: transl must be [%d,3], got %s' % (B, tuple(transl.shape)))
+            transl = transl.contiguous().float()
+        if cam_ext is not None:
+            if cam_ext.dim() != 3 or tuple(cam_ext.shape[1:]) != (4, 4) or cam_ext.shape[0] not in (1, B):
+                raise ValueError('sdf_counts: cam_ext must be [%d,4,4] or [1,4,4], got %s' % (B, tuple(cam_ext.shape)))
+            cam_ext = cam_ext.expand(B, 4, 4).contiguous().float()
+        if sdf.dim() == 3:
+            sdf = sdf.unsqueeze(0)
+        sdf = sdf.contiguous().float()
+        S, D = sdf.shape[0], sdf.shape[1]
+        if tuple(sdf.shape) != (S, D, D, D):
+            raise ValueError('sdf_counts: sdf must be [S,D,D,D], got %s' % (tuple(sdf.shape),))
+        gmin = grid_min.reshape(-1, 3).contiguous().float()
+        gmax = grid_max.reshape(-1, 3).contiguous().float()
+        if gmin.shape[0] != S or gmax.shape[0] != S:
+            raise ValueError('grid_min/grid_max must have one row per scene volume')
+        if scene_id is not None:
+            scene_id = scene_id.to(device=shape.device, dtype=torch.int32).contiguous()
+            if tuple(scene_id.shape) != (B,):
+                raise ValueError('sdf_counts: scene_id must be [%d]' % B)
+        counts = torch.empty(B, 2, dtype=torch.int32, device=shape.device)
+        hip.check(hip.lib().psi_lbs_sdf_counts(model.handle, hip.ptr(shape), hip.ptr(full_pose), hip.ptr(transl), hip.ptr(cam_ext), B,
+                                               hip.ptr(sdf), hip.ptr(scene_id), hip.ptr(gmin), hip.ptr(gmax), D, S,
+                                               int(bool(align_corners)), hip.ptr(counts), hip.ptr(model.workspace(B)), hip.stream()),
+                  'psi_lbs_sdf_counts')
+        return counts
 
 
 def load_smplx_npz(path):

@@ -18,7 +18,7 @@ void psi_set_error(const char *fmt, ...)
 }
 
 extern "C" const char *psi_last_error(void) { return g_err; }
-extern "C" int psi_version(void) { return 100; }
+extern "C" int psi_version(void) { return 101; }
 
 extern "C" int psi_device_info(int *cu_count, int *wave_size, int *clock_khz, int *is_gfx950)
 {

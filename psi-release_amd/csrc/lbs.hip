@@ -658,6 +658,21 @@ int psi_lbs_blend_forward(const psi_lbs_model *mdl, int B, float *ws, hipStream_
     return lbs_launch_blend(m, ws_layout(m, B), B, ws, st);
 }
 
+// the stages of psi_lbs_forward in front of its skinning kernel, for a caller that skins with an epilogue of its own (eval.hip): A and
+// v_posed are left in the workspace (psi_lbs_view)
+int psi_lbs_pose_blend_forward(const psi_lbs_model *mdl, const float *betas, const float *pose, const float *transl, int B, float *ws,
+                               hipStream_t st)
+{
+    PSI_REQUIRE(mdl && betas && pose && ws && B > 0, "bad arguments");
+    const LbsDev &m = mdl->d;
+    WsLayout L = ws_layout(m, B);
+    hipLaunchKernelGGL(pose_fwd_kernel, dim3(B), dim3(64), 0, st, m, betas, pose, transl, B, ws + L.feat, ws + L.R, ws + L.Jl,
+                       ws + L.G, ws + L.A, (float *)nullptr);
+    PSI_CHECK_LAUNCH("pose_fwd_kernel");
+    psi_mark("pose_fwd_kernel", st);
+    return lbs_launch_blend(m, L, B, ws, st);
+}
+
 static int lbs_launch_bwd_joint_parts(const LbsDev &m, const WsLayout &L, int B, float *ws, hipStream_t st);
 
 static int lbs_launch_bwd_partials(const LbsDev &m, const WsLayout &L, const float *grad_verts, const float *cam_ext, int B, float *ws,

@@ -58,6 +58,9 @@ static inline int psi_ska_nbody(int rule, int limit, int override_) { return ove
 struct PsiLbsView;
 int psi_lbs_view(const psi_lbs_model *mdl, int B, float *ws, PsiLbsView *out);
 int psi_lbs_blend_forward(const psi_lbs_model *mdl, int B, float *ws, hipStream_t st);          // v_posed = v_t + feat @ dirs
+// pose_fwd + blend_fwd of psi_lbs_forward for given betas / pose: A and v_posed in the workspace, no vertices (eval.hip skins with its own epilogue)
+int psi_lbs_pose_blend_forward(const psi_lbs_model *mdl, const float *betas, const float *pose, const float *transl, int B, float *ws,
+                               hipStream_t st);
 int psi_lbs_backward_joint_parts(const psi_lbs_model *mdl, int B, float *ws, float *g_transl, hipStream_t st,
                                  bool reduce = true);   // skin_bwd_A + blend_bwd partials (+ their reduction: gA, gfeat in the workspace)
 

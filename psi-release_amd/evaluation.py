@@ -1,18 +1,25 @@
-"""Physical-plausibility metrics of generated / fitted bodies.
+"""Physical-plausibility and diversity metrics of generated / fitted bodies.
 
-Reference: utils/utils_eval_collision_habitat.py:91-175 — per body: ``non-collision score`` = #(sdf > 0) / 10475 and
+Plausibility: utils/utils_eval_collision_habitat.py:91-175 — per body: ``non-collision score`` = #(sdf > 0) / 10475 and
 ``contact score`` = 1 if any vertex has sdf < 0 else 0 (with the all-outside convention: collision 1.0, contact 0).
-Same SMPL-X + SDF path as fitting (HIP operators), Habitat camera flip (:160-165).
+Same SMPL-X + SDF path as fitting (HIP operators), Habitat camera flip (:160-165).  ``scores`` / ``eval_folder`` score one pkl at a
+time through the operators; ``scores_many`` / ``eval_folder_batched`` / ``evaluate_scenes`` score whole folders with one fused
+skin + sign-count launch per chunk of bodies (psi_lbs_sdf_counts) and one device -> host copy.
+
+Diversity: utils/utils_eval_diversity.py:93-104 — ``diversity_reference`` runs the reference's ``scipy.cluster.vq.kmeans`` protocol
+on the GPU (psi_kmeans_*, psi_vq); ``diversity_scores`` is the older k-means++ variant (a different algorithm, kept as it is).
 """
 from __future__ import annotations
 
 import os
 import pickle
 
+import ctypes
+
 import numpy as np
 import torch
 
-from . import ops
+from . import hip, ops
 from .geometry import BodyParamParser, GeometryTransformer
 
 
@@ -60,6 +67,224 @@ class PlausibilityEvaluator:
             coll.extend(c if isinstance(c, list) else [c])
             cont.extend(k if isinstance(k, list) else [k])
         return coll, cont
+
+
+    # ---- batched path: psi_lbs_sdf_counts ------------------------------------------------------------------------------------
+    def _volumes(self):
+        op = self.op
+        return op.s_sdf, op.s_grid_min_batch.reshape(-1, 3), op.s_grid_max_batch.reshape(-1, 3)
+
+    @staticmethod
+    def _scores_from_counts(counts):
+        """counts [N,2] (host, integers) -> (non-collision, contact) float64 [N], formed exactly as ``scores`` forms them."""
+        neg, pos = counts[:, 0].astype(np.int64), counts[:, 1].astype(np.int64)
+        hit = neg >= 1
+        coll = np.where(hit, pos.astype(np.float64) / 10475.0, 10475.0 / 10475.0)
+        cont = np.where(hit, 1.0, 0.0)
+        return coll, cont
+
+    @torch.no_grad()
+    def scores_many(self, xh72, cam_ext, scene_id=None, chunk=512, volumes=None):
+        """(non-collision scores, contact scores), two float64 arrays [N], of N bodies ``xh72`` [N,72] with cameras ``cam_ext``
+        [N,4,4] or [1,4,4] (the pkl's, before the Habitat flip).  One batched 6D round trip and VPoser decode for all N, the fused
+        skin + SDF sign count in chunks of ``chunk`` bodies, ONE device -> host copy.  ``scene_id`` [N] selects the volume per body
+        when the evaluator holds several (``evaluate_scenes``)."""
+        op = self.op
+        dev = op.device
+        xh = torch.as_tensor(xh72, dtype=torch.float32, device=dev).reshape(-1, 72)
+        cam = torch.as_tensor(cam_ext, dtype=torch.float32, device=dev).reshape(-1, 4, 4)
+        N = xh.shape[0]
+        if cam.shape[0] not in (1, N):
+            raise ValueError('scores_many: cam_ext must be [%d,4,4] or [1,4,4], got %s' % (N, tuple(cam.shape)))
+        if chunk < 1:
+            raise ValueError('scores_many: chunk must be >= 1')
+        if N == 0:
+            return np.zeros(0), np.zeros(0)
+        if self.flip:
+            T_mat = torch.diag(torch.tensor([1.0, -1.0, -1.0, 1.0], device=dev)).unsqueeze(0)
+            cam = torch.matmul(cam, T_mat)
+        cam = cam.expand(N, 4, 4).contiguous()
+        sdf, gmin, gmax = volumes if volumes is not None else self._volumes()
+        if scene_id is not None:
+            scene_id = torch.as_tensor(scene_id, device=dev).to(torch.int32).reshape(N)
+        xh_rec = GeometryTransformer.convert_to_3D_rot(GeometryTransformer.convert_to_6D_rot(xh))
+        par = BodyParamParser.body_params_encapsulate_batch(xh_rec)
+        par['body_pose'] = op.vposer.decode(par.pop('body_pose_vp'), output_type='aa').view(N, -1)
+        counts = torch.empty(N, 2, dtype=torch.int32, device=dev)
+        for lo in range(0, N, chunk):
+            hi = min(N, lo + chunk)
+            counts[lo:hi] = op.body_mesh_model.sdf_counts(sdf, gmin, gmax, scene_id=None if scene_id is None else scene_id[lo:hi],
+                                                          align_corners=op.align_corners, cam_ext=cam[lo:hi],
+                                                          **{k: v[lo:hi] for k, v in par.items()})
+        return self._scores_from_counts(counts.cpu().numpy())
+
+    @staticmethod
+    def _read_folder(folder, max_files):
+        """(xh72 [N,72], cam_ext [N,4,4]) of the pkls of a folder, host arrays; a pkl of B bodies gives B rows with its first camera."""
+        xs, cams = [], []
+        for ii in range(max_files):
+            fn = os.path.join(folder, 'body_gen_{:06d}.pkl'.format(ii))
+            if not os.path.exists(fn):
+                continue
+            with open(fn, 'rb') as f:
+                rec = pickle.load(f)
+            x = np.asarray(BodyParamParser._vector(rec), dtype=np.float32).reshape(-1, 72)
+            c = np.asarray(rec['cam_ext'], dtype=np.float32).reshape(-1, 4, 4)[:1]
+            xs.append(x)
+            cams.append(np.repeat(c, x.shape[0], axis=0))
+        if not xs:
+            return np.zeros((0, 72), np.float32), np.zeros((0, 4, 4), np.float32)
+        return np.concatenate(xs), np.concatenate(cams)
+
+    def eval_folder_batched(self, folder, max_files=8000, chunk=512):
+        """The two lists ``eval_folder`` returns, through ``scores_many``."""
+        xh, cam = self._read_folder(folder, max_files)
+        coll, cont = self.scores_many(xh, cam, chunk=chunk)
+        return coll.tolist(), cont.tolist()
+
+    @classmethod
+    def evaluate_scenes(cls, ops_by_scene, gen_path, flip_camera_yz=True, max_files=8000, chunk=512):
+        """Several scenes in one pass.  ``ops_by_scene``: ordered mapping (or list of pairs) scene name -> FittingOP; the bodies of
+        scene ``name`` are the pkls of ``gen_path/name``.  The volumes are stacked [S,D,D,D] (all scenes must share D) and every body
+        carries its ``scene_id``; VPoser and body model are the first op's.  Returns ``{name: (coll list, cont list)}`` in the order given."""
+        items = list(ops_by_scene.items()) if hasattr(ops_by_scene, 'items') else list(ops_by_scene)
+        if not items:
+            return {}
+        Ds = [tuple(op.s_sdf.shape[1:]) for _, op in items]
+        if any(d != Ds[0] for d in Ds):
+            raise ValueError('evaluate_scenes: all scenes must share the SDF resolution D, got %s' % (Ds,))
+        if any(bool(op.align_corners) != bool(items[0][1].align_corners) for _, op in items):
+            raise ValueError('evaluate_scenes: all scenes must share align_corners')
+        ev = cls(items[0][1], flip_camera_yz=flip_camera_yz)
+        vols = (torch.cat([op.s_sdf.reshape(1, *Ds[0]) for _, op in items]).contiguous(),
+                torch.cat([op.s_grid_min_batch.reshape(1, 3) for _, op in items]).contiguous(),
+                torch.cat([op.s_grid_max_batch.reshape(1, 3) for _, op in items]).contiguous())
+        xs, cams, sids = [], [], []
+        for si, (name, _) in enumerate(items):
+            x, c = cls._read_folder(os.path.join(gen_path, name), max_files)
+            xs.append(x)
+            cams.append(c)
+            sids.append(np.full(x.shape[0], si, np.int32))
+        coll, cont = ev.scores_many(np.concatenate(xs), np.concatenate(cams), scene_id=np.concatenate(sids), chunk=chunk, volumes=vols)
+        out, lo = {}, 0
+        for (name, _), x in zip(items, xs):
+            out[name] = (coll[lo:lo + x.shape[0]].tolist(), cont[lo:lo + x.shape[0]].tolist())
+            lo += x.shape[0]
+        return out
+
+
+class KMeansRestarts:
+    """Owns a ``psi_kmeans`` handle: R restarts of scipy's k-means loop on ``obs`` [N,d] from the initial codebooks ``guess`` [R,k,d]."""
+
+    def __init__(self, obs, guess, thresh=1e-5):
+        if not obs.is_cuda:
+            raise hip.PsiHipError('KMeansRestarts needs GPU tensors (no CPU implementation exists in this package)')
+        self.obs = obs.contiguous().float()                       # borrowed by the handle: kept alive here
+        guess = guess.to(self.obs.device).contiguous().float()
+        self.N, self.d = self.obs.shape
+        self.R, self.k = guess.shape[0], guess.shape[1]
+        if guess.dim() != 3 or guess.shape[2] != self.d:
+            raise ValueError('KMeansRestarts: guess must be [R,k,%d], got %s' % (self.d, tuple(guess.shape)))
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.obs.device):
+            hip.check(hip.lib().psi_kmeans_create(ctypes.byref(h), hip.ptr(self.obs), self.N, self.d, hip.ptr(guess), self.k, self.R,
+                                                  float(thresh)), 'psi_kmeans_create')
+        self.handle = h
+        self.launches = 0             # kernel launches enqueued by iterate() (three per Lloyd iteration)
+        self.syncs = 0                # host synchronisations (converged())
+
+    def iterate(self, n_iter):
+        hip.check(hip.lib().psi_kmeans_iterate(self.handle, int(n_iter), hip.stream()), 'psi_kmeans_iterate')
+        self.launches += 3 * int(n_iter)
+
+    def converged(self):
+        """Number of converged restarts (synchronises the stream)."""
+        n = ctypes.c_int()
+        hip.check(hip.lib().psi_kmeans_read(self.handle, None, None, None, None, ctypes.byref(n), hip.stream()), 'psi_kmeans_read')
+        self.syncs += 1
+        return n.value
+
+    def read(self):
+        """(book [R,k,d] float32, k_eff [R] int32, avg_dist [R] float64, iters [R] int32), device tensors."""
+        dev = self.obs.device
+        book = torch.empty(self.R, self.k, self.d, device=dev)
+        k_eff = torch.empty(self.R, dtype=torch.int32, device=dev)
+        avg = torch.empty(self.R, dtype=torch.float64, device=dev)
+        iters = torch.empty(self.R, dtype=torch.int32, device=dev)
+        hip.check(hip.lib().psi_kmeans_read(self.handle, hip.ptr(book), hip.ptr(k_eff), hip.ptr(avg), hip.ptr(iters), None, hip.stream()),
+                  'psi_kmeans_read')
+        return book, k_eff, avg, iters
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            torch.cuda.synchronize(self.obs.device)
+            hip.lib().psi_kmeans_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def vq(obs, book):
+    """``scipy.cluster.vq.vq`` on the GPU: (code [N] int32 = lowest index of the nearest row of ``book`` [k,d], dist [N] float32)."""
+    obs, book = obs.contiguous().float(), book.contiguous().float()
+    N, d = obs.shape
+    if book.dim() != 2 or book.shape[1] != d:
+        raise ValueError('vq: book must be [k,%d], got %s' % (d, tuple(book.shape)))
+    code = torch.empty(N, dtype=torch.int32, device=obs.device)
+    dist = torch.empty(N, device=obs.device)
+    hip.check(hip.lib().psi_vq(hip.ptr(obs), N, d, hip.ptr(book), book.shape[0], hip.ptr(code), hip.ptr(dist), hip.stream()), 'psi_vq')
+    return code, dist
+
+
+def code_histogram(code, n_codes):
+    """(counts, entropy) of utils_eval_diversity.py:96-99: ``scipy.histogram(vecs, len(codes))`` — ``n_codes`` equal-width bins over
+    [min(code), max(code)], NOT ``bincount`` (they differ when the highest or lowest code has no member) — and ``entropy(counts)``
+    = -sum p ln p over p = counts / N."""
+    counts = np.histogram(np.asarray(code), int(n_codes))[0]
+    p = counts.astype(np.float64) / counts.sum()
+    p = p[p > 0]
+    return counts, float(-(p * np.log(p)).sum())
+
+
+def diversity_reference(bodies72, k=20, n_restarts=20, thresh=1e-5, seed=None, device='cuda', stats=None):
+    """utils/utils_eval_diversity.py:93-104 in the reference's own protocol — ``scipy.cluster.vq.kmeans(ar, 20)`` (20 restarts from
+    codebooks drawn from the observations, iteration until the mean Euclidean distance changes by <= 1e-5, empty codes dropped, the
+    lowest-distortion codebook kept), ``vq``, ``histogram(vecs, len(codes))``, ``entropy(counts)``, ``mean(dist)`` — with every restart
+    advancing in the same GPU launches.  ``seed``: an int seeds ``np.random.RandomState`` (what scipy builds from it); None draws
+    from numpy's global generator like the reference.  Returns dict(entropy, mean_dist, counts, codes, distortion, winner, labels = vecs);
+    ``stats`` (a dict, optional) receives the launch / synchronisation counts."""
+    x = np.ascontiguousarray(np.asarray(bodies72, dtype=np.float32))
+    N = x.shape[0]
+    rng = np.random.RandomState(seed) if seed is not None else np.random.mtrand._rand
+    idx = np.stack([rng.choice(N, size=int(k), replace=False) for _ in range(n_restarts)])
+    dev = torch.device(device)
+    obs = torch.tensor(x, device=dev)
+    km = KMeansRestarts(obs, obs[torch.tensor(idx.reshape(-1), device=dev)].reshape(n_restarts, int(k), x.shape[1]), thresh)
+    try:
+        while True:
+            km.iterate(16)
+            if km.converged() == n_restarts:
+                break
+        book, k_eff, avg, iters = km.read()
+        avg_h, k_eff_h, iters_h = avg.cpu().numpy(), k_eff.cpu().numpy(), iters.cpu().numpy()
+        winner, best = 0, np.inf
+        for r in range(n_restarts):                      # `if dist < best_dist` of scipy's kmeans: the FIRST on a tie
+            if avg_h[r] < best:
+                winner, best = r, avg_h[r]
+        codes = book[winner, :int(k_eff_h[winner])].contiguous()
+        code, dist = vq(obs, codes)
+        code_h, dist_h, codes_h = code.cpu().numpy(), dist.cpu().numpy(), codes.cpu().numpy()
+        if stats is not None:
+            stats.update(launches=km.launches, syncs=km.syncs, iters=iters_h.tolist(), launches_per_iteration=3)
+    finally:
+        km.close()
+    counts, ent = code_histogram(code_h, len(codes_h))
+    return dict(entropy=ent, mean_dist=float(np.mean(dist_h.astype(np.float64))), counts=counts,
+                codes=codes_h, distortion=float(best), winner=int(winner), labels=code_h)
 
 
 def diversity_scores(bodies_72: np.ndarray, n_clusters: int = 20, seed: int = 0):
