@@ -188,6 +188,30 @@ int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_fit
                    const float *h_pose_mean, const int32_t *h_contact_ids,
                    const float *d_scene_verts, const float *d_sdf, const float *h_gmin, const float *h_gmax);
 void psi_fit_destroy(psi_fit_engine *engine);
+/* Several scenes in one engine: body b of a run is fitted in scene slot[b].  Every scene-aware operator of this ABI takes a scene table
+ * and a per-body scene index (psi_sdf_sample_forward, psi_nn_index_set_query, psi_lbs_sdf_counts); this is the fitting engine's form.
+ * psi_fit_create_scenes is psi_fit_create with S scenes instead of one (cfg->m_scene and cfg->D are ignored; m and D may differ from
+ * scene to scene).  Per scene the engine builds its own exact NN index (as psi_nn_index_create) and its own re-ordered copy of the
+ * volume, which costs 8 x the volume per scene: 537 MB at 256^3, 3.8 GB for seven such rooms (PSI_ENOMEM when the allocation fails).
+ * PSI_EINVAL: S < 1 or a null scene pointer; cfg->nn_mode != 1 (no brute-force search over several scenes); a D the re-ordered copy
+ * cannot hold (D % 4 != 0, D > 480: this engine has no plain-volume fallback); cfg->world_size > 1 (data-parallel runs over several
+ * scenes are not supported).  The scene slots are an engine-owned device buffer, all 0 after create; captured graphs stay valid when
+ * they change.  psi_fit_set_scene_slots copies d_slot [B] (device int32; values outside [0,S) are clamped, the rule of
+ * psi_lbs_sdf_counts) on `stream` — never inside a stream capture — and resets the nearest-neighbour warm-start hints, which index one
+ * scene's cloud; the slots persist across psi_fit_set_problem.  On a psi_fit_create engine (one scene) the call only resets the hints. */
+typedef struct psi_fit_scene {
+    const float *d_verts;   /* DEVICE [m,3], caller-owned, must outlive the engine */
+    const float *d_sdf;     /* DEVICE [D,D,D], element [ix][iy][iz], caller-owned  */
+    int m, D;
+    float gmin[3], gmax[3];
+} psi_fit_scene;
+int psi_fit_create_scenes(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_fit_config *cfg,
+                          const float *h_w1, const float *h_b1, const float *h_w2, const float *h_b2,
+                          const float *h_w3, const float *h_b3, const float *h_lh_comp, const float *h_rh_comp,
+                          const float *h_pose_mean, const int32_t *h_contact_ids,
+                          const psi_fit_scene *h_scenes, int S);
+int psi_fit_set_scene_slots(psi_fit_engine *engine, const int32_t *d_slot, void *stream);
+int psi_fit_scene_count(const psi_fit_engine *engine);   /* 1 for psi_fit_create engines */
 /* xhr = target body vectors [B,75]; x_init = starting parameters (NULL: start at xhr, fitting_proxe.py:175);
  * cam_ext [B,4,4]; reset_optimizer != 0 zeroes the Adam state and step count. */
 int psi_fit_set_problem(psi_fit_engine *engine, const float *d_xhr, const float *d_x_init, const float *d_cam_ext,

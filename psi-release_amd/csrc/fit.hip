@@ -531,7 +531,9 @@ struct SdfPenEpilogue {
         if ((cw >> 24) > 1)
             for (int ci = cs_ptr[v] + 1; ci < cs_ptr[v + 1]; ci++) psi_st(row, (unsigned)cs_idx[ci] * 12u, psi_p3{x, y, z});
     }
-    __device__ __forceinline__ void vertex(int n, int b, int v, float x, float y, float z, bool live)
+    __device__ __forceinline__ void vertex(int n, int b, int v, float x, float y, float z, bool live) { vertex_at(G, n, b, v, x, y, z, live); }
+    // (the lookup with the sampling constants as an argument: SdfPenEpilogueScenes below passes the grid of the body's own scene)
+    __device__ __forceinline__ void vertex_at(const PsiSdfGrid &G, int n, int b, int v, float x, float y, float z, bool live)
     {
         s[n] = 0.0f;
         neg[n] = false;
@@ -640,6 +642,34 @@ static inline SdfPenEpilogue make_sdf_epilogue(const FitDev &f, const PsiSdfGrid
         e.gtp = bwd->gt_part_w;
         e.Npad = bwd->m.Npad;
     }
+    return e;
+}
+
+// The epilogue of an engine with SEVERAL scenes (psi_fit_create_scenes): body b samples the volume of scene slot[b].  The workgroup's
+// bodies are uniform over its lanes, so their grids are fetched once per workgroup (load_grids, before the blend) and wait in scalar
+// registers — two of them, because the two bodies of a two-body workgroup may sit in different scenes.  Such an engine always has a
+// re-ordered copy of every volume (G.brick != nullptr); everything behind the lookup is the single-scene epilogue's.
+struct SdfPenEpilogueScenes : SdfPenEpilogue {
+    const PsiSdfGrid *gtab;       // [S] sampling constants per scene slot
+    const int *slot;              // [B] scene slot per body (engine-owned; psi_fit_set_scene_slots keeps it inside [0, S))
+    PsiSdfGrid Gb[2];
+    template <int NB>
+    __device__ __forceinline__ void load_grids(int b0, int B)
+    {
+#pragma unroll
+        for (int n = 0; n < NB; n++) Gb[n] = gtab[slot[min(b0 + n, B - 1)]];
+    }
+    __device__ __forceinline__ void vertex(int n, int b, int v, float x, float y, float z, bool live) { vertex_at(Gb[n], n, b, v, x, y, z, live); }
+};
+
+static inline SdfPenEpilogueScenes make_sdf_epilogue_scenes(const FitDev &f, const PsiSdfGrid *gtab, const int *slot, bool contact_vertices_only = false,
+                                                            const PsiLbsView *bwd = nullptr)
+{
+    SdfPenEpilogueScenes e;
+    static_cast<SdfPenEpilogue &>(e) = make_sdf_epilogue(f, PsiSdfGrid{}, contact_vertices_only, bwd);
+    e.gtab = gtab;
+    e.slot = slot;
+    e.Gb[0] = e.Gb[1] = PsiSdfGrid{};
     return e;
 }
 
@@ -847,6 +877,46 @@ __global__ __launch_bounds__(256, 6) void fwd_scene_kernel(FitDev f, LbsDev m, c
         const int i = bid;
         psi_skin_fwd_body<NB, PsiBlendCompact>(m, As, v_posed, f.transl, f.cam, f.B, f.verts, epi, i % f.nsdfblk, (i / f.nsdfblk) * NB, f.nsdfblk);
     }
+}
+
+// The same launch for an engine with SEVERAL scenes (psi_fit_create_scenes): the search workgroups of body b walk the tree tab[slot[b]]
+// (kd_query_body<CONTACT, MULTI>; `rows` = the largest stack of the set), the skinning workgroups sample the grid of their bodies' scenes
+// (SdfPenEpilogueScenes).  A kernel of its own, so that the single-scene engine's launch stays the code it was.
+template <int NB>
+__global__ __launch_bounds__(256, 6) void fwd_scene_scenes_kernel(FitDev f, LbsDev m, const float *__restrict__ As, const float *__restrict__ v_posed,
+                                                                  const psikd::KdDev *__restrict__ tab, int n_kd, int nqb, int rows, float gscale,
+                                                                  int skin_first, SdfPenEpilogueScenes epi)
+{
+    extern __shared__ int smem_i[];
+    int bid = blockIdx.x;
+    bool is_kd;
+    if (skin_first) {
+        const int n_sk = (int)gridDim.x - n_kd;
+        is_kd = bid >= n_sk;
+        if (is_kd) bid -= n_sk;
+    } else {
+        is_kd = bid < n_kd;
+        if (!is_kd) bid -= n_kd;
+    }
+    if (is_kd) {
+        const int b = bid / nqb, bx = bid % nqb;
+        psikd::kd_query_body<true, true>(psikd::KdDev(), ContactSkinSrc{f, m, As, v_posed, nullptr, {}, 0.0f, 0, 0.0f, 0.0f, 0.0f, nullptr, {}, 0}, f.n_c, (float *)nullptr, (int *)nullptr,
+                                         f.cconst, gscale, f.fused_bwd ? (float *)nullptr : f.gq, f.fpart, f.nn_hint, rows, tab, epi.slot, bx, b, nqb, smem_i);
+    } else {
+        const int i = bid;
+        epi.template load_grids<NB>((i / f.nsdfblk) * NB, f.B);
+        psi_skin_fwd_body<NB, PsiBlendCompact>(m, As, v_posed, f.transl, f.cam, f.B, f.verts, epi, i % f.nsdfblk, (i / f.nsdfblk) * NB, f.nsdfblk);
+    }
+}
+
+// the skinning + SDF kernel as a launch of its own (large batches), over several scenes
+template <int NB>
+__global__ __launch_bounds__(PSI_SKIN_BLK, 6) void skin_fwd_scenes_kernel(LbsDev m, const float *__restrict__ As, const float *__restrict__ v_posed,
+                                                                        const float *__restrict__ transl, const float *__restrict__ cam_ext,
+                                                                        int B, float *__restrict__ verts, SdfPenEpilogueScenes epi)
+{
+    epi.template load_grids<NB>((int)blockIdx.y * NB, B);
+    psi_skin_fwd_body<NB, PsiBlendPipelined>(m, As, v_posed, transl, cam_ext, B, verts, epi, (int)blockIdx.x, (int)blockIdx.y * NB, (int)gridDim.x);
 }
 
 __global__ void contact_weight_table_kernel(const float *__restrict__ WT, int Vpad, const int *__restrict__ vid, int n_c, int J, float *__restrict__ Wct)
@@ -1509,6 +1579,13 @@ __global__ void sdf_to_cells_kernel(const float *__restrict__ src, float *__rest
     dst[i] = src[((size_t)ix * D + iy) * D + iz];
 }
 
+// psi_fit_set_scene_slots: the caller's slots, clamped into [0, S) (the rule of psi_lbs_sdf_counts), into the engine's own buffer
+__global__ void scene_slots_kernel(const int *__restrict__ src, int *__restrict__ dst, int B, int S)
+{
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b < B) dst[b] = min(max(src[b], 0), S - 1);
+}
+
 __global__ void adam_reset_kernel(float *m, float *v, int *step, int n)
 {
     int i = blockIdx.x * 256 + threadIdx.x;
@@ -1692,6 +1769,15 @@ struct psi_fit_engine {
     bool keep_verts;              // the forward skinning kernel stores the camera-frame vertices (only needed when !self_skin)
     bool fused_bwd;               // the skinning backward rides on fwd_scene (see fit_bwd_joint_kernel): six launches per iteration, no per-vertex backward launch
     int skin_nb;                  // bodies per workgroup of the forward skinning + SDF kernel (1 or 2: lbs_device.h)
+    // ---- several scenes (psi_fit_create_scenes; all null / 0 in a psi_fit_create engine): per scene slot an NN index and a re-ordered copy of
+    // the volume, both owned by the engine; their device descriptors as tables indexed by slot; the bodies' slots.  nn_index is scene 0's.
+    int n_scenes;                 // 0: a psi_fit_create engine (one scene, the single-scene kernels)
+    psi_nn_index **scene_index;   // [n_scenes]
+    float **scene_vol;            // [n_scenes] device
+    psikd::KdDev *d_kd_tab;       // device [n_scenes]
+    PsiSdfGrid *d_grid_tab;       // device [n_scenes]
+    int *d_slot;                  // device [B], every entry inside [0, n_scenes)
+    int kd_rows;                  // the largest traversal stack of the set (the search's LDS)
     FitGraph graphs[FIT_N_GRAPHS];
     // the captured graphs bake the statistics pointer (and the data-parallel ones the communicator) in
     const float *half_stats[2];
@@ -1775,8 +1861,18 @@ static int fit_forward(psi_fit_engine *e, float *stats, hipStream_t st, FitStats
     hipLaunchKernelGGL(fwd_scene_kernel<NB_>, dim3(n_kd + f.nsdfblk * psi_cdiv(f.B, NB_)), dim3(256), psikd::kd_lds_bytes(T.rows), st, fk, e->lv.m, \
                        e->lv.A, e->lv.v_posed, T, n_kd, nqb, T.rows, gscale, e->knobs.scene_skin_first ? 1 : 0,                                \
                        make_sdf_epilogue(f, e->grid, false, e->fused_bwd ? &e->lv : nullptr))
-        if (e->skin_nb == 2) PSI_LAUNCH_FWD_SCENE(2);
+#define PSI_LAUNCH_FWD_SCENES(NB_)                                                                                                             \
+    hipLaunchKernelGGL(fwd_scene_scenes_kernel<NB_>, dim3(n_kd + f.nsdfblk * psi_cdiv(f.B, NB_)), dim3(256), psikd::kd_lds_bytes(e->kd_rows), st, fk, \
+                       e->lv.m, e->lv.A, e->lv.v_posed, (const psikd::KdDev *)e->d_kd_tab, n_kd, nqb, e->kd_rows, gscale,                      \
+                       e->knobs.scene_skin_first ? 1 : 0,                                                                                      \
+                       make_sdf_epilogue_scenes(f, e->d_grid_tab, e->d_slot, false, e->fused_bwd ? &e->lv : nullptr))
+        if (e->n_scenes) {
+            if (e->skin_nb == 2) PSI_LAUNCH_FWD_SCENES(2);
+            else PSI_LAUNCH_FWD_SCENES(1);
+        }
+        else if (e->skin_nb == 2) PSI_LAUNCH_FWD_SCENE(2);
         else PSI_LAUNCH_FWD_SCENE(1);
+#undef PSI_LAUNCH_FWD_SCENES
 #undef PSI_LAUNCH_FWD_SCENE
         PSI_CHECK_LAUNCH("fwd_scene_kernel");
         psi_mark("fwd_scene_kernel", st);
@@ -1793,12 +1889,23 @@ static int fit_forward(psi_fit_engine *e, float *stats, hipStream_t st, FitStats
 #define PSI_LAUNCH_SKIN_FWD(NB_)                                                                                                               \
     hipLaunchKernelGGL((psi_skin_fwd_kernel<SdfPenEpilogue, NB_>), dim3(f.nsdfblk, psi_cdiv(f.B, NB_)), dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A, \
                        e->lv.v_posed, f.transl, f.cam, f.B, f.verts, make_sdf_epilogue(f, e->grid, !all_verts))
-        if (e->skin_nb == 2) PSI_LAUNCH_SKIN_FWD(2);
+#define PSI_LAUNCH_SKIN_FWD_SCENES(NB_)                                                                                                        \
+    hipLaunchKernelGGL(skin_fwd_scenes_kernel<NB_>, dim3(f.nsdfblk, psi_cdiv(f.B, NB_)), dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A, e->lv.v_posed, \
+                       f.transl, f.cam, f.B, f.verts, make_sdf_epilogue_scenes(f, e->d_grid_tab, e->d_slot, !all_verts))
+        if (e->n_scenes) {
+            if (e->skin_nb == 2) PSI_LAUNCH_SKIN_FWD_SCENES(2);
+            else PSI_LAUNCH_SKIN_FWD_SCENES(1);
+        }
+        else if (e->skin_nb == 2) PSI_LAUNCH_SKIN_FWD(2);
         else PSI_LAUNCH_SKIN_FWD(1);
+#undef PSI_LAUNCH_SKIN_FWD_SCENES
 #undef PSI_LAUNCH_SKIN_FWD
         PSI_CHECK_LAUNCH("skin_fwd_sdf_kernel");
         psi_mark("skin_fwd_sdf_kernel", st);
-        if (e->nn_index && !all_verts)                               // the contact rows in slot order: query j is row j
+        if (e->n_scenes)                                             // every body in the tree of its own scene (rows as below)
+            rc = psi_nn_index_contact_set(e->d_kd_tab, e->d_slot, e->kd_rows, all_verts ? f.verts : f.cverts, all_verts ? (long)f.V * 3 : (long)f.n_c * 3,
+                                          all_verts ? f.vid : nullptr, f.B, f.n_c, f.cconst, gscale, f.gq, f.fpart, f.nn_hint, st);
+        else if (e->nn_index && !all_verts)                               // the contact rows in slot order: query j is row j
             rc = psi_nn_index_contact(e->nn_index, f.cverts, (long)f.n_c * 3, nullptr, f.B, f.n_c, f.cconst, gscale, f.gq, f.fpart, f.nn_hint, st);
         else if (e->nn_index)
             rc = psi_nn_index_contact(e->nn_index, f.verts, (long)f.V * 3, f.vid, f.B, f.n_c, f.cconst, gscale, f.gq, f.fpart, f.nn_hint, st);
@@ -1876,11 +1983,16 @@ static int fit_backward(psi_fit_engine *e, float *stats, hipStream_t st, FitStat
     return 0;
 }
 
-extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_fit_config *cfg,
-                              const float *h_w1, const float *h_b1, const float *h_w2, const float *h_b2,
-                              const float *h_w3, const float *h_b3, const float *h_lh_comp, const float *h_rh_comp,
-                              const float *h_pose_mean, const int32_t *h_contact_ids,
-                              const float *d_scene_verts, const float *d_sdf, const float *h_gmin, const float *h_gmax)
+static int fit_build_scenes(psi_fit_engine *e, const psi_fit_scene *h_scenes, int S);
+
+// psi_fit_create (h_scenes == nullptr: the one scene of the four scene arguments) and psi_fit_create_scenes (the four arguments are those of
+// scene 0, for the fields that describe "the" scene; the kernels read the per-slot tables instead)
+static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_fit_config *cfg,
+                      const float *h_w1, const float *h_b1, const float *h_w2, const float *h_b2,
+                      const float *h_w3, const float *h_b3, const float *h_lh_comp, const float *h_rh_comp,
+                      const float *h_pose_mean, const int32_t *h_contact_ids,
+                      const float *d_scene_verts, const float *d_sdf, const float *h_gmin, const float *h_gmax,
+                      const psi_fit_scene *h_scenes, int S)
 {
     PSI_REQUIRE(out && lbs && cfg && h_w1 && h_b1 && h_w2 && h_b2 && h_w3 && h_b3 && h_lh_comp && h_rh_comp && h_pose_mean &&
                 h_contact_ids && d_scene_verts && d_sdf && h_gmin && h_gmax, "null pointer");
@@ -2013,7 +2125,8 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
         }
     }
     // (the bricked copy is addressed with 32-bit byte offsets: 512 bytes x (D / 4)^3 must stay below 4 GB, D <= 800)
-    const bool bricks = (cfg->D % 4 == 0) && cfg->D <= (PSI_SDF_CELLS ? 480 : 800) && !knobs.sdf_linear;
+    // (several scenes: one copy per scene, allocated by fit_build_scenes)
+    const bool bricks = !h_scenes && (cfg->D % 4 == 0) && cfg->D <= (PSI_SDF_CELLS ? 480 : 800) && !knobs.sdf_linear;
 #if PSI_SDF_CELLS
     size_t o_brick = bricks ? take((size_t)f.D * f.D * f.D * 32) : 0;             // D <= 480 keeps the byte offsets below 4 GB
 #else
@@ -2087,7 +2200,9 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
         return (int)err;
     }
     e->nn_ws = bl + o_nws;
-    if (cfg->nn_mode == 1) {
+    if (h_scenes) {
+        if (int rc = fit_build_scenes(e, h_scenes, S)) return rc;
+    } else if (cfg->nn_mode == 1) {
         std::vector<float> hs((size_t)f.m * 3);
         err = hipMemcpy(hs.data(), d_scene_verts, hs.size() * 4, hipMemcpyDeviceToHost);
         if (int rc = err == hipSuccess ? psi_nn_index_create(&e->nn_index, hs.data(), f.m) : (int)err) return rc;
@@ -2097,10 +2212,139 @@ extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, co
     return 0;
 }
 
+extern "C" int psi_fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_fit_config *cfg,
+                              const float *h_w1, const float *h_b1, const float *h_w2, const float *h_b2,
+                              const float *h_w3, const float *h_b3, const float *h_lh_comp, const float *h_rh_comp,
+                              const float *h_pose_mean, const int32_t *h_contact_ids,
+                              const float *d_scene_verts, const float *d_sdf, const float *h_gmin, const float *h_gmax)
+{
+    return fit_create(out, lbs, cfg, h_w1, h_b1, h_w2, h_b2, h_w3, h_b3, h_lh_comp, h_rh_comp, h_pose_mean, h_contact_ids, d_scene_verts, d_sdf,
+                      h_gmin, h_gmax, nullptr, 0);
+}
+
+// The per-scene half of psi_fit_create_scenes: NN index and re-ordered volume of every scene, the two device tables, the slot buffer (all 0).
+// On failure the partially filled arrays stay with the engine: psi_fit_destroy frees what exists.
+static int fit_build_scenes(psi_fit_engine *e, const psi_fit_scene *h_scenes, int S)
+{
+    FitDev &f = e->d;
+    e->n_scenes = S;
+    e->scene_index = new psi_nn_index *[S]();
+    e->scene_vol = new float *[S]();
+    std::vector<psikd::KdDev> kd(S);
+    std::vector<PsiSdfGrid> grids(S);
+    for (int s = 0; s < S; s++) {
+        const psi_fit_scene &sc = h_scenes[s];
+        const int D = sc.D;
+#if PSI_SDF_CELLS
+        const size_t n = (size_t)D * D * D * 8;
+#else
+        const size_t n = (size_t)(D / 4) * (D / 4) * (D / 4) * PSI_BRICK_FLOATS;
+#endif
+        hipError_t err = hipMalloc((void **)&e->scene_vol[s], n * 4);
+        if (err != hipSuccess) {
+            (void)hipGetLastError();
+            e->scene_vol[s] = nullptr;
+            psi_set_error("psi_fit_create_scenes: no memory for the copy of scene %d's volume (%zu bytes, 8 x the volume): %s", s, n * 4, hipGetErrorString(err));
+            return PSI_ENOMEM;
+        }
+#if PSI_SDF_CELLS
+        hipLaunchKernelGGL(sdf_to_cells_kernel, dim3((unsigned)psi_cdiv((long)n, 256)), dim3(256), 0, 0, sc.d_sdf, e->scene_vol[s], D);
+#else
+        hipLaunchKernelGGL(sdf_to_bricks_kernel, dim3((unsigned)psi_cdiv((long)n, 256)), dim3(256), 0, 0, sc.d_sdf, e->scene_vol[s], D);
+#endif
+        grids[s] = psi_sdf_grid_make(e->scene_vol[s], sc.gmin, sc.gmax, D, f.align_corners);
+        std::vector<float> hs((size_t)sc.m * 3);
+        err = hipMemcpy(hs.data(), sc.d_verts, hs.size() * 4, hipMemcpyDeviceToHost);
+        if (int rc = err == hipSuccess ? psi_nn_index_create(&e->scene_index[s], hs.data(), sc.m) : (int)err) {
+            if (err != hipSuccess) psi_set_error("psi_fit_create_scenes: reading scene %d's vertices failed: %s", s, hipGetErrorString(err));
+            return rc;
+        }
+        kd[s] = psi_nn_index_dev(e->scene_index[s]);
+        e->kd_rows = std::max(e->kd_rows, kd[s].rows);
+    }
+    e->nn_index = e->scene_index[0];
+    hipError_t err = hipMalloc((void **)&e->d_kd_tab, sizeof(psikd::KdDev) * S);
+    if (err == hipSuccess) err = hipMalloc((void **)&e->d_grid_tab, sizeof(PsiSdfGrid) * S);
+    if (err == hipSuccess) err = hipMalloc((void **)&e->d_slot, sizeof(int) * (size_t)f.B);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        psi_set_error("psi_fit_create_scenes: no memory for the scene tables: %s", hipGetErrorString(err));
+        return PSI_ENOMEM;
+    }
+    err = hipMemcpy(e->d_kd_tab, kd.data(), sizeof(psikd::KdDev) * S, hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(e->d_grid_tab, grids.data(), sizeof(PsiSdfGrid) * S, hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemset(e->d_slot, 0, sizeof(int) * (size_t)f.B);
+    if (err == hipSuccess) err = hipDeviceSynchronize();         // the layout kernels above ran on the NULL stream
+    if (err == hipSuccess) err = hipGetLastError();
+    if (err != hipSuccess) {
+        psi_set_error("psi_fit_create_scenes: scene tables / layout kernels failed: %s", hipGetErrorString(err));
+        return (int)err;
+    }
+    return 0;
+}
+
+extern "C" int psi_fit_create_scenes(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_fit_config *cfg,
+                                     const float *h_w1, const float *h_b1, const float *h_w2, const float *h_b2,
+                                     const float *h_w3, const float *h_b3, const float *h_lh_comp, const float *h_rh_comp,
+                                     const float *h_pose_mean, const int32_t *h_contact_ids,
+                                     const psi_fit_scene *h_scenes, int S)
+{
+    PSI_REQUIRE(out, "null pointer");
+    *out = nullptr;
+    PSI_REQUIRE(cfg, "null pointer");
+    PSI_REQUIRE(S >= 1, "psi_fit_create_scenes: S must be at least 1");
+    PSI_REQUIRE(h_scenes, "psi_fit_create_scenes: null scene table");
+    PSI_REQUIRE(cfg->nn_mode == 1, "psi_fit_create_scenes: nn_mode must be 1 (there is no brute-force search over several scenes)");
+    PSI_REQUIRE(cfg->world_size <= 1, "psi_fit_create_scenes: world_size > 1 (data-parallel runs over several scenes) is not supported");
+    for (int s = 0; s < S; s++) {
+        const psi_fit_scene &sc = h_scenes[s];
+        PSI_REQUIRE(sc.d_verts && sc.d_sdf, "psi_fit_create_scenes: null scene pointer");
+        PSI_REQUIRE(sc.m > 0, "psi_fit_create_scenes: a scene without vertices");
+        PSI_REQUIRE(sc.D >= 4 && sc.D % 4 == 0 && sc.D <= (PSI_SDF_CELLS ? 480 : 800),
+                    "psi_fit_create_scenes: D must be a multiple of 4, at most 480 (the engine samples a re-ordered copy of the volume and has no plain-volume fallback)");
+    }
+    psi_fit_config c = *cfg;                                     // (m_scene, D: ignored by contract; the shared path checks and records scene 0's)
+    c.m_scene = h_scenes[0].m;
+    c.D = h_scenes[0].D;
+    c.world_size = 1;
+    return fit_create(out, lbs, &c, h_w1, h_b1, h_w2, h_b2, h_w3, h_b3, h_lh_comp, h_rh_comp, h_pose_mean, h_contact_ids, h_scenes[0].d_verts,
+                      h_scenes[0].d_sdf, h_scenes[0].gmin, h_scenes[0].gmax, h_scenes, S);
+}
+
+extern "C" int psi_fit_scene_count(const psi_fit_engine *e) { return e ? (e->n_scenes ? e->n_scenes : 1) : 0; }
+
+extern "C" int psi_fit_set_scene_slots(psi_fit_engine *e, const int32_t *d_slot, void *stream)
+{
+    PSI_REQUIRE(e && d_slot, "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    PSI_CHECK_HIP(hipStreamIsCapturing(st, &cap));
+    PSI_REQUIRE(cap == hipStreamCaptureStatusNone, "psi_fit_set_scene_slots: not inside a stream capture (the captured iterations read the engine's own slot buffer)");
+    FitDev &f = e->d;
+    if (e->n_scenes) {
+        hipLaunchKernelGGL(scene_slots_kernel, dim3(psi_cdiv(f.B, 256)), dim3(256), 0, st, (const int *)d_slot, e->d_slot, f.B, e->n_scenes);
+        PSI_CHECK_LAUNCH("scene_slots_kernel");
+    }
+    // a hint is an index into ONE scene's cloud: against another scene it would be a wrong candidate
+    PSI_CHECK_HIP(hipMemsetAsync(f.nn_hint, 0xff, (size_t)f.B * f.n_c * 4, st));
+    return 0;
+}
+
 extern "C" void psi_fit_destroy(psi_fit_engine *e)
 {
     if (!e) return;
-    if (e->nn_index) psi_nn_index_destroy(e->nn_index);
+    if (e->scene_index) {                                        // several scenes: nn_index is scene 0's
+        for (int s = 0; s < e->n_scenes; s++)
+            if (e->scene_index[s]) psi_nn_index_destroy(e->scene_index[s]);
+        delete[] e->scene_index;
+    } else if (e->nn_index) psi_nn_index_destroy(e->nn_index);
+    if (e->scene_vol) {
+        for (int s = 0; s < e->n_scenes; s++) (void)hipFree(e->scene_vol[s]);
+        delete[] e->scene_vol;
+    }
+    (void)hipFree(e->d_kd_tab);
+    (void)hipFree(e->d_grid_tab);
+    (void)hipFree(e->d_slot);
     for (FitGraph &G : e->graphs) fit_graph_drop(&G);
     (void)hipFree(e->blob);
     delete e;

@@ -356,5 +356,15 @@ int psi_nn_index_contact(const psi_nn_index *ix, const float *verts, long vstrid
     psi_mark("kd_query_kernel", st);
     return 0;
 }
+// ... over a set of scenes: body b is searched in tab[slot[b]] (tab, slot: device; rows: the largest stack the set needs)
+int psi_nn_index_contact_set(const KdDev *tab, const int *slot, int rows, const float *verts, long vstride, const int *vid, int B, int n,
+                             float cconst, float gscale, float *gq, float *fpart, int *hint, hipStream_t st)
+{
+    hipLaunchKernelGGL((kd_query_kernel<true, true>), dim3(psi_cdiv(n, QPB), B), dim3(QBLK), kd_lds_bytes(rows), st, KdDev(), verts, vid,
+                       vstride, n, (float *)nullptr, (int *)nullptr, cconst, gscale, gq, fpart, hint, rows, tab, slot);
+    PSI_CHECK_LAUNCH("kd_query_kernel<contact, multi>");
+    psi_mark("kd_query_kernel", st);
+    return 0;
+}
 int psi_nn_index_fparts(int n) { return psi_cdiv(n, QPB); }
 psikd::KdDev psi_nn_index_dev(const psi_nn_index *ix) { return ix->d; }

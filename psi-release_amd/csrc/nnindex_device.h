@@ -490,3 +490,6 @@ static inline size_t kd_lds_bytes(int rows) { return (size_t)QPB * rows * 8; }
 
 struct psi_nn_index;
 psikd::KdDev psi_nn_index_dev(const psi_nn_index *ix);          // nnindex.hip
+// psi_nn_index_contact (psi_internal.h) over a set of scenes: body b is searched in tab[slot[b]] (both device), rows = the set's largest stack
+int psi_nn_index_contact_set(const psikd::KdDev *tab, const int *slot, int rows, const float *verts, long vstride, const int *vid, int B, int n,
+                             float cconst, float gscale, float *gq, float *fpart, int *hint, hipStream_t st);

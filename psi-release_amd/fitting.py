@@ -16,6 +16,11 @@ kept once per scene instead of ``.repeat(batch_size)`` (fitting_proxe.py:90,96);
 every iteration (cvae.py:105-109); both ``contact_id_folder`` and ``body_segments_folder`` are accepted
 (fitting_proxe.py:131 vs :238); no ``.item()`` host sync for the penetration mask (fitting_proxe.py:155).
 ``align_corners`` of the SDF lookup is explicit: True reproduces the pinned torch 1.2.0 behaviour.
+
+Several scenes in one op: ``scenes=[SceneData, ...]`` (or ``scene_sdf_paths`` / ``scene_verts_paths`` lists) next to the single-scene
+keys; ``fitting(input, scene_id=)`` / ``fitting_many(inputs, concurrency, scene_ids=)`` say which scene every body (record) is fitted
+in.  The fused engine is then built by ``psi_fit_create_scenes`` and selects kd-tree and SDF volume per body on the device; the modular
+engine samples through ``ops.sdf_sample(..., scene_id=)`` and ``ops.SceneSet``.
 """
 from __future__ import annotations
 
@@ -84,16 +89,46 @@ class FittingOP:
         self.xhr_rec = torch.randn(self.batch_size, 75, device=self.device).requires_grad_(True)
         self.optimizer = optim.Adam([self.xhr_rec], lr=self.init_lr_h)
 
-        # scene: one SDF volume and one point cloud (not replicated per batch row)
+        # scene: one SDF volume and one point cloud (not replicated per batch row) — or a list of them, one scene slot each
+        t = lambda a: torch.tensor(np.asarray(a), dtype=torch.float32, device=self.device)
         scene = getattr(self, 'scene', None)
+        scene_list = getattr(self, 'scenes', None)
+        sdf_paths, verts_paths = getattr(self, 'scene_sdf_paths', None), getattr(self, 'scene_verts_paths', None)
+        self._scene_tab = None
+        if scene_list is not None or sdf_paths is not None or verts_paths is not None:
+            if scene_list is None:
+                if sdf_paths is None or verts_paths is None or len(sdf_paths) != len(verts_paths):
+                    raise ValueError('scene_sdf_paths and scene_verts_paths must be lists of the same length')
+                from .synth import SceneData
+                scene_list = []
+                for sp, vp in zip(sdf_paths, verts_paths):
+                    sdf_s, gmin_s, gmax_s, _ = scene_io.read_sdf(sp)
+                    scene_list.append(SceneData(scene_io.read_ply_vertices(vp), sdf_s, np.asarray(gmin_s), np.asarray(gmax_s), int(np.asarray(sdf_s).shape[0]), None))
+            scene_list = list(scene_list)
+            if not scene_list:
+                raise ValueError('scenes: an empty list')
+            # the contact vertex ids belong to the BODY: every scene must name the same ones
+            parts0 = scene_list[0].contact_parts
+            for sc in scene_list[1:]:
+                if (sc.contact_parts is None) != (parts0 is None) or (parts0 is not None and any(
+                        list(sc.contact_parts.get(p, {}).get('verts_ind', [])) != list(parts0.get(p, {}).get('verts_ind', [None]))
+                        for p in self.contact_part)):
+                    raise ValueError('scenes: all scenes of one FittingOP must list the same contact parts (the contact ids belong to the body)')
+            self._scene_tab = [{'sdf': t(sc.sdf).contiguous(), 'verts': t(sc.verts).reshape(-1, 3).contiguous(),
+                                'gmin': np.asarray(sc.grid_min, np.float32).reshape(3), 'gmax': np.asarray(sc.grid_max, np.float32).reshape(3)}
+                               for sc in scene_list]
+            scene = scene_list[0]               # (the single-scene fields below describe scene 0)
+        self.n_scenes = len(self._scene_tab) if self._scene_tab else 1
+        self._slot_host = np.zeros(self.batch_size, np.int32)          # scene slot per body
+        self._slot_dev = torch.zeros(self.batch_size, dtype=torch.int32, device=self.device)
+        self._scene_set = None
         if scene is not None:
             sdf, grid_min, grid_max, scene_verts = scene.sdf, scene.grid_min, scene.grid_max, scene.verts
-            self._contact_parts = scene.contact_parts
+            self._contact_parts = scene.contact_parts or None
         else:
             sdf, grid_min, grid_max, _ = scene_io.read_sdf(self.scene_sdf_path)
             scene_verts = scene_io.read_ply_vertices(self.scene_verts_path)
             self._contact_parts = None
-        t = lambda a: torch.tensor(np.asarray(a), dtype=torch.float32, device=self.device)
         self.s_grid_min_batch = t(grid_min).unsqueeze(0)
         self.s_grid_max_batch = t(grid_max).unsqueeze(0)
         self.s_sdf = t(sdf).unsqueeze(0).contiguous()                  # [1,D,D,D]
@@ -119,6 +154,57 @@ class FittingOP:
             self._vid = torch.tensor(np.asarray(vid).astype(np.int64), device=self.device)
         return self._vid
 
+    # ---- several scenes ---------------------------------------------------------------------
+    def scene_slots(self, scene_id, n=None):
+        """``scene_id`` (an int, or one int per body) as a checked int32 array of ``n`` (default batch_size) scene slots."""
+        n = self.batch_size if n is None else n
+        a = np.asarray(scene_id.detach().cpu().numpy() if torch.is_tensor(scene_id) else scene_id)
+        if a.ndim == 0:
+            a = np.full(n, int(a))
+        if a.shape != (n,):
+            raise ValueError('scene_id must be an int or hold %d entries, got shape %s' % (n, a.shape))
+        if a.size and (a.min() < 0 or a.max() >= self.n_scenes):
+            raise ValueError('scene_id outside [0, %d)' % self.n_scenes)
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def set_scene_ids(self, scene_id):
+        """Body b of the following fits lives in scene ``scene_id[b]``; the choice holds until it is changed."""
+        self._slot_host = self.scene_slots(scene_id)
+        self._slot_dev = torch.tensor(self._slot_host, dtype=torch.int32, device=self.device)
+
+    def _scene_contact_dist(self, xyz):
+        """dist1 [B,n] of every body's contact vertices against ITS scene's cloud (ops.SceneSet: one launch, per-body slot)."""
+        if self._scene_set is None:
+            # one table [S,m,3]: shorter clouds are padded with copies of their last point, which changes no nearest distance
+            mmax = max(sc['verts'].shape[0] for sc in self._scene_tab)
+            tab = torch.stack([torch.cat([sc['verts'], sc['verts'][-1:].expand(mmax - sc['verts'].shape[0], 3)]) for sc in self._scene_tab])
+            self._scene_set = ops.SceneSet(tab.contiguous(), self.device)
+        return ops.chamfer_to_scenes(xyz, self._scene_set, self._slot_dev)
+
+    def _scene_sdf(self, verts):
+        """SDF values [B,V] of every body in ITS scene's volume (ops.sdf_sample with scene_id).  A table [S,D,D,D] needs one D: scenes are
+        grouped by their D, one lookup per group over the bodies that live in it."""
+        groups = {}
+        for si, sc in enumerate(self._scene_tab):
+            groups.setdefault(int(sc['sdf'].shape[0]), []).append(si)
+        pieces, rows_all = [], []
+        for D, members in sorted(groups.items()):
+            local = {si: k for k, si in enumerate(members)}
+            rows = [b for b in range(self.batch_size) if int(self._slot_host[b]) in local]
+            if not rows:
+                continue
+            tab = torch.stack([self._scene_tab[si]['sdf'] for si in members])
+            gmin = torch.tensor(np.stack([self._scene_tab[si]['gmin'] for si in members]), device=self.device)
+            gmax = torch.tensor(np.stack([self._scene_tab[si]['gmax'] for si in members]), device=self.device)
+            sid = torch.tensor([local[int(self._slot_host[b])] for b in rows], dtype=torch.int32, device=self.device)
+            v = verts if len(rows) == self.batch_size else verts[torch.tensor(rows, device=self.device)]
+            pieces.append(ops.sdf_sample(v.contiguous(), tab, gmin, gmax, scene_id=sid, align_corners=self.align_corners))
+            rows_all += rows
+        out = torch.cat(pieces) if len(pieces) > 1 else pieces[0]
+        if rows_all != list(range(self.batch_size)):
+            out = out[torch.tensor(np.argsort(np.asarray(rows_all)), device=self.device)]
+        return out
+
     def body_verts(self, xh_rec, cam_ext):
         body_param_rec = BodyParamParser.body_params_encapsulate_batch(xh_rec)
         joint_rot_batch = self.vposer.decode(body_param_rec['body_pose_vp'], output_type='aa').view(xh_rec.shape[0], -1)
@@ -135,7 +221,9 @@ class FittingOP:
 
         body_verts_batch = self.body_verts(xh_rec, cam_ext)
         body_verts_contact_batch = body_verts_batch[:, self.contact_vertex_ids(), :]
-        if self.nn_mode == 'kdtree':
+        if self.n_scenes > 1:
+            contact_dist = self._scene_contact_dist(body_verts_contact_batch.contiguous())
+        elif self.nn_mode == 'kdtree':
             if getattr(self, '_nn_index', None) is None:
                 self._nn_index = ops.SceneNNIndex(self.s_verts[0], self.device)
             contact_dist = ops.chamfer_to_scene(body_verts_contact_batch.contiguous(), self._nn_index)
@@ -144,8 +232,11 @@ class FittingOP:
         s = torch.sqrt(contact_dist + 1e-4)
         loss_contact = self.weight_contact * torch.mean(s / (s + self.contact_const))
 
-        body_sdf_batch = ops.sdf_sample(body_verts_batch, self.s_sdf, self.s_grid_min_batch, self.s_grid_max_batch,
-                                        scene_id=None, align_corners=self.align_corners)
+        if self.n_scenes > 1:
+            body_sdf_batch = self._scene_sdf(body_verts_batch)
+        else:
+            body_sdf_batch = ops.sdf_sample(body_verts_batch, self.s_sdf, self.s_grid_min_batch, self.s_grid_max_batch,
+                                            scene_id=None, align_corners=self.align_corners)
         if self.dp_world() > 1:
             # data-parallel batch: global-batch normalisers through ONE all-reduce (dist.py)
             loss_rec, loss_vposer, loss_contact, pen = psi_dist.fitting_loss_reduce(loss_rec, loss_vposer, loss_contact,
@@ -178,8 +269,11 @@ class FittingOP:
             return _FusedRunner(self, xhr, self._camera(self.cam_ext))
         return _ModularRunner(self, xhr, self._camera(self.cam_ext))
 
-    def fitting(self, input_data_file):
-        """fitting_proxe.py:167-195; ``input_data_file`` is a pkl path or the already-loaded dict."""
+    def fitting(self, input_data_file, scene_id=None):
+        """fitting_proxe.py:167-195; ``input_data_file`` is a pkl path or the already-loaded dict.  ``scene_id`` (an op with several
+        scenes): the scene of the bodies, an int or one per body; None keeps the last choice (all 0 at first)."""
+        if scene_id is not None:
+            self.set_scene_ids(scene_id)
         runner = self.make_step_runner(input_data_file)
         if not self.verbose:
             runner.steps(self.num_iter)                 # fused engine: the loop is device-resident, 10 iterations per graph launch
@@ -192,14 +286,15 @@ class FittingOP:
         print('[INFO][fitting] fitting finish, returning optimal value')
         return GeometryTransformer.convert_to_3D_rot(self.xhr_rec)
 
-    def fitting_many(self, inputs, concurrency=4):
+    def fitting_many(self, inputs, concurrency=4, scene_ids=None):
         """Fit a list of INDEPENDENT generated-body records (pkl paths or dicts; what the entry points' file loop feeds one at a time,
         fitting_proxe.py:252-263) with up to ``concurrency`` engine runs in flight: every run has its own fused engine and HIP stream, so
         the latency-bound kernels of different runs overlap on the GPU (the reference's batch size per file is 1: a single file leaves
         most of the chip idle).  With ``independent_bodies=True`` the engine normalises every loss per body, and the records are PACKED:
         ``batch_size // bodies_per_record`` files form one engine run that equals fitting them one by one — 32 files per 0.16 ms
         iteration instead of one.  Per-file semantics are unchanged except that every run starts from a fresh Adam state (the reference
-        carries one optimizer across the files of a scene).  Returns the fitted 72-D body vectors per file, in input order, and the
+        carries one optimizer across the files of a scene).  ``scene_ids`` (an op with several scenes): one scene slot per record; packed
+        runs may mix records of different scenes.  Returns the fitted 72-D body vectors per file, in input order, and the
         per-file cameras."""
         if self.engine != 'fused':
             raise ValueError('fitting_many needs engine="fused"')
@@ -229,9 +324,12 @@ class FittingOP:
         else:
             pack = 1
         n_real = len(recs)
+        rec_slots = list(self.scene_slots(scene_ids if scene_ids is not None else 0, n_real))
         while len(recs) % pack:                                                # the last run is padded with copies of the last record
             recs.append(recs[-1])
+            rec_slots.append(rec_slots[-1])
         B = nb_rec
+        slot_all = torch.tensor(np.repeat(np.asarray(rec_slots, np.int32), B), dtype=torch.int32, device=self.device)          # [N*B]
         xh_all = torch.tensor(np.concatenate([np.concatenate([np.asarray(r[k], dtype=np.float32).reshape(B, -1) for k in keys], axis=1) for r in recs]),
                               dtype=torch.float32, device=self.device)
         def cam_rows(r):
@@ -268,6 +366,7 @@ class FittingOP:
         for i in range(n_runs):
             eng = engines[i % K]
             xs = xhr_all[i * R:(i + 1) * R]
+            eng.set_scene_slots(slot_all[i * R:(i + 1) * R])
             hip.check(L.psi_fit_set_problem(eng.handle, hip.ptr(xs), hip.ptr(xs), hip.ptr(cam_run[i * R:(i + 1) * R]), 1, eng.stream.cuda_stream),
                       'psi_fit_set_problem')
             eng.iterate(self.num_iter, self.use_graph)
@@ -371,14 +470,34 @@ class FusedEngine:
         self._keep = (op.s_verts, op.s_sdf)                    # device arrays the engine points into
         h = ctypes.c_void_p()
         p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        # several scenes (or scene_table_engine=True: the same engine over a table of one): psi_fit_create_scenes, scene selected per body
+        tab = getattr(op, '_scene_tab', None)
+        self.n_scenes = len(tab) if tab and (len(tab) > 1 or getattr(op, 'scene_table_engine', False)) else 0
         with torch.cuda.device(dev):
-            hip.check(hip.lib().psi_fit_create(ctypes.byref(h), bm.lbs_model.handle, ctypes.byref(cfg), p(w1), p(b1), p(w2), p(b2),
-                                               p(w3), p(b3), p(lhc), p(rhc), p(pm), p(vid), hip.ptr(op.s_verts), hip.ptr(op.s_sdf),
-                                               p(gmin), p(gmax)), 'psi_fit_create')
+            if self.n_scenes:
+                arr = (hip.FitScene * self.n_scenes)()
+                for s_, sc in zip(arr, tab):
+                    s_.d_verts, s_.d_sdf, s_.m, s_.D = hip.ptr(sc['verts']), hip.ptr(sc['sdf']), sc['verts'].shape[0], sc['sdf'].shape[0]
+                    s_.gmin[:], s_.gmax[:] = [float(v) for v in sc['gmin']], [float(v) for v in sc['gmax']]
+                self._keep = tuple(tab)
+                hip.check(hip.lib().psi_fit_create_scenes(ctypes.byref(h), bm.lbs_model.handle, ctypes.byref(cfg), p(w1), p(b1), p(w2), p(b2),
+                                                          p(w3), p(b3), p(lhc), p(rhc), p(pm), p(vid), arr, self.n_scenes), 'psi_fit_create_scenes')
+            else:
+                hip.check(hip.lib().psi_fit_create(ctypes.byref(h), bm.lbs_model.handle, ctypes.byref(cfg), p(w1), p(b1), p(w2), p(b2),
+                                                   p(w3), p(b3), p(lhc), p(rhc), p(pm), p(vid), hip.ptr(op.s_verts), hip.ptr(op.s_sdf),
+                                                   p(gmin), p(gmax)), 'psi_fit_create')
         self.handle = h
         self.stream = torch.cuda.Stream(device=dev)
         self.stats = torch.zeros(8, device=dev)
         self.max_history = 4096
+
+    def set_scene_slots(self, slot):
+        """Scene slot per body (int32 device [B]) from the next set_problem on; an engine with one scene has nothing to select."""
+        if not self.n_scenes:
+            return
+        self._slots = slot.contiguous()
+        self.stream.wait_stream(torch.cuda.current_stream())
+        hip.check(hip.lib().psi_fit_set_scene_slots(self.handle, hip.ptr(self._slots), self.stream.cuda_stream), 'psi_fit_set_scene_slots')
 
     def set_problem(self, xhr, x_init, cam, reset):
         B = self.op.batch_size
@@ -386,6 +505,8 @@ class FusedEngine:
             raise ValueError('FusedEngine was built for batch_size=%d: expected body vectors of shape (%d, 75), got %s / %s (a generated-body '
                              'pkl must hold batch_size rows)' % (B, B, tuple(xhr.shape), tuple(x_init.shape)))
         cam = expand_cam_ext(cam, B)
+        if self.n_scenes:
+            self.set_scene_slots(self.op._slot_dev)
         cur = torch.cuda.current_stream()
         self.stream.wait_stream(cur)
         self._args = (xhr.contiguous(), x_init.contiguous(), cam.contiguous())

@@ -56,6 +56,9 @@ SIGNATURES = {
     'psi_adam_step': (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p] + [c_double] * 5 + [c_void_p]),
     'psi_fit_create': (c_int, [c_void_p] * 17),
     'psi_fit_destroy': (None, [c_void_p]),
+    'psi_fit_create_scenes': (c_int, [c_void_p] * 14 + [c_int]),
+    'psi_fit_set_scene_slots': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'psi_fit_scene_count': (c_int, [c_void_p]),
     'psi_fit_set_problem': (c_int, [c_void_p] * 4 + [c_int, c_void_p]),
     'psi_fit_forward': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     'psi_fit_backward_step': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
@@ -126,6 +129,12 @@ class FitConfig(ctypes.Structure):
                 ('contact_const', c_float), ('lr', c_float), ('beta1', c_float), ('beta2', c_float), ('eps', c_float),
                 ('independent_bodies', c_int), ('concurrent_engines', c_int),
                 ('lr_d', ctypes.c_double), ('beta1_d', ctypes.c_double), ('beta2_d', ctypes.c_double)]
+
+
+class FitScene(ctypes.Structure):
+    """struct psi_fit_scene (include/psi_hip.h): one scene of psi_fit_create_scenes."""
+    _fields_ = [('d_verts', c_void_p), ('d_sdf', c_void_p), ('m', c_int), ('D', c_int),
+                ('gmin', c_float * 3), ('gmax', c_float * 3)]
 
 
 class PsiHipError(RuntimeError):

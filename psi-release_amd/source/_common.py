@@ -44,7 +44,12 @@ def fit_files(fop_cls, fittingconfig, lossconfig, gen_dir, fit_dir, max_files, s
     optimizer for every run, whereas the default file loop carries one optimizer across the files of a scene like the reference,
     fitting_proxe.py:73-74), at the cost of one.
     shard='rows' : every rank opens every file and fits rows [r*B/world, (r+1)*B/world) of its B bodies; the loss normalisers are
-    global through the one all-reduce per iteration (psi_release_amd/dist.py), rank 0 gathers the rows and writes the pkl."""
+    global through the one all-reduce per iteration (psi_release_amd/dist.py), rank 0 gathers the rows and writes the pkl.
+    ACROSS SCENES: `gen_dir` / `fit_dir` are LISTS with one directory per scene slot of the op (whose config lists the scenes:
+    scene_sdf_paths / scene_verts_paths or scenes) — one FittingOP over all scenes, the files of all of them packed together into
+    runs (run_plan.plan_runs), outputs in the same per-scene directories under the same skip-if-exists rule."""
+    if isinstance(gen_dir, (list, tuple)):
+        return _fit_files_across_scenes(fop_cls, fittingconfig, lossconfig, list(gen_dir), list(fit_dir), max_files, shard, rank, world, concurrency, pack)
     import os
     import pickle
     import torch
@@ -101,3 +106,44 @@ def fit_files(fop_cls, fittingconfig, lossconfig, gen_dir, fit_dir, max_files, s
             for inp, outp in mine:
                 fop.save_result(fop.fitting(inp), outp)
     return len(todo)
+
+
+def _fit_files_across_scenes(fop_cls, fittingconfig, lossconfig, gen_dirs, fit_dirs, max_files, shard, rank, world, concurrency, pack):
+    import torch
+    from psi_release_amd.run_plan import plan_runs
+    B = fittingconfig['batch_size']
+    if shard != 'files' or not (pack > 1 or B == 1):
+        raise SystemExit('--across_scenes packs INDEPENDENT files of different scenes into one run: it needs --shard files and --pack > 1 '
+                         '(or --batch_size 1)')
+    if len(gen_dirs) != len(fit_dirs):
+        raise ValueError('one output directory per scene')
+    cfg = dict(fittingconfig)
+    cfg['data_parallel'] = False
+    if pack > 1:
+        cfg['batch_size'] = B * pack
+        cfg['independent_bodies'] = True
+    fop = fop_cls(cfg, lossconfig)
+    work = []
+    for gen_dir, fit_dir in zip(gen_dirs, fit_dirs):
+        lst = []
+        for ii in range(max_files):
+            inp = os.path.join(gen_dir, 'body_gen_{:06d}.pkl'.format(ii))
+            outp = os.path.join(fit_dir, 'body_gen_{:06d}.pkl'.format(ii))
+            if os.path.exists(inp) and not os.path.exists(outp):
+                lst.append((inp, outp))
+        work.append(lst)
+    if world > 1:                      # all ranks must agree on the work lists
+        box = [work]
+        torch.distributed.broadcast_object_list(box, src=0)
+        work = box[0]
+    n_all = sum(len(lst) for lst in work)
+    if world > 1:                      # file-sharded: rank r takes every world-th file of every scene
+        work = [lst[rank::world] for lst in work]
+    records, runs = plan_runs(work, pack)
+    if records:
+        order = [pair for run in runs for pair in run][:len(records)]          # (the padding copies sit at the end of the last run)
+        results, cams = fop.fitting_many([records[i][0] for i, _ in order], concurrency, scene_ids=[s for _, s in order])
+        for (i, _), xh, (cam_ext, cam_int) in zip(order, results, cams):
+            fop.cam_ext, fop.cam_int = cam_ext, cam_int
+            fop.save_result(xh, records[i][1])
+    return n_all

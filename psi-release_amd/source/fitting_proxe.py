@@ -41,6 +41,10 @@ def main(argv=None):
     ap.add_argument('--reset_optimizer', action='store_true',
                     help='fresh Adam state for every file (the reference carries one optimizer across the files of a scene, fitting_proxe.py:73-74; '
                          'with --shard files the carried state depends on which files a rank sees)')
+    ap.add_argument('--across_scenes', action='store_true',
+                    help='ONE FittingOP over all --scenes: the files of all scenes are packed together into engine runs, every body fitted in its own '
+                         'scene (needs --shard files and --pack > 1 or --batch_size 1; outputs as without the flag: per-scene directories, '
+                         'existing files skipped, a fresh Adam state per file)')
     ap.add_argument('--save_all_rows', action='store_true', help='batch_size > 1: write every fitted row (the reference keeps the last one)')
     a = ap.parse_args(argv)
     rank, world = _common.dist_setup()
@@ -52,7 +56,21 @@ def main(argv=None):
             torch.distributed.barrier()
         a.proxe_path, a.gen_path, extra['smplx_data'], extra['vposer_state'] = _common.synthetic_prox_tree(
             a.synthetic, a.scenes, batch=a.batch_size, write=False)
-    for scenename in a.scenes:
+    lossconfig = {'weight_loss_rec': 1, 'weight_loss_vposer': 0.01, 'weight_contact': 0.1, 'weight_collision': 0.5}
+    if a.across_scenes:
+        fittingconfig = {
+            'scene_verts_paths': [os.path.join(a.proxe_path, 'scenes_downsampled/' + sc + '.ply') for sc in a.scenes],
+            'scene_sdf_paths': [os.path.join(a.proxe_path, 'scenes_sdf/' + sc) for sc in a.scenes],
+            'human_model_path': a.human_model_path, 'vposer_ckpt_path': a.vposer_ckpt_path,
+            'init_lr_h': a.init_lr_h, 'num_iter': a.num_iter, 'batch_size': a.batch_size,
+            'device': torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu'),
+            'contact_part': ['back', 'butt', 'L_Hand', 'R_Hand', 'L_Leg', 'R_Leg', 'thighs'],
+            'contact_id_folder': os.path.join(a.proxe_path, 'body_segments'), 'verbose': a.verbose,
+            'engine': a.engine, 'align_corners': bool(a.align_corners), 'save_all_rows': a.save_all_rows, 'reset_optimizer': a.reset_optimizer}
+        fittingconfig.update(extra)
+        _common.fit_files(FittingOP, fittingconfig, lossconfig, [os.path.join(a.gen_path, sc) for sc in a.scenes],
+                          [os.path.join(a.fit_path, sc) for sc in a.scenes], a.max_files, a.shard, rank, world, a.concurrency, a.pack)
+    for scenename in ([] if a.across_scenes else a.scenes):
         fittingconfig = {
             'scene_verts_path': os.path.join(a.proxe_path, 'scenes_downsampled/' + scenename + '.ply'),
             'scene_sdf_path': os.path.join(a.proxe_path, 'scenes_sdf/' + scenename),
@@ -63,7 +81,6 @@ def main(argv=None):
             'contact_id_folder': os.path.join(a.proxe_path, 'body_segments'), 'verbose': a.verbose,
             'engine': a.engine, 'align_corners': bool(a.align_corners), 'save_all_rows': a.save_all_rows, 'reset_optimizer': a.reset_optimizer}
         fittingconfig.update(extra)
-        lossconfig = {'weight_loss_rec': 1, 'weight_loss_vposer': 0.01, 'weight_contact': 0.1, 'weight_collision': 0.5}
         _common.fit_files(FittingOP, fittingconfig, lossconfig, os.path.join(a.gen_path, scenename), os.path.join(a.fit_path, scenename),
                           a.max_files, a.shard, rank, world, a.concurrency, a.pack)
     if world > 1:
