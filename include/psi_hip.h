@@ -497,6 +497,39 @@ int psi_kmeans_read(psi_kmeans *km, float *book, int32_t *k_eff, double *avg_dis
 /* scipy.cluster.vq.vq: code[i] = lowest index of the nearest row of book [k,d], dist[i] = its Euclidean distance (nullable). */
 int psi_vq(const float *obs, int N, int d, const float *book, int k, int32_t *code, float *dist, void *stream);
 
+/* ---- scene snapshots: depth / triangle id / label images of a triangle mesh (utils/utils_prox_snapshots_virtualcam.py:342-378, 502-541) ----
+ * A tile-binned rasteriser with exact integer coverage; every view of a call is rendered by the same launches.  Arithmetic (fp32, not
+ * contracted; DESIGN.md "Snapshot rasteriser" has the full statement):
+ *   camera space  xc = ((m00*X + m01*Y) + m02*Z) + m03 (yc, zc alike) with the view's world-to-camera rows m; the camera looks along +z,
+ *                 x right, y down
+ *   near clip     a vertex is inside when zc >= near_z; a triangle crossing the plane becomes one or two pieces; a new vertex is computed
+ *                 from the inside vertex a towards the outside vertex b: t = (near_z - za)/(zb - za), p = a + t*(b - a)
+ *   projection    u = (fx*xc)/zc + cx, U = (int)rintf(u*256) (IEEE division, round half to even), v / V alike; a piece with |U| or |V| above
+ *                 2^28 is not drawn and is counted; pieces of integer area 0 are dropped; both windings are drawn
+ *   coverage      sample (256*px + 128, 256*py + 128), int64 edge functions, top-left rule
+ *   depth         li = (float)ei/(float)area, 1/z = (l0/z0 + l1/z1) + l2/z2; the pixel keeps the minimum of (bits of z) << 32 | triangle
+ *                 index, so the images do not depend on the order of the work and equal depths go to the lower index
+ * No floating-point atomics: the three images are bit-identical from run to run, for any batching of the views.
+ *
+ * psi_raster_mesh_create copies verts [nv,3] fp32, faces [nf,3] int32 and vlabel [nv] fp32 (NULL: all labels 0) from device memory and
+ * checks every face index (PSI_EINVAL outside [0, nv)); it synchronises the device, like psi_kmeans_create. */
+typedef struct psi_raster_mesh psi_raster_mesh;
+int psi_raster_mesh_create(psi_raster_mesh **out, const float *d_verts, const int32_t *d_faces, const float *d_vlabel, int nv, int nf);
+void psi_raster_mesh_destroy(psi_raster_mesh *mesh);
+/* Host function: bytes of the workspace of one psi_raster_render call (piece records, tile counts, bins). */
+size_t psi_raster_workspace_bytes(int nf, int n_views, int W, int H);
+/* d_w2c [n_views,3,4] fp32 world-to-camera rows; d_intr [n_views,4] fp32 = fx, fy, cx, cy; W, H <= 4096; near_z > 0.
+ * Outputs (device, overwritten): d_depth [n_views,H,W] fp32, z of the winner or 0.0f where nothing was hit; d_tri [n_views,H,W] int32, the
+ * triangle index or -1; d_seg [n_views,H,W] fp32 or NULL, z * ((l0*lab0/z0 + l1*lab1/z1) + l2*lab2/z2), the perspective-correct vertex
+ * label, or 0; d_stats [n_views,2] int32 = { (tile, piece) pairs binned, pieces not drawn because of the 2^28 guard }.
+ * d_workspace: psi_raster_workspace_bytes(nf, n_views, W, H) bytes, or NULL for the library's per-stream scratch.  The bins are sized from
+ * the counts, which the host reads: the call synchronises the stream once, after the binning counts (it cannot be captured into a graph);
+ * a call whose pairs exceed the workspace's bin space takes the bins from a buffer that the mesh object owns and grows.  Because of that
+ * buffer a mesh object is rendered by ONE call at a time: calls on the same mesh from several threads or streams must be serialised by the
+ * caller (different mesh objects are independent).  A view with 2^31 or more pairs is refused (PSI_EINVAL). */
+int psi_raster_render(psi_raster_mesh *mesh, const float *d_w2c, const float *d_intr, int n_views, int W, int H, float near_z,
+                      float *d_depth, int32_t *d_tri, float *d_seg, int32_t *d_stats, void *d_workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

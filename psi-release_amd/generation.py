@@ -137,6 +137,26 @@ class TestOP:
             bodies = self.sample_view(depth, seg, t(cam_params['cam_int']).unsqueeze(0), t(cam_params['cam_ext']).unsqueeze(0), max_d, latents=lat)
             self.write(bodies, self.outdir, self.n_samples * ii)
 
+    def test_mesh(self, mesh, cam_ext, cam_int, size, near=0.05):
+        """From a scene mesh to ``body_gen_*.pkl`` with no image files in between: ``mesh`` (a ``rendering.SceneMesh``) is rendered from all
+        the cameras in one call (cam_ext [n,4,4] camera-to-world, cam_int [n,3,3] or [3,3], size = (H, W)), then every view goes through the
+        steps of ``test_habitat`` — the same files as ``rendering.write_sensor_folder`` followed by ``test_habitat`` on that folder."""
+        from .rendering import SnapshotRenderer
+        if not self._loaded:
+            self.load()
+        ext = np.asarray(cam_ext.detach().cpu().numpy() if torch.is_tensor(cam_ext) else cam_ext).reshape(-1, 4, 4)
+        K = np.asarray(cam_int.detach().cpu().numpy() if torch.is_tensor(cam_int) else cam_int)
+        K = np.broadcast_to(K, (len(ext), 3, 3)) if K.ndim == 2 else K.reshape(len(ext), 3, 3)
+        depth_all, seg_all, _ = SnapshotRenderer(mesh).render(ext, K, size, near)
+        t = lambda a: torch.tensor(np.asarray(a, np.float32), dtype=torch.float32, device=self.device)
+        for ii in range(len(ext)):
+            depth0, seg0 = depth_all[ii].to(self.device).clone(), seg_all[ii].to(self.device).clone()
+            depth, _, max_d = data_preprocessing(depth0, 'depth', [128, 128])
+            seg, _, _ = data_preprocessing(seg0, 'depth', [128, 128])          # sic: 'depth', as test_habitat
+            lat = self.latent_source(ii, self.n_samples) if self.latent_source is not None else None
+            bodies = self.sample_view(depth, seg, t(K[ii]).unsqueeze(0), t(ext[ii]).unsqueeze(0), max_d, latents=lat)
+            self.write(bodies, self.outdir, self.n_samples * ii)
+
     def test_proxe(self, test_data, scene_name):
         """test_proxe_s1.py:74-134: ``test_data`` = (depth, seg, max_d, cam_int, cam_ext) of one snapshot; files start at 900."""
         if not self._loaded:

@@ -118,6 +118,10 @@ SIGNATURES = {
     'psi_kmeans_iterate': (c_int, [c_void_p, c_int, c_void_p]),
     'psi_kmeans_read': (c_int, [c_void_p] * 7),
     'psi_vq': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'psi_raster_mesh_create': (c_int, [c_void_p] * 4 + [c_int, c_int]),
+    'psi_raster_mesh_destroy': (None, [c_void_p]),
+    'psi_raster_workspace_bytes': (c_size_t, [c_int] * 4),
+    'psi_raster_render': (c_int, [c_void_p] * 3 + [c_int, c_int, c_int, c_float] + [c_void_p] * 6),
 }
 
 

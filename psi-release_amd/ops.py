@@ -931,3 +931,47 @@ def scene_losses(body_verts, vid, scenes: SceneSet, slot, sdf, grid_min, grid_ma
     out = _SceneLosses.apply(body_verts, vid, scenes, slot, sdf.contiguous().float(), grid_min.reshape(-1, 3).contiguous().float(),
                              grid_max.reshape(-1, 3).contiguous().float(), align_corners, w_contact, w_collision, gate, vid32)
     return out[0], out[1]
+
+
+# ------------------------------------------------------------------------------------------
+# Scene snapshots (psi_raster_*)
+# ------------------------------------------------------------------------------------------
+def raster_mesh_create(verts, faces, vertex_labels=None):
+    """Upload-side half of ``rendering.SceneMesh``: verts [nv,3] fp32, faces [nf,3] int32, vertex_labels [nv] fp32 or None, all on the GPU.
+    Returns the ``psi_raster_mesh`` handle (free it with ``raster_mesh_destroy``)."""
+    import ctypes
+    if verts.dtype != torch.float32 or faces.dtype != torch.int32 or verts.dim() != 2 or faces.dim() != 2 or verts.shape[1] != 3 or faces.shape[1] != 3:
+        raise ValueError('expected verts [nv,3] float32 and faces [nf,3] int32')
+    if vertex_labels is not None and (vertex_labels.dtype != torch.float32 or vertex_labels.shape != (verts.shape[0],)):
+        raise ValueError('expected vertex_labels [nv] float32')
+    h = ctypes.c_void_p()
+    pv, pf, pl = hip.ptr(verts), hip.ptr(faces), hip.ptr(vertex_labels)
+    with torch.cuda.device(verts.device):
+        hip.check(hip.lib().psi_raster_mesh_create(ctypes.byref(h), pv, pf, pl, verts.shape[0], faces.shape[0]), 'psi_raster_mesh_create')
+    return h
+
+
+def raster_mesh_destroy(handle):
+    if handle:
+        hip.lib().psi_raster_mesh_destroy(handle)
+
+
+def raster_render(handle, nf, w2c, intr, size, near=0.05, with_seg=True):
+    """All views of one call through the tile-binned rasteriser (include/psi_hip.h: psi_raster_render).
+
+    w2c [n,3,4] fp32 world-to-camera rows, intr [n,4] fp32 = fx, fy, cx, cy, size = (H, W).  Returns depth [n,H,W] fp32 (0 = no hit),
+    tri [n,H,W] int32 (-1 = no hit), seg [n,H,W] fp32 or None, stats [n,2] int32 (binned pairs, pieces dropped by the 2^28 guard)."""
+    pw, pi = hip.ptr(w2c), hip.ptr(intr)
+    if w2c.dtype != torch.float32 or intr.dtype != torch.float32 or w2c.dim() != 3 or tuple(w2c.shape[1:]) != (3, 4) or tuple(intr.shape) != (w2c.shape[0], 4):
+        raise ValueError('expected w2c [n,3,4] and intr [n,4], float32')
+    n, (H, W), dev = w2c.shape[0], (int(size[0]), int(size[1])), w2c.device
+    depth = torch.empty(n, H, W, device=dev)
+    tri = torch.empty(n, H, W, dtype=torch.int32, device=dev)
+    seg = torch.empty(n, H, W, device=dev) if with_seg else None
+    stats = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    L = hip.lib()
+    ws = torch.empty(max(L.psi_raster_workspace_bytes(nf, n, W, H), 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        hip.check(L.psi_raster_render(handle, pw, pi, n, W, H, float(near), hip.ptr(depth), hip.ptr(tri), hip.ptr(seg), hip.ptr(stats),
+                                      hip.ptr(ws), hip.stream()), 'psi_raster_render')
+    return depth, tri, seg, stats

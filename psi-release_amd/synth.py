@@ -252,3 +252,105 @@ def make_cvae_inputs(seed: int = 13, B: int = 4) -> dict:
             'x75': _f32(rs.standard_normal((B, 75)) * 0.5),
             'eps32': _f32(rs.standard_normal((B, 32))),
             'eps32b': _f32(rs.standard_normal((B, 32)))}
+
+
+@dataclass
+class RoomMesh:
+    verts: np.ndarray        # [nv,3] fp32, z up, the floor at z = 0
+    faces: np.ndarray        # [nf,3] int32; the first n_room_faces are the closed room box
+    labels: np.ndarray       # [nv] fp32 semantic label per vertex (mpcat40-style ids, 0..41)
+    n_room_faces: int
+    box_min: np.ndarray      # [3] the room box
+    box_max: np.ndarray
+
+    def without_room(self) -> 'RoomMesh':
+        """The furniture and the free triangles alone (a camera outside then sees background pixels)."""
+        return RoomMesh(self.verts, np.ascontiguousarray(self.faces[self.n_room_faces:]), self.labels, 0, self.box_min, self.box_max)
+
+    def rgb(self) -> np.ndarray:
+        """Vertex colours that ``scene_io.labels_from_colors`` maps back to round(labels): grey = 5 * label."""
+        return np.repeat(np.clip(np.rint(self.labels * 5.0), 0, 255).astype(np.uint8)[:, None], 3, axis=1)
+
+    def planes(self) -> np.ndarray:
+        """[6,2,3]: (point, inward normal) of the six room planes, the ``room_planes`` of ``rendering.sample_virtual_cams``."""
+        c = 0.5 * (self.box_min.astype(np.float64) + self.box_max)
+        out = []
+        for ax in range(3):
+            for side, sgn in ((self.box_min, 1.0), (self.box_max, -1.0)):
+                p, n = c.copy(), np.zeros(3)
+                p[ax], n[ax] = side[ax], sgn
+                out.append(np.stack([p, n]))
+        return np.stack(out)
+
+
+def _quad_grid(p0, du, dv, k):
+    """(k+1)^2 vertices and 2 k^2 triangles of the parallelogram p0 + s du + t dv, s, t in [0,1]."""
+    s = np.linspace(0.0, 1.0, k + 1)
+    S, T = np.meshgrid(s, s, indexing='ij')
+    v = p0[None, None] + S[..., None] * du[None, None] + T[..., None] * dv[None, None]
+    idx = np.arange((k + 1) * (k + 1)).reshape(k + 1, k + 1)
+    a, b, c, d = idx[:-1, :-1].ravel(), idx[1:, :-1].ravel(), idx[1:, 1:].ravel(), idx[:-1, 1:].ravel()
+    return v.reshape(-1, 3), np.concatenate([np.stack([a, b, c], 1), np.stack([a, c, d], 1)], 0)
+
+
+def _box_quads(lo, hi):
+    """The six faces of an axis-aligned box as (p0, du, dv, axis, side)."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    quads = []
+    for ax in range(3):
+        u, v = (ax + 1) % 3, (ax + 2) % 3
+        du, dv = np.zeros(3), np.zeros(3)
+        du[u], dv[v] = hi[u] - lo[u], hi[v] - lo[v]
+        for side in (0, 1):
+            p0 = lo.copy()
+            p0[ax] = hi[ax] if side else lo[ax]
+            quads.append((p0, du, dv, ax, side))
+    return quads
+
+
+def make_room_mesh(seed: int = 0, n_extra: int = 180, subdiv: int = 1, extra_size: float = 0.6) -> RoomMesh:
+    """Stand-in scene mesh: a closed 5 x 4 x 2.6 m box room (walls 1, floor 2, ceiling 17), three labelled furniture boxes standing on
+    the floor, and ``n_extra`` random free triangles of edge ~``extra_size`` that intersect each other and the furniture, with a random
+    label per VERTEX (so labels vary inside a triangle).  ``subdiv`` = k cuts every box face into 2 k^2 triangles (k = 64 gives
+    ~197 k triangles for timing); the default is 12 + 36 + n_extra triangles."""
+    rs = np.random.RandomState(seed)
+    lo, hi = np.array([-2.5, -2.0, 0.0]), np.array([2.5, 2.0, 2.6])
+    verts, faces, labels = [], [], []
+    nv = 0
+
+    def add_box(blo, bhi, label_of):
+        nonlocal nv
+        for p0, du, dv, ax, side in _box_quads(blo, bhi):
+            v, f = _quad_grid(p0, du, dv, subdiv)
+            verts.append(v)
+            faces.append(f + nv)
+            labels.append(np.full(len(v), label_of(ax, side), np.float64))
+            nv += len(v)
+
+    add_box(lo, hi, lambda ax, side: 1.0 if ax < 2 else (17.0 if side else 2.0))
+    n_room = sum(len(f) for f in faces)
+    for label in (3.0, 5.0, 10.0):                                   # chair, table, sofa
+        size = rs.uniform([0.5, 0.5, 0.4], [1.4, 1.0, 1.0])
+        ctr = rs.uniform(lo[:2] + 0.9, hi[:2] - 0.9)
+        blo = np.array([ctr[0] - size[0] / 2, ctr[1] - size[1] / 2, 0.0])
+        add_box(blo, blo + size, lambda ax, side, label=label: label)
+    if n_extra:
+        c = rs.uniform(lo + 0.3, hi - 0.3, (n_extra, 3))
+        tri = c[:, None, :] + rs.uniform(-extra_size / 2, extra_size / 2, (n_extra, 3, 3))
+        verts.append(np.clip(tri.reshape(-1, 3), lo + 0.02, hi - 0.02))
+        faces.append(np.arange(3 * n_extra).reshape(n_extra, 3) + nv)
+        labels.append(rs.randint(0, 42, 3 * n_extra).astype(np.float64))
+    return RoomMesh(_f32(np.concatenate(verts)), np.ascontiguousarray(np.concatenate(faces), dtype=np.int32), _f32(np.concatenate(labels)),
+                    n_room, _f32(lo), _f32(hi))
+
+
+def make_room_cams(which: str = 'inside') -> np.ndarray:
+    """Camera-to-world poses [n,4,4] fp64 for ``make_room_mesh``: 'inside' = three cameras in the room looking at a point above the floor
+    (parts of the walls lie behind each of them, so the near clip runs), 'outside' = one camera 7 m away looking at the room's centre."""
+    from .rendering import look_at
+    target = np.array([0.2, -0.1, 0.9])
+    if which == 'inside':
+        eyes = [[-2.1, -1.6, 1.7], [2.0, 1.5, 2.2], [1.9, -1.7, 1.2]]
+    else:
+        eyes = [[-6.0, -4.5, 3.4]]
+    return np.stack([look_at(np.array(e), target) for e in eyes])
