@@ -530,6 +530,36 @@ size_t psi_raster_workspace_bytes(int nf, int n_views, int W, int H);
 int psi_raster_render(psi_raster_mesh *mesh, const float *d_w2c, const float *d_intr, int n_views, int W, int H, float near_z,
                       float *d_depth, int32_t *d_tri, float *d_seg, int32_t *d_stats, void *d_workspace, void *stream);
 
+/* ---- mesh -> signed distance volume: the {scene}_sdf.npy of a scene from its triangle mesh (the reference ships the volumes as downloads) ----
+ * Contract (fp32, not contracted; DESIGN.md "Mesh -> SDF volume" has the full statement):
+ *   node       (ix, iy, iz) lies at gmin[a] + (float)i_a * ((gmax[a] - gmin[a]) / (float)(D - 1)): the sampler's align_corners = True positions
+ *   magnitude  sqrtf of the minimum over the kept triangles of d2 = |p - c|^2, c the closest point of the triangle from one fixed
+ *              seven-region routine on the record (a, b - a, c - a); the minimum is taken over bits(d2) << 32 | triangle index, so it does
+ *              not depend on the visiting order and equal d2 goes to the lower index
+ *   sign       that of (p - c) . n, n the angle-weighted pseudonormal of the face, edge or vertex of the winning triangle that c lies on;
+ *              exactly 0 counts as positive.  Triangles face free space: free space is positive, solid negative
+ *   topology   vertices with bit-identical positions are welded (-0.0 equals +0.0); triangles with two equal welded vertices or an fp64
+ *              cross product of exactly 0 are dropped; pseudonormals in fp64 on the host, stored as fp32; an edge with one triangle uses
+ *              that triangle's normal
+ * No floating-point atomics: the volume is bit-identical from run to run, and mode 0 and mode 1 give the same bits.
+ *
+ * psi_mesh_sdf_create reads verts [nv,3] fp32 and faces [nf,3] int32 from device memory, does the topology on the host and uploads the scan
+ * records, the normals and the cell grid; it synchronises the device and launches no kernel.  PSI_EINVAL: a face index outside [0, nv), a
+ * non-finite vertex coordinate, no triangle left. */
+typedef struct psi_mesh_sdf psi_mesh_sdf;
+int psi_mesh_sdf_create(psi_mesh_sdf **out, const float *d_verts, const int32_t *d_faces, int nv, int nf);
+void psi_mesh_sdf_destroy(psi_mesh_sdf *m);
+/* info[0] kept triangles, [1] dropped degenerate triangles, [2] welded vertices (distinct positions among the nv), [3] edges not shared by
+ * exactly two triangles */
+int psi_mesh_sdf_info(const psi_mesh_sdf *m, int32_t info[4]);
+/* gmin, gmax: host pointers.  d_out: device [D,D,D] fp32, element [ix][iy][iz].  mode 0 = pruned search, 1 = every node against every
+ * triangle.  PSI_EINVAL when D < 2 or D > 1024, when gmax[a] <= gmin[a], when a bound is not finite.  One kernel on `stream`, no host sync. */
+int psi_mesh_sdf_compute(psi_mesh_sdf *m, const float gmin[3], const float gmax[3], int D, int mode, float *d_out, void *stream);
+/* The same search in a build of the kernel that also counts the (node, triangle) tests it executes: *d_pairs (device, 64-bit) receives the
+ * count.  For measurements (tools/time_mesh_sdf.py); psi_mesh_sdf_compute carries no counter. */
+int psi_mesh_sdf_count_pairs(psi_mesh_sdf *m, const float gmin[3], const float gmax[3], int D, int mode, unsigned long long *d_pairs,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

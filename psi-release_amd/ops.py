@@ -975,3 +975,61 @@ def raster_render(handle, nf, w2c, intr, size, near=0.05, with_seg=True):
         hip.check(L.psi_raster_render(handle, pw, pi, n, W, H, float(near), hip.ptr(depth), hip.ptr(tri), hip.ptr(seg), hip.ptr(stats),
                                       hip.ptr(ws), hip.stream()), 'psi_raster_render')
     return depth, tri, seg, stats
+
+
+# ------------------------------------------------------------------------------------------
+# Mesh -> signed distance volume (psi_mesh_sdf_*)
+# ------------------------------------------------------------------------------------------
+def mesh_sdf_create(verts, faces):
+    """Upload-side half of ``scene_sdf.MeshSDF``: verts [nv,3] fp32 and faces [nf,3] int32 on the GPU.  Returns the ``psi_mesh_sdf`` handle
+    (free it with ``mesh_sdf_destroy``); a face index out of range, a non-finite vertex or a mesh of degenerate triangles only is refused."""
+    import ctypes
+    pv, pf = hip.ptr(verts), hip.ptr(faces)
+    if verts.dtype != torch.float32 or faces.dtype != torch.int32 or verts.dim() != 2 or faces.dim() != 2 or verts.shape[1] != 3 or faces.shape[1] != 3:
+        raise ValueError('expected verts [nv,3] float32 and faces [nf,3] int32')
+    h = ctypes.c_void_p()
+    with torch.cuda.device(verts.device):
+        hip.check(hip.lib().psi_mesh_sdf_create(ctypes.byref(h), pv, pf, verts.shape[0], faces.shape[0]), 'psi_mesh_sdf_create')
+    return h
+
+
+def mesh_sdf_destroy(handle):
+    if handle:
+        hip.lib().psi_mesh_sdf_destroy(handle)
+
+
+def mesh_sdf_info(handle):
+    """(kept triangles, dropped degenerate triangles, welded vertices, edges not shared by exactly two triangles)."""
+    import ctypes
+    info = (ctypes.c_int32 * 4)()
+    hip.check(hip.lib().psi_mesh_sdf_info(handle, info), 'psi_mesh_sdf_info')
+    return tuple(int(x) for x in info)
+
+
+def _mesh_sdf_bounds(grid_min, grid_max):
+    import ctypes
+    import numpy as np
+    lo, hi = (np.asarray(a, dtype=np.float32).reshape(3) for a in (grid_min, grid_max))
+    return (ctypes.c_float * 3)(*lo.tolist()), (ctypes.c_float * 3)(*hi.tolist())
+
+
+def mesh_sdf_compute(handle, grid_min, grid_max, dim, mode=0, device='cuda'):
+    """The volume [D,D,D] fp32, element [ix][iy][iz], of the mesh behind ``handle`` on the node grid grid_min .. grid_max (host values).
+    mode 0: pruned search; 1: every node against every triangle (the same bits)."""
+    lo, hi = _mesh_sdf_bounds(grid_min, grid_max)
+    dim = int(dim)
+    if dim < 2 or dim > 1024:
+        raise hip.PsiHipError('psi_mesh_sdf_compute: 2 <= D <= 1024 (got %d)' % dim)
+    out = torch.empty(dim, dim, dim, device=device)
+    with torch.cuda.device(out.device):
+        hip.check(hip.lib().psi_mesh_sdf_compute(handle, lo, hi, dim, int(mode), hip.ptr(out), hip.stream()), 'psi_mesh_sdf_compute')
+    return out
+
+
+def mesh_sdf_count_pairs(handle, grid_min, grid_max, dim, mode=0, device='cuda'):
+    """Number of (node, triangle) tests the search of ``mesh_sdf_compute`` executes, from the counting build of the kernel."""
+    lo, hi = _mesh_sdf_bounds(grid_min, grid_max)
+    n = torch.zeros(1, dtype=torch.int64, device=device)
+    with torch.cuda.device(n.device):
+        hip.check(hip.lib().psi_mesh_sdf_count_pairs(handle, lo, hi, int(dim), int(mode), hip.ptr(n), hip.stream()), 'psi_mesh_sdf_count_pairs')
+    return int(n.item())

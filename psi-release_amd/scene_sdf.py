@@ -1,0 +1,116 @@
+"""From a scene mesh to what the fitting loop and the plausibility table need from a scene: the signed distance volume ({scene}.json +
+{scene}_sdf.npy) and the scene point cloud (scenes_downsampled/{scene}.ply).  The reference ships both as downloads and has no code that
+makes them; here the volume comes from the mesh on the GPU (csrc/mesh_sdf.hip through ``ops.mesh_sdf_compute``; DESIGN.md "Mesh -> SDF
+volume" states the contract).
+
+* ``MeshSDF``          the mesh on the GPU: welded, zero-area triangles dropped, pseudonormals; ``compute`` returns a volume
+* ``scene_cloud``      the welded vertex positions, optionally one per occupied voxel (NumPy, on the host)
+* ``scene_from_mesh``  both, as the ``synth.SceneData`` that ``FittingOP(scene=...)``, ``scenes=[...]`` and ``write_prox_layout`` take
+
+Convention: triangles face free space, so free space is positive and solid is negative — what the collision term and
+``psi_lbs_sdf_counts`` assume.  An open or non-manifold mesh gets its sign from the orientation of the nearest triangle.  Two coincident,
+oppositely oriented surfaces (a box standing exactly on the floor) leave the sign below them ambiguous.  Computing needs the GPU; there is
+no CPU path.
+"""
+from __future__ import annotations
+
+import warnings
+
+import numpy as np
+import torch
+
+from . import ops, scene_io, synth
+
+MODES = {'grid': 0, 'brute': 1}
+ENGINE_MAX_DIM = 480       # the several-scenes engine samples a re-ordered copy of the volume: D % 4 == 0, D <= 480 (psi_fit_create_scenes)
+
+
+class MeshSDF:
+    """A triangle mesh prepared for distance queries: verts [nv,3], faces [nf,3].  Owns the ``psi_mesh_sdf`` handle.  ``info`` =
+    (kept triangles, dropped zero-area triangles, welded vertices, edges not shared by exactly two triangles).  A face index out of range,
+    a non-finite vertex and a mesh without a triangle of non-zero area are refused (``PsiHipError``)."""
+
+    def __init__(self, verts, faces, device='cuda'):
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise ops.hip.PsiHipError('MeshSDF needs a GPU device (the HIP kernel is the only implementation)')
+        as_np = lambda a, dt: np.ascontiguousarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=dt)
+        v, f = as_np(verts, np.float32).reshape(-1, 3), as_np(faces, np.int64).reshape(-1, 3)
+        if len(f) == 0 or len(v) == 0:
+            raise ValueError('empty mesh')
+        if np.abs(f).max() >= 2 ** 31:
+            raise ops.hip.PsiHipError('a face index lies outside [0, nv)')
+        self.nv, self.nf = len(v), len(f)
+        self.handle = None
+        self.handle = ops.mesh_sdf_create(torch.tensor(v, device=self.device), torch.tensor(f.astype(np.int32), device=self.device))
+        self.info = ops.mesh_sdf_info(self.handle)
+        self._warned = False
+
+    @classmethod
+    def from_ply(cls, path, device='cuda'):
+        verts, faces, _ = scene_io.read_ply_mesh(path)
+        return cls(verts, faces, device=device)
+
+    def compute(self, grid_min, grid_max, dim, mode='grid'):
+        """The volume [D,D,D] fp32 on the GPU, element [ix][iy][iz]; node i of axis a lies at
+        grid_min[a] + i * ((grid_max[a] - grid_min[a]) / (D - 1)).  ``mode``: 'grid' (pruned search) or 'brute' (every node against every
+        triangle; the same bits, for checking)."""
+        if mode not in MODES:
+            raise ValueError("mode is 'grid' or 'brute'")
+        if self.info[3] > 0 and not self._warned:
+            self._warned = True
+            warnings.warn('mesh is not closed: the sign follows the triangle orientation (%d edges are not shared by exactly two triangles)'
+                          % self.info[3])
+        return ops.mesh_sdf_compute(self.handle, grid_min, grid_max, dim, MODES[mode], device=self.device)
+
+    def __del__(self):
+        try:
+            if getattr(self, 'handle', None):
+                ops.mesh_sdf_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def scene_cloud(verts, voxel=None) -> np.ndarray:
+    """The welded vertex positions [m,3] fp32 (one per distinct position, -0.0 equal to +0.0, in the order of first appearance).  With
+    ``voxel`` the first of them, in that order, of every occupied cell of a ``voxel``-sized lattice anchored at the cloud's minimum: the
+    role of scenes_downsampled/*.ply."""
+    v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3) + np.float32(0.0)
+    _, first = np.unique(v.view(np.uint32).reshape(-1, 3), axis=0, return_index=True)
+    v = v[np.sort(first)]
+    if voxel is None:
+        return v
+    if not voxel > 0:
+        raise ValueError('voxel must be positive')
+    cell = np.floor((v.astype(np.float64) - v.min(0).astype(np.float64)) / float(voxel)).astype(np.int64)
+    _, first = np.unique(cell, axis=0, return_index=True)
+    return v[np.sort(first)]
+
+
+def check_engine_dim(dim):
+    if dim % 4 != 0 or dim > ENGINE_MAX_DIM or dim < 4:
+        raise ValueError('dim = %d: the fitting engine needs a multiple of 4, at most %d (pass check_engine=False for a volume that is '
+                         'only sampled elsewhere)' % (dim, ENGINE_MAX_DIM))
+
+
+def grid_box(verts, margin):
+    """(grid_min, grid_max) fp32: the box of the vertices grown by ``margin`` on every side."""
+    v = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+    return (v.min(0) - np.float32(margin)).astype(np.float32), (v.max(0) + np.float32(margin)).astype(np.float32)
+
+
+def scene_from_mesh(verts, faces, dim=256, margin=0.5, voxel=None, contact_parts=None, check_engine=True, device='cuda') -> synth.SceneData:
+    """The ``synth.SceneData`` of a scene mesh: ``sdf`` [D,D,D] computed on the GPU over the mesh's box grown by ``margin`` on every side,
+    ``verts`` = ``scene_cloud(verts, voxel)``.  ``FittingOP(scene=...)``, ``scenes=[...]`` and ``SceneData.write_prox_layout`` take it as
+    is.  The several-scenes engine refuses D % 4 != 0 and D > 480: the same ``ValueError`` is raised here, before any work, unless
+    ``check_engine=False``."""
+    dim = int(dim)
+    if check_engine:
+        check_engine_dim(dim)
+    if not margin >= 0:
+        raise ValueError('margin must not be negative')
+    mesh = MeshSDF(verts, faces, device=device)
+    lo, hi = grid_box(verts, margin)
+    sdf = mesh.compute(lo, hi, dim).cpu().numpy()
+    return synth.SceneData(scene_cloud(verts, voxel), sdf, lo, hi, dim, dict(contact_parts or {}))

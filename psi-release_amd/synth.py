@@ -354,3 +354,52 @@ def make_room_cams(which: str = 'inside') -> np.ndarray:
     else:
         eyes = [[-6.0, -4.5, 3.4]]
     return np.stack([look_at(np.array(e), target) for e in eyes])
+
+
+@dataclass
+class OrientedRoom:
+    """A closed, consistently oriented stand-in scene with an exact distance field (``make_oriented_room``)."""
+    verts: np.ndarray        # [nv,3] fp32, per-face vertices (unwelded)
+    faces: np.ndarray        # [nf,3] int32; every triangle faces free space
+    box_min: np.ndarray      # [3] the room box
+    box_max: np.ndarray
+    boxes: list              # (centre [3], half sizes [3], rotation [3,3]) of the solids in the room, fp64
+
+    def analytic_sdf(self, points) -> np.ndarray:
+        """Signed distance (fp64) of points [..., 3] to the scene the mesh describes before its vertices were rounded to fp32: positive in
+        the free space of the room, negative inside a box and outside the room.  The minimum of the room-interior distance and the box
+        distances, which is exact because the solids are disjoint."""
+        p = np.asarray(points, np.float64)
+
+        def box_sdf(q):                                           # q = |local p| - half sizes
+            return np.linalg.norm(np.maximum(q, 0.0), axis=-1) + np.minimum(q.max(-1), 0.0)
+
+        c, h = 0.5 * (self.box_min.astype(np.float64) + self.box_max), 0.5 * (self.box_max.astype(np.float64) - self.box_min)
+        out = -box_sdf(np.abs(p - c) - h)
+        for centre, half, rot in self.boxes:
+            out = np.minimum(out, box_sdf(np.abs((p - centre) @ rot) - half))
+        return out
+
+
+def make_oriented_room(subdiv: int = 2) -> OrientedRoom:
+    """The 5 x 4 x 2.6 m room box of ``make_room_mesh`` oriented inward, an axis-aligned box [0.3,1.5] x [-1.2,-0.4] x [0.05,0.8] and a box
+    of half sizes (0.5, 0.3, 0.4) rotated 30 degrees about z and centred at (-1.0, 0.7, 0.5), both oriented outward and floating 5 cm above
+    the floor (no coincident surfaces).  Every face is cut into 2 subdiv^2 triangles with vertices of its own, rounded to fp32: welding
+    them gives a closed manifold whose every triangle faces free space, the convention of a signed distance volume (free space positive).
+    ``subdiv`` = 64 gives ~147 k triangles for timing."""
+    lo, hi = np.array([-2.5, -2.0, 0.0]), np.array([2.5, 2.0, 2.6])
+    ang = np.radians(30.0)
+    rot = np.array([[np.cos(ang), -np.sin(ang), 0.0], [np.sin(ang), np.cos(ang), 0.0], [0.0, 0.0, 1.0]])
+    solids = [(np.array([0.9, -0.8, 0.425]), np.array([0.6, 0.4, 0.375]), np.eye(3)),
+              (np.array([-1.0, 0.7, 0.5]), np.array([0.5, 0.3, 0.4]), rot)]
+    verts, faces = [], []
+    nv = 0
+    for centre, half, R, outward in [(0.5 * (lo + hi), 0.5 * (hi - lo), np.eye(3), False)] + [s + (True,) for s in solids]:
+        for p0, du, dv, ax, side in _box_quads(-half, half):
+            v, f = _quad_grid(p0, du, dv, subdiv)                  # its triangles face +axis
+            if bool(side) != outward:
+                f = f[:, ::-1]
+            verts.append(v @ R.T + centre)
+            faces.append(f + nv)
+            nv += len(v)
+    return OrientedRoom(_f32(np.concatenate(verts)), np.ascontiguousarray(np.concatenate(faces), dtype=np.int32), _f32(lo), _f32(hi), solids)

@@ -1,0 +1,61 @@
+#!/usr/bin/env python
+"""python utils_scene_sdf.py SCENE_PLY OUT_ROOT --name N [--dim 256 --margin 0.5 --voxel V]     (or: OUT_ROOT --name N --synthetic)
+
+From a scene mesh to the two scene files of the fitting and evaluation scripts, on the GPU: OUT_ROOT/scenes_sdf/N.json + N_sdf.npy (the
+signed distance volume over the mesh's box grown by --margin, [ix][iy][iz], positive in free space) and OUT_ROOT/scenes_downsampled/N.ply
+(the welded vertices, one per --voxel cell when given).  The reference ships these as downloads.  Triangles must face free space; an open
+mesh gets its sign from the orientation of the nearest triangle.  Prints the three config paths of the fitting scripts."""
+import argparse
+
+import _eval_common  # noqa: F401  (path setup)
+
+from psi_release_amd import scene_sdf, synth
+from psi_release_amd.scene_io import read_ply_mesh
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('scene_ply', nargs='?')
+    ap.add_argument('out_root', nargs='?')
+    ap.add_argument('--name', required=True, help='scene name: the files are scenes_sdf/NAME.json, scenes_sdf/NAME_sdf.npy, scenes_downsampled/NAME.ply')
+    ap.add_argument('--dim', type=int, default=256, help='nodes per axis (a multiple of 4, at most 480: what the fitting engine samples)')
+    ap.add_argument('--margin', type=float, default=0.5, help='the grid box is the mesh box grown by this on every side (m)')
+    ap.add_argument('--voxel', type=float, default=None, help='keep one vertex per cell of this size in the point cloud')
+    ap.add_argument('--synthetic', action='store_true', help='use the stand-in room synth.make_oriented_room instead of a PLY')
+    ap.add_argument('--subdiv', type=int, default=2, help='--synthetic: cuts per box face edge')
+    a = ap.parse_args(argv)
+    if a.synthetic:
+        if a.out_root is None:
+            a.scene_ply, a.out_root = None, a.scene_ply
+        if a.scene_ply is not None:
+            ap.error('--synthetic takes OUT_ROOT only')
+    if not a.out_root or not (a.synthetic or a.scene_ply):
+        ap.error('SCENE_PLY and OUT_ROOT are required (or OUT_ROOT --synthetic)')
+    try:
+        scene_sdf.check_engine_dim(a.dim)
+    except ValueError as e:
+        ap.error(str(e))
+    if a.margin < 0 or (a.voxel is not None and a.voxel <= 0):
+        ap.error('--margin must not be negative and --voxel must be positive')
+    return a
+
+
+def main(argv=None):
+    a = parse(argv)
+    parts = None
+    if a.synthetic:
+        room = synth.make_oriented_room(a.subdiv)
+        verts, faces = room.verts, room.faces
+        parts = synth.make_scene(0, m=8, D=2).contact_parts          # stand-in body_segments/*.json (the real ones ship with PROX)
+    else:
+        verts, faces, _ = read_ply_mesh(a.scene_ply)
+    scene = scene_sdf.scene_from_mesh(verts, faces, dim=a.dim, margin=a.margin, voxel=a.voxel, contact_parts=parts)
+    paths = scene.write_prox_layout(a.out_root, a.name)
+    print('[INFO] %d triangles -> %d^3 volume, %d cloud points' % (len(faces), a.dim, len(scene.verts)))
+    for k in ('scene_verts_path', 'scene_sdf_path', 'contact_id_folder'):
+        print('%s: %s' % (k, paths[k]))
+    return paths
+
+
+if __name__ == '__main__':
+    main()
