@@ -530,6 +530,49 @@ size_t psi_raster_workspace_bytes(int nf, int n_views, int W, int H);
 int psi_raster_render(psi_raster_mesh *mesh, const float *d_w2c, const float *d_intr, int n_views, int W, int H, float near_z,
                       float *d_depth, int32_t *d_tri, float *d_seg, int32_t *d_stats, void *d_workspace, void *stream);
 
+/* ---- result images: bodies drawn into the snapshots of their scene (utils/utils_show_test_results.py, img_%06d_cam1.png / _cam2.png) ----
+ * The bodies are B meshes [B,V,3] of one topology (faces [F,3]) made on the device.  A draw is a (body, view) pair with its own colour;
+ * any number of draws may share a view, a body may appear in several views, a view may have none.  Body triangles go through the
+ * statements of the snapshot rasteriser above, word for word; the index of a piece is d * F + face.  The rest of the contract (fp32, not
+ * contracted, IEEE division and square root; DESIGN.md "Result images"):
+ *   normal    of a vertex: the unnormalised world-frame (v1 - v0) x (v2 - v0) of its faces (each component two products and one
+ *             subtraction), summed left to right in ascending face index; (0,0,0) for a vertex of no face
+ *   owner     the body owns a pixel iff a body piece covers it and the scene has no hit there or z_body < z_scene; equal depths go to the scene
+ *   shade     s = 0.3 + (0.7*|N_z|)/sqrtf((N_x*N_x + N_y*N_y) + N_z*N_z), s = 0.3 when the length is 0 or not finite
+ *   body      N = (l0*(n0*iz0) + l1*(n1*iz1)) + l2*(n2*iz2) per component, n the camera-space vertex normal ((m00*nx + m01*ny) + m02*nz, ...),
+ *             interpolated like the label, near clip included; colour = draw_rgb[d] * s
+ *   scene     N = the flat normal (v1 - v0) x (v2 - v0) of the parent triangle's camera-space vertices; base colour = the label formula per
+ *             channel of the vertex colours, 0.8 without them; colour = base * s
+ *   channel   (unsigned char)rintf(255.f * fminf(fmaxf(c, 0.f), 1.f)); background pixels carry the caller's colour
+ * No floating-point atomics: every output is bit-identical from run to run, for any batching of the views and any draws_per_pass.
+ *
+ * psi_raster_bodies_create reads faces [F,3] int32 from device memory, checks every index (PSI_EINVAL outside [0, V)) and builds the
+ * per-vertex face lists on the host; it synchronises the device. */
+typedef struct psi_raster_bodies psi_raster_bodies;
+int psi_raster_bodies_create(psi_raster_bodies **out, const int32_t *d_faces, int V, int F);
+void psi_raster_bodies_destroy(psi_raster_bodies *bodies);
+/* d_bverts [B,V,3] fp32 -> d_normals [B,V,3] fp32, one lane per (body, vertex); one kernel on `stream`, no host sync. */
+int psi_raster_bodies_normals(psi_raster_bodies *bodies, const float *d_bverts, int B, float *d_normals, void *stream);
+/* Host function: bytes of the workspace of one psi_raster_bodies_render call whose passes hold at most draws_per_pass draws (their piece
+ * records, 2 * draws_per_pass * F * 52 bytes), plus the tile counts, the bins and the 64-bit body key image.  0 for arguments the render
+ * call refuses, draws_per_pass * F >= 2^30 among them. */
+size_t psi_raster_bodies_workspace_bytes(int F, int draws_per_pass, int n_views, int W, int H);
+/* scene, d_sdepth, d_stri: the scene's mesh object and the depth / tri images [n_views,H,W] of a psi_raster_render of the same views and
+ * near_z; all NULL for no scene.  d_vrgb [nv,3] fp32 vertex colours in [0,1] or NULL.  d_bverts [B,V,3]; d_draw_body, d_draw_view [M] int32,
+ * d_draw_rgb [M,3] fp32; M * F < 2^31; M = 0 composes the scene alone.  Views as psi_raster_render.  A draw whose body lies outside [0, B)
+ * or whose view lies outside [0, n_views) is found on the device and refused (PSI_EINVAL) before anything is drawn.
+ * Outputs (device, overwritten): d_rgb [n_views,H,W,3] uint8; d_depth the owner's z or 0; d_draw the draw index where a body owns the pixel,
+ * else -1; d_bdepth / d_bid the nearest body piece alone, z and d * F + face, or 0 / -1; d_counts [M,2] int32 = { pixels whose nearest body
+ * piece belongs to draw d, those of them that also beat the scene }; d_stats [n_views,2] as psi_raster_render, over the bodies' pieces.
+ * d_workspace: psi_raster_bodies_workspace_bytes(F, draws_per_pass, n_views, W, H) bytes, or NULL for the library's per-stream scratch.
+ * The call loops over the passes itself and synchronises the stream once per pass, after the binning counts; bins beyond the workspace's
+ * come from a buffer the bodies object owns, so a bodies object is rendered by ONE call at a time, like a mesh object. */
+int psi_raster_bodies_render(psi_raster_mesh *scene, const float *d_vrgb, psi_raster_bodies *bodies, const float *d_bverts, int B,
+                             const int32_t *d_draw_body, const int32_t *d_draw_view, const float *d_draw_rgb, int M, const float *d_w2c,
+                             const float *d_intr, int n_views, int W, int H, float near_z, const float *d_sdepth, const int32_t *d_stri,
+                             float bg_r, float bg_g, float bg_b, int draws_per_pass, uint8_t *d_rgb, float *d_depth, int32_t *d_draw,
+                             float *d_bdepth, int32_t *d_bid, int32_t *d_counts, int32_t *d_stats, void *d_workspace, void *stream);
+
 /* ---- mesh -> signed distance volume: the {scene}_sdf.npy of a scene from its triangle mesh (the reference ships the volumes as downloads) ----
  * Contract (fp32, not contracted; DESIGN.md "Mesh -> SDF volume" has the full statement):
  *   node       (ix, iy, iz) lies at gmin[a] + (float)i_a * ((gmax[a] - gmin[a]) / (float)(D - 1)): the sampler's align_corners = True positions

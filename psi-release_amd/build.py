@@ -31,6 +31,7 @@ COMMON = ['-O3', '-std=c++17', '--offload-arch=' + ARCH, '-fPIC', '-fno-gpu-rdc'
 PER_FILE = {'chamfer.hip': ['-ffp-contract=off', '-fno-slp-vectorize'], 'nnindex.hip': ['-ffp-contract=off'],
             'cvae_loss.hip': ['-ffp-contract=off'],     # the operator sequence of geometry.py, association for association
             'raster.hip': ['-ffp-contract=off'],        # the rounding of the projection decides which pixels a triangle covers
+            'raster_bodies.hip': ['-ffp-contract=off'], # the same statements as raster.hip (csrc/raster_device.h), hence the same pieces
             'mesh_sdf.hip': ['-ffp-contract=off']}      # pruned and brute-force search must give the same bits
 
 

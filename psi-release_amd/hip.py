@@ -122,6 +122,12 @@ SIGNATURES = {
     'psi_raster_mesh_destroy': (None, [c_void_p]),
     'psi_raster_workspace_bytes': (c_size_t, [c_int] * 4),
     'psi_raster_render': (c_int, [c_void_p] * 3 + [c_int, c_int, c_int, c_float] + [c_void_p] * 6),
+    'psi_raster_bodies_create': (c_int, [c_void_p] * 2 + [c_int, c_int]),
+    'psi_raster_bodies_destroy': (None, [c_void_p]),
+    'psi_raster_bodies_normals': (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2),
+    'psi_raster_bodies_workspace_bytes': (c_size_t, [c_int] * 5),
+    'psi_raster_bodies_render': (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int] + [c_void_p] * 2 + [c_int] * 3 + [c_float] + [c_void_p] * 2
+                                 + [c_float] * 3 + [c_int] + [c_void_p] * 9),
     'psi_mesh_sdf_create': (c_int, [c_void_p] * 3 + [c_int, c_int]),
     'psi_mesh_sdf_destroy': (None, [c_void_p]),
     'psi_mesh_sdf_info': (c_int, [c_void_p, c_void_p]),

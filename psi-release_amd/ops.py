@@ -978,6 +978,91 @@ def raster_render(handle, nf, w2c, intr, size, near=0.05, with_seg=True):
 
 
 # ------------------------------------------------------------------------------------------
+# Result images (psi_raster_bodies_*)
+# ------------------------------------------------------------------------------------------
+def raster_bodies_create(faces, V):
+    """faces [F,3] int32 on the GPU, the one topology of every body; V vertices per body.  Returns the ``psi_raster_bodies`` handle (free it
+    with ``raster_bodies_destroy``); a face index outside [0, V) is refused."""
+    import ctypes
+    pf = hip.ptr(faces)
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError('expected faces [F,3] int32')
+    h = ctypes.c_void_p()
+    with torch.cuda.device(faces.device):
+        hip.check(hip.lib().psi_raster_bodies_create(ctypes.byref(h), pf, int(V), faces.shape[0]), 'psi_raster_bodies_create')
+    return h
+
+
+def raster_bodies_destroy(handle):
+    if handle:
+        hip.lib().psi_raster_bodies_destroy(handle)
+
+
+def _body_verts_ptr(bverts, V):
+    p = hip.ptr(bverts)
+    if bverts.dtype != torch.float32 or bverts.dim() != 3 or tuple(bverts.shape[1:]) != (V, 3):
+        raise ValueError('expected body vertices [B,%d,3] float32' % V)
+    return p
+
+
+def raster_bodies_normals(handle, V, bverts):
+    """Unnormalised vertex normals [B,V,3] of bverts [B,V,3]: the faces' cross products summed in ascending face index."""
+    pv = _body_verts_ptr(bverts, V)
+    out = torch.empty_like(bverts)
+    with torch.cuda.device(bverts.device):
+        hip.check(hip.lib().psi_raster_bodies_normals(handle, pv, bverts.shape[0], hip.ptr(out), hip.stream()), 'psi_raster_bodies_normals')
+    return out
+
+
+def raster_bodies_workspace_bytes(F, draws_per_pass, n_views, W, H):
+    """Bytes of the workspace of ``raster_bodies_render``; ``ValueError`` for arguments the render call refuses (draws_per_pass * F >= 2^30,
+    an image beyond 4096 pixels, ...)."""
+    if min(F, draws_per_pass, n_views, W, H) < 1 or max(F, draws_per_pass, n_views, W, H) >= 2 ** 31:
+        raise ValueError('F, draws_per_pass, n_views, W and H must be positive 32-bit integers')
+    n = hip.lib().psi_raster_bodies_workspace_bytes(int(F), int(draws_per_pass), int(n_views), int(W), int(H))
+    if n == 0:
+        raise ValueError('no workspace for F=%d, draws_per_pass=%d, n_views=%d, W=%d, H=%d: draws_per_pass * F must stay below 2^30, n_views '
+                         'at most 65535 and the image within 4096 x 4096' % (F, draws_per_pass, n_views, W, H))
+    return n
+
+
+def raster_bodies_render(bodies, V, F, bverts, draw_body, draw_view, draw_rgb, w2c, intr, size, near, background, draws_per_pass,
+                         scene=None, vrgb=None, sdepth=None, stri=None):
+    """Bodies composited into scene snapshots (include/psi_hip.h: psi_raster_bodies_render).  bverts [B,V,3] fp32; draw_body, draw_view [M]
+    int32; draw_rgb [M,3] fp32; w2c / intr / size as ``raster_render``; scene, sdepth, stri: the ``psi_raster_mesh`` handle and the depth /
+    tri images of its ``raster_render`` with the same views, or None.  Returns rgb [n,H,W,3] uint8, depth, draw (int32), body_depth,
+    body_id (int32) [n,H,W], counts [M,2] int32, stats [n,2] int32."""
+    pv = _body_verts_ptr(bverts, V)
+    pw, pi = hip.ptr(w2c), hip.ptr(intr)
+    if w2c.dtype != torch.float32 or intr.dtype != torch.float32 or w2c.dim() != 3 or tuple(w2c.shape[1:]) != (3, 4) or tuple(intr.shape) != (w2c.shape[0], 4):
+        raise ValueError('expected w2c [n,3,4] and intr [n,4], float32')
+    M = draw_body.shape[0]
+    if draw_body.dtype != torch.int32 or draw_view.dtype != torch.int32 or draw_rgb.dtype != torch.float32 or tuple(draw_view.shape) != (M,) \
+            or tuple(draw_rgb.shape) != (M, 3) or draw_body.dim() != 1:
+        raise ValueError('expected draw_body, draw_view [M] int32 and draw_rgb [M,3] float32')
+    if M * F >= 2 ** 31:
+        raise ValueError('M * F = %d: the piece index d * F + face must stay below 2^31' % (M * F))
+    n, (H, W), dev = w2c.shape[0], (int(size[0]), int(size[1])), w2c.device
+    if scene is not None and (tuple(sdepth.shape) != (n, H, W) or tuple(stri.shape) != (n, H, W) or sdepth.dtype != torch.float32
+                              or stri.dtype != torch.int32):
+        raise ValueError("expected the scene's depth (float32) and tri (int32) images [n,H,W] of the same views")
+    ws = torch.empty(raster_bodies_workspace_bytes(F, draws_per_pass, n, W, H), dtype=torch.uint8, device=dev)
+    rgb = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
+    depth, bdepth = torch.empty(n, H, W, device=dev), torch.empty(n, H, W, device=dev)
+    draw, bid = torch.empty(n, H, W, dtype=torch.int32, device=dev), torch.empty(n, H, W, dtype=torch.int32, device=dev)
+    counts = torch.zeros(M, 2, dtype=torch.int32, device=dev)
+    stats = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    bg = [float(c) for c in background]
+    args = [hip.ptr(t) if t is not None else None for t in (vrgb, sdepth, stri)] if scene is not None else [None] * 3
+    with torch.cuda.device(dev):
+        hip.check(hip.lib().psi_raster_bodies_render(scene, args[0], bodies, pv, bverts.shape[0], hip.ptr(draw_body), hip.ptr(draw_view),
+                                                     hip.ptr(draw_rgb), M, pw, pi, n, W, H, float(near), args[1], args[2], bg[0], bg[1], bg[2],
+                                                     int(draws_per_pass), hip.ptr(rgb), hip.ptr(depth), hip.ptr(draw), hip.ptr(bdepth), hip.ptr(bid),
+                                                     hip.ptr(counts), hip.ptr(stats), hip.ptr(ws), hip.stream()), 'psi_raster_bodies_render')
+    return rgb, depth, draw, bdepth, bid, counts, stats
+
+
+# ------------------------------------------------------------------------------------------
 # Mesh -> signed distance volume (psi_mesh_sdf_*)
 # ------------------------------------------------------------------------------------------
 def mesh_sdf_create(verts, faces):

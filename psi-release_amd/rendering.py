@@ -6,14 +6,20 @@ with an open3d OpenGL window (utils/utils_prox_snapshots_virtualcam.py: ``get_ne
 * ``sample_virtual_cams``               the reference's camera lattice around a target point, with its two filters
 * ``view_is_usable``                    the reference's occlusion test, negated
 * ``write_sensor_folder``               ``cam_%06d.npy`` / ``depth_%06d.npy`` / ``seg_%06d.npy`` as ``generation.TestOP.test_habitat`` reads them
+* ``ResultRenderer`` / ``write_png``    generated bodies drawn, shaded, into the snapshots of their scene (csrc/raster_bodies.hip): the images the
+                                        reference captures from its window in utils/utils_show_test_results.py, and per body the pixels it
+                                        covers and the pixels of those that the scene does not hide
 
 Conventions: ``cam_ext`` is camera-to-world (the matrix the generated pkl files carry and ``verts_transform`` applies); the camera looks
 along +z with x right and y down; ``cam_int`` is the 3x3 pinhole matrix.  Rendering needs the GPU; there is no CPU path.
 """
 from __future__ import annotations
 
+import collections
 import os
+import struct
 import warnings
+import zlib
 
 import numpy as np
 import torch
@@ -23,9 +29,10 @@ from . import ops, scene_io
 
 class SceneMesh:
     """A triangle mesh uploaded once: verts [nv,3], faces [nf,3], vertex_labels [nv] (None: all 0).  Owns the ``psi_raster_mesh`` handle;
-    a face index outside [0, nv) is refused by ``psi_raster_mesh_create`` (``PsiHipError``).  One render call at a time per mesh."""
+    a face index outside [0, nv) is refused by ``psi_raster_mesh_create`` (``PsiHipError``).  One render call at a time per mesh.
+    ``vertex_rgb`` [nv,3] (uint8 0..255, or floats in [0,1]) are kept as ``rgb`` [nv,3] fp32 in [0,1] for the result images (None: grey)."""
 
-    def __init__(self, verts, faces, vertex_labels=None, device='cuda'):
+    def __init__(self, verts, faces, vertex_labels=None, device='cuda', vertex_rgb=None):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise ops.hip.PsiHipError('SceneMesh needs a GPU device (the HIP rasteriser is the only implementation)')
@@ -37,13 +44,18 @@ class SceneMesh:
         self.verts = torch.tensor(v, device=self.device)
         self.faces = torch.tensor(f.astype(np.int32), device=self.device)
         self.labels = None if vertex_labels is None else torch.tensor(as_np(vertex_labels, np.float32).reshape(self.nv), device=self.device)
+        self.rgb = None
+        if vertex_rgb is not None:
+            c = vertex_rgb.detach().cpu().numpy() if torch.is_tensor(vertex_rgb) else np.asarray(vertex_rgb)
+            scale = np.float32(255.0) if c.dtype == np.uint8 else np.float32(1.0)
+            self.rgb = torch.tensor(np.ascontiguousarray(c.reshape(self.nv, 3), dtype=np.float32) / scale, device=self.device)
         self.handle = ops.raster_mesh_create(self.verts, self.faces, self.labels)
 
     @classmethod
     def from_ply(cls, path, device='cuda'):
         """Positions, triangles and (when the file has red / green / blue) labels = min(mean(rgb) / 5, 41) of a PLY file."""
         verts, faces, rgb = scene_io.read_ply_mesh(path)
-        return cls(verts, faces, None if rgb is None else scene_io.labels_from_colors(rgb), device=device)
+        return cls(verts, faces, None if rgb is None else scene_io.labels_from_colors(rgb), device=device, vertex_rgb=rgb)
 
     def __del__(self):
         try:
@@ -184,3 +196,129 @@ def write_sensor_folder(folder, depth, seg, cam_ext, cam_int) -> list:
         np.save(os.path.join(folder, 'seg_%06d.npy' % i), np.asarray(seg[i], np.float32))
         files.append(fn)
     return files
+
+
+# ------------------------------------------------------------------------------------------
+# Result images: bodies in their scene
+# ------------------------------------------------------------------------------------------
+RESULT_WORKSPACE_BUDGET = 256 << 20     # bytes: ``draws_per_pass=None`` takes the most draws per pass whose workspace stays below this
+BODY_RGB = (0.85, 0.62, 0.5)            # the colour of a draw that is given none
+
+ResultImages = collections.namedtuple('ResultImages', 'rgb depth draw body_depth body_id counts')
+ResultImages.__doc__ = """Device tensors of one ``ResultRenderer.render`` call: rgb [n,H,W,3] uint8; depth [n,H,W] fp32, the z of whoever owns
+the pixel (0: background); draw [n,H,W] int32, the draw whose body owns the pixel (-1: scene or background); body_depth / body_id [n,H,W], the
+nearest body triangle alone (z and draw * F + face; 0 / -1); counts [M,2] int32 = per draw (pixels its body covers in front of the other
+bodies, those of them the scene does not hide)."""
+
+
+class ResultRenderer:
+    """Bodies of one topology drawn into the snapshots of ``scene_mesh`` (a ``SceneMesh``, or None: bodies over the background).
+    ``body_faces`` [F,3]; a face index outside [0, V) is refused when the first bodies arrive (V is theirs).  One call at a time."""
+
+    def __init__(self, scene_mesh, body_faces, device=None):
+        self.scene = scene_mesh
+        self.device = torch.device(device) if device is not None else (scene_mesh.device if scene_mesh is not None else torch.device('cuda'))
+        if self.device.type != 'cuda':
+            raise ops.hip.PsiHipError('ResultRenderer needs a GPU device (the HIP rasteriser is the only implementation)')
+        f = body_faces.detach().cpu().numpy() if torch.is_tensor(body_faces) else np.asarray(body_faces)
+        self.faces = torch.tensor(np.ascontiguousarray(f.reshape(-1, 3), dtype=np.int32), device=self.device)
+        self.F = self.faces.shape[0]
+        if self.F == 0:
+            raise ValueError('no body faces')
+        self.V, self.handle = None, None
+        self.snapshots = SnapshotRenderer(scene_mesh) if scene_mesh is not None else None
+        self.last_stats = None
+
+    def _bodies(self, body_verts):
+        if not torch.is_tensor(body_verts) or not body_verts.is_cuda:
+            raise ValueError('body vertices must be a GPU tensor [B,V,3] (they come from the skinning kernel; there is no CPU path)')
+        if body_verts.dim() != 3 or body_verts.shape[2] != 3:
+            raise ValueError('expected body vertices [B,V,3]')
+        bv = body_verts.detach().to(self.device, torch.float32).contiguous()
+        if self.handle is None:
+            try:
+                self.handle = ops.raster_bodies_create(self.faces, bv.shape[1])
+            except ops.hip.PsiHipError as e:
+                raise ValueError(str(e))
+            self.V = bv.shape[1]
+        if bv.shape[1] != self.V:
+            raise ValueError('bodies of %d vertices after bodies of %d: a ResultRenderer draws one topology' % (bv.shape[1], self.V))
+        return bv
+
+    def normals(self, body_verts):
+        """[B,V,3] fp32 unnormalised vertex normals, as the shading uses them: per vertex the sum, in ascending face index, of its faces'
+        (v1 - v0) x (v2 - v0); zeros for a vertex that no face lists."""
+        bv = self._bodies(body_verts)
+        return ops.raster_bodies_normals(self.handle, self.V, bv)
+
+    def pick_draws_per_pass(self, M, n_views, size):
+        """The most draws per pass (at most M) whose workspace stays below ``RESULT_WORKSPACE_BUDGET``; at least 1."""
+        H, W = int(size[0]), int(size[1])
+        fixed = ops.raster_bodies_workspace_bytes(self.F, 1, n_views, W, H)
+        per_draw = ops.raster_bodies_workspace_bytes(self.F, 2, n_views, W, H) - fixed
+        return int(max(1, min(max(M, 1), 1 + (RESULT_WORKSPACE_BUDGET - fixed) // max(per_draw, 1), (2 ** 30 - 1) // self.F)))
+
+    def render(self, body_verts, cam_ext, cam_int, size, draw_body=None, draw_view=None, body_rgb=None, near=0.05, background=(1, 1, 1),
+               draws_per_pass=None):
+        """body_verts [B,V,3] world-frame GPU tensor; cameras and size as ``SnapshotRenderer.render``.  Draw i shows body draw_body[i] in view
+        draw_view[i] with the colour body_rgb[i] ([M,3] or one colour for all, in [0,1]); by default draw i is (body i, view i), the
+        reference's cam1 picture, which needs B == n.  Returns ``ResultImages``."""
+        bv = self._bodies(body_verts)
+        ext = cam_ext.detach().cpu().numpy() if torch.is_tensor(cam_ext) else cam_ext
+        K = cam_int.detach().cpu().numpy() if torch.is_tensor(cam_int) else cam_int
+        w2c = world_to_camera(ext)
+        n, B, dev = len(w2c), bv.shape[0], self.device
+        if (draw_body is None) != (draw_view is None):
+            raise ValueError('draw_body and draw_view come together')
+        if draw_body is None:
+            if B != n:
+                raise ValueError('%d bodies and %d views: without draw_body / draw_view, draw i is (body i, view i)' % (B, n))
+            draw_body = draw_view = np.arange(B)
+        db, dv = (np.ascontiguousarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.int64).reshape(-1) for a in (draw_body, draw_view))
+        if len(db) != len(dv):
+            raise ValueError('draw_body and draw_view differ in length')
+        M = len(db)
+        if M and (db.min() < 0 or db.max() >= B or dv.min() < 0 or dv.max() >= n):
+            raise ValueError('a draw names a body outside [0, %d) or a view outside [0, %d)' % (B, n))
+        if M * self.F >= 2 ** 31:
+            raise ValueError('%d draws of %d faces: draw * F + face must stay below 2^31' % (M, self.F))
+        rgb = np.broadcast_to(np.asarray(BODY_RGB if body_rgb is None else (body_rgb.detach().cpu().numpy() if torch.is_tensor(body_rgb) else body_rgb),
+                                         dtype=np.float32), (M, 3))
+        if draws_per_pass is None:
+            draws_per_pass = self.pick_draws_per_pass(M, n, size)
+        t_w2c, t_intr = torch.tensor(w2c, device=dev), torch.tensor(intrinsics_rows(K, n), device=dev)
+        scene = {}
+        if self.scene is not None:
+            sdepth, _, stri = self.snapshots.render(ext, K, size, near)
+            scene = dict(scene=self.scene.handle, vrgb=self.scene.rgb, sdepth=sdepth, stri=stri)
+        out = ops.raster_bodies_render(self.handle, self.V, self.F, bv, torch.tensor(db, dtype=torch.int32, device=dev),
+                                       torch.tensor(dv, dtype=torch.int32, device=dev), torch.tensor(np.ascontiguousarray(rgb), device=dev), t_w2c,
+                                       t_intr, size, near, background, draws_per_pass, **scene)
+        self.last_stats = out[6].cpu().numpy()
+        for view in np.nonzero(self.last_stats[:, 1])[0]:
+            warnings.warn('view %d: %d body triangle pieces project beyond the 2^28 sub-pixel range and were not drawn' % (view, self.last_stats[view, 1]))
+        return ResultImages(*out[:6])
+
+    def __del__(self):
+        try:
+            if getattr(self, 'handle', None):
+                ops.raster_bodies_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def write_png(path, rgb_uint8):
+    """An [H,W,3] uint8 image (array or tensor) as an 8-bit RGB PNG: one zlib stream, every row with filter 0."""
+    img = rgb_uint8.detach().cpu().numpy() if torch.is_tensor(rgb_uint8) else np.asarray(rgb_uint8)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError('expected an [H,W,3] uint8 image')
+    H, W = img.shape[:2]
+    rows = np.concatenate([np.zeros((H, 1), np.uint8), np.ascontiguousarray(img).reshape(H, W * 3)], axis=1)
+
+    def chunk(tag, data):
+        return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
+
+    with open(path, 'wb') as f:
+        f.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', struct.pack('>IIBBBBB', W, H, 8, 2, 0, 0, 0)) + chunk(b'IDAT', zlib.compress(rows.tobytes(), 6))
+                + chunk(b'IEND', b''))

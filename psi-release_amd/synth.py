@@ -356,6 +356,30 @@ def make_room_cams(which: str = 'inside') -> np.ndarray:
     return np.stack([look_at(np.array(e), target) for e in eyes])
 
 
+def make_capsule_mesh(n_ring: int = 12, n_seg: int = 16, r: float = 0.16, h: float = 1.7):
+    """Stand-in body surface (``make_smplx``'s vertices are a random cloud with random faces): a closed capsule of radius ``r`` and height
+    ``h`` along z with its base at z = 0.  Two pole vertices and ``n_ring - 1`` rings of ``n_seg`` vertices at the polar angles
+    pi * i / n_ring: those up to the equator on the sphere around (0, 0, r), those above it on the sphere around (0, 0, h - r), so the band
+    between the two middle rings is the (slightly conical) trunk; faces wound outwards.  Returns (verts [V,3] fp32, faces [F,3] int32),
+    V = 2 + (n_ring - 1) * n_seg, F = 2 * n_seg * (n_ring - 1): 178 and 352."""
+    if n_ring < 3 or n_seg < 3 or h <= 2 * r:
+        raise ValueError('a capsule needs n_ring >= 3, n_seg >= 3 and h > 2 r')
+    theta = np.pi * np.arange(1, n_ring) / n_ring
+    phi = 2.0 * np.pi * np.arange(n_seg) / n_seg
+    zc = np.where(theta <= np.pi / 2 + 1e-12, r, h - r)
+    ring = np.stack([r * np.sin(theta)[:, None] * np.cos(phi)[None], r * np.sin(theta)[:, None] * np.sin(phi)[None],
+                     np.broadcast_to((zc - r * np.cos(theta))[:, None], (n_ring - 1, n_seg))], -1)
+    verts = np.concatenate([[[0.0, 0.0, 0.0]], ring.reshape(-1, 3), [[0.0, 0.0, h]]])
+    idx = 1 + np.arange((n_ring - 1) * n_seg).reshape(n_ring - 1, n_seg)
+    nxt = np.roll(idx, -1, axis=1)
+    top = len(verts) - 1
+    faces = [np.stack([np.zeros(n_seg, np.int64), nxt[0], idx[0]], 1)]
+    for i in range(n_ring - 2):
+        faces += [np.stack([idx[i], nxt[i], nxt[i + 1]], 1), np.stack([idx[i], nxt[i + 1], idx[i + 1]], 1)]
+    faces.append(np.stack([np.full(n_seg, top), idx[-1], nxt[-1]], 1))
+    return _f32(verts), np.ascontiguousarray(np.concatenate(faces), dtype=np.int32)
+
+
 @dataclass
 class OrientedRoom:
     """A closed, consistently oriented stand-in scene with an exact distance field (``make_oriented_room``)."""

@@ -1,0 +1,252 @@
+"""Result images (csrc/raster_bodies.hip, rendering.ResultRenderer) on the GPU against the NumPy restatement of their contract
+(tests/compose_ref.py): owner, ids, depths, colours and counts; bit identity over reruns, passes, batching and draw order; a streamed
+bin; no scene; empty views; the normals; the refusals; the entry script."""
+import functools
+import glob
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import compose_ref as C
+from conftest import ROOT
+from psi_release_amd import generation, hip, ops, rendering, synth
+from test_result_images_cpu import decode_png
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+FIELDS = ('rgb', 'depth', 'draw', 'body_depth', 'body_id', 'counts')
+
+
+@functools.lru_cache(None)
+def scene():
+    fx = C.fixture()
+    return rendering.SceneMesh(fx['room'].verts, fx['room'].faces, fx['room'].labels, device=DEV, vertex_rgb=fx['vrgb'])
+
+
+@functools.lru_cache(None)
+def renderer():
+    return rendering.ResultRenderer(scene(), C.fixture()['bfaces'])
+
+
+def to_np(res):
+    return {k: getattr(res, k).cpu().numpy() for k in FIELDS}
+
+
+def render_fixture(size, views=slice(None), order=None, r=None, **kw):
+    """The fixture's draws (those of ``views``, renumbered; in the order ``order``) through ``ResultRenderer.render``."""
+    fx = C.fixture()
+    cams = fx['cams'][views]
+    first = 0 if views == slice(None) else views.start
+    keep = np.nonzero((fx['draw_view'] >= first) & (fx['draw_view'] < first + len(cams)))[0]
+    if order is not None:
+        keep = keep[order]
+    res = (r or renderer()).render(torch.tensor(fx['bverts'], device=DEV), cams, C.K_of(size), size, draw_body=fx['draw_body'][keep],
+                                   draw_view=fx['draw_view'][keep] - first, body_rgb=fx['draw_rgb'][keep], background=C.BACKGROUND, **kw)
+    return to_np(res), keep
+
+
+@functools.lru_cache(None)
+def rendered(size):
+    return render_fixture(size)[0]
+
+
+@pytest.mark.parametrize('size', C.SIZES)
+def test_composite_against_the_restatement(size):
+    """Test 1 of the contract.  Body-only hit mask equal on every pixel; body_id equal where the restatement's body pass is clear; draw
+    equal wherever body and scene depth differ by more than 1e-4 relative; no pixel of the fixture is excluded (asserted); depth and
+    body_depth within 1e-5 relative where the owner agrees; rgb within one level per channel (the fp32 chain is about ten roundings of
+    terms <= 1, under 2e-6 x 255: it can move a value across a rounding boundary, never by two levels); counts equal the
+    restatement's, and the counts recomputed from the returned body_id, body_depth and the scene's depth."""
+    fx, ref, got = C.fixture(), C.fixture_reference(size), rendered(size)
+    nF = len(fx['bfaces'])
+    assert not ref['near_tie'].any() and ref['body_clear'].all()
+    excluded, derr, berr, share = C.check_images(got, ref, nF)
+    assert excluded == 0.0
+    print('counts', got['counts'].reshape(6, 8).tolist())
+    assert np.array_equal(got['counts'], ref['counts'])
+    sdepth, _, stri = rendering.SnapshotRenderer(scene()).render(fx['cams'], C.K_of(size), size)
+    assert np.array_equal(C.counts_from_images(got['body_id'], got['body_depth'], sdepth.cpu().numpy(), stri.cpu().numpy() >= 0, 24, nF), got['counts'])
+    if size == (48, 64):
+        c = got['counts'].reshape(6, 4, 2)
+        assert c[5, 2].tolist() == [3072, 3072] and c[1, 1, 0] == c[1, 1, 1] > 200 and 0 < c[2, 0, 1] < c[2, 0, 0] and c[2, 3, 0] > 0 == c[2, 3, 1]
+
+
+def test_bit_identity_over_reruns_passes_batching_and_draw_order():
+    size = C.SIZES[1]
+    base = rendered(size)
+    again, _ = render_fixture(size)
+    for k in FIELDS:
+        assert np.array_equal(base[k], again[k]), k
+    for dpp in (1, 5, 24):
+        got, _ = render_fixture(size, draws_per_pass=dpp)
+        for k in FIELDS:
+            assert np.array_equal(base[k], got[k]), (dpp, k)
+    nF = len(C.fixture()['bfaces'])
+    for v in range(4):
+        one, keep = render_fixture(size, views=slice(v, v + 1))
+        for k in ('rgb', 'depth', 'body_depth'):
+            assert np.array_equal(base[k][v], one[k][0]), (v, k)
+        back = lambda img, per: np.where(img >= 0, keep[np.maximum(img, 0) // per] * per + np.maximum(img, 0) % per, -1)
+        assert np.array_equal(base['draw'][v], back(one['draw'][0], 1)) and np.array_equal(base['body_id'][v], back(one['body_id'][0], nF))
+        assert np.array_equal(base['counts'][keep], one['counts'])
+    perm = np.random.RandomState(7).permutation(24)
+    got, keep = render_fixture(size, order=perm, draws_per_pass=7)
+    for k in ('depth', 'body_depth'):
+        assert np.array_equal(base[k], got[k]), k
+    assert np.array_equal(base['draw'], np.where(got['draw'] >= 0, keep[np.maximum(got['draw'], 0)], -1))
+    assert np.array_equal(base['counts'][keep], got['counts'])
+    ids = np.where(got['body_id'] >= 0, keep[np.maximum(got['body_id'], 0) // nF] * nF + np.maximum(got['body_id'], 0) % nF, -1)
+    differ = ids != base['body_id']
+    assert differ.mean() <= 0.001                                                   # exact depth ties go to the lower index of each order
+    assert np.array_equal(base['rgb'][~differ], got['rgb'][~differ])
+
+
+def pixel_to_world(u, v, z, K):
+    return np.stack([(u - K[0, 2]) * z / K[0, 0], (v - K[1, 2]) * z / K[1, 1], z], -1)
+
+
+def test_many_tiny_body_triangles_in_one_tile_cut_by_a_plane():
+    """A body of 3000 triangles of about a pixel inside the tile [16,32) x [16,32), depths 1 .. 3 (the bin is streamed in 12 chunks),
+    behind and in front of a two-triangle scene plane at z = 2; identity camera."""
+    size, K, rs = (48, 64), C.K_of((48, 64)), np.random.RandomState(3)
+    n = 3000
+    c = rs.uniform(17.5, 30.5, (n, 1, 2)) + rs.uniform(-1.2, 1.2, (n, 3, 2))
+    z = rs.uniform(1.0, 3.0, (n, 3))
+    bverts = pixel_to_world(c[..., 0], c[..., 1], z, K).reshape(1, -1, 3).astype(np.float32)
+    bfaces = np.arange(3 * n).reshape(n, 3)
+    plane = pixel_to_world(np.array([-10.0, 80.0, 80.0, -10.0]), np.array([-10.0, -10.0, 60.0, 60.0]), np.full(4, 2.0), K).astype(np.float32)
+    pfaces = np.array([[0, 1, 2], [0, 2, 3]])
+    prgb = np.array([[0.9, 0.2, 0.1], [0.1, 0.8, 0.3], [0.2, 0.3, 0.9], [0.7, 0.7, 0.1]], np.float32)
+    colour = np.array([[0.3, 0.6, 0.9]], np.float32)
+    ref = C.compose_views((plane, pfaces, prgb), bverts, bfaces, [0], [0], colour, np.eye(4)[None], K, size, background=C.BACKGROUND)
+    mesh = rendering.SceneMesh(plane, pfaces, device=DEV, vertex_rgb=prgb)
+    got = to_np(rendering.ResultRenderer(mesh, bfaces).render(torch.tensor(bverts, device=DEV), np.eye(4)[None], K, size, body_rgb=colour,
+                                                              background=C.BACKGROUND))
+    C.check_images(got, ref, n, max_excluded=1.0)
+    assert np.array_equal(C.counts_from_images(got['body_id'], got['body_depth'], np.where(ref['scene_hit'], 2.0, 0.0), ref['scene_hit'], 1, n)[:, 0],
+                          got['counts'][:, 0])
+    covered, visible = got['counts'][0]
+    print('covered %d visible %d' % (covered, visible))
+    assert 0 < visible < covered
+    assert len(np.unique(got['body_id'][got['body_id'] >= 0])) > 100
+
+
+def test_no_scene():
+    fx, size = C.fixture(), C.SIZES[1]
+    r = rendering.ResultRenderer(None, fx['bfaces'])
+    bg = (0.25, 0.5, 1.0)
+    res = to_np(r.render(torch.tensor(fx['bverts'], device=DEV), fx['cams'], C.K_of(size), size, draw_body=fx['draw_body'], draw_view=fx['draw_view'],
+                         body_rgb=fx['draw_rgb'], background=bg))
+    empty = res['body_id'] < 0
+    assert empty.any() and (~empty).any()
+    assert (res['rgb'][empty] == np.array([64, 128, 255], np.uint8)).all()          # rint(63.75), rint(127.5) to even, 255
+    assert np.array_equal(res['counts'][:, 0], res['counts'][:, 1]) and res['counts'].sum() > 0
+    assert np.array_equal(res['depth'], res['body_depth'])
+    assert np.array_equal(res['draw'], np.where(empty, -1, res['body_id'] // len(fx['bfaces'])))
+    assert np.array_equal(res['body_id'], rendered(size)['body_id']) and np.array_equal(res['body_depth'], rendered(size)['body_depth'])
+
+
+def test_view_without_a_draw_and_body_behind_its_camera():
+    fx, size = C.fixture(), C.SIZES[0]
+    cams, K = fx['cams'], C.K_of(size)
+    bverts = torch.tensor(fx['bverts'], device=DEV)
+    behind = cams[0][:3, 3] - 2.0 * cams[0][:3, 2] - np.array([0.0, 0.0, 0.85])     # 2 m behind camera 0
+    bverts = torch.cat([bverts, torch.tensor((synth.make_capsule_mesh()[0] + behind).astype(np.float32), device=DEV)[None]])
+    # view 1 has no draw; body 6 is wholly behind its camera (view 0)
+    res = to_np(renderer().render(bverts, cams, K, size, draw_body=[1, 6, 2, 3], draw_view=[0, 0, 2, 3], background=C.BACKGROUND))
+    none = to_np(renderer().render(bverts[:0], cams, K, size, draw_body=[], draw_view=[], background=C.BACKGROUND))
+    assert (res['draw'][1] == -1).all() and (res['body_id'][1] == -1).all()
+    assert np.array_equal(res['rgb'][1], none['rgb'][1]) and np.array_equal(res['depth'][1], none['depth'][1])
+    assert res['counts'][1].tolist() == [0, 0] and res['counts'][0, 0] > 0
+    assert none['counts'].shape == (0, 2) and (none['draw'] == -1).all()
+    sdepth, _, _ = rendering.SnapshotRenderer(scene()).render(cams, K, size)
+    assert np.array_equal(none['depth'], sdepth.cpu().numpy())
+
+
+def test_normals():
+    """Against the fp64 sums: the absolute error per component is at most 1e-5 x sum |cross_i| of that vertex (under ten fp32 additions of
+    already-rounded products, about 1e-6 relative, with a tenfold margin); a vertex listed by no face gives exact zeros."""
+    fx = C.fixture()
+    got = renderer().normals(torch.tensor(fx['bverts'], device=DEV)).cpu().numpy()
+    n64, a64 = C.vertex_normal_sums(fx['bverts'], fx['bfaces'])
+    err = np.abs(got - n64)
+    print('normals: max error / bound %.3f' % (err / (1e-5 * a64)).max())
+    assert (err <= 1e-5 * a64).all() and np.abs(got).max() > 1e-3
+    verts = np.concatenate([fx['bverts'], np.ones((6, 2, 3), np.float32)], 1)       # two vertices that no face lists
+    r = rendering.ResultRenderer(None, fx['bfaces'])
+    more = r.normals(torch.tensor(verts, device=DEV)).cpu().numpy()
+    assert np.array_equal(more[:, :178], got) and (more[:, 178:] == 0).all()
+
+
+def test_argument_checks():
+    fx = C.fixture()
+    bverts = torch.tensor(fx['bverts'], device=DEV)
+    faces = torch.tensor(fx['bfaces'], device=DEV)
+    bad = fx['bfaces'].copy()
+    bad[17, 1] = 178
+    with pytest.raises(hip.PsiHipError, match='face index'):
+        ops.raster_bodies_create(torch.tensor(bad, device=DEV), 178)
+    with pytest.raises(ValueError):
+        rendering.ResultRenderer(None, bad).normals(bverts)
+    size, K = C.SIZES[0], C.K_of(C.SIZES[0])
+    for db, dv in (([0, 6], [0, 1]), ([0, -1], [0, 1]), ([0, 1], [0, 4]), ([0, 1], [-1, 0])):
+        with pytest.raises(ValueError):
+            renderer().render(bverts, fx['cams'], K, size, draw_body=db, draw_view=dv)
+        # the device's own check, under the Python one
+        h = ops.raster_bodies_create(faces, 178)
+        w2c = torch.tensor(rendering.world_to_camera(fx['cams']), device=DEV)
+        intr = torch.tensor(rendering.intrinsics_rows(K, 4), device=DEV)
+        with pytest.raises(hip.PsiHipError, match='draw'):
+            ops.raster_bodies_render(h, 178, 352, bverts, torch.tensor(db, dtype=torch.int32, device=DEV), torch.tensor(dv, dtype=torch.int32, device=DEV),
+                                     torch.ones(2, 3, device=DEV), w2c, intr, size, 0.05, (1, 1, 1), 2)
+        ops.raster_bodies_destroy(h)
+    with pytest.raises(ValueError):
+        renderer().render(bverts, fx['cams'], K, size)                              # 6 bodies, 4 views, no draws given
+    with pytest.raises(ValueError):
+        ops.raster_bodies_workspace_bytes(1 << 27, 16, 1, 64, 48)                   # M * F = 2^31 with a faked F: nothing is allocated
+    assert hip.lib().psi_raster_bodies_workspace_bytes(1 << 27, 16, 1, 64, 48) == 0
+    with pytest.raises((ValueError, hip.PsiHipError)):
+        renderer().render(torch.tensor(fx['bverts']), fx['cams'], K, size, draw_body=[0], draw_view=[0])
+    with pytest.raises((ValueError, hip.PsiHipError)):
+        renderer().normals(torch.tensor(fx['bverts']))
+
+
+def _testop(tmp, tag, test_data_path=None):
+    """The recipe of test_render_gpu.py."""
+    ckpt, out = os.path.join(tmp, 'ckpt'), os.path.join(tmp, 'gen_' + tag)
+    op = generation.TestOP({'outdir': out, 'ckpt_dir': ckpt, 'device': torch.device(DEV), 'test_data_path': test_data_path, 'n_samples': 1,
+                            'use_cont_rot': True, 'stage': 's2'})
+    if not os.path.exists(ckpt):
+        os.makedirs(ckpt)
+        shapes = {k: tuple(v.shape) for k, v in op.model_h.state_dict().items()}
+        torch.save({'epoch': 1, 'model_h_state_dict': {k: torch.tensor(v) for k, v in synth.make_state_like(shapes, 2).items()}},
+                   os.path.join(ckpt, 'epoch-000001.ckp'))
+    rs = np.random.RandomState(11)
+    lat = [(rs.standard_normal((1, 32)).astype(np.float32), rs.standard_normal((1, 32)).astype(np.float32)) for _ in range(8)]
+    op.latent_source = lambda view, n: (torch.tensor(lat[view][0], device=DEV), torch.tensor(lat[view][1], device=DEV))
+    return op, out
+
+
+def test_entry_script(tmp_path):
+    tmp = str(tmp_path)
+    room = synth.make_room_mesh(0, 180)
+    mesh = rendering.SceneMesh(room.verts, room.faces, room.labels, device=DEV)
+    op, gen = _testop(tmp, 'show')
+    op.test_mesh(mesh, C.fixture()['cams'][:3], C.K_of((54, 96), 70.0), (54, 96))
+    assert len(glob.glob(os.path.join(gen, 'body_gen_*.pkl'))) == 3
+    script = os.path.join(ROOT, 'psi-release_amd', 'utils', 'utils_show_test_results.py')
+    out = os.path.join(tmp, 'img')
+    r = subprocess.run([sys.executable, script, gen, '-', out, '--synthetic', os.path.join(tmp, 'syn'), '--size', '54', '96', '--no_flip'],
+                       capture_output=True, text=True, timeout=600, cwd=os.path.dirname(script))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    files = sorted(glob.glob(os.path.join(out, 'img_*_cam1.png')))
+    assert len(files) == 3
+    for fn in files:
+        assert decode_png(fn).shape == (54, 96, 3)
+    report = json.load(open(os.path.join(out, 'visibility.json')))
+    assert len(report) == 3 and all(0 <= row['cam1']['visible'] <= row['cam1']['covered'] for row in report)
