@@ -603,6 +603,28 @@ int psi_mesh_sdf_compute(psi_mesh_sdf *m, const float gmin[3], const float gmax[
 int psi_mesh_sdf_count_pairs(psi_mesh_sdf *m, const float gmin[3], const float gmax[3], int D, int mode, unsigned long long *d_pairs,
                              void *stream);
 
+/* ---- generalised winding number of the same mesh: the sign of the volume for open, touching and interpenetrating meshes ----
+ * Contract (DESIGN.md "Winding-number sign"): with a = A - p, b = B - p, c = C - p of a kept triangle,
+ *   Omega = 2 atan2(a . (b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|), atan2(0, 0) = 0, and f(p) = -(1 / 4 pi) sum Omega:
+ * 1 in the free space of a closed room whose triangles face free space, 0 inside furniture and outside the room.  A node is solid iff
+ * f < level (0.5 for a room, -0.5 for objects standing in open space).  The sum is fp32 within a chunk of 256 records and fp64 across
+ * chunks, in a fixed order (kept order when beta = 0; cluster order, then the order within the cluster, otherwise): bit-identical from run
+ * to run, no floating-point atomics; unlike the distance it may change in the last bits under a permutation of the faces.
+ * beta > 0: the kept triangles, sorted by the Morton code of their centroids, are cut into clusters of `cluster` triangles; a cluster whose
+ * area-weighted centroid c lies farther than beta * r (r = its largest vertex distance from c) from the box of an 8 x 8 x 8 brick of nodes
+ * contributes -N . (c - p) / (4 pi |c - p|^3) to the f of that brick's nodes (N = the sum of its area vectors), a nearer one its
+ * triangles.  The records of beta = 0 and the clusters of each `cluster` value are built on the host and uploaded at first use (that call
+ * synchronises the device) and cached on the handle; every later call is one kernel on `stream` with no host synchronisation.
+ * d_f: device [D,D,D] fp32, element [ix][iy][iz], the node positions of psi_mesh_sdf_compute.  PSI_EINVAL: the cases of
+ * psi_mesh_sdf_compute, beta < 0 or not finite, cluster outside 8 .. 256. */
+int psi_mesh_winding_compute(psi_mesh_sdf *m, const float gmin[3], const float gmax[3], int D, float beta, int cluster, float *d_f, void *stream);
+/* The counting build of the same kernel: d_counts[0] receives the (node, triangle) tests, d_counts[1] the (node, dipole) tests, over
+ * the D^3 nodes. */
+int psi_mesh_winding_count(psi_mesh_sdf *m, const float gmin[3], const float gmax[3], int D, float beta, int cluster,
+                           unsigned long long *d_counts /*[2]*/, void *stream);
+/* d_vol[i] = d_f[i] < level ? -|d_vol[i]| : |d_vol[i]| for i < n: one elementwise kernel on `stream`. */
+int psi_mesh_sdf_apply_sign(const float *d_f, float level, float *d_vol, long long n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,8 +21,7 @@
 //               shell loop is bounded by the extent of the cell grid.  mode 1: every record is streamed through the same routine.
 // No floating-point atomics, no communication between workgroups, no spinning: the volume is bit-identical from run to run, and pruning
 // changes no bit (the bounds carry an explicit slack, below).
-#include "psi_common.h"
-#include <math.h>
+#include "mesh_sdf_shared.h"
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -61,7 +60,6 @@ struct NodeGrid {
     float slack;
 };
 
-#define MS_FN __host__ __device__ __forceinline__
 #ifdef __HIP_DEVICE_COMPILE__
 #define MS_DIV(a, b) __fdiv_rn((a), (b))
 #define MS_SQRT(a) __fsqrt_rn(a)
@@ -116,7 +114,7 @@ MS_FN int closest_point(float abx, float aby, float abz, float acx, float acy, f
     return region;
 }
 
-MS_FN float node_pos(const NodeGrid &g, int axis, int i) { return g.gmin[axis] + (float)i * g.step[axis]; }
+MS_FN float node_pos(const NodeGrid &g, int axis, int i) { return psi_mesh_node_pos(g.gmin[axis], g.step[axis], i); }
 
 // the cell of the grid a coordinate lies in (clamped): monotone in x, which is all that binning and search need from it
 MS_FN int cell_of(const CellGrid &g, int axis, float x)
@@ -468,6 +466,7 @@ struct HostMesh {
     std::vector<TriRec> recs;
     std::vector<NrmRec> nrm;
     std::vector<int> cell_start, bins;
+    std::vector<float> kept;   // [nk][3][3]: the vertices A, B, C of the kept triangles (what the winding number is summed over)
     CellGrid cg;
     int32_t info[4];
     float scale;       // the largest coordinate magnitude of the kept triangles
@@ -546,6 +545,7 @@ int build_host_mesh(const std::vector<float> &hv, const std::vector<int32_t> &hf
         i = j;
     }
     std::vector<TriRec> hr((size_t)nk);
+    hm.kept.resize((size_t)nk * 9);
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int t = 0; t < nk; t++) {
         TriRec &r = hr[t];
@@ -554,6 +554,9 @@ int build_host_mesh(const std::vector<float> &hv, const std::vector<int32_t> &hf
             r.a[k] = hv[(size_t)a * 3 + k];
             r.ab[k] = hv[(size_t)b * 3 + k] - r.a[k];          // fp32, rounded once: the statement the contract names
             r.ac[k] = hv[(size_t)c * 3 + k] - r.a[k];
+            hm.kept[(size_t)t * 9 + k] = hv[(size_t)a * 3 + k];
+            hm.kept[(size_t)t * 9 + 3 + k] = hv[(size_t)b * 3 + k];
+            hm.kept[(size_t)t * 9 + 6 + k] = hv[(size_t)c * 3 + k];
             lo[k] = fminf(lo[k], fminf(r.a[k], fminf(hv[(size_t)b * 3 + k], hv[(size_t)c * 3 + k])));
             hi[k] = fmaxf(hi[k], fmaxf(r.a[k], fmaxf(hv[(size_t)b * 3 + k], hv[(size_t)c * 3 + k])));
         }
@@ -637,7 +640,17 @@ struct psi_mesh_sdf {
     int32_t info[4];
     CellGrid cg;
     float scale;
+    std::vector<float> kept;   // host copy of the kept triangles, for csrc/mesh_winding.hip
+    psi_mesh_aux aux;          // what it builds from them at first use
 };
+
+const float *psi_mesh_sdf_kept_tris(const psi_mesh_sdf *m, int *nk)
+{
+    *nk = m->nk;
+    return m->kept.data();
+}
+
+psi_mesh_aux *psi_mesh_sdf_aux(psi_mesh_sdf *m) { return &m->aux; }
 
 extern "C" int psi_mesh_sdf_create(psi_mesh_sdf **out, const float *d_verts, const int32_t *d_faces, int nv, int nf)
 {
@@ -661,6 +674,8 @@ extern "C" int psi_mesh_sdf_create(psi_mesh_sdf **out, const float *d_verts, con
     m->nk = nk;
     m->cg = hm.cg;
     m->scale = hm.scale;
+    m->kept.swap(hm.kept);
+    m->aux = psi_mesh_aux{nullptr, nullptr};
     for (int k = 0; k < 4; k++) m->info[k] = hm.info[k];
     auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_rec = pad((size_t)nk * sizeof(TriRec)), b_nrm = pad((size_t)nk * sizeof(NrmRec)), b_start = pad((ncell + 1) * 4),
@@ -693,6 +708,7 @@ extern "C" int psi_mesh_sdf_create(psi_mesh_sdf **out, const float *d_verts, con
 extern "C" void psi_mesh_sdf_destroy(psi_mesh_sdf *m)
 {
     if (!m) return;
+    if (m->aux.p && m->aux.destroy) m->aux.destroy(m->aux.p);
     (void)hipFree(m->blob);
     delete m;
 }
@@ -708,16 +724,13 @@ static int mesh_sdf_launch(psi_mesh_sdf *m, const float gmin[3], const float gma
                            void *stream)
 {
     PSI_REQUIRE(m && gmin && gmax && (d_out || d_pairs), "null pointer");
-    PSI_REQUIRE(D >= 2 && D <= 1024, "2 <= D <= 1024");
     PSI_REQUIRE(mode == 0 || mode == 1, "mode is 0 (pruned search) or 1 (every node against every triangle)");
     NodeGrid ng;
+    const int rc = psi_mesh_node_steps(gmin, gmax, D, ng.step);
+    if (rc != 0) return rc;
     float scale = m->scale;
     for (int k = 0; k < 3; k++) {
-        PSI_REQUIRE(std::isfinite(gmin[k]) && std::isfinite(gmax[k]), "the grid bounds must be finite");
-        PSI_REQUIRE(gmax[k] > gmin[k], "gmax > gmin on every axis");
         ng.gmin[k] = gmin[k];
-        ng.step[k] = (gmax[k] - gmin[k]) / (float)(D - 1);
-        PSI_REQUIRE(std::isfinite(ng.step[k]) && ng.step[k] > 0.0f, "the grid spacing must be a positive finite fp32 number");
         scale = fmaxf(scale, fmaxf(fabsf(gmin[k]), fabsf(gmax[k])));
     }
     ng.D = D;

@@ -133,6 +133,9 @@ SIGNATURES = {
     'psi_mesh_sdf_info': (c_int, [c_void_p, c_void_p]),
     'psi_mesh_sdf_compute': (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p, c_void_p]),
     'psi_mesh_sdf_count_pairs': (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p, c_void_p]),
+    'psi_mesh_winding_compute': (c_int, [c_void_p] * 3 + [c_int, c_float, c_int, c_void_p, c_void_p]),
+    'psi_mesh_winding_count': (c_int, [c_void_p] * 3 + [c_int, c_float, c_int, c_void_p, c_void_p]),
+    'psi_mesh_sdf_apply_sign': (c_int, [c_void_p, c_float, c_void_p, ctypes.c_longlong, c_void_p]),
 }
 
 

@@ -1118,3 +1118,50 @@ def mesh_sdf_count_pairs(handle, grid_min, grid_max, dim, mode=0, device='cuda')
     with torch.cuda.device(n.device):
         hip.check(hip.lib().psi_mesh_sdf_count_pairs(handle, lo, hi, int(dim), int(mode), hip.ptr(n), hip.stream()), 'psi_mesh_sdf_count_pairs')
     return int(n.item())
+
+
+# ------------------------------------------------------------------------------------------
+# Generalised winding number of the same mesh (psi_mesh_winding_*, psi_mesh_sdf_apply_sign)
+# ------------------------------------------------------------------------------------------
+def _mesh_winding_args(dim, beta, cluster):
+    import math
+    dim, beta, cluster = int(dim), float(beta), int(cluster)
+    if dim < 2 or dim > 1024:
+        raise hip.PsiHipError('psi_mesh_winding: 2 <= D <= 1024 (got %d)' % dim)
+    if not math.isfinite(beta) or beta < 0:
+        raise hip.PsiHipError('psi_mesh_winding: beta is finite and not negative (got %r)' % beta)
+    if cluster < 8 or cluster > 256:
+        raise hip.PsiHipError('psi_mesh_winding: 8 <= cluster <= 256 (got %d)' % cluster)
+    return dim, beta, cluster
+
+
+def mesh_winding_compute(handle, grid_min, grid_max, dim, beta=3.0, cluster=64, device='cuda'):
+    """The free-space winding number f [D,D,D] fp32, element [ix][iy][iz], of the mesh behind ``handle`` on the nodes of
+    ``mesh_sdf_compute``: 1 in the free space of a closed room, 0 in furniture and outside.  ``beta`` = 0: every node against every
+    triangle; ``beta`` > 0: clusters of ``cluster`` triangles farther than beta x their radius from a brick of nodes count as dipoles."""
+    lo, hi = _mesh_sdf_bounds(grid_min, grid_max)
+    dim, beta, cluster = _mesh_winding_args(dim, beta, cluster)
+    out = torch.empty(dim, dim, dim, device=device)
+    with torch.cuda.device(out.device):
+        hip.check(hip.lib().psi_mesh_winding_compute(handle, lo, hi, dim, beta, cluster, hip.ptr(out), hip.stream()), 'psi_mesh_winding_compute')
+    return out
+
+
+def mesh_winding_count(handle, grid_min, grid_max, dim, beta=3.0, cluster=64, device='cuda'):
+    """(exact (node, triangle) tests, (node, dipole) tests) that ``mesh_winding_compute`` executes, from the counting build of the kernel."""
+    lo, hi = _mesh_sdf_bounds(grid_min, grid_max)
+    dim, beta, cluster = _mesh_winding_args(dim, beta, cluster)
+    n = torch.zeros(2, dtype=torch.int64, device=device)
+    with torch.cuda.device(n.device):
+        hip.check(hip.lib().psi_mesh_winding_count(handle, lo, hi, dim, beta, cluster, hip.ptr(n), hip.stream()), 'psi_mesh_winding_count')
+    return tuple(int(x) for x in n.tolist())
+
+
+def mesh_sdf_apply_sign(f, level, vol):
+    """In place: vol = -|vol| where f < level, |vol| elsewhere (f and vol fp32 on the GPU, the same number of elements).  Returns vol."""
+    pf, pv = hip.ptr(f), hip.ptr(vol)
+    if f.dtype != torch.float32 or vol.dtype != torch.float32 or f.numel() != vol.numel() or f.numel() == 0:
+        raise ValueError('expected f and vol float32 with the same, non-zero number of elements')
+    with torch.cuda.device(vol.device):
+        hip.check(hip.lib().psi_mesh_sdf_apply_sign(pf, float(level), pv, vol.numel(), hip.stream()), 'psi_mesh_sdf_apply_sign')
+    return vol

@@ -8,9 +8,10 @@ volume" states the contract).
 * ``scene_from_mesh``  both, as the ``synth.SceneData`` that ``FittingOP(scene=...)``, ``scenes=[...]`` and ``write_prox_layout`` take
 
 Convention: triangles face free space, so free space is positive and solid is negative — what the collision term and
-``psi_lbs_sdf_counts`` assume.  An open or non-manifold mesh gets its sign from the orientation of the nearest triangle.  Two coincident,
-oppositely oriented surfaces (a box standing exactly on the floor) leave the sign below them ambiguous.  Computing needs the GPU; there is
-no CPU path.
+``psi_lbs_sdf_counts`` assume.  With the default ``sign='pseudonormal'`` an open or non-manifold mesh gets its sign from the orientation
+of the nearest triangle, and two coincident, oppositely oriented surfaces (a box standing exactly on the floor) leave the sign below them
+ambiguous.  ``sign='winding'`` takes the sign from the generalised winding number instead (csrc/mesh_winding.hip, DESIGN.md
+"Winding-number sign"), which is robust to both.  Computing needs the GPU; there is no CPU path.
 """
 from __future__ import annotations
 
@@ -22,6 +23,8 @@ import torch
 from . import ops, scene_io, synth
 
 MODES = {'grid': 0, 'brute': 1}
+SIGNS = ('pseudonormal', 'winding')
+LEVELS = {'solid': 0.5, 'free': -0.5}      # a node is solid iff its free-space winding number is below the level
 ENGINE_MAX_DIM = 480       # the several-scenes engine samples a re-ordered copy of the volume: D % 4 == 0, D <= 480 (psi_fit_create_scenes)
 
 
@@ -51,12 +54,29 @@ class MeshSDF:
         verts, faces, _ = scene_io.read_ply_mesh(path)
         return cls(verts, faces, device=device)
 
-    def compute(self, grid_min, grid_max, dim, mode='grid'):
+    def winding(self, grid_min, grid_max, dim, beta=3.0, cluster=64):
+        """The free-space winding number f [D,D,D] fp32 on the GPU at the nodes of ``compute``: 1 in the free space of a closed room whose
+        triangles face free space, 0 inside furniture and outside the room, in between near the holes of an open mesh.  ``beta`` = 0 sums
+        every triangle at every node; ``beta`` > 0 replaces clusters of ``cluster`` triangles that lie farther than beta x their radius
+        from an 8 x 8 x 8 brick of nodes by their dipoles."""
+        return ops.mesh_winding_compute(self.handle, grid_min, grid_max, dim, beta, cluster, device=self.device)
+
+    def compute(self, grid_min, grid_max, dim, mode='grid', sign='pseudonormal', exterior='solid', beta=3.0, cluster=64):
         """The volume [D,D,D] fp32 on the GPU, element [ix][iy][iz]; node i of axis a lies at
         grid_min[a] + i * ((grid_max[a] - grid_min[a]) / (D - 1)).  ``mode``: 'grid' (pruned search) or 'brute' (every node against every
-        triangle; the same bits, for checking)."""
+        triangle; the same bits, for checking).  ``sign``: 'pseudonormal' (of the nearest feature: exact for a closed, consistently
+        oriented mesh) or 'winding' (the same magnitudes, negative where ``winding(..., beta, cluster)`` is below the level: 0.5 with
+        ``exterior='solid'``, a room, what lies behind its walls is solid; -0.5 with ``exterior='free'``, objects standing in open space)."""
         if mode not in MODES:
             raise ValueError("mode is 'grid' or 'brute'")
+        if sign not in SIGNS:
+            raise ValueError("sign is 'pseudonormal' or 'winding'")
+        if exterior not in LEVELS:
+            raise ValueError("exterior is 'solid' or 'free'")
+        if sign == 'winding':
+            f = self.winding(grid_min, grid_max, dim, beta, cluster)
+            vol = ops.mesh_sdf_compute(self.handle, grid_min, grid_max, dim, MODES[mode], device=self.device)
+            return ops.mesh_sdf_apply_sign(f, LEVELS[exterior], vol)
         if self.info[3] > 0 and not self._warned:
             self._warned = True
             warnings.warn('mesh is not closed: the sign follows the triangle orientation (%d edges are not shared by exactly two triangles)'
@@ -100,17 +120,20 @@ def grid_box(verts, margin):
     return (v.min(0) - np.float32(margin)).astype(np.float32), (v.max(0) + np.float32(margin)).astype(np.float32)
 
 
-def scene_from_mesh(verts, faces, dim=256, margin=0.5, voxel=None, contact_parts=None, check_engine=True, device='cuda') -> synth.SceneData:
+def scene_from_mesh(verts, faces, dim=256, margin=0.5, voxel=None, contact_parts=None, check_engine=True, device='cuda', sign='pseudonormal',
+                    exterior='solid', beta=3.0) -> synth.SceneData:
     """The ``synth.SceneData`` of a scene mesh: ``sdf`` [D,D,D] computed on the GPU over the mesh's box grown by ``margin`` on every side,
     ``verts`` = ``scene_cloud(verts, voxel)``.  ``FittingOP(scene=...)``, ``scenes=[...]`` and ``SceneData.write_prox_layout`` take it as
     is.  The several-scenes engine refuses D % 4 != 0 and D > 480: the same ``ValueError`` is raised here, before any work, unless
-    ``check_engine=False``."""
+    ``check_engine=False``.  ``sign``, ``exterior`` and ``beta`` are those of ``MeshSDF.compute``."""
     dim = int(dim)
     if check_engine:
         check_engine_dim(dim)
     if not margin >= 0:
         raise ValueError('margin must not be negative')
+    if sign not in SIGNS or exterior not in LEVELS:
+        raise ValueError("sign is 'pseudonormal' or 'winding', exterior is 'solid' or 'free'")
     mesh = MeshSDF(verts, faces, device=device)
     lo, hi = grid_box(verts, margin)
-    sdf = mesh.compute(lo, hi, dim).cpu().numpy()
+    sdf = mesh.compute(lo, hi, dim, sign=sign, exterior=exterior, beta=beta).cpu().numpy()
     return synth.SceneData(scene_cloud(verts, voxel), sdf, lo, hi, dim, dict(contact_parts or {}))

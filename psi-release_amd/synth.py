@@ -427,3 +427,22 @@ def make_oriented_room(subdiv: int = 2) -> OrientedRoom:
             faces.append(f + nv)
             nv += len(v)
     return OrientedRoom(_f32(np.concatenate(verts)), np.ascontiguousarray(np.concatenate(faces), dtype=np.int32), _f32(lo), _f32(hi), solids)
+
+
+def make_open_room(subdiv: int = 2, drop_ceiling: bool = True, sink: float = 0.0) -> OrientedRoom:
+    """``make_oriented_room`` with the defects of real scans: the ceiling triangles removed (``drop_ceiling``: the mesh is open, 4 subdiv
+    edges of the walls lose their second triangle) and/or the first, axis-aligned box lowered by ``sink`` metres (0.05: it stands exactly
+    on the floor, two coincident and oppositely oriented surfaces; more: it interpenetrates the floor).  The faces keep the order of
+    ``make_oriented_room``; ``analytic_sdf`` is that of the closed room with the moved box (where the box reaches below the floor the
+    minimum over the solids still has the right sign, which is what it is used for)."""
+    room = make_oriented_room(subdiv)
+    nq, nt = (subdiv + 1) ** 2, 2 * subdiv * subdiv              # vertices and triangles per box face
+    centre, half, rot = room.boxes[0]
+    moved = (centre - np.array([0.0, 0.0, float(sink)]), half, rot)
+    verts = room.verts.copy()
+    box = [_quad_grid(p0, du, dv, subdiv)[0] @ rot.T + moved[0] for p0, du, dv, _, _ in _box_quads(-half, half)]
+    verts[6 * nq:12 * nq] = _f32(np.concatenate(box))
+    faces = room.faces
+    if drop_ceiling:                                             # the sixth face of the room box: axis 2, upper side
+        faces = np.ascontiguousarray(np.concatenate([faces[:5 * nt], faces[6 * nt:]]))
+    return OrientedRoom(verts, faces, room.box_min, room.box_max, [moved] + list(room.boxes[1:]))

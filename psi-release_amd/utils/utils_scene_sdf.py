@@ -1,10 +1,11 @@
 #!/usr/bin/env python
-"""python utils_scene_sdf.py SCENE_PLY OUT_ROOT --name N [--dim 256 --margin 0.5 --voxel V]     (or: OUT_ROOT --name N --synthetic)
+"""python utils_scene_sdf.py SCENE_PLY OUT_ROOT --name N [--dim 256 --margin 0.5 --voxel V --sign winding]     (or: OUT_ROOT --name N --synthetic)
 
 From a scene mesh to the two scene files of the fitting and evaluation scripts, on the GPU: OUT_ROOT/scenes_sdf/N.json + N_sdf.npy (the
 signed distance volume over the mesh's box grown by --margin, [ix][iy][iz], positive in free space) and OUT_ROOT/scenes_downsampled/N.ply
-(the welded vertices, one per --voxel cell when given).  The reference ships these as downloads.  Triangles must face free space; an open
-mesh gets its sign from the orientation of the nearest triangle.  Prints the three config paths of the fitting scripts."""
+(the welded vertices, one per --voxel cell when given).  The reference ships these as downloads.  Triangles must face free space; with
+the default --sign pseudonormal an open mesh gets its sign from the orientation of the nearest triangle, --sign winding takes it from the
+generalised winding number (open scans, furniture that touches or enters the floor).  Prints the three config paths of the fitting scripts."""
 import argparse
 
 import _eval_common  # noqa: F401  (path setup)
@@ -21,6 +22,11 @@ def parse(argv=None):
     ap.add_argument('--dim', type=int, default=256, help='nodes per axis (a multiple of 4, at most 480: what the fitting engine samples)')
     ap.add_argument('--margin', type=float, default=0.5, help='the grid box is the mesh box grown by this on every side (m)')
     ap.add_argument('--voxel', type=float, default=None, help='keep one vertex per cell of this size in the point cloud')
+    ap.add_argument('--sign', choices=scene_sdf.SIGNS, default='pseudonormal', help='where the sign comes from: the pseudonormal of the nearest '
+                    'feature (closed, clean meshes) or the generalised winding number (open, touching or interpenetrating meshes)')
+    ap.add_argument('--exterior', choices=sorted(scene_sdf.LEVELS), default='solid', help='--sign winding: what lies outside the mesh, solid '
+                    '(a room) or free (objects standing in open space)')
+    ap.add_argument('--beta', type=float, default=3.0, help='--sign winding: clusters farther than beta x their radius count as dipoles; 0 = exact')
     ap.add_argument('--synthetic', action='store_true', help='use the stand-in room synth.make_oriented_room instead of a PLY')
     ap.add_argument('--subdiv', type=int, default=2, help='--synthetic: cuts per box face edge')
     a = ap.parse_args(argv)
@@ -35,6 +41,8 @@ def parse(argv=None):
         scene_sdf.check_engine_dim(a.dim)
     except ValueError as e:
         ap.error(str(e))
+    if not (a.beta >= 0 and a.beta < float('inf')):
+        ap.error('--beta must be finite and not negative')
     if a.margin < 0 or (a.voxel is not None and a.voxel <= 0):
         ap.error('--margin must not be negative and --voxel must be positive')
     return a
@@ -49,7 +57,8 @@ def main(argv=None):
         parts = synth.make_scene(0, m=8, D=2).contact_parts          # stand-in body_segments/*.json (the real ones ship with PROX)
     else:
         verts, faces, _ = read_ply_mesh(a.scene_ply)
-    scene = scene_sdf.scene_from_mesh(verts, faces, dim=a.dim, margin=a.margin, voxel=a.voxel, contact_parts=parts)
+    scene = scene_sdf.scene_from_mesh(verts, faces, dim=a.dim, margin=a.margin, voxel=a.voxel, contact_parts=parts, sign=a.sign, exterior=a.exterior,
+                                      beta=a.beta)
     paths = scene.write_prox_layout(a.out_root, a.name)
     print('[INFO] %d triangles -> %d^3 volume, %d cloud points' % (len(faces), a.dim, len(scene.verts)))
     for k in ('scene_verts_path', 'scene_sdf_path', 'contact_id_folder'):
