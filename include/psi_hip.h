@@ -281,7 +281,9 @@ int psi_fit_profile(psi_fit_engine *engine, int n_rep, char *h_names, int name_s
 /* Test/diagnostic copy of an engine-owned device buffer by name ("verts" [B,V,3], "g_verts", "pose" [B,165],
  * "g_pose", "g_rot" [B,55,9], "stats" [8], "adam_m"/"adam_v" [B,75]; the backward's intermediates "gA" [B,64,16], "gfeat" [B,Kpad],
  * "g_transl" [B,3], "gl" / "g_vp" / "v_posed" [B,Npad], and — engines whose per-vertex backward runs inside the scene launch — the
- * contact class of rows "glc" / "gvpc" / "vpc" [B,3 ncp] in slot order) into d_out (device). */
+ * contact class of rows "glc" / "gvpc" / "vpc" [B,3 ncp] in slot order, and "penmask" [B][Vpad/64] 64-bit words = 2 floats' worth of bits
+ * each, Vpad = V rounded up to 256: bit v % 64 of word v / 64 is set when vertex v of the body had sdf < 0 in the last forward, i.e. when
+ * its rows of "gl" / "g_vp" may be non-zero) into d_out (device). */
 int psi_fit_copy_buffer(psi_fit_engine *engine, const char *name, float *d_out, long n_floats, void *stream);
 
 /* ---------------------------------------------------------------------------------------------

@@ -148,6 +148,10 @@ struct FitDev {
     float *gA_part, *gfeat_part;          // [nsv + nsv_c][B][JP][16], [nsn_m + nsn_c][B][Kpad] split-contraction partials of both classes
     float *spb;                           // [B] independent-bodies mode: -w_col / N_b (0 when N_b == 0) written by the statistics workgroup
     int nsv, nsv_c, nsn_m, nsn_c, spm, spc;   // slices of the model's vertices / the contact slots (skin_bwd_A), of their columns (blend_bwd) and steps per slice
+    unsigned long long *penmask;          // [B][Vpad / 64] bit v % 64 of word v / 64: vertex v of the body has sdf < 0 in THIS iteration, i.e. its rows of gl / g_vp may be
+                                          // non-zero.  Every skinning wave of fwd_scene stores its word in every iteration (padding lanes: 0): nothing to zero, nothing
+                                          // carried over.  fit_bwd_joint_kernel skips the model-class work the mask proves to be sums of zeros
+    int pen_skip;                         // 0: fit_bwd_joint_kernel ignores the mask (PSI_FIT_PEN_SKIP=0)
 };
 
 __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.0f ? v : v * slope; }
@@ -514,6 +518,7 @@ struct SdfPenEpilogue {
     float gvmax[2];               // per body of the workgroup: max |g_vposed entry| this lane has stored (-> gmaxp, one integer atomicMax per workgroup and body)
     unsigned *gmaxp;              // the penetration class's per-body slots (FitDev::gvbits)
     int gv_sps;
+    unsigned long long *penmask;  // with gl: [B][Vpad / 64] the waves' lane masks of sdf < 0 (FitDev::penmask)
     // the vertex store of the skinning kernel.  All vertices: [B][V][3] as always.  Contact vertices only (large batches, where the NN search is
     // a launch of its own and reads them): the rows go to their contact SLOT, not to their vertex — the slot list follows the vertex order
     // within a contact part, so the 12-byte pieces of neighbouring lanes are neighbours in memory again (scattered through [B][V][3] they
@@ -594,9 +599,13 @@ struct SdfPenEpilogue {
         __shared__ float red3[PSI_SKIN_BLK / 64][3];
         __shared__ float redm[PSI_SKIN_BLK / 64];
         const float ws = psi_wave_sum(s[n]);
-        const float wc = (float)(int)__builtin_popcountll(__builtin_amdgcn_ballot_w64(neg[n]));
+        const unsigned long long negm = __builtin_amdgcn_ballot_w64(neg[n]);
+        const float wc = (float)(int)__builtin_popcountll(negm);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = (psi_f2){ws, wc};
         if (gl) {
+            // the exact mask travels with the rows it zeroes: lane <-> vertex vblock * 256 + threadIdx.x, one word per wave (plain store; the
+            // kernel boundary orders it before its reader)
+            if ((threadIdx.x & 63) == 0) penmask[((size_t)b * nvb + vblock) * (PSI_SKIN_BLK / 64) + (threadIdx.x >> 6)] = negm;
             const float sx = psi_wave_sum(gs[n][0]), sy = psi_wave_sum(gs[n][1]), sz = psi_wave_sum(gs[n][2]);
             float mx = gvmax[n];
 #pragma unroll
@@ -635,8 +644,9 @@ struct SdfPenEpilogue {
 static inline SdfPenEpilogue make_sdf_epilogue(const FitDev &f, const PsiSdfGrid &G, bool contact_vertices_only = false, const PsiLbsView *bwd = nullptr)
 {
     SdfPenEpilogue e = {G, f.sdf, f.gmin, f.gmax, f.og, f.penpart, f.D, f.align_corners, f.Vpad, contact_vertices_only ? f.cs_first : nullptr,
-                        {0.0f, 0.0f}, {false, false}, f.cverts, f.cs_ptr, f.cs_idx, f.n_c, nullptr, nullptr, nullptr, 0, f.B, {}, {}, {0.0f, 0.0f}, f.gvbits, f.gv_sps};
+                        {0.0f, 0.0f}, {false, false}, f.cverts, f.cs_ptr, f.cs_idx, f.n_c, nullptr, nullptr, nullptr, 0, f.B, {}, {}, {0.0f, 0.0f}, f.gvbits, f.gv_sps, nullptr};
     if (bwd) {
+        e.penmask = f.penmask;
         e.gl = bwd->gl;
         e.gvp = bwd->g_vp;
         e.gtp = bwd->gt_part_w;
@@ -1047,7 +1057,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         float *part = f.gA_part + (size_t)sl * f.B * PSI_JP * 16;
         if (sl < f.nsv) {
             const PsiSkaSlice o = {m.WTt + (size_t)sl * 4 * PSI_JP * 64, gl + (size_t)sl * 768, v_posed + (size_t)sl * 768, (size_t)m.Npad, part};
-            skin_bwd_A_dispatch(o, f.B, b0, nbody, smem);
+            // no penetrating vertex in this slice in any of my bodies: gl is zero there, the slice's partial is +0 (no weights, no operands, no MFMAs)
+            if (f.pen_skip && psi_pen_slice_clear(f.penmask, f.Vpad / 64, sl, f.B, b0, nbody)) skin_bwd_A_zero(o, f.B, b0, nbody);
+            else skin_bwd_A_dispatch(o, f.B, b0, nbody, smem);
         } else {
             const int c = sl - f.nsv;
             const PsiSkaSlice o = {f.WTt_c + (size_t)c * 4 * PSI_JP * 64, f.glc + (size_t)c * 768, f.vpc + (size_t)c * 768, (size_t)f.ncp3, part};
@@ -1064,11 +1076,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // fwd_scene_kernel; the matrix's own scale is static)
         const float dsc_inv = m.dirs_unscale * PSI_FEAT_SCALE;
         if (slice < f.nsn_m) {
-            const PsiBlendBwdColsH o = {m.dirs_bh, g_vp, (size_t)m.Npad, m.Kpad, m.Npad / 16, f.gvbits, f.gv_sps, dsc_inv};
+            const PsiBlendBwdColsH o = {m.dirs_bh, g_vp, (size_t)m.Npad, m.Kpad, m.Npad / 16, f.gvbits, f.gv_sps, dsc_inv, f.pen_skip ? f.penmask : nullptr, f.Vpad / 64};
             blend_bwd_h_body<(MT + 1) / 2>(o, f.B, slice * f.spm, (slice + 1) * f.spm, part, kg, bg, smem);
         } else {
             const int c = slice - f.nsn_m;
-            const PsiBlendBwdColsH o = {f.dirs_ch, f.gvpc, (size_t)f.ncp3, m.Kpad, f.ncp3 / 16, f.gvbits + PSI_GV_SLOTS, f.gv_sps, dsc_inv};
+            const PsiBlendBwdColsH o = {f.dirs_ch, f.gvpc, (size_t)f.ncp3, m.Kpad, f.ncp3 / 16, f.gvbits + PSI_GV_SLOTS, f.gv_sps, dsc_inv, nullptr, 0};
             blend_bwd_h_body<(MT + 1) / 2>(o, f.B, c * f.spc, (c + 1) * f.spc, part, kg, bg, smem);
         }
     } else {
@@ -1604,7 +1616,7 @@ constexpr int GRAPH_UNROLL = PSI_GRAPH_UNROLL;
 // Every development switch of the engine, read ONCE per engine at psi_fit_create (README, "Environment knobs"); a value that is not
 // accepted leaves the default (0 in the int fields)
 struct FitKnobs {
-    bool split_scene, keep_verts, no_fused_bwd, sdf_linear, scene_skin_first, bwdv_mb;
+    bool split_scene, keep_verts, no_fused_bwd, sdf_linear, scene_skin_first, bwdv_mb, no_pen_skip;
     int head_cluster, skin_nb, ska_nbody;
 #ifdef PSI_HEAD_STOPS
     int head_stop, tail_stop, skin_stop;      // tools/head_stops.sh
@@ -1619,6 +1631,7 @@ static FitKnobs fit_read_knobs()
     k.split_scene = is("PSI_SPLIT_SCENE", '1');
     k.keep_verts = is("PSI_KEEP_VERTS", '1');
     k.no_fused_bwd = is("PSI_FIT_FUSED_BWD", '0');
+    k.no_pen_skip = is("PSI_FIT_PEN_SKIP", '0');
     k.sdf_linear = is("PSI_SDF_LINEAR", '1');
     k.scene_skin_first = is("PSI_SCENE_ORDER", '1');
     k.bwdv_mb = is("PSI_BWDV_MB", '1');
@@ -2097,7 +2110,7 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     // search workgroups: a few producers per address, where one address for a whole class cost 6 us), all inside the class's PSI_GV_SLOTS
     f.gv_sps = 16;
     while (f.gv_sps > 1 && (long)f.gv_sps * B > PSI_GV_SLOTS) f.gv_sps >>= 1;
-    size_t o_glc = 0, o_gvpc = 0, o_vpc = 0, o_gtc = 0, o_gvb = 0, o_wttc = 0, o_dirsc = 0, o_gap = 0, o_gfp = 0, o_spb = 0;
+    size_t o_glc = 0, o_gvpc = 0, o_vpc = 0, o_gtc = 0, o_gvb = 0, o_wttc = 0, o_dirsc = 0, o_gap = 0, o_gfp = 0, o_spb = 0, o_pmask = 0;
     {
         // slice counts of the model's own rows: from the LBS workspace layout (offsets only: no memory is touched through this view)
         PsiLbsView lv0;
@@ -2122,6 +2135,7 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
             o_gtc = take((size_t)B * f.nfp * 4 * 4); o_gvb = take(2 * PSI_GV_SLOTS * 4); o_wttc = take((size_t)f.ncp * PSI_JP * 4); o_dirsc = take((size_t)f.ncp3 * Kpad * 4);
             o_gap = take((size_t)(f.nsv + f.nsv_c) * B * PSI_JP * 16 * 4); o_gfp = take((size_t)(f.nsn_m + f.nsn_c) * B * Kpad * 4);
             o_spb = take((size_t)B * 4);
+            o_pmask = take((size_t)B * (f.Vpad / 64) * 8);
         }
     }
     // (the bricked copy is addressed with 32-bit byte offsets: 512 bytes x (D / 4)^3 must stay below 4 GB, D <= 800)
@@ -2168,6 +2182,8 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     if (e->fused_bwd) {
         f.glc = F(o_glc); f.gvpc = F(o_gvpc); f.vpc = F(o_vpc); f.gtc_part = F(o_gtc); f.WTt_c = F(o_wttc); f.dirs_ch = F(o_dirsc); f.gvbits = (unsigned *)(bl + o_gvb);
         f.gA_part = F(o_gap); f.gfeat_part = F(o_gfp); f.spb = F(o_spb);
+        f.penmask = (unsigned long long *)(bl + o_pmask);
+        f.pen_skip = knobs.no_pen_skip ? 0 : 1;
     }
     // two bodies per skinning workgroup share one pass over the vertex's weight row: from the batch size at which the kernel is
     // throughput-bound (its own launch, B > 128); PSI_SKIN_NB=1|2 overrides
@@ -2628,6 +2644,8 @@ extern "C" int psi_fit_copy_buffer(psi_fit_engine *e, const char *name, float *d
     else if (!strcmp(name, "gvpc") && e->fused_bwd) { src = f.gvpc; cap = (long)f.B * f.ncp3; }
     else if (!strcmp(name, "vpc") && e->fused_bwd) { src = f.vpc; cap = (long)f.B * f.ncp3; }
     else if (!strcmp(name, "spb") && e->fused_bwd) { src = f.spb; cap = f.B; }      // independent bodies: each body's penetration factor -w / N_b
+    // the penetration mask of the last forward, [B][Vpad / 64] 64-bit words as pairs of floats' worth of bits
+    else if (!strcmp(name, "penmask") && e->fused_bwd) { src = (const float *)f.penmask; cap = (long)f.B * (f.Vpad / 64) * 2; }
     PSI_REQUIRE(src != nullptr, "unknown buffer name");
     PSI_REQUIRE(n_floats <= cap, "buffer is smaller than requested");
     PSI_CHECK_HIP(hipMemcpyAsync(d_out, src, (size_t)n_floats * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));

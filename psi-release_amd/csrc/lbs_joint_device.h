@@ -7,6 +7,7 @@
 // slices of the same split contractions and meet, with the 1 / N of the penetration term (fitting_proxe.py:155-158), in the reduction.
 #pragma once
 #include "lbs_device.h"
+#include "pen_steps.h"
 
 #ifndef PSI_SKA_MARK
 #define PSI_SKA_MARK(k)
@@ -140,6 +141,27 @@ __device__ __forceinline__ void skin_bwd_A_dispatch(const PsiSkaSlice &o, int B,
     }
 }
 
+// ---- rows that a penetration mask proves zero (the fused fitting engine, fit.hip: FitDev::penmask [B][pm_words], bit = vertex with sdf < 0;
+// every other vertex's rows of g_local / g_vposed are exact zeros).  A slice whose mask words are clear in all of the workgroup's bodies
+// contributes sums of products with a zero factor to accumulators that start at +0: the workgroup stores the +0 itself.
+// Each wave looks for itself (the same words, nobody writes them in this launch: the same answer in every wave, no barrier).
+__device__ __forceinline__ bool psi_pen_slice_clear(const unsigned long long *penmask, int pm_words, int slice, int B, int b0, int nbody)
+{
+    const int lane = threadIdx.x & 63, nb = min(nbody, B - b0);
+    unsigned long long any = 0ull;
+    for (int i = lane; i < 4 * nb; i += 64) any |= penmask[(size_t)(b0 + (i >> 2)) * pm_words + 4 * slice + (i & 3)];
+    return __builtin_amdgcn_ballot_w64(any != 0ull) == 0ull;
+}
+// +0 in exactly the elements skin_bwd_A_body stores: 64 joints x the 12 (r, s) entries of the workgroup's bodies
+__device__ __forceinline__ void skin_bwd_A_zero(const PsiSkaSlice &o, int B, int b0, int nbody)
+{
+    const int nb = min(nbody, B - b0);
+    for (int i = threadIdx.x; i < nb * 64 * 12; i += blockDim.x) {
+        const int bb = i / 768, r = i - 768 * bb, j = r / 12, rs = r - 12 * j;
+        o.part[((size_t)(b0 + bb) * PSI_JP + j) * 16 + rs] = 0.0f;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // blend backward (MFMA): g_feat[b][k] = sum_n g_vp[b][n] dirs[k][n]
 // Rounds 3-6 ran this product on the fp32 MFMA (v_mfma_f32_16x16x4_f32 over a 16-column-tiled fp32 copy of the matrix; workgroup = 4 waves
@@ -174,7 +196,13 @@ struct PsiBlendBwdColsH {
     const unsigned *gvbits;    // [B][gv_slots] bit patterns of maxima of |row entry|: the largest of a body's slots is the largest entry of its rows
     int gv_slots;              // slots per body (>= 1)
     float dsc_inv;             // 1 / matrix scale (the rows' own scale 2^s is applied per body)
+    // != nullptr: [B][pm_words] bit v % 64 of word v / 64 clear = the three columns of vertex v are exact zeros in that body's row (fit.hip:
+    // FitDev::penmask).  A step whose vertices are clear in every body of the workgroup is not loaded and not multiplied: it would add
+    // products with a zero factor.  nullptr: every step is walked
+    const unsigned long long *penmask;
+    int pm_words;
 };
+constexpr int PSI_BWH_PM_WORDS = 16;      // mask words per body a stream workgroup looks at (a slice of up to ~170 steps; a longer one is walked whole)
 // scale for rows whose largest |entry| has the bit pattern `bits` (0: nothing stored this iteration)
 __device__ __forceinline__ float psi_fp16_row_scale(unsigned bits)
 {
@@ -211,6 +239,23 @@ __device__ __forceinline__ void blend_bwd_h_body(const PsiBlendBwdColsH &o, int 
 #pragma unroll
     for (int t = 0; t < MTB; t++) grow[t] = o.g_vp + (size_t)min(b0 + t * 32 + li, B - 1) * o.row_stride + 8 * kh;
     const char *dbase = (const char *)o.dirs_bh + ((size_t)(2 * kgroup) * 2) * 1024 + (size_t)(kh * 32 + li) * 16;
+    // the mask words of my columns, lane = body, wave w the words w, w + 4, ...: requested together with the scales' slots below
+    __shared__ unsigned long long s_pm[PSI_BWH_PM_WORDS];
+    static_assert(32 * MTB <= 64, "the mask words are loaded one body per lane: a body group is at most one wave wide");
+    int pw0 = 0, pnw = 0;
+    bool use_pm = o.penmask != nullptr && s_begin < s_end;       // (uniform over the workgroup)
+    if (use_pm) {
+        psi_pen_step_words(s_begin, s_end, pw0, pnw);
+        pnw = max(min(pnw, o.pm_words - pw0), 0);                // (steps past the last word are padding columns: clear)
+        use_pm = pnw <= PSI_BWH_PM_WORDS;
+    }
+    unsigned long long mw[PSI_BWH_PM_WORDS / 4];
+    if (use_pm) {
+        const int nb = min(32 * MTB, B - b0);
+#pragma unroll
+        for (int k = 0; k < PSI_BWH_PM_WORDS / 4; k++)
+            mw[k] = (4 * k + w < pnw && lane < nb) ? o.penmask[(size_t)(b0 + lane) * o.pm_words + pw0 + 4 * k + w] : 0ull;
+    }
     // the scale of body tile t's column li (body b0 + 32 t + li) and the inverse of both scales for the same output column: lanes li and
     // li + 32 hold the same body and split its slots between them
     float gsc[MTB], us[MTB];
@@ -228,42 +273,65 @@ __device__ __forceinline__ void blend_bwd_h_body(const PsiBlendBwdColsH &o, int 
 #define PSI_BWH_PF 1
 #endif
     constexpr int PF = PSI_BWH_PF;
-    for (int st0 = s_begin + w; st0 < s_end; st0 += 4 * PF) {
-        psi_u4 d[PF][2][2];
-        f4 g[PF][MTB][2];
+    if (use_pm) {
+        // OR over the bodies (almost always nothing to OR: one ballot), one word per wave and round -> LDS -> every wave
 #pragma unroll
-        for (int p = 0; p < PF; p++) {
-            const int st = min(st0 + 4 * p, o.total_steps - 1);
+        for (int k = 0; k < PSI_BWH_PM_WORDS / 4; k++) {
+            unsigned long long r = mw[k];
+            if (__builtin_amdgcn_ballot_w64(r != 0ull) != 0ull) {
 #pragma unroll
-            for (int kt = 0; kt < 2; kt++)
-#pragma unroll
-                for (int q = 0; q < 2; q++) d[p][kt][q] = *(const psi_u4 *)(dbase + ((size_t)st * KT * 2 + (size_t)(kt * 2 + q)) * 1024);
-#pragma unroll
-            for (int t = 0; t < MTB; t++) {
-                g[p][t][0] = *(const f4 *)(grow[t] + (size_t)st * 16);
-                g[p][t][1] = *(const f4 *)(grow[t] + (size_t)st * 16 + 4);
+                for (int o2 = 32; o2 > 0; o2 >>= 1) r |= __shfl_xor(r, o2, 64);
             }
+            if (lane == 0 && 4 * k + w < pnw) s_pm[4 * k + w] = r;
         }
-        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();
+    }
+    // my steps s_begin + w + 4 i, i < n_i, 64 at a time: lane i decides step i, the wave walks the set bits in increasing order
+    const int n_i = s_end - s_begin > w ? (s_end - s_begin - w + 3) >> 2 : 0;
+    for (int i0 = 0; i0 < n_i; i0 += 64) {
+        bool mine = i0 + lane < n_i;
+        if (use_pm && mine) mine = psi_pen_step_live(s_pm, pw0, pnw, s_begin + w + 4 * (i0 + lane));
+        unsigned long long todo = __builtin_amdgcn_ballot_w64(mine);
+        while (todo != 0ull) {
+            psi_u4 d[PF][2][2];
+            f4 g[PF][MTB][2];
+            bool has[PF];
 #pragma unroll
-        for (int p = 0; p < PF; p++) {
-            if (st0 + 4 * p < s_end) {
+            for (int p = 0; p < PF; p++) {
+                has[p] = todo != 0ull;
+                const int st = s_begin + w + 4 * (i0 + (has[p] ? (int)__builtin_ctzll(todo) : 0));
+                todo &= todo - 1ull;
+#pragma unroll
+                for (int kt = 0; kt < 2; kt++)
+#pragma unroll
+                    for (int q = 0; q < 2; q++) d[p][kt][q] = *(const psi_u4 *)(dbase + ((size_t)st * KT * 2 + (size_t)(kt * 2 + q)) * 1024);
 #pragma unroll
                 for (int t = 0; t < MTB; t++) {
-                    psi_h8 gh, gl;
+                    g[p][t][0] = *(const f4 *)(grow[t] + (size_t)st * 16);
+                    g[p][t][1] = *(const f4 *)(grow[t] + (size_t)st * 16 + 4);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int e = 0; e < 8; e++) {
-                        const float x = g[p][t][e >> 2][e & 3] * gsc[t];
-                        const _Float16 hi = (_Float16)x;
-                        gh[e] = hi;
-                        gl[e] = (_Float16)((x - (float)hi) * 2048.0f);
-                    }
+            for (int p = 0; p < PF; p++) {
+                if (has[p]) {
 #pragma unroll
-                    for (int kt = 0; kt < 2; kt++) {
-                        const psi_h8 dh = __builtin_bit_cast(psi_h8, d[p][kt][0]), dl = __builtin_bit_cast(psi_h8, d[p][kt][1]);
-                        acc[kt][t][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(dh, gh, acc[kt][t][0], 0, 0, 0);
-                        acc[kt][t][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(dh, gl, acc[kt][t][1], 0, 0, 0);
-                        acc[kt][t][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(dl, gh, acc[kt][t][1], 0, 0, 0);
+                    for (int t = 0; t < MTB; t++) {
+                        psi_h8 gh, gl;
+#pragma unroll
+                        for (int e = 0; e < 8; e++) {
+                            const float x = g[p][t][e >> 2][e & 3] * gsc[t];
+                            const _Float16 hi = (_Float16)x;
+                            gh[e] = hi;
+                            gl[e] = (_Float16)((x - (float)hi) * 2048.0f);
+                        }
+#pragma unroll
+                        for (int kt = 0; kt < 2; kt++) {
+                            const psi_h8 dh = __builtin_bit_cast(psi_h8, d[p][kt][0]), dl = __builtin_bit_cast(psi_h8, d[p][kt][1]);
+                            acc[kt][t][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(dh, gh, acc[kt][t][0], 0, 0, 0);
+                            acc[kt][t][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(dh, gl, acc[kt][t][1], 0, 0, 0);
+                            acc[kt][t][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(dl, gh, acc[kt][t][1], 0, 0, 0);
+                        }
                     }
                 }
             }
