@@ -60,9 +60,6 @@ extern "C" int psi_dbg_timeline(unsigned long long *out, int nblocks)
 #include "lbs_device.h"
 #include "lbs_joint_device.h"
 #include "sdf_device.h"
-#ifndef PSI_SDF_CELLS
-#define PSI_SDF_CELLS 1      // the engine's copy of the SDF volume: 1 = cell-major records (two 16-byte gathers per sample), 0 = apron bricks (four 8-byte)
-#endif
 #include "nnindex_device.h"
 #include <initializer_list>
 #include <limits.h>
@@ -70,6 +67,7 @@ extern "C" int psi_dbg_timeline(unsigned long long *out, int nblocks)
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -105,7 +103,7 @@ struct FitDev {
     const int *cs_ptr, *cs_idx;                       // vertex -> contact slots (CSR, V+1 / n_c)
     const int *cs_first;                              // [V] first contact slot of the vertex | number of its slots << 24 (0: none)
     const float *scene, *sdf, *gmin, *gmax;           // scene cloud [m,3], volume [D^3], bounds [3]
-    const float *sdf_brick;                           // engine-owned copy of the volume in apron-brick order (sdf_device.h; nullptr: D % 4 != 0)
+    const float *sdf_cells;                           // engine-owned copy of the volume in cell-major order (sdf_device.h; nullptr: the plain volume is sampled)
     const float *Wct;                                 // [n_c][64] skinning weights of the contact vertices, one row per contact slot
     // state
     float *x, *xhr, *cam, *adam_m, *adam_v;
@@ -499,7 +497,7 @@ __global__ __launch_bounds__(HB) void head_fwd_kernel(FitDev f, PsiLbsView lv)
 // vertex is still in registers; per workgroup it leaves sum(-sdf) and the count over penetrating vertices, per vertex
 // the SDF gradient masked to sdf < 0.
 struct SdfPenEpilogue {
-    PsiSdfGrid G;             // sampling constants of the bricked volume (G.brick == nullptr: the plain volume below)
+    PsiSdfGrid G;             // sampling constants of the cell-major copy (G.cells == nullptr: the plain volume below)
     const float *sdf, *gmin, *gmax;
     float *og, *penpart;
     int D, align_corners, Vpad;
@@ -546,13 +544,9 @@ struct SdfPenEpilogue {
         for (int a = 0; a < 3; a++) gm[n][a] = 0.0f;
         if (!live) return;
         float g[3];
-        if (G.brick) {
+        if (G.cells) {
             bool in[3];
-#if PSI_SDF_CELLS
             const float val = psi_sdf_sample_cells(G, x, y, z, g, in);
-#else
-            const float val = psi_sdf_sample_fast(G, x, y, z, g, in);
-#endif
             neg[n] = val < 0.0f;
 #pragma unroll
             for (int a = 0; a < 3; a++) g[a] = (neg[n] && in[a]) ? g[a] : 0.0f;
@@ -622,9 +616,8 @@ struct SdfPenEpilogue {
             float mx = redm[0];
 #pragma unroll
             for (int w = 1; w < PSI_SKIN_BLK / 64; w++) mx = fmaxf(mx, redm[w]);
-#ifndef PSI_NO_GVMAX_ATOMIC
+            // (non-negative floats order like their bit patterns; max is order-independent)
             if (mx > 0.0f) atomicMax(gmaxp + (size_t)b * gv_sps + (vblock & (gv_sps - 1)), __float_as_uint(mx));
-#endif       // (non-negative floats order like their bit patterns; max is order-independent)
         }
         if (threadIdx.x == 0) {
             psi_f2 a = red[0];
@@ -641,24 +634,10 @@ struct SdfPenEpilogue {
     }
 };
 
-static inline SdfPenEpilogue make_sdf_epilogue(const FitDev &f, const PsiSdfGrid &G, bool contact_vertices_only = false, const PsiLbsView *bwd = nullptr)
-{
-    SdfPenEpilogue e = {G, f.sdf, f.gmin, f.gmax, f.og, f.penpart, f.D, f.align_corners, f.Vpad, contact_vertices_only ? f.cs_first : nullptr,
-                        {0.0f, 0.0f}, {false, false}, f.cverts, f.cs_ptr, f.cs_idx, f.n_c, nullptr, nullptr, nullptr, 0, f.B, {}, {}, {0.0f, 0.0f}, f.gvbits, f.gv_sps, nullptr};
-    if (bwd) {
-        e.penmask = f.penmask;
-        e.gl = bwd->gl;
-        e.gvp = bwd->g_vp;
-        e.gtp = bwd->gt_part_w;
-        e.Npad = bwd->m.Npad;
-    }
-    return e;
-}
-
 // The epilogue of an engine with SEVERAL scenes (psi_fit_create_scenes): body b samples the volume of scene slot[b].  The workgroup's
 // bodies are uniform over its lanes, so their grids are fetched once per workgroup (load_grids, before the blend) and wait in scalar
 // registers — two of them, because the two bodies of a two-body workgroup may sit in different scenes.  Such an engine always has a
-// re-ordered copy of every volume (G.brick != nullptr); everything behind the lookup is the single-scene epilogue's.
+// cell-major copy of every volume (G.cells != nullptr); everything behind the lookup is the single-scene epilogue's.
 struct SdfPenEpilogueScenes : SdfPenEpilogue {
     const PsiSdfGrid *gtab;       // [S] sampling constants per scene slot
     const int *slot;              // [B] scene slot per body (engine-owned; psi_fit_set_scene_slots keeps it inside [0, S))
@@ -672,14 +651,31 @@ struct SdfPenEpilogueScenes : SdfPenEpilogue {
     __device__ __forceinline__ void vertex(int n, int b, int v, float x, float y, float z, bool live) { vertex_at(Gb[n], n, b, v, x, y, z, live); }
 };
 
-static inline SdfPenEpilogueScenes make_sdf_epilogue_scenes(const FitDev &f, const PsiSdfGrid *gtab, const int *slot, bool contact_vertices_only = false,
-                                                            const PsiLbsView *bwd = nullptr)
+// the epilogue of the scene stage's two forms: SCENES = one scene in the kernel arguments / a table of scenes, selected per body
+template <bool SCENES>
+using SdfEpilogue = std::conditional_t<SCENES, SdfPenEpilogueScenes, SdfPenEpilogue>;
+
+// G: the one scene's grid (SCENES: unused); gtab, slot: the scene table and the bodies' slots (SCENES only)
+template <bool SCENES>
+static inline SdfEpilogue<SCENES> make_sdf_epilogue(const FitDev &f, const PsiSdfGrid &G, bool contact_vertices_only, const PsiLbsView *bwd,
+                                                    const PsiSdfGrid *gtab = nullptr, const int *slot = nullptr)
 {
-    SdfPenEpilogueScenes e;
-    static_cast<SdfPenEpilogue &>(e) = make_sdf_epilogue(f, PsiSdfGrid{}, contact_vertices_only, bwd);
-    e.gtab = gtab;
-    e.slot = slot;
-    e.Gb[0] = e.Gb[1] = PsiSdfGrid{};
+    SdfEpilogue<SCENES> e;
+    static_cast<SdfPenEpilogue &>(e) = {SCENES ? PsiSdfGrid{} : G, f.sdf, f.gmin, f.gmax, f.og, f.penpart, f.D, f.align_corners, f.Vpad,
+                                        contact_vertices_only ? f.cs_first : nullptr, {0.0f, 0.0f}, {false, false}, f.cverts, f.cs_ptr, f.cs_idx, f.n_c,
+                                        nullptr, nullptr, nullptr, 0, f.B, {}, {}, {0.0f, 0.0f}, f.gvbits, f.gv_sps, nullptr};
+    if (bwd) {
+        e.penmask = f.penmask;
+        e.gl = bwd->gl;
+        e.gvp = bwd->g_vp;
+        e.gtp = bwd->gt_part_w;
+        e.Npad = bwd->m.Npad;
+    }
+    if constexpr (SCENES) {
+        e.gtab = gtab;
+        e.slot = slot;
+        e.Gb[0] = e.Gb[1] = PsiSdfGrid{};
+    }
     return e;
 }
 
@@ -826,9 +822,7 @@ struct ContactSkinSrc {
             float m2 = wmax[0];
 #pragma unroll
             for (int w = 1; w < psikd::QBLK / 64; w++) m2 = fmaxf(m2, wmax[w]);
-#ifndef PSI_NO_GVMAX_ATOMIC
             if (m2 > 0.0f) atomicMax(f.gvbits + PSI_GV_SLOTS + (size_t)b * f.gv_sps + (bx & (f.gv_sps - 1)), __float_as_uint(m2));
-#endif
         }
         if (threadIdx.x < 3) {
             float a = 0.0f;
@@ -854,9 +848,18 @@ extern "C" int psi_dbg_kd_stat(int *out, int nblocks)
 // one body each; long, VALU-issue-bound pointer chases — dispatched first), the rest are the skinning + SDF workgroups (256
 // vertices of one body each; gather-latency-bound).  As two launches they ran back to back (23 + 18 us); they depend on the same
 // inputs only, so in one grid their waves share the SIMDs and hide each other's stalls.
-template <int NB>
+// SCENES (an engine with several scenes, psi_fit_create_scenes): T is the table of the scenes' trees and the search workgroups of body b walk
+// T[slot[b]] (`rows` = the largest stack of the set), the skinning workgroups sample the grids of their bodies' scenes (SdfPenEpilogueScenes).
+// The single-scene instances are, instruction for instruction, the kernel this was before it had the parameter; so are the several-scenes
+// ones, for which the __restrict__ INSIDE the conditional type matters: without it they keep 88-104 bytes of scratch per lane instead of 28
+// (profiles/fit_scene_unify_isa.txt).  The launch sits at the edge of its register budget: a wrapper around the search call (a lambda, a
+// shared __device__ body under two kernels) already reorders 38 instructions.
+template <bool SCENES>
+using SceneTrees = std::conditional_t<SCENES, const psikd::KdDev *__restrict__, psikd::KdDev>;      // one tree in the arguments / a table on the device
+
+template <int NB, bool SCENES>
 __global__ __launch_bounds__(256, 6) void fwd_scene_kernel(FitDev f, LbsDev m, const float *__restrict__ As, const float *__restrict__ v_posed,
-                                                           psikd::KdDev T, int n_kd, int nqb, int rows, float gscale, int skin_first, SdfPenEpilogue epi)
+                                                           SceneTrees<SCENES> T, int n_kd, int nqb, int rows, float gscale, int skin_first, SdfEpilogue<SCENES> epi)
 {
     extern __shared__ int smem_i[];
 #ifdef PSI_HEAD_STOPS
@@ -881,51 +884,31 @@ __global__ __launch_bounds__(256, 6) void fwd_scene_kernel(FitDev f, LbsDev m, c
     }
     if (is_kd) {
         const int b = bid / nqb, bx = bid % nqb;
-        psikd::kd_query_body<true, false>(T, ContactSkinSrc{f, m, As, v_posed, nullptr, {}, 0.0f, 0, 0.0f, 0.0f, 0.0f, nullptr, {}, 0}, f.n_c, (float *)nullptr, (int *)nullptr, f.cconst, gscale,
-                                          f.fused_bwd ? (float *)nullptr : f.gq, f.fpart, f.nn_hint, rows, (const psikd::KdDev *)nullptr, (const int *)nullptr, bx, b, nqb, smem_i);
+        // one scene: its tree; several: the table of trees and the bodies' slots (kd_query_body<CONTACT, MULTI>)
+        psikd::KdDev tree = psikd::KdDev();
+        const psikd::KdDev *__restrict__ tab = nullptr;
+        const int *slot = nullptr;
+        if constexpr (SCENES) {
+            tab = T;
+            slot = epi.slot;
+        } else tree = T;
+        psikd::kd_query_body<true, SCENES>(tree, ContactSkinSrc{f, m, As, v_posed, nullptr, {}, 0.0f, 0, 0.0f, 0.0f, 0.0f, nullptr, {}, 0}, f.n_c, (float *)nullptr, (int *)nullptr,
+                                           f.cconst, gscale, f.fused_bwd ? (float *)nullptr : f.gq, f.fpart, f.nn_hint, rows, tab, slot, bx, b, nqb, smem_i);
     } else {
         const int i = bid;
+        if constexpr (SCENES) epi.template load_grids<NB>((i / f.nsdfblk) * NB, f.B);
         psi_skin_fwd_body<NB, PsiBlendCompact>(m, As, v_posed, f.transl, f.cam, f.B, f.verts, epi, i % f.nsdfblk, (i / f.nsdfblk) * NB, f.nsdfblk);
     }
 }
 
-// The same launch for an engine with SEVERAL scenes (psi_fit_create_scenes): the search workgroups of body b walk the tree tab[slot[b]]
-// (kd_query_body<CONTACT, MULTI>; `rows` = the largest stack of the set), the skinning workgroups sample the grid of their bodies' scenes
-// (SdfPenEpilogueScenes).  A kernel of its own, so that the single-scene engine's launch stays the code it was.
-template <int NB>
-__global__ __launch_bounds__(256, 6) void fwd_scene_scenes_kernel(FitDev f, LbsDev m, const float *__restrict__ As, const float *__restrict__ v_posed,
-                                                                  const psikd::KdDev *__restrict__ tab, int n_kd, int nqb, int rows, float gscale,
-                                                                  int skin_first, SdfPenEpilogueScenes epi)
+// the skinning + SDF kernel as a launch of its own (large batches): lbs_device.h's psi_skin_fwd_kernel with this file's epilogue and, over
+// several scenes, the grids of the workgroup's bodies fetched first
+template <int NB, bool SCENES>
+__global__ __launch_bounds__(PSI_SKIN_BLK, 6) void skin_fwd_sdf_kernel(LbsDev m, const float *__restrict__ As, const float *__restrict__ v_posed,
+                                                                     const float *__restrict__ transl, const float *__restrict__ cam_ext,
+                                                                     int B, float *__restrict__ verts, SdfEpilogue<SCENES> epi)
 {
-    extern __shared__ int smem_i[];
-    int bid = blockIdx.x;
-    bool is_kd;
-    if (skin_first) {
-        const int n_sk = (int)gridDim.x - n_kd;
-        is_kd = bid >= n_sk;
-        if (is_kd) bid -= n_sk;
-    } else {
-        is_kd = bid < n_kd;
-        if (!is_kd) bid -= n_kd;
-    }
-    if (is_kd) {
-        const int b = bid / nqb, bx = bid % nqb;
-        psikd::kd_query_body<true, true>(psikd::KdDev(), ContactSkinSrc{f, m, As, v_posed, nullptr, {}, 0.0f, 0, 0.0f, 0.0f, 0.0f, nullptr, {}, 0}, f.n_c, (float *)nullptr, (int *)nullptr,
-                                         f.cconst, gscale, f.fused_bwd ? (float *)nullptr : f.gq, f.fpart, f.nn_hint, rows, tab, epi.slot, bx, b, nqb, smem_i);
-    } else {
-        const int i = bid;
-        epi.template load_grids<NB>((i / f.nsdfblk) * NB, f.B);
-        psi_skin_fwd_body<NB, PsiBlendCompact>(m, As, v_posed, f.transl, f.cam, f.B, f.verts, epi, i % f.nsdfblk, (i / f.nsdfblk) * NB, f.nsdfblk);
-    }
-}
-
-// the skinning + SDF kernel as a launch of its own (large batches), over several scenes
-template <int NB>
-__global__ __launch_bounds__(PSI_SKIN_BLK, 6) void skin_fwd_scenes_kernel(LbsDev m, const float *__restrict__ As, const float *__restrict__ v_posed,
-                                                                        const float *__restrict__ transl, const float *__restrict__ cam_ext,
-                                                                        int B, float *__restrict__ verts, SdfPenEpilogueScenes epi)
-{
-    epi.template load_grids<NB>((int)blockIdx.y * NB, B);
+    if constexpr (SCENES) epi.template load_grids<NB>((int)blockIdx.y * NB, B);
     psi_skin_fwd_body<NB, PsiBlendPipelined>(m, As, v_posed, transl, cam_ext, B, verts, epi, (int)blockIdx.x, (int)blockIdx.y * NB, (int)gridDim.x);
 }
 
@@ -1560,24 +1543,7 @@ __global__ __launch_bounds__(HB) void head_bwd_adam_kernel(FitDev f, PsiLbsView 
     }
 }
 
-// one-off re-layout of the caller's [ix][iy][iz] volume into the engine's brick order (sdf_device.h)
-__global__ void sdf_to_bricks_kernel(const float *__restrict__ src, float *__restrict__ dst, int D)
-{
-    const int nbr = D >> 2;
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, n = (size_t)nbr * nbr * nbr * PSI_BRICK_FLOATS;
-    if (i >= n) return;
-    const int e = (int)(i % PSI_BRICK_FLOATS);
-    const size_t br = i / PSI_BRICK_FLOATS;
-    const int bz = (int)(br % nbr), by = (int)((br / nbr) % nbr), bx = (int)(br / ((size_t)nbr * nbr));
-    float v = 0.0f;
-    if (e < 125) {
-        const int ix = min(4 * bx + e / 25, D - 1), iy = min(4 * by + (e / 5) % 5, D - 1), iz = min(4 * bz + e % 5, D - 1);
-        v = src[((size_t)ix * D + iy) * D + iz];
-    }
-    dst[i] = v;
-}
-
-// ... and into the cell-major order (sdf_device.h): one thread per stored float, [brick][lx][ly][lz][dx][dy][dz]
+// one-off re-layout of the caller's [ix][iy][iz] volume into the engine's cell-major order (sdf_device.h): one thread per stored float, [brick][lx][ly][lz][dx][dy][dz]
 __global__ void sdf_to_cells_kernel(const float *__restrict__ src, float *__restrict__ dst, int D)
 {
     const int nbr = D >> 2;
@@ -1767,7 +1733,7 @@ enum {
 
 struct psi_fit_engine {
     FitDev d;
-    PsiSdfGrid grid;              // sampling constants of the bricked SDF volume (sdf_device.h)
+    PsiSdfGrid grid;              // sampling constants of the cell-major copy of the SDF volume (sdf_device.h)
     const psi_lbs_model *lbs;
     psi_nn_index *nn_index;
     float *lbs_ws;
@@ -1855,6 +1821,52 @@ static int fit_launch_stats(psi_fit_engine *e, float *stats, hipStream_t st)
     return 0;
 }
 
+// The scene stage's two launch kinds, each for one (bodies per skinning workgroup, one scene / a table of scenes); fit_scene_dispatch
+// picks the instance of an engine
+template <int NB, bool SCENES>
+static void launch_fwd_scene(const psi_fit_engine *e, float gscale, hipStream_t st)
+{
+    const FitDev &f = e->d;
+    const int nqb = f.nfp, n_kd = nqb * f.B, skin_first = e->knobs.scene_skin_first ? 1 : 0;
+    const dim3 grid(n_kd + f.nsdfblk * psi_cdiv(f.B, NB));
+    FitDev fk = f;
+    if (!e->keep_verts) fk.verts = nullptr;
+    const auto epi = make_sdf_epilogue<SCENES>(f, e->grid, false, e->fused_bwd ? &e->lv : nullptr, e->d_grid_tab, e->d_slot);
+    SceneTrees<SCENES> T;
+    int rows;                                                    // traversal stack of the search (its LDS): the tree's, or the largest of the set
+    if constexpr (SCENES) {
+        T = e->d_kd_tab;
+        rows = e->kd_rows;
+    } else {
+        T = psi_nn_index_dev(e->nn_index);
+        rows = T.rows;
+    }
+    hipLaunchKernelGGL((fwd_scene_kernel<NB, SCENES>), grid, dim3(256), psikd::kd_lds_bytes(rows), st, fk, e->lv.m, e->lv.A, e->lv.v_posed, T, n_kd, nqb, rows,
+                       gscale, skin_first, epi);
+}
+
+template <int NB, bool SCENES>
+static void launch_skin_fwd_sdf(const psi_fit_engine *e, bool all_verts, hipStream_t st)
+{
+    const FitDev &f = e->d;
+    hipLaunchKernelGGL((skin_fwd_sdf_kernel<NB, SCENES>), dim3(f.nsdfblk, psi_cdiv(f.B, NB)), dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A, e->lv.v_posed,
+                       f.transl, f.cam, f.B, f.verts, make_sdf_epilogue<SCENES>(f, e->grid, !all_verts, nullptr, e->d_grid_tab, e->d_slot));
+}
+
+// launch(nb, scenes) with the engine's two choices as compile-time constants
+template <class L>
+static void fit_scene_dispatch(const psi_fit_engine *e, L &&launch)
+{
+    using One = std::integral_constant<int, 1>;
+    using Two = std::integral_constant<int, 2>;
+    switch ((e->n_scenes ? 2 : 0) | (e->skin_nb == 2 ? 1 : 0)) {
+    case 0: launch(One{}, std::false_type{}); break;
+    case 1: launch(Two{}, std::false_type{}); break;
+    case 2: launch(One{}, std::true_type{}); break;
+    default: launch(Two{}, std::true_type{}); break;
+    }
+}
+
 static int fit_forward(psi_fit_engine *e, float *stats, hipStream_t st, FitStats who)
 {
     FitDev &f = e->d;
@@ -1866,27 +1878,7 @@ static int fit_forward(psi_fit_engine *e, float *stats, hipStream_t st, FitStats
     float gscale = f.w_contact / ((f.indep ? 1.0f : (float)f.B * (float)f.world) * (float)f.n_c);
     if (e->nn_index && e->merged_scene) {
         // skinning + SDF and the NN search of the contact vertices as ONE launch (fwd_scene_kernel)
-        const psikd::KdDev T = psi_nn_index_dev(e->nn_index);
-        const int nqb = f.nfp, n_kd = nqb * f.B;
-        FitDev fk = f;
-        if (!e->keep_verts) fk.verts = nullptr;
-#define PSI_LAUNCH_FWD_SCENE(NB_)                                                                                                              \
-    hipLaunchKernelGGL(fwd_scene_kernel<NB_>, dim3(n_kd + f.nsdfblk * psi_cdiv(f.B, NB_)), dim3(256), psikd::kd_lds_bytes(T.rows), st, fk, e->lv.m, \
-                       e->lv.A, e->lv.v_posed, T, n_kd, nqb, T.rows, gscale, e->knobs.scene_skin_first ? 1 : 0,                                \
-                       make_sdf_epilogue(f, e->grid, false, e->fused_bwd ? &e->lv : nullptr))
-#define PSI_LAUNCH_FWD_SCENES(NB_)                                                                                                             \
-    hipLaunchKernelGGL(fwd_scene_scenes_kernel<NB_>, dim3(n_kd + f.nsdfblk * psi_cdiv(f.B, NB_)), dim3(256), psikd::kd_lds_bytes(e->kd_rows), st, fk, \
-                       e->lv.m, e->lv.A, e->lv.v_posed, (const psikd::KdDev *)e->d_kd_tab, n_kd, nqb, e->kd_rows, gscale,                      \
-                       e->knobs.scene_skin_first ? 1 : 0,                                                                                      \
-                       make_sdf_epilogue_scenes(f, e->d_grid_tab, e->d_slot, false, e->fused_bwd ? &e->lv : nullptr))
-        if (e->n_scenes) {
-            if (e->skin_nb == 2) PSI_LAUNCH_FWD_SCENES(2);
-            else PSI_LAUNCH_FWD_SCENES(1);
-        }
-        else if (e->skin_nb == 2) PSI_LAUNCH_FWD_SCENE(2);
-        else PSI_LAUNCH_FWD_SCENE(1);
-#undef PSI_LAUNCH_FWD_SCENES
-#undef PSI_LAUNCH_FWD_SCENE
+        fit_scene_dispatch(e, [&](auto nb, auto scenes) { launch_fwd_scene<decltype(nb)::value, decltype(scenes)::value>(e, gscale, st); });
         PSI_CHECK_LAUNCH("fwd_scene_kernel");
         psi_mark("fwd_scene_kernel", st);
     } else {
@@ -1899,20 +1891,7 @@ static int fit_forward(psi_fit_engine *e, float *stats, hipStream_t st, FitStats
         // themselves, as in the shared launch, measured 157 us against 113 for the search at B = 512 — so the skinning kernel stores those
         // rows, and ONLY those (2048 of 10475: the rest of the 64 MB was written for nobody; PSI_KEEP_VERTS=1 stores all of them)
         const bool all_verts = !e->nn_index || e->knobs.keep_verts;
-#define PSI_LAUNCH_SKIN_FWD(NB_)                                                                                                               \
-    hipLaunchKernelGGL((psi_skin_fwd_kernel<SdfPenEpilogue, NB_>), dim3(f.nsdfblk, psi_cdiv(f.B, NB_)), dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A, \
-                       e->lv.v_posed, f.transl, f.cam, f.B, f.verts, make_sdf_epilogue(f, e->grid, !all_verts))
-#define PSI_LAUNCH_SKIN_FWD_SCENES(NB_)                                                                                                        \
-    hipLaunchKernelGGL(skin_fwd_scenes_kernel<NB_>, dim3(f.nsdfblk, psi_cdiv(f.B, NB_)), dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A, e->lv.v_posed, \
-                       f.transl, f.cam, f.B, f.verts, make_sdf_epilogue_scenes(f, e->d_grid_tab, e->d_slot, !all_verts))
-        if (e->n_scenes) {
-            if (e->skin_nb == 2) PSI_LAUNCH_SKIN_FWD_SCENES(2);
-            else PSI_LAUNCH_SKIN_FWD_SCENES(1);
-        }
-        else if (e->skin_nb == 2) PSI_LAUNCH_SKIN_FWD(2);
-        else PSI_LAUNCH_SKIN_FWD(1);
-#undef PSI_LAUNCH_SKIN_FWD_SCENES
-#undef PSI_LAUNCH_SKIN_FWD
+        fit_scene_dispatch(e, [&](auto nb, auto scenes) { launch_skin_fwd_sdf<decltype(nb)::value, decltype(scenes)::value>(e, all_verts, st); });
         PSI_CHECK_LAUNCH("skin_fwd_sdf_kernel");
         psi_mark("skin_fwd_sdf_kernel", st);
         if (e->n_scenes)                                             // every body in the tree of its own scene (rows as below)
@@ -1997,6 +1976,22 @@ static int fit_backward(psi_fit_engine *e, float *stats, hipStream_t st, FitStat
 }
 
 static int fit_build_scenes(psi_fit_engine *e, const psi_fit_scene *h_scenes, int S);
+
+// the engine's cell-major copy of a [D][D][D] volume (sdf_device.h; psi_sdf_cells_fit(D) holds): its size, and the one-off re-layout into it
+// (NULL stream: the caller synchronises)
+static inline size_t sdf_cells_bytes(int D) { return (size_t)D * D * D * 32; }
+static void sdf_cells_fill(const float *d_sdf, float *d_cells, int D)
+{
+    hipLaunchKernelGGL(sdf_to_cells_kernel, dim3((unsigned)psi_cdiv((long)(sdf_cells_bytes(D) / 4), 256)), dim3(256), 0, 0, d_sdf, d_cells, D);
+}
+
+// the kd-tree index over a scene's m vertices, which the caller holds on the device
+static int fit_scene_index(psi_nn_index **out, const float *d_verts, int m, hipError_t *err)
+{
+    std::vector<float> hs((size_t)m * 3);
+    *err = hipMemcpy(hs.data(), d_verts, hs.size() * 4, hipMemcpyDeviceToHost);
+    return *err == hipSuccess ? psi_nn_index_create(out, hs.data(), m) : (int)*err;
+}
 
 // psi_fit_create (h_scenes == nullptr: the one scene of the four scene arguments) and psi_fit_create_scenes (the four arguments are those of
 // scene 0, for the fields that describe "the" scene; the kernels read the per-slot tables instead)
@@ -2138,14 +2133,10 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
             o_pmask = take((size_t)B * (f.Vpad / 64) * 8);
         }
     }
-    // (the bricked copy is addressed with 32-bit byte offsets: 512 bytes x (D / 4)^3 must stay below 4 GB, D <= 800)
+    // the cell-major copy of the one scene's volume; without it (a D it cannot hold, PSI_SDF_LINEAR=1) the plain volume is sampled
     // (several scenes: one copy per scene, allocated by fit_build_scenes)
-    const bool bricks = !h_scenes && (cfg->D % 4 == 0) && cfg->D <= (PSI_SDF_CELLS ? 480 : 800) && !knobs.sdf_linear;
-#if PSI_SDF_CELLS
-    size_t o_brick = bricks ? take((size_t)f.D * f.D * f.D * 32) : 0;             // D <= 480 keeps the byte offsets below 4 GB
-#else
-    size_t o_brick = bricks ? take((size_t)(f.D / 4) * (f.D / 4) * (f.D / 4) * PSI_BRICK_FLOATS * 4) : 0;
-#endif
+    const bool cells = !h_scenes && psi_sdf_cells_fit(f.D) && !knobs.sdf_linear;
+    size_t o_cells = cells ? take(sdf_cells_bytes(f.D)) : 0;
     size_t lbs_floats = psi_lbs_workspace_floats(lbs, B);
     size_t o_lws = take(lbs_floats * 4), o_nws = take(psi_nn_ws_bytes(B, f.n_c, f.m));
     hipError_t err = hipMalloc((void **)&e->blob, o);
@@ -2197,19 +2188,13 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
         hipLaunchKernelGGL(contact_dirs_h_kernel, dim3(psi_cdiv((long)f.ncp3 * e->lv.m.Kpad, 256)), dim3(256), 0, 0, e->lv.m.dirs_bh, e->lv.m.Kpad, f.vid,
                            f.n_c, f.ncp3, (float *)f.dirs_ch);
     }
-    f.sdf_brick = nullptr;
-    if (bricks) {
-#if PSI_SDF_CELLS
-        const size_t n = (size_t)f.D * f.D * f.D * 8;
-        hipLaunchKernelGGL(sdf_to_cells_kernel, dim3((unsigned)psi_cdiv((long)n, 256)), dim3(256), 0, 0, d_sdf, F(o_brick), f.D);
-#else
-        const size_t n = (size_t)(f.D / 4) * (f.D / 4) * (f.D / 4) * PSI_BRICK_FLOATS;
-        hipLaunchKernelGGL(sdf_to_bricks_kernel, dim3((unsigned)psi_cdiv((long)n, 256)), dim3(256), 0, 0, d_sdf, F(o_brick), f.D);
-#endif
-        f.sdf_brick = F(o_brick);
+    f.sdf_cells = nullptr;
+    if (cells) {
+        sdf_cells_fill(d_sdf, F(o_cells), f.D);
+        f.sdf_cells = F(o_cells);
     }
-    e->grid = psi_sdf_grid_make(f.sdf_brick, h_gmin, h_gmax, f.D, f.align_corners);
-    err = hipDeviceSynchronize();                                // the two one-off layout kernels above ran on the NULL stream
+    e->grid = psi_sdf_grid_make(f.sdf_cells, h_gmin, h_gmax, f.D, f.align_corners);
+    err = hipDeviceSynchronize();                                // the one-off layout kernels above ran on the NULL stream
     if (err == hipSuccess) err = hipGetLastError();
     if (err != hipSuccess) {
         psi_set_error("psi_fit_create: layout kernels failed: %s", hipGetErrorString(err));
@@ -2219,9 +2204,7 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     if (h_scenes) {
         if (int rc = fit_build_scenes(e, h_scenes, S)) return rc;
     } else if (cfg->nn_mode == 1) {
-        std::vector<float> hs((size_t)f.m * 3);
-        err = hipMemcpy(hs.data(), d_scene_verts, hs.size() * 4, hipMemcpyDeviceToHost);
-        if (int rc = err == hipSuccess ? psi_nn_index_create(&e->nn_index, hs.data(), f.m) : (int)err) return rc;
+        if (int rc = fit_scene_index(&e->nn_index, d_scene_verts, f.m, &err)) return rc;
     }
     owner.release();
     *out = e;
@@ -2251,27 +2234,17 @@ static int fit_build_scenes(psi_fit_engine *e, const psi_fit_scene *h_scenes, in
     for (int s = 0; s < S; s++) {
         const psi_fit_scene &sc = h_scenes[s];
         const int D = sc.D;
-#if PSI_SDF_CELLS
-        const size_t n = (size_t)D * D * D * 8;
-#else
-        const size_t n = (size_t)(D / 4) * (D / 4) * (D / 4) * PSI_BRICK_FLOATS;
-#endif
-        hipError_t err = hipMalloc((void **)&e->scene_vol[s], n * 4);
+        const size_t bytes = sdf_cells_bytes(D);
+        hipError_t err = hipMalloc((void **)&e->scene_vol[s], bytes);
         if (err != hipSuccess) {
             (void)hipGetLastError();
             e->scene_vol[s] = nullptr;
-            psi_set_error("psi_fit_create_scenes: no memory for the copy of scene %d's volume (%zu bytes, 8 x the volume): %s", s, n * 4, hipGetErrorString(err));
+            psi_set_error("psi_fit_create_scenes: no memory for the copy of scene %d's volume (%zu bytes, 8 x the volume): %s", s, bytes, hipGetErrorString(err));
             return PSI_ENOMEM;
         }
-#if PSI_SDF_CELLS
-        hipLaunchKernelGGL(sdf_to_cells_kernel, dim3((unsigned)psi_cdiv((long)n, 256)), dim3(256), 0, 0, sc.d_sdf, e->scene_vol[s], D);
-#else
-        hipLaunchKernelGGL(sdf_to_bricks_kernel, dim3((unsigned)psi_cdiv((long)n, 256)), dim3(256), 0, 0, sc.d_sdf, e->scene_vol[s], D);
-#endif
+        sdf_cells_fill(sc.d_sdf, e->scene_vol[s], D);
         grids[s] = psi_sdf_grid_make(e->scene_vol[s], sc.gmin, sc.gmax, D, f.align_corners);
-        std::vector<float> hs((size_t)sc.m * 3);
-        err = hipMemcpy(hs.data(), sc.d_verts, hs.size() * 4, hipMemcpyDeviceToHost);
-        if (int rc = err == hipSuccess ? psi_nn_index_create(&e->scene_index[s], hs.data(), sc.m) : (int)err) {
+        if (int rc = fit_scene_index(&e->scene_index[s], sc.d_verts, sc.m, &err)) {
             if (err != hipSuccess) psi_set_error("psi_fit_create_scenes: reading scene %d's vertices failed: %s", s, hipGetErrorString(err));
             return rc;
         }
@@ -2316,8 +2289,11 @@ extern "C" int psi_fit_create_scenes(psi_fit_engine **out, const psi_lbs_model *
         const psi_fit_scene &sc = h_scenes[s];
         PSI_REQUIRE(sc.d_verts && sc.d_sdf, "psi_fit_create_scenes: null scene pointer");
         PSI_REQUIRE(sc.m > 0, "psi_fit_create_scenes: a scene without vertices");
-        PSI_REQUIRE(sc.D >= 4 && sc.D % 4 == 0 && sc.D <= (PSI_SDF_CELLS ? 480 : 800),
-                    "psi_fit_create_scenes: D must be a multiple of 4, at most 480 (the engine samples a re-ordered copy of the volume and has no plain-volume fallback)");
+        if (!psi_sdf_cells_fit(sc.D)) {
+            psi_set_error("invalid argument: psi_fit_create_scenes: D = %d of scene %d: D must be a multiple of 4, at least 4 and at most %d (the engine samples "
+                          "a cell-major copy of the volume and has no plain-volume fallback)", sc.D, s, PSI_SDF_CELLS_MAX_D);
+            return PSI_EINVAL;
+        }
     }
     psi_fit_config c = *cfg;                                     // (m_scene, D: ignored by contract; the shared path checks and records scene 0's)
     c.m_scene = h_scenes[0].m;

@@ -25,7 +25,7 @@ from . import ops, scene_io, synth
 MODES = {'grid': 0, 'brute': 1}
 SIGNS = ('pseudonormal', 'winding')
 LEVELS = {'solid': 0.5, 'free': -0.5}      # a node is solid iff its free-space winding number is below the level
-ENGINE_MAX_DIM = 480       # the several-scenes engine samples a re-ordered copy of the volume: D % 4 == 0, D <= 480 (psi_fit_create_scenes)
+ENGINE_MAX_DIM = 480       # the fitting engine samples a cell-major copy of the volume: D % 4 == 0, D <= PSI_SDF_CELLS_MAX_D (csrc/sdf_device.h)
 
 
 class MeshSDF:

@@ -94,15 +94,17 @@ def test_modular_reference_is_anchored_to_the_single_scene_op(smplx_data, vposer
     assert rel_err(modular_first_step(smplx_data, vposer_sd, [A, B_], 3, bodies, 0)[0], modular_first_step(smplx_data, vposer_sd, [A, B_], 3, bodies, 1)[0]) > 1e-2
 
 
-@pytest.mark.parametrize('variant', ['default', 'skin_nb2', 'split_scene', 'unfused_bwd', 'align_corners0', 'sparse_weights'])
+@pytest.mark.parametrize('variant', ['default', 'skin_nb2', 'split_scene', 'split_scene_nb2', 'unfused_bwd', 'align_corners0', 'sparse_weights'])
 def test_first_step_matches_autograd(smplx_data, vposer_sd, monkeypatch, variant):
     """B = 3 over scenes (A, B), slots [1, 0, 1]: gradient (Adam's first moment / 0.1) and the four loss values of the fused engine's first
     step against autograd over the per-scene operators — the bounds test_full_baseline_size_properties uses for the same comparison.
-    skin_nb2: two bodies of DIFFERENT scenes in one workgroup of the scene launch, the third alone."""
+    skin_nb2: two bodies of DIFFERENT scenes in one workgroup of the scene launch, the third alone; split_scene_nb2: the same pairing in the
+    skinning + SDF kernel as a launch of its own."""
     A, B_, _ = scenes_abc()
-    env = {'skin_nb2': ('PSI_SKIN_NB', '2'), 'split_scene': ('PSI_SPLIT_SCENE', '1'), 'unfused_bwd': ('PSI_FIT_FUSED_BWD', '0')}
-    if variant in env:
-        monkeypatch.setenv(*env[variant])
+    env = {'skin_nb2': {'PSI_SKIN_NB': '2'}, 'split_scene': {'PSI_SPLIT_SCENE': '1'}, 'split_scene_nb2': {'PSI_SPLIT_SCENE': '1', 'PSI_SKIN_NB': '2'},
+           'unfused_bwd': {'PSI_FIT_FUSED_BWD': '0'}}
+    for k, v in env.get(variant, {}).items():
+        monkeypatch.setenv(k, v)
     ac = variant != 'align_corners0'
     smplx = synth.make_smplx(7, weight_nnz=4) if variant == 'sparse_weights' else smplx_data
     g_ref, l_ref = _reference(('ref', ac, variant == 'sparse_weights'), smplx, vposer_sd, ac)
@@ -134,6 +136,33 @@ def test_independent_bodies_keep_to_their_own_scene(smplx_data, vposer_sd):
     print('several scenes vs single-scene engines: max abs %.3g, bit-exact: %s' % (d, np.array_equal(multi, want)))
     assert d < 2e-5
     assert np.abs(multi - wrong).max() > 1e-3
+
+
+ONE_SCENE_ARMS = {'default': {}, 'skin_nb2': {'PSI_SKIN_NB': '2'}, 'split_scene': {'PSI_SPLIT_SCENE': '1'},
+                  'split_scene_nb2': {'PSI_SPLIT_SCENE': '1', 'PSI_SKIN_NB': '2'}}
+
+
+@pytest.mark.parametrize('arm', list(ONE_SCENE_ARMS))
+def test_table_of_one_scene_equals_the_single_scene_engine(smplx_data, vposer_sd, monkeypatch, arm):
+    """A several-scenes engine (psi_fit_create_scenes) over a table of ONE scene, A, against the psi_fit_create engine of A: the same B = 3
+    bodies, independent_bodies, 4 iterations, both engines built under the arm's knobs.  The two run the same scene stage, with the scene
+    selected per body or taken from the kernel arguments, so they agree bit for bit: all four arms were bit-equal (np.array_equal) when the
+    two forms of the stage were still separate kernels, which is where this bound comes from."""
+    A = scenes_abc()[0]
+    for k, v in ONE_SCENE_ARMS[arm].items():
+        monkeypatch.setenv(k, v)
+    B = 3
+    bodies = bodies_of(B, 60, 60)
+    op1 = make_op(smplx_data, vposer_sd, A, B, 'fused', num_iter=4, independent_bodies=True)
+    single = op1.fitting(dict(bodies)).detach().cpu().numpy().copy()
+    assert op1._fused.n_scenes == 0
+    opS = make_op(smplx_data, vposer_sd, [A], B, 'fused', num_iter=4, independent_bodies=True, scene_table_engine=True)
+    table = opS.fitting(dict(bodies), scene_id=0).detach().cpu().numpy()
+    assert opS._fused.n_scenes == 1
+    d = np.abs(table - single).max()
+    print('%s: table of one scene vs single-scene engine: max abs %.3g, bit-exact: %s' % (arm, d, np.array_equal(table, single)))
+    assert np.isfinite(single).all()
+    assert np.array_equal(table, single)
 
 
 # ---- 3. slots change under captured graphs ------------------------------------------------------------------------------
