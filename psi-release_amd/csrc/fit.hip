@@ -1021,28 +1021,44 @@ __device__ __forceinline__ void fit_stats_body(const FitDev &f, float *__restric
     }
 }
 
-// grid: [n_ska skin_bwd_A workgroups: (nsv + nsv_c) slices x body groups] [n_blend stream workgroups: k-groups x (nsn_m + nsn_c) column slices x
-// body groups] [one statistics workgroup when with_stats] — the short kinds first, as in bwd_joint_kernel (lbs.hip), whose bodies these are
-template <int MT>
+// grid: [n_ska skin_bwd_A workgroups: the contact slices x their body groups, then the model's (ska_plan.h)] [n_blend stream workgroups:
+// k-groups x (nsn_m + nsn_c) column slices x body groups] [one statistics workgroup when with_stats] — the short kinds first, as in
+// bwd_joint_kernel (lbs.hip), whose bodies these are.
+// PF_MODEL / PF_CONTACT: steps in flight per stream wave of each class (blend_bwd_h_body).  Once the fit is under way the mask leaves the
+// model class next to nothing, and what the launch waits for is the contact class — 16 dependent steps per wave at the production shape:
+// two in flight there (-1.7 us; four measured the same and cost 34 registers, scratch at MT = 4).  The model class keeps one (see the
+// comment above blend_bwd_h_body).  <MT, 1, 1> is the schedule before the depths were split (PSI_FIT_BWD_PF=1): same sums, same bits.
+#ifndef PSI_FIT_PF_MODEL
+#define PSI_FIT_PF_MODEL 1
+#endif
+#ifndef PSI_FIT_PF_CONTACT
+#define PSI_FIT_PF_CONTACT 2
+#endif
+template <int MT, int PF_MODEL, int PF_CONTACT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void fit_bwd_joint_kernel(
-    FitDev f, LbsDev m, const float *__restrict__ g_vp, const float *__restrict__ gl, const float *__restrict__ v_posed, int n_ska, int n_blend,
-    int kgroups, int nbody, float *__restrict__ stats)
+    FitDev f, LbsDev m, const float *__restrict__ g_vp, const float *__restrict__ gl, const float *__restrict__ v_posed, PsiSkaPlan ska, int n_blend,
+    int kgroups, float *__restrict__ stats)
 {
+    const int n_ska = ska.n_ska;
     constexpr int SMEM_B = psi_blend_bwd_h_smem_f4<(MT + 1) / 2>();
     __shared__ f4 smem[SMEM_B > SKA_SMEM_F4 ? SMEM_B : SKA_SMEM_F4];
     const int bid = blockIdx.x;
 #ifdef PSI_HEAD_STOPS
     PsiBlockTrace trace(11, 11);                         // dev (PSI_SKIN_STOP=11): this launch's workgroup timeline instead of fwd_scene's (tools/timeline_joint.py)
-    trace.kind = bid < n_ska ? (bid % (f.nsv + f.nsv_c) < f.nsv ? 0 : 1) : (bid < n_ska + n_blend ? 2 : 4);
+    trace.kind = bid < n_ska ? (bid < ska.n_c ? 1 : 0) : (bid < n_ska + n_blend ? 2 : 4);
 #endif
     if (bid < n_ska) {
-        const int nsl = f.nsv + f.nsv_c, sl = bid % nsl, b0 = (bid / nsl) * nbody;
+        int sl, b0, nbody;
+        psi_ska_map(ska, bid, sl, b0, nbody);
         float *part = f.gA_part + (size_t)sl * f.B * PSI_JP * 16;
         if (sl < f.nsv) {
             const PsiSkaSlice o = {m.WTt + (size_t)sl * 4 * PSI_JP * 64, gl + (size_t)sl * 768, v_posed + (size_t)sl * 768, (size_t)m.Npad, part};
-            // no penetrating vertex in this slice in any of my bodies: gl is zero there, the slice's partial is +0 (no weights, no operands, no MFMAs)
-            if (f.pen_skip && psi_pen_slice_clear(f.penmask, f.Vpad / 64, sl, f.B, b0, nbody)) skin_bwd_A_zero(o, f.B, b0, nbody);
-            else skin_bwd_A_dispatch(o, f.B, b0, nbody, smem);
+            // a body without a penetrating vertex in this slice: gl is zero there, its part of the slice's partial is +0; the contraction runs
+            // over the other bodies (none: no weights, no operands, no MFMAs)
+            const unsigned all = (1u << min(nbody, f.B - b0)) - 1u;
+            const unsigned live = f.pen_skip ? psi_pen_slice_live(f.penmask, f.Vpad / 64, sl, f.B, b0, nbody) : all;
+            skin_bwd_A_zero(o, b0, all & ~live);
+            if (live) skin_bwd_A_dispatch_live(o, b0, live, smem);
         } else {
             const int c = sl - f.nsv;
             const PsiSkaSlice o = {f.WTt_c + (size_t)c * 4 * PSI_JP * 64, f.glc + (size_t)c * 768, f.vpc + (size_t)c * 768, (size_t)f.ncp3, part};
@@ -1060,11 +1076,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const float dsc_inv = m.dirs_unscale * PSI_FEAT_SCALE;
         if (slice < f.nsn_m) {
             const PsiBlendBwdColsH o = {m.dirs_bh, g_vp, (size_t)m.Npad, m.Kpad, m.Npad / 16, f.gvbits, f.gv_sps, dsc_inv, f.pen_skip ? f.penmask : nullptr, f.Vpad / 64};
-            blend_bwd_h_body<(MT + 1) / 2>(o, f.B, slice * f.spm, (slice + 1) * f.spm, part, kg, bg, smem);
+            blend_bwd_h_body<(MT + 1) / 2, PF_MODEL>(o, f.B, slice * f.spm, (slice + 1) * f.spm, part, kg, bg, smem);
         } else {
             const int c = slice - f.nsn_m;
             const PsiBlendBwdColsH o = {f.dirs_ch, f.gvpc, (size_t)f.ncp3, m.Kpad, f.ncp3 / 16, f.gvbits + PSI_GV_SLOTS, f.gv_sps, dsc_inv, nullptr, 0};
-            blend_bwd_h_body<(MT + 1) / 2>(o, f.B, c * f.spc, (c + 1) * f.spc, part, kg, bg, smem);
+            blend_bwd_h_body<(MT + 1) / 2, PF_CONTACT>(o, f.B, c * f.spc, (c + 1) * f.spc, part, kg, bg, smem);
         }
     } else {
         fit_stats_body(f, stats);
@@ -1582,7 +1598,7 @@ constexpr int GRAPH_UNROLL = PSI_GRAPH_UNROLL;
 // Every development switch of the engine, read ONCE per engine at psi_fit_create (README, "Environment knobs"); a value that is not
 // accepted leaves the default (0 in the int fields)
 struct FitKnobs {
-    bool split_scene, keep_verts, no_fused_bwd, sdf_linear, scene_skin_first, bwdv_mb, no_pen_skip;
+    bool split_scene, keep_verts, no_fused_bwd, sdf_linear, scene_skin_first, bwdv_mb, no_pen_skip, bwd_pf1;
     int head_cluster, skin_nb, ska_nbody;
 #ifdef PSI_HEAD_STOPS
     int head_stop, tail_stop, skin_stop;      // tools/head_stops.sh
@@ -1598,6 +1614,7 @@ static FitKnobs fit_read_knobs()
     k.keep_verts = is("PSI_KEEP_VERTS", '1');
     k.no_fused_bwd = is("PSI_FIT_FUSED_BWD", '0');
     k.no_pen_skip = is("PSI_FIT_PEN_SKIP", '0');
+    k.bwd_pf1 = is("PSI_FIT_BWD_PF", '1');
     k.sdf_linear = is("PSI_SDF_LINEAR", '1');
     k.scene_skin_first = is("PSI_SCENE_ORDER", '1');
     k.bwdv_mb = is("PSI_BWDV_MB", '1');
@@ -1617,23 +1634,24 @@ static FitKnobs fit_read_knobs()
 struct FitPlan {
     int mt;                       // 16-body tiles per stream workgroup (the template instance)
     int kgroups, n_blend;         // stream workgroups: kgroups x column slices of both row classes x body groups
-    int nbody, n_ska;             // bodies per skin_bwd_A workgroup; number of those workgroups
+    PsiSkaPlan ska;               // skin_bwd_A workgroups: bodies per workgroup of each row class, bid -> (slice, body group) (ska_plan.h)
+    bool pf1;                     // one step in flight in both classes of stream workgroups (PSI_FIT_BWD_PF=1)
 };
-static FitPlan fit_plan_make(const FitDev &f, const LbsDev &m, int ska_nbody_override)
+static FitPlan fit_plan_make(const FitDev &f, const LbsDev &m, int ska_nbody_override, bool pf1)
 {
     FitPlan p;
     p.kgroups = m.Kpad / 64;
     p.mt = f.B > 32 ? 4 : (f.B > 16 ? 2 : 1);
     p.n_blend = p.kgroups * (f.nsn_m + f.nsn_c) * psi_cdiv(f.B, 16 * p.mt);
-    // bodies per skin_bwd_A workgroup: about one such workgroup per CU beside its stream workgroup
-    const int nsl = f.nsv + f.nsv_c;
+    // bodies per skin_bwd_A workgroup, per row class (the rule and its reasons: ska_plan.h): about one such workgroup per CU beside its
+    // stream workgroup
     // (AT MOST one: the body groups are whole, so 32 bodies in groups of 6 are 6 groups, not 5.33 — 45 slices x 6 = 270 workgroups put two on
     // 14 CUs and the launch waited for those: bwd_joint 37.6 us at n_c = 1024 against 28.4 at 2048)
-    int nbody = psi_cdiv((long)f.B * nsl, 256);
-    if (nbody < 1) nbody = 1;
-    while (nbody < SKA_NBODY && (long)nsl * psi_cdiv(f.B, nbody) > 256) nbody++;
-    p.nbody = psi_ska_nbody(nbody, SKA_NBODY, ska_nbody_override);
-    p.n_ska = nsl * psi_cdiv(f.B, p.nbody);
+    // and the model class no more workgroups than its column tiles need, the contact class — the one the mask never empties — as few
+    // bodies as the launch has room for: at B = 32, n_c = 2048 that is 41 x 4 workgroups of 8 bodies and 8 x 8 of 4 (3 column tiles: half
+    // the MFMAs per wave of the 7-body workgroups both classes had), 228 + 256 + 1 workgroups in one occupancy round
+    p.ska = psi_ska_plan(f.B, f.nsv, f.nsv_c, SKA_NBODY, ska_nbody_override);
+    p.pf1 = pf1;
     return p;
 }
 
@@ -1914,12 +1932,18 @@ static int fit_backward_joint(psi_fit_engine *e, float *stats, hipStream_t st, F
 {
     FitDev &f = e->d;
     const FitPlan &p = e->plan;
-    const dim3 grid(p.n_ska + p.n_blend + (fit_stats_source(e, who) == FitStats::Backward ? 1 : 0));
-#define PSI_LAUNCH_FIT_JOINT(MT_)                                                                                                  \
-    hipLaunchKernelGGL(fit_bwd_joint_kernel<MT_>, grid, dim3(256), 0, st, f, e->lv.m, e->lv.g_vp, e->lv.gl, e->lv.v_posed, p.n_ska, p.n_blend, p.kgroups, p.nbody, stats)
-    if (p.mt == 4) PSI_LAUNCH_FIT_JOINT(4);
-    else if (p.mt == 2) PSI_LAUNCH_FIT_JOINT(2);
-    else PSI_LAUNCH_FIT_JOINT(1);
+    const dim3 grid(p.ska.n_ska + p.n_blend + (fit_stats_source(e, who) == FitStats::Backward ? 1 : 0));
+#define PSI_LAUNCH_FIT_JOINT(MT_, PFM_, PFC_)                                                                                      \
+    hipLaunchKernelGGL((fit_bwd_joint_kernel<MT_, PFM_, PFC_>), grid, dim3(256), 0, st, f, e->lv.m, e->lv.g_vp, e->lv.gl, e->lv.v_posed, p.ska, p.n_blend, p.kgroups, stats)
+#define PSI_LAUNCH_FIT_JOINT_MT(MT_)                                                                                               \
+    do {                                                                                                                           \
+        if (p.pf1) PSI_LAUNCH_FIT_JOINT(MT_, 1, 1);                                                                                \
+        else PSI_LAUNCH_FIT_JOINT(MT_, PSI_FIT_PF_MODEL, PSI_FIT_PF_CONTACT);                                                      \
+    } while (0)
+    if (p.mt == 4) PSI_LAUNCH_FIT_JOINT_MT(4);
+    else if (p.mt == 2) PSI_LAUNCH_FIT_JOINT_MT(2);
+    else PSI_LAUNCH_FIT_JOINT_MT(1);
+#undef PSI_LAUNCH_FIT_JOINT_MT
 #undef PSI_LAUNCH_FIT_JOINT
     PSI_CHECK_LAUNCH("fit_bwd_joint_kernel");
     psi_mark("bwd_joint_kernel", st);
@@ -2168,7 +2192,7 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     e->stats_local = F(o_stats);
     e->lbs_ws = F(o_lws);
     if (int rcv = psi_lbs_view(lbs, B, e->lbs_ws, &e->lv)) return rcv;
-    e->plan = fit_plan_make(f, e->lv.m, knobs.ska_nbody);
+    e->plan = fit_plan_make(f, e->lv.m, knobs.ska_nbody, knobs.bwd_pf1);
     f.Wct = F(o_wct);
     if (e->fused_bwd) {
         f.glc = F(o_glc); f.gvpc = F(o_gvpc); f.vpc = F(o_vpc); f.gtc_part = F(o_gtc); f.WTt_c = F(o_wttc); f.dirs_ch = F(o_dirsc); f.gvbits = (unsigned *)(bl + o_gvb);

@@ -308,7 +308,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         psi_blend_bwd_place(bid, kgroups, nslices, kg, slice, bg);
         // (the rows' fp16 scales: per body, from the gvparts maxima gv_rowmax_kernel left for each body)
         const PsiBlendBwdColsH cols = {m.dirs_bh, g_vp, (size_t)m.Npad, m.Kpad, m.Npad / 16, gvbits, gvparts, m.dirs_unscale * PSI_FEAT_SCALE};
-        blend_bwd_h_body<(MT + 1) / 2>(cols, B, slice * steps_per_slice, (slice + 1) * steps_per_slice, gfeat_part + (size_t)slice * B * m.Kpad, kg, bg, smem);
+        blend_bwd_h_body<(MT + 1) / 2, 1>(cols, B, slice * steps_per_slice, (slice + 1) * steps_per_slice, gfeat_part + (size_t)slice * B * m.Kpad, kg, bg, smem);
     } else {
         const int i = bid - n_blend, vslice = i % nsv;
         // (weights from the wave-tiled copy — the copy skin_bwd_v streamed just before this launch, so most of it is still in L2 / MALL)

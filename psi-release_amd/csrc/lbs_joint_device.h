@@ -8,6 +8,7 @@
 #pragma once
 #include "lbs_device.h"
 #include "pen_steps.h"
+#include "ska_plan.h"
 
 #ifndef PSI_SKA_MARK
 #define PSI_SKA_MARK(k)
@@ -40,15 +41,25 @@ struct PsiSkaSlice {
     float *part;               // [B][PSI_JP][16]: this slice's partial joint-transform gradients
 };
 
-// NT: column tiles of a full workgroup, (12 nbody + 15) / 16 — a compile-time count keeps the 16 quads straight-line code with all weight
-// quads in registers (a workgroup with fewer bodies than nbody repeats its last column in the spare tiles)
+// index of the k-th set bit of m (k < popcount(m))
+__device__ __forceinline__ int psi_nth_bit(unsigned m, int k)
+{
+    for (int i = 0; i < k; i++) m &= m - 1u;
+    return __builtin_ctz(m);
+}
+
+// NT: column tiles of the workgroup, (12 nb + 15) / 16 for its nb bodies — a compile-time count keeps the 16 quads straight-line code with
+// all weight quads in registers (the spare columns of the last tile repeat the last column)
+// live: bit i set = body b0 + i is one of the workgroup's bodies (uniform; at most SKA_NBODY bits).  The set bodies' 12 columns each are
+// packed side by side in the order of their bits — a column is its own sum over the vertices, whichever columns share its tile
+// (tests/test_bwd_joint_schedule_gpu.py) — so a workgroup that leaves bodies out (fit.hip: their rows are zero) runs fewer tiles
 template <int NT>
-__device__ __forceinline__ void skin_bwd_A_body(const PsiSkaSlice &o, int B, int b0, int nbody, psi_f4 *smem)
+__device__ __forceinline__ void skin_bwd_A_body(const PsiSkaSlice &o, int b0, unsigned live, psi_f4 *smem)
 {
     typedef psi_f4 f4;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int li = lane & 15, lk = lane >> 4;
-    const int nb = min(nbody, B - b0);
+    const int nb = __builtin_popcount(live);
     const int ncol = 12 * nb;
     // my weight row: joint 16 w + li, vertices 64 lk .. 64 lk + 63 of the slice — all 16 quads requested now (behind the stream's traffic
     // a load takes ~2 us: requested two quads ahead of their use, they made every quad wait, 1 us per quad)
@@ -66,12 +77,16 @@ __device__ __forceinline__ void skin_bwd_A_body(const PsiSkaSlice &o, int B, int
     {
         f4 og[SKA_NBODY], op[SKA_NBODY];
         const int t4 = threadIdx.x;
+        unsigned rest = live;
 #pragma unroll
-        for (int bb = 0; bb < SKA_NBODY; bb++)
+        for (int bb = 0; bb < SKA_NBODY; bb++) {
             if (bb < nb && t4 < 192) {
-                og[bb] = *(const f4 *)(o.gl + (size_t)(b0 + bb) * o.row_stride + t4 * 4);
-                op[bb] = *(const f4 *)(o.vp + (size_t)(b0 + bb) * o.row_stride + t4 * 4);
+                const size_t row = (size_t)(b0 + __builtin_ctz(rest)) * o.row_stride;
+                og[bb] = *(const f4 *)(o.gl + row + t4 * 4);
+                op[bb] = *(const f4 *)(o.vp + row + t4 * 4);
             }
+            rest &= rest - 1u;
+        }
 #pragma unroll
         for (int bb = 0; bb < SKA_NBODY; bb++)
             if (bb < nb && t4 < 192) {
@@ -121,44 +136,61 @@ __device__ __forceinline__ void skin_bwd_A_body(const PsiSkaSlice &o, int B, int
         const int c = 16 * nt + li;
         if (c < ncol) {
             const int bb = c / 12, rs = c - 12 * bb;
-            float *po = o.part + (((size_t)(b0 + bb)) * PSI_JP + w * 16 + lk * 4) * 16 + rs;
+            float *po = o.part + (((size_t)(b0 + psi_nth_bit(live, bb))) * PSI_JP + w * 16 + lk * 4) * 16 + rs;
 #pragma unroll
             for (int e = 0; e < 4; e++) po[e * 16] = acc[nt][e];
         }
     }
 }
 
-// the same, column-tile count chosen at run time (12 nbody columns)
+// the same, column-tile count chosen at run time (12 columns per set bit of `live`, at least one)
+__device__ __forceinline__ void skin_bwd_A_dispatch_live(const PsiSkaSlice &o, int b0, unsigned live, psi_f4 *smem)
+{
+    switch ((12 * __builtin_popcount(live) + 15) >> 4) {
+    case 1: skin_bwd_A_body<1>(o, b0, live, smem); break;
+    case 2: skin_bwd_A_body<2>(o, b0, live, smem); break;
+    case 3: skin_bwd_A_body<3>(o, b0, live, smem); break;
+    case 4: skin_bwd_A_body<4>(o, b0, live, smem); break;
+    case 5: skin_bwd_A_body<5>(o, b0, live, smem); break;
+    default: skin_bwd_A_body<SKA_MAXT>(o, b0, live, smem); break;
+    }
+}
+// all of the workgroup's bodies b0 .. min(b0 + nbody, B) - 1
 __device__ __forceinline__ void skin_bwd_A_dispatch(const PsiSkaSlice &o, int B, int b0, int nbody, psi_f4 *smem)
 {
-    switch ((12 * nbody + 15) >> 4) {
-    case 1: skin_bwd_A_body<1>(o, B, b0, nbody, smem); break;
-    case 2: skin_bwd_A_body<2>(o, B, b0, nbody, smem); break;
-    case 3: skin_bwd_A_body<3>(o, B, b0, nbody, smem); break;
-    case 4: skin_bwd_A_body<4>(o, B, b0, nbody, smem); break;
-    case 5: skin_bwd_A_body<5>(o, B, b0, nbody, smem); break;
-    default: skin_bwd_A_body<SKA_MAXT>(o, B, b0, nbody, smem); break;
-    }
+    skin_bwd_A_dispatch_live(o, b0, (1u << min(nbody, B - b0)) - 1u, smem);
 }
 
 // ---- rows that a penetration mask proves zero (the fused fitting engine, fit.hip: FitDev::penmask [B][pm_words], bit = vertex with sdf < 0;
-// every other vertex's rows of g_local / g_vposed are exact zeros).  A slice whose mask words are clear in all of the workgroup's bodies
-// contributes sums of products with a zero factor to accumulators that start at +0: the workgroup stores the +0 itself.
+// every other vertex's rows of g_local / g_vposed are exact zeros).  A body whose mask words of the slice are clear contributes sums of
+// products with a zero factor to accumulators that start at +0: the workgroup stores the +0 itself and runs the contraction over the
+// other bodies only (none: no weights, no operands, no MFMAs).  Once a fit is under way a slice that is live at all is live in one or two
+// bodies: one or two column tiles where all of the workgroup's bodies are six, and such a workgroup is what the launch then waits for.
 // Each wave looks for itself (the same words, nobody writes them in this launch: the same answer in every wave, no barrier).
-__device__ __forceinline__ bool psi_pen_slice_clear(const unsigned long long *penmask, int pm_words, int slice, int B, int b0, int nbody)
+// -> bit i set = body b0 + i has a set bit in the slice's four words
+__device__ __forceinline__ unsigned psi_pen_slice_live(const unsigned long long *penmask, int pm_words, int slice, int B, int b0, int nbody)
 {
+    static_assert(4 * SKA_NBODY <= 64, "one lane per (body, word)");
     const int lane = threadIdx.x & 63, nb = min(nbody, B - b0);
     unsigned long long any = 0ull;
-    for (int i = lane; i < 4 * nb; i += 64) any |= penmask[(size_t)(b0 + (i >> 2)) * pm_words + 4 * slice + (i & 3)];
-    return __builtin_amdgcn_ballot_w64(any != 0ull) == 0ull;
+    if (lane < 4 * nb) any = penmask[(size_t)(b0 + (lane >> 2)) * pm_words + 4 * slice + (lane & 3)];
+    unsigned long long x = __builtin_amdgcn_ballot_w64(any != 0ull);
+    x |= x >> 1;
+    x |= x >> 2;                                                // bit 4 i: any of body i's four words
+    unsigned live = 0u;
+#pragma unroll
+    for (int i = 0; i < SKA_NBODY; i++) live |= (unsigned)((x >> (4 * i)) & 1ull) << i;
+    return live;
 }
-// +0 in exactly the elements skin_bwd_A_body stores: 64 joints x the 12 (r, s) entries of the workgroup's bodies
-__device__ __forceinline__ void skin_bwd_A_zero(const PsiSkaSlice &o, int B, int b0, int nbody)
+// +0 in exactly the elements skin_bwd_A_body would store for the bodies b0 + i, i a set bit of `dead`: 64 joints x the 12 (r, s) entries each
+__device__ __forceinline__ void skin_bwd_A_zero(const PsiSkaSlice &o, int b0, unsigned dead)
 {
-    const int nb = min(nbody, B - b0);
-    for (int i = threadIdx.x; i < nb * 64 * 12; i += blockDim.x) {
-        const int bb = i / 768, r = i - 768 * bb, j = r / 12, rs = r - 12 * j;
-        o.part[((size_t)(b0 + bb) * PSI_JP + j) * 16 + rs] = 0.0f;
+    for (; dead != 0u; dead &= dead - 1u) {
+        float *pb = o.part + (size_t)(b0 + __builtin_ctz(dead)) * PSI_JP * 16;
+        for (int r = threadIdx.x; r < 64 * 12; r += blockDim.x) {
+            const int j = r / 12, rs = r - 12 * j;
+            pb[j * 16 + rs] = 0.0f;
+        }
     }
 }
 
@@ -166,9 +198,11 @@ __device__ __forceinline__ void skin_bwd_A_zero(const PsiSkaSlice &o, int B, int
 // blend backward (MFMA): g_feat[b][k] = sum_n g_vp[b][n] dirs[k][n]
 // Rounds 3-6 ran this product on the fp32 MFMA (v_mfma_f32_16x16x4_f32 over a 16-column-tiled fp32 copy of the matrix; workgroup = 4 waves
 // sharing a 64-row k group and an n-slice, wave w taking n-steps w, w + 4, ..., LDS reduce).  What was learnt on that form and still holds for
-// the one below: ONE step of operands in flight per wave serves the launch best (with the skin_bwd_A waves sharing the SIMDs: 22.0 us at 1
-// step, 22.6 / 23.9 / 25.1 at 2 / 3 / 4), and the step loop as straight-line code with a register ring does not pay
-// (profiles/r06_ab_bwd_joint_pipeline.txt).
+// the one below: ONE step of operands in flight per wave serves the launch best WHERE LIVE skin_bwd_A WAVES SHARE THE SIMDs' MATRIX PIPE
+// (the operator's own backward, the dense iterations of a fit: 22.0 us at 1 step, 22.6 / 23.9 / 25.1 at 2 / 3 / 4), and the step loop as
+// straight-line code with a register ring does not pay (profiles/r06_ab_bwd_joint_pipeline.txt).  Hence PF is a parameter: the fitting
+// engine's contact class, which in a sparse iteration is what the launch waits for, keeps two steps in flight (-1.7 us; four measured the
+// same, two in the model class gained nothing sparse and lost 0.2-0.5 us dense: profiles/bwd_joint_chains_ab.txt).
 // The product on the fp16 matrix pipe at fp32-class accuracy (round 6; what lbs.hip's blend_fwd_h_kernel does for the forward product):
 // the fp32 MFMA runs at 1/16 of the fp16 rate, and the stream workgroups' 608 fp32 MFMAs per SIMD were what this launch waited for beside its
 // skin_bwd_A waves (with a quarter of them: 25.3 -> 21.2 us, profiles/r06_ab_blend_fp16x3.txt).  The matrix arrives as TWO fp16 parts per
@@ -215,7 +249,8 @@ __device__ __forceinline__ float psi_fp16_row_scale(unsigned bits)
 template <int MTB>
 constexpr int psi_blend_bwd_h_smem_f4() { return 4 * 2 * MTB * 4 * 64; }
 
-template <int MTB>
+// PF: steps of operands a wave keeps in flight (below)
+template <int MTB, int PF>
 __device__ __forceinline__ void blend_bwd_h_body(const PsiBlendBwdColsH &o, int B, int s_begin, int s_end, float *__restrict__ part, int kgroup,
                                                  int bgroup, psi_f4 *smem)
 {
@@ -262,17 +297,17 @@ __device__ __forceinline__ void blend_bwd_h_body(const PsiBlendBwdColsH &o, int 
 #pragma unroll
     for (int t = 0; t < MTB; t++) {
         const unsigned *sl = o.gvbits + (size_t)min(b0 + t * 32 + li, B - 1) * o.gv_slots;
+        // (a lane's up to eight slots requested together instead of one after the other: no gain, profiles/bwd_joint_chains_ab.txt)
         unsigned cbits = 0u;
         for (int p = kh; p < o.gv_slots; p += 2) cbits = max(cbits, sl[p]);
         cbits = max(cbits, (unsigned)__shfl_xor((int)cbits, 32, 64));
         gsc[t] = psi_fp16_row_scale(cbits);
         us[t] = o.dsc_inv / gsc[t];
     }
-    // PF steps' operands (PF x (4 + 2 MTB) 16-byte loads per lane) are requested before the first of them is split and multiplied
-#ifndef PSI_BWH_PF
-#define PSI_BWH_PF 1
-#endif
-    constexpr int PF = PSI_BWH_PF;
+    // PF steps' operands (PF x (4 + 2 MTB) 16-byte loads per lane) are requested before the first of them is split and multiplied, in
+    // the order of the steps: the depth changes no sum.  A last group with fewer than PF live steps requests its first step again for the
+    // missing ones (has[p] false: loaded, not multiplied)
+    static_assert(PF >= 1 && PF <= 4, "8 steps in flight spill (256 VGPRs and scratch); 4 do at MTB = 2");
     if (use_pm) {
         // OR over the bodies (almost always nothing to OR: one ballot), one word per wave and round -> LDS -> every wave
 #pragma unroll

@@ -1,13 +1,22 @@
 """dev: workgroup timeline of the last fit_bwd_joint_kernel launch (needs the -DPSI_HEAD_STOPS build, tools/_variants/stops.so).
-usage (GPU box): PSI_HIP_LIB=tools/_variants/stops.so PSI_SKIN_STOP=11 python tools/timeline_joint.py [bench args]"""
+usage (GPU box): PSI_HIP_LIB=tools/_variants/stops.so PSI_SKIN_STOP=11 python tools/timeline_joint.py [bench args | --nothing]"""
 import ctypes, os, sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bench  # noqa: E402
 
-sys.argv = [sys.argv[0]] + (sys.argv[1:] or ['--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--secondary', '0'])
-bench.main()
+if sys.argv[1:2] == ['--nothing']:
+    # the scene of tools/time_pen_share.py in which nothing penetrates, at the baseline shape: the launch with its model class skipped
+    import time_pen_share as tps
+    from psi_release_amd import synth
+    r = tps.runner(synth.make_smplx(7), synth.make_vposer_state(3), synth.make_scene(0, tps.M, tps.D, tps.NC, kind='room', radius=10.0), True)
+    r.steps(30)
+    tps.torch.cuda.synchronize()
+else:
+    sys.argv = [sys.argv[0]] + (sys.argv[1:] or ['--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--secondary', '0'])
+    bench.main()
 from psi_release_amd import hip
 lib = hip.lib()
 N = 8192
