@@ -627,6 +627,29 @@ int psi_mesh_winding_count(psi_mesh_sdf *m, const float gmin[3], const float gma
 /* d_vol[i] = d_f[i] < level ? -|d_vol[i]| : |d_vol[i]| for i < n: one elementwise kernel on `stream`. */
 int psi_mesh_sdf_apply_sign(const float *d_f, float level, float *d_vol, long long n, void *stream);
 
+/* ---- training records: the CVAE's input images of n rendered views, both modalities, in one call ----
+ * Replaces, per view, two calls of data_preprocessing (utils/utils_prox_snapshots_virtualcam.py:266-330, batch_gen_hdf5.py:398-439) and the
+ * window test of is_body_occluded (:342-378).  Contract, fp32, not contracted:
+ *   clip, maximum  c = min(x, clip); the view's maximum of c is exact (integer atomicMax on the bits of non-negative floats; NaN pixels are
+ *                  left out of it and flag the view)
+ *   scale          v = (2 c) / max - 1
+ *   resize         F.interpolate(mode='bilinear', align_corners=False): scale = float(in) / out, src = max(fma(scale, dst + 0.5, -0.5), 0),
+ *                  i0 = int(src), i1 = min(i0 + 1, in - 1), l1 = src - i0, l0 = 1 - l1, out = l0y (l0x a + l1x b) + l1y (l0x c + l1x d)
+ *   placement      H >= W: the image becomes th x (int(W (th / H)) / 2 * 2), centred in the columns; H < W the symmetric case; 0 elsewhere
+ *   window         usable = sum / count > z, the sum of the UNCLIPPED depth over [x0,x1) x [y0,y1) (cut to the image) in fp64, row-major,
+ *                  one adder; an empty window is not usable; without windows usable = 1
+ *   degenerate     a view whose depth or seg maximum is not > 0, or that holds a NaN: usable = 0 and both canvases all 0
+ * d_depth, d_seg [n,H,W] fp32, values >= 0 (a negative value counts as 0 in the maximum); they are only read.  d_windows [n,4] int32 =
+ * x0, y0, x1, y1 and d_target_z [n] fp32 come together or are both NULL.  Outputs: canvases [n,1,th,tw] fp32, d_max_d / d_seg_max [n] fp32
+ * (the clipped maxima), d_usable [n] int32.  Every output of a view is bit-identical whatever other views the call holds, and from run to
+ * run: no floating-point atomics.  d_workspace: psi_snapshot_canvas_workspace_bytes(n) bytes (the call zeroes it), or NULL for the
+ * library's per-stream scratch.  One memset and two kernels on `stream`, no host synchronisation.
+ * PSI_EINVAL: n, H or W < 1, H * W >= 2^31, th or tw odd or < 2, a clip <= 0, a resized image that is empty or wider than the canvas. */
+size_t psi_snapshot_canvas_workspace_bytes(int n_views);
+int psi_snapshot_canvas(const float *d_depth, const float *d_seg, int n_views, int H, int W, int th, int tw, float clip_depth, float clip_seg,
+                        const int32_t *d_windows, const float *d_target_z, float *d_depth_canvas, float *d_seg_canvas, float *d_max_d,
+                        float *d_seg_max, int32_t *d_usable, void *d_workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

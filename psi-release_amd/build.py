@@ -33,7 +33,8 @@ PER_FILE = {'chamfer.hip': ['-ffp-contract=off', '-fno-slp-vectorize'], 'nnindex
             'raster.hip': ['-ffp-contract=off'],        # the rounding of the projection decides which pixels a triangle covers
             'raster_bodies.hip': ['-ffp-contract=off'], # the same statements as raster.hip (csrc/raster_device.h), hence the same pieces
             'mesh_sdf.hip': ['-ffp-contract=off'],      # pruned and brute-force search must give the same bits
-            'mesh_winding.hip': []}                     # default contraction: its contract is a tolerance; the node positions and the far
+            'canvas.hip': ['-ffp-contract=off'],        # the scale and the interpolation as written
+            'mesh_winding.hip': []}               # default contraction: its contract is a tolerance; the node positions and the far
                                                         # test switch contraction off in their own statements
 
 

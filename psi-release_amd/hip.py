@@ -136,6 +136,8 @@ SIGNATURES = {
     'psi_mesh_winding_compute': (c_int, [c_void_p] * 3 + [c_int, c_float, c_int, c_void_p, c_void_p]),
     'psi_mesh_winding_count': (c_int, [c_void_p] * 3 + [c_int, c_float, c_int, c_void_p, c_void_p]),
     'psi_mesh_sdf_apply_sign': (c_int, [c_void_p, c_float, c_void_p, ctypes.c_longlong, c_void_p]),
+    'psi_snapshot_canvas_workspace_bytes': (c_size_t, [c_int]),
+    'psi_snapshot_canvas': (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 9),
 }
 
 

@@ -1165,3 +1165,42 @@ def mesh_sdf_apply_sign(f, level, vol):
     with torch.cuda.device(vol.device):
         hip.check(hip.lib().psi_mesh_sdf_apply_sign(pf, float(level), pv, vol.numel(), hip.stream()), 'psi_mesh_sdf_apply_sign')
     return vol
+
+
+# ------------------------------------------------------------------------------------------
+# Training records (psi_snapshot_canvas)
+# ------------------------------------------------------------------------------------------
+CANVAS_CLIP_DEPTH, CANVAS_CLIP_SEG = 6.0, 41.0
+
+
+def snapshot_canvas(depth, seg, size=(128, 128), windows=None, target_z=None):
+    """The CVAE's input images of n rendered views in one call (include/psi_hip.h: psi_snapshot_canvas).
+
+    depth, seg [n,H,W] fp32 on the GPU, as ``rendering.SnapshotRenderer.render`` returns them (only read); size = (th, tw), both even;
+    windows [n,4] int32 = x0, y0, x1, y1 and target_z [n] fp32 (GPU tensors, or anything ``torch.as_tensor`` takes) come together or not at
+    all.  Returns depth_canvas, seg_canvas [n,1,th,tw], max_d, seg_max [n] fp32 and usable [n] int32."""
+    pd, ps = hip.ptr(depth), hip.ptr(seg)
+    if depth.dtype != torch.float32 or seg.dtype != torch.float32 or depth.dim() != 3 or depth.shape != seg.shape or depth.device != seg.device:
+        raise ValueError('expected depth and seg [n,H,W] float32 of the same shape on the same device')
+    if (windows is None) != (target_z is None):
+        raise ValueError('windows and target_z come together')
+    n, H, W = depth.shape
+    th, tw = int(size[0]), int(size[1])
+    dev = depth.device
+    dc, sc = torch.empty(n, 1, th, tw, device=dev), torch.empty(n, 1, th, tw, device=dev)
+    max_d, seg_max = torch.empty(n, device=dev), torch.empty(n, device=dev)
+    usable = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return dc, sc, max_d, seg_max, usable
+    if windows is not None:
+        windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
+        target_z = torch.as_tensor(target_z, dtype=torch.float32).to(dev).contiguous()
+        if tuple(windows.shape) != (n, 4) or tuple(target_z.shape) != (n,):
+            raise ValueError('expected windows [n,4] and target_z [n]')
+    L = hip.lib()
+    ws = torch.empty(max(L.psi_snapshot_canvas_workspace_bytes(n), 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        hip.check(L.psi_snapshot_canvas(pd, ps, n, H, W, th, tw, CANVAS_CLIP_DEPTH, CANVAS_CLIP_SEG, hip.ptr(windows), hip.ptr(target_z),
+                                        hip.ptr(dc), hip.ptr(sc), hip.ptr(max_d), hip.ptr(seg_max), hip.ptr(usable), hip.ptr(ws), hip.stream()),
+                  'psi_snapshot_canvas')
+    return dc, sc, max_d, seg_max, usable

@@ -4,7 +4,8 @@
 From a scene mesh to a sensor folder (cam_*.npy, depth_*.npy, seg_*.npy) that the generation scripts read, on the GPU and without a
 window: virtual cameras on the reference's lattice around a target point (utils/utils_prox_snapshots_virtualcam.py:102-180), all rendered
 in one call, the views whose target is outside the image or occluded left out (:342-378), the first --n_cams of the rest written.
-Not included: moving recorded PROX-D bodies into the virtual cameras and the .mat training records (they need the licensed recordings)."""
+Moving recorded bodies into the virtual cameras and writing the training records (the second half of the reference's script) is
+utils_make_training_set.py."""
 import argparse
 import os
 
