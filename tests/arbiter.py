@@ -163,20 +163,25 @@ MIN_RULE_A = {'default': 1.0,       # measured: every body of every test passes 
 MIN_STRICT_A = {'default': 0.98}           # measured shares: 0.9896 .. 1.0 (one or two bodies of 136 / 137 / 192, each with an ambiguous vertex: sdf ~ 0 on the mask's edge)
 
 
-def record(name, report, min_rule_a=None):
+def record(name, report, min_rule_a=None, sub=None):
     """Keep the per-iteration summaries of an arbiter-checked test (which rule every body passed by, how much of each bound was used) as
     JSON under gpurun_out/arbiter/ (merged back from the GPU box; profiles/r05_arbiter.json is the committed copy) and hold the share of
-    bodies that needed no more than rule (a) to its pinned floor."""
+    bodies that needed no more than rule (a) to its pinned floor.  ``sub``: keep the rows of another kind of test in the sibling directory
+    of that name instead, without the arbiter's floors (tests/layer_bounds.py)."""
     import json
     import os
     rows = report if isinstance(report, list) else [report]
     out_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out', 'arbiter')
+    if sub:
+        out_dir = os.path.join(os.path.dirname(out_dir), sub)
     try:
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, name + '.json'), 'w') as f:
             json.dump(rows, f, indent=1, default=float)
     except OSError:
         pass
+    if sub:
+        return rows
     floor = MIN_RULE_A.get(name, MIN_RULE_A['default']) if min_rule_a is None else min_rule_a
     for r in rows:
         by = r['bodies_by_rule']

@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import layer_bounds
 import library_paths
 from conftest import golden, rel_err
 from psi_release_amd import models, ops, synth
@@ -22,18 +23,28 @@ DEV = 'cuda'
 SPLIT3 = 2.0 ** -16               # |hi*hi + hi*lo + lo*hi - a*b| per product, relative to |a b|: the dropped lo*lo term and the two split residues are
                                   # 3 x 2^-18 with round-to-nearest splits; the worst ratio measured over these tests is 1.5e-5 = 2^-16 (3-term inner products)
 
-# (N, Cin, Cout, K, stride, pad, H, bias): the convolutions of the scene trunk and the heads, plus odd batch sizes (M not a multiple of 128)
-CONVS = [(2, 2, 64, 7, 2, 3, 128, False), (3, 64, 64, 3, 1, 1, 32, False), (2, 64, 128, 3, 2, 1, 32, False), (2, 64, 128, 1, 2, 0, 32, False),
-         (5, 128, 128, 3, 1, 1, 16, False), (3, 128, 32, 3, 1, 1, 16, True), (1, 128, 128, 3, 1, 1, 16, True), (128, 64, 64, 3, 1, 1, 32, False),
-         (3, 2, 64, 7, 2, 3, 50, True), (100, 2, 64, 7, 2, 3, 36, False)]      # the stem's own kernels (conv_stem.hip): partial 8 x 16 tiles, bias, more tiles than workgroups
+# (N, Cin, Cout, K, stride, pad, H, W, bias): the convolutions of the scene trunk and the heads, plus odd batch sizes (M not a multiple of 128)
+CONVS = [(2, 2, 64, 7, 2, 3, 128, 128, False), (3, 64, 64, 3, 1, 1, 32, 32, False), (2, 64, 128, 3, 2, 1, 32, 32, False), (2, 64, 128, 1, 2, 0, 32, 32, False),
+         (5, 128, 128, 3, 1, 1, 16, 16, False), (3, 128, 32, 3, 1, 1, 16, 16, True), (1, 128, 128, 3, 1, 1, 16, 16, True), (128, 64, 64, 3, 1, 1, 32, 32, False),
+         (3, 2, 64, 7, 2, 3, 50, 50, True), (100, 2, 64, 7, 2, 3, 36, 36, False),      # the stem's own kernels (conv_stem.hip): partial 8 x 16 tiles, bias, more tiles than workgroups
+         # maps that are not square (an H / W swap in a kernel passes every row above): the stem with different tile counts per axis, the
+         # general kernel at stride 2, the stride-1 3x3 kernel of conv.hip with two tile columns
+         (2, 2, 64, 7, 2, 3, 40, 56, True), (3, 64, 128, 3, 2, 1, 24, 40, False), (3, 64, 64, 3, 1, 1, 16, 64, False)]
+CONV_IDS = ['-'.join(map(str, c[:7] + c[8:])) if c[6] == c[7] else '-'.join(map(str, c[:6])) + '-%dx%d-%s' % c[6:] for c in CONVS]
 
 
-@pytest.mark.parametrize('N,Cin,Cout,K,stride,pad,H,bias', CONVS)
-def test_conv2d_split_matches_double_precision(N, Cin, Cout, K, stride, pad, H, bias):
+def _one_term_operands(x, conv, g=None):
+    """float64 CPU copies of the bf16-rounded operands of the one-term (bf16) mode"""
+    r = lambda t: t.detach().to(torch.bfloat16).double().cpu()
+    return r(x), r(conv.weight), (r(g) if g is not None else None)
+
+
+@pytest.mark.parametrize('N,Cin,Cout,K,stride,pad,H,W,bias', CONVS, ids=CONV_IDS)
+def test_conv2d_split_matches_double_precision(N, Cin, Cout, K, stride, pad, H, W, bias):
     torch.manual_seed(N + Cin + Cout + K)
     conv = torch.nn.Conv2d(Cin, Cout, K, stride, pad, bias=bias).to(DEV).to(memory_format=torch.channels_last)
     assert ops.conv2d_supported(conv)
-    x = torch.randn(N, Cin, H, H, device=DEV).contiguous(memory_format=torch.channels_last)
+    x = torch.randn(N, Cin, H, W, device=DEV).contiguous(memory_format=torch.channels_last)
     with torch.no_grad():
         y = ops.conv2d_split(x, conv, nterm=3)
         ref = F.conv2d(x.double().cpu(), conv.weight.double().cpu(), conv.bias.double().cpu() if bias else None, stride, pad)
@@ -47,18 +58,24 @@ def test_conv2d_split_matches_double_precision(N, Cin, Cout, K, stride, pad, H, 
         y1 = ops.conv2d_split(x.to(torch.bfloat16), conv, nterm=1, out_bf16=True)
         r1 = F.conv2d(x.to(torch.bfloat16).float(), conv.weight.to(torch.bfloat16).float(), conv.bias if bias else None, stride, pad)
     assert y1.dtype == torch.bfloat16 and float((y1.float() - r1).abs().max()) <= 2 ** -7 * float(r1.abs().max())
+    # ... and every element against float64 on those operands: half a bf16 ulp + the worst case of the fp32 sum (layer_bounds.py)
+    x64, w64, _ = _one_term_operands(x, conv)
+    row = layer_bounds.conv_report(x64, w64, conv.bias.detach().double().cpu() if bias else None, None, stride, pad, y=y1)
+    layer_bounds.record('conv2d_split_fwd_%s' % '-'.join(map(str, (N, Cin, Cout, K, stride, pad, H, W, bias))),
+                        dict(row, op='conv2d_split nterm=1', case=[N, Cin, Cout, K, stride, pad, H, W, bias]))
+    layer_bounds.assert_conv_report(row)
 
 
-@pytest.mark.parametrize('N,Cin,Cout,K,stride,pad,H,bias', CONVS)
-def test_conv2d_split_gradients_match_double_precision(N, Cin, Cout, K, stride, pad, H, bias):
+@pytest.mark.parametrize('N,Cin,Cout,K,stride,pad,H,W,bias', CONVS, ids=CONV_IDS)
+def test_conv2d_split_gradients_match_double_precision(N, Cin, Cout, K, stride, pad, H, W, bias):
     """Input gradient (the forward kernel in its transposed-gather form) and weight gradient (conv_wgrad_kernel: pixel-contraction with
     transposed LDS tiles, ordered split sums) of ops.conv2d_split against double precision, three-term and one-term products; the
     library path (tests/library_paths.py) gives the same numbers to fp32 rounding."""
     torch.manual_seed(N + Cin + Cout + K + 1)
     conv = torch.nn.Conv2d(Cin, Cout, K, stride, pad, bias=bias).to(DEV).to(memory_format=torch.channels_last)
-    x = torch.randn(N, Cin, H, H, device=DEV).contiguous(memory_format=torch.channels_last).requires_grad_(Cin > 2)     # (the stem's input needs none)
-    OH = (H + 2 * pad - K) // stride + 1
-    g = torch.randn(N, Cout, OH, OH, device=DEV).contiguous(memory_format=torch.channels_last)
+    x = torch.randn(N, Cin, H, W, device=DEV).contiguous(memory_format=torch.channels_last).requires_grad_(Cin > 2)     # (the stem's input needs none)
+    OH, OW = (H + 2 * pad - K) // stride + 1, (W + 2 * pad - K) // stride + 1
+    g = torch.randn(N, Cout, OH, OW, device=DEV).contiguous(memory_format=torch.channels_last)
     ops.conv2d_split(x, conv, nterm=3).backward(g)
     gx = x.grad.clone() if Cin > 2 else None
     gw, gb = conv.weight.grad.clone(), (conv.bias.grad.clone() if bias else None)
@@ -85,6 +102,13 @@ def test_conv2d_split_gradients_match_double_precision(N, Cin, Cout, K, stride, 
     if Cin > 2:
         assert float((xb.grad.float() - xr.grad).abs().max()) <= 2 ** -7 * float(xr.grad.abs().max())
     assert float((conv.weight.grad - wr.grad).abs().max()) <= 2e-5 * float(wr.grad.abs().max()) + 1e-6
+    # ... and per element against float64 on those operands: the bf16 input gradient to half a bf16 ulp + the worst case of the fp32 sum,
+    # the fp32 weight gradient in the accuracy class of a plain fp32 evaluation (layer_bounds.py)
+    x64, w64, g64 = _one_term_operands(x, conv, g)
+    row = layer_bounds.conv_report(x64, w64, None, g64, stride, pad, dx=xb.grad if Cin > 2 else None, gw=conv.weight.grad)
+    layer_bounds.record('conv2d_split_bwd_%s' % '-'.join(map(str, (N, Cin, Cout, K, stride, pad, H, W, bias))),
+                        dict(row, op='conv2d_split nterm=1', case=[N, Cin, Cout, K, stride, pad, H, W, bias]))
+    layer_bounds.assert_conv_report(row)
 
 
 @pytest.mark.parametrize('N,Cin,Cout,K,stride,pad,H,nterm', [(4, 64, 64, 3, 1, 1, 32, 3), (3, 64, 128, 3, 2, 1, 32, 3), (2, 64, 128, 1, 2, 0, 32, 1),
