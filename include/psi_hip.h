@@ -650,6 +650,44 @@ int psi_snapshot_canvas(const float *d_depth, const float *d_seg, int n_views, i
                         const int32_t *d_windows, const float *d_target_z, float *d_depth_canvas, float *d_seg_canvas, float *d_max_d,
                         float *d_seg_max, int32_t *d_usable, void *d_workspace, void *stream);
 
+/* ---- scene contact cloud: even surface samples of a mesh, about one per `spacing` cell whatever the tessellation ----
+ * Contract (csrc/mesh_cloud_shared.h holds the statements), fp32, not contracted, IEEE division and square root.
+ * With h = spacing / 2, for every triangle of d_faces in the caller's numbering:
+ *   candidates  none for a triangle whose |ab x ac| is 0; the three corners for one whose longest edge is shorter than h; otherwise the
+ *               corners are rotated so that ab is the longest edge (a tie takes the first of ab, bc, ca), L = |ab|, Ht = |ab x ac| / L,
+ *               m = max(1, ceil(Ht / h)); row r < m lies at s = r / m between P = a + s (c - a) and Q = b + s (c - b) and holds
+ *               P + (j / k)(Q - P), j = 0 .. k, with k = max(1, ceil(((1 - s) L) / h)); row m is the point c.  Candidates are numbered
+ *               triangle by triangle, row by row, j ascending
+ *   selection   o = (minimum over the vertices the faces refer to) - h per axis, cell = floor((p - o) / spacing), centre =
+ *               o + (cell + 0.5) spacing; of the candidates of a cell the one with the smallest squared distance to the centre is kept,
+ *               on a tie the smallest candidate number; the output is the kept candidates in ascending candidate number
+ * Every surface point lies within 2.3 spacing of an output point and no cell holds two.  No floating-point atomics: bit-identical from run
+ * to run.  The five calls are the passes of one computation; the scans and the sort between them are the caller's (ops.mesh_cloud):
+ *   count    d_verts [nv,3] fp32, d_faces [nf,3] int32 (device).  Writes d_tri_rows [nf] int32 (rows per triangle), then reads the verdict
+ *            back (it synchronises `stream`) and fills the host values origin[3], *n_rows and *n_cands.  PSI_EINVAL, with nothing but
+ *            d_tri_rows written: spacing not finite or <= 0; nf < 1; a face index outside [0, nv); a non-finite coordinate of a
+ *            referenced vertex; no triangle with area; more than 2^21 cells along an axis; more than 2^31 - 1 candidates (*n_cands then
+ *            holds the count)
+ *   rows     d_tri_row_off [nf] int64 = exclusive scan of d_tri_rows.  Writes d_row_tri, d_row_cnt [n_rows] int32: the triangle and the
+ *            candidate count of every row
+ *   emit     d_row_off [n_rows] int64 = exclusive scan of d_row_cnt.  Writes d_pos [n_cands,3] fp32, d_tri [n_cands] int32, d_cell
+ *            [n_cands] int64 (the linear cell index, 21 bits per axis) and d_key [n_cands] uint32 (the bits of the squared distance)
+ *   winners  d_cell_sorted, d_perm [n] int64 = a STABLE ascending sort of d_cell and its permutation.  Writes d_keep [n] int32: 1 for the
+ *            kept candidate of every cell, 0 elsewhere
+ *   compact  d_keep_scan [n] int64 = inclusive scan of d_keep, n_out its last element.  Writes d_points [n_out,3] fp32, d_out_tri [n_out]
+ * rows, emit, winners and compact are one kernel each on `stream` (winners after one memset) with no host synchronisation. */
+int psi_mesh_cloud_count(const float *d_verts, const int32_t *d_faces, int nv, int nf, float spacing, int32_t *d_tri_rows, float origin[3],
+                         long long *n_rows, long long *n_cands, void *stream);
+int psi_mesh_cloud_rows(const float *d_verts, const int32_t *d_faces, int nv, int nf, float spacing, const int64_t *d_tri_row_off,
+                        long long n_rows, int32_t *d_row_tri, int32_t *d_row_cnt, void *stream);
+int psi_mesh_cloud_emit(const float *d_verts, const int32_t *d_faces, int nv, int nf, float spacing, const float origin[3],
+                        const int64_t *d_tri_row_off, const int32_t *d_row_tri, const int64_t *d_row_off, long long n_rows, long long n_cands,
+                        float *d_pos, int32_t *d_tri, int64_t *d_cell, uint32_t *d_key, void *stream);
+int psi_mesh_cloud_winners(const int64_t *d_cell_sorted, const int64_t *d_perm, const uint32_t *d_key, long long n, int32_t *d_keep,
+                           void *stream);
+int psi_mesh_cloud_compact(const float *d_pos, const int32_t *d_tri, const int32_t *d_keep, const int64_t *d_keep_scan, long long n,
+                           long long n_out, float *d_points, int32_t *d_out_tri, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,11 @@ SIGNATURES = {
     'psi_mesh_sdf_apply_sign': (c_int, [c_void_p, c_float, c_void_p, ctypes.c_longlong, c_void_p]),
     'psi_snapshot_canvas_workspace_bytes': (c_size_t, [c_int]),
     'psi_snapshot_canvas': (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 9),
+    'psi_mesh_cloud_count': (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_float] + [c_void_p] * 5),
+    'psi_mesh_cloud_rows': (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_float, c_void_p, ctypes.c_longlong] + [c_void_p] * 3),
+    'psi_mesh_cloud_emit': (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_float] + [c_void_p] * 4 + [ctypes.c_longlong] * 2 + [c_void_p] * 5),
+    'psi_mesh_cloud_winners': (c_int, [c_void_p] * 3 + [ctypes.c_longlong] + [c_void_p] * 2),
+    'psi_mesh_cloud_compact': (c_int, [c_void_p] * 4 + [ctypes.c_longlong] * 2 + [c_void_p] * 3),
 }
 
 

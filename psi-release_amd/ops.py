@@ -1204,3 +1204,83 @@ def snapshot_canvas(depth, seg, size=(128, 128), windows=None, target_z=None):
                                         hip.ptr(dc), hip.ptr(sc), hip.ptr(max_d), hip.ptr(seg_max), hip.ptr(usable), hip.ptr(ws), hip.stream()),
                   'psi_snapshot_canvas')
     return dc, sc, max_d, seg_max, usable
+
+
+# ------------------------------------------------------------------------------------------
+# Scene contact cloud: even surface samples of a mesh (psi_mesh_cloud_*)
+# ------------------------------------------------------------------------------------------
+MESH_CLOUD_MAX_CANDIDATES = 2 ** 31 - 1
+
+
+def mesh_cloud(verts, faces, spacing, out=None, return_counts=False):
+    """Points on the surface of a mesh, about one per ``spacing`` cell whatever the tessellation (include/psi_hip.h: psi_mesh_cloud_*;
+    DESIGN.md section 10b).  verts [nv,3] fp32 and faces [nf,3] int32 on the GPU, the caller's own (unwelded) mesh.  Returns points [m,3]
+    fp32 and tri [m] int32 (the caller's face index of every point) on the GPU, in ascending candidate number; with ``return_counts``
+    also (candidates, rows).  ``out`` = (points [cap,3] fp32, tri [cap] int32) receives the result in its first m rows (the returned tensors
+    are views of them); nothing is written to them when the call is refused.
+
+    The five kernels run on the current stream; the scans (``torch.cumsum``, int64) and the stable sort of the cell indices between them
+    are plumbing, and two values are read back: the verdict and the totals of the count pass, and the number of kept points.
+    ``PsiHipError`` (PSI_EINVAL) for what the library refuses; ``ValueError`` when the mesh has more than 2^31 - 1 candidates at this
+    spacing."""
+    import ctypes
+    import math
+    pv, pf = hip.ptr(verts), hip.ptr(faces)
+    if verts.dtype != torch.float32 or faces.dtype != torch.int32 or verts.dim() != 2 or faces.dim() != 2 or verts.shape[1] != 3 or faces.shape[1] != 3:
+        raise ValueError('expected verts [nv,3] float32 and faces [nf,3] int32')
+    if verts.device != faces.device:
+        raise ValueError('verts and faces lie on different devices')
+    spacing = float(spacing)
+    if not math.isfinite(spacing) or spacing <= 0:
+        raise hip.PsiHipError('psi_mesh_cloud: spacing is finite and positive (got %r)' % spacing)
+    nv, nf = int(verts.shape[0]), int(faces.shape[0])
+    if nf < 1 or nv < 1:
+        raise hip.PsiHipError('psi_mesh_cloud: nf >= 1 and nv >= 1')
+    dev = verts.device
+    if out is not None:
+        out_p, out_t = out
+        hip.ptr(out_p), hip.ptr(out_t)
+        if out_p.dtype != torch.float32 or out_t.dtype != torch.int32 or out_p.dim() != 2 or out_p.shape[1] != 3 or out_t.dim() != 1 \
+                or out_p.shape[0] != out_t.shape[0] or out_p.device != dev or out_t.device != dev:
+            raise ValueError('expected out = (points [cap,3] float32, tri [cap] int32) on the device of the mesh')
+    L = hip.lib()
+    with torch.cuda.device(dev):
+        st = hip.stream()
+        tri_rows = torch.empty(nf, dtype=torch.int32, device=dev)
+        origin = (ctypes.c_float * 3)()
+        n_rows, n_cands = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        rc = L.psi_mesh_cloud_count(pv, pf, nv, nf, spacing, hip.ptr(tri_rows), origin, ctypes.byref(n_rows), ctypes.byref(n_cands), st)
+        if rc != 0 and n_cands.value > MESH_CLOUD_MAX_CANDIDATES:
+            raise ValueError('the mesh has %d candidates at spacing %g: more than 2^31 - 1 (use a larger spacing)' % (n_cands.value, spacing))
+        hip.check(rc, 'psi_mesh_cloud_count')
+        n_rows, n_cands = n_rows.value, n_cands.value
+        tri_row_inc = torch.cumsum(tri_rows, 0, dtype=torch.int64)
+        tri_row_off = tri_row_inc - tri_rows
+        row_tri = torch.empty(n_rows, dtype=torch.int32, device=dev)
+        row_cnt = torch.empty(n_rows, dtype=torch.int32, device=dev)
+        hip.check(L.psi_mesh_cloud_rows(pv, pf, nv, nf, spacing, hip.ptr(tri_row_off), n_rows, hip.ptr(row_tri), hip.ptr(row_cnt), st),
+                  'psi_mesh_cloud_rows')
+        row_off = torch.cumsum(row_cnt, 0, dtype=torch.int64) - row_cnt
+        pos = torch.empty(n_cands, 3, dtype=torch.float32, device=dev)
+        tri = torch.empty(n_cands, dtype=torch.int32, device=dev)
+        cell = torch.empty(n_cands, dtype=torch.int64, device=dev)
+        key = torch.empty(n_cands, dtype=torch.int32, device=dev)
+        hip.check(L.psi_mesh_cloud_emit(pv, pf, nv, nf, spacing, origin, hip.ptr(tri_row_off), hip.ptr(row_tri), hip.ptr(row_off), n_rows, n_cands,
+                                        hip.ptr(pos), hip.ptr(tri), hip.ptr(cell), hip.ptr(key), st), 'psi_mesh_cloud_emit')
+        cell_sorted, perm = torch.sort(cell, stable=True)
+        keep = torch.empty(n_cands, dtype=torch.int32, device=dev)
+        hip.check(L.psi_mesh_cloud_winners(hip.ptr(cell_sorted), hip.ptr(perm), hip.ptr(key), n_cands, hip.ptr(keep), st), 'psi_mesh_cloud_winners')
+        keep_scan = torch.cumsum(keep, 0, dtype=torch.int64)
+        m = int(keep_scan[-1].item())
+        if m < 1:
+            raise hip.PsiHipError('psi_mesh_cloud_winners marked no candidate')
+        if out is None:
+            out_p, out_t = torch.empty(m, 3, dtype=torch.float32, device=dev), torch.empty(m, dtype=torch.int32, device=dev)
+        elif out_p.shape[0] < m:
+            raise ValueError('out holds %d points, the cloud has %d' % (out_p.shape[0], m))
+        hip.check(L.psi_mesh_cloud_compact(hip.ptr(pos), hip.ptr(tri), hip.ptr(keep), hip.ptr(keep_scan), n_cands, m, hip.ptr(out_p), hip.ptr(out_t),
+                                           st), 'psi_mesh_cloud_compact')
+    points, tri_out = out_p[:m], out_t[:m]
+    if return_counts:
+        return points, tri_out, (n_cands, n_rows)
+    return points, tri_out

@@ -5,6 +5,9 @@ volume" states the contract).
 
 * ``MeshSDF``          the mesh on the GPU: welded, zero-area triangles dropped, pseudonormals; ``compute`` returns a volume
 * ``scene_cloud``      the welded vertex positions, optionally one per occupied voxel (NumPy, on the host)
+* ``surface_cloud``    points ON the surface, about one per ``spacing`` cell whatever the tessellation (csrc/mesh_cloud.hip through
+                       ``ops.mesh_cloud``): for CAD, synthetic and decimated meshes, whose vertices say little
+                       about where their floors and walls are
 * ``scene_from_mesh``  both, as the ``synth.SceneData`` that ``FittingOP(scene=...)``, ``scenes=[...]`` and ``write_prox_layout`` take
 
 Convention: triangles face free space, so free space is positive and solid is negative — what the collision term and
@@ -108,6 +111,54 @@ def scene_cloud(verts, voxel=None) -> np.ndarray:
     return v[np.sort(first)]
 
 
+def surface_cloud_device(verts, faces, spacing, device='cuda'):
+    """``surface_cloud`` with both results left on the GPU: (points [m,3] fp32, tri [m] int32).  ``verts`` and ``faces`` are arrays or
+    tensors on any device; tensors that already lie on ``device`` as fp32 / int32 are used as they are."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise ops.hip.PsiHipError('surface_cloud needs a GPU device (the HIP kernels are the only implementation)')
+    if not (spacing is not None and float(spacing) > 0 and np.isfinite(float(spacing))):
+        raise ValueError('spacing must be positive and finite')
+    v = verts if torch.is_tensor(verts) else torch.from_numpy(np.ascontiguousarray(verts, dtype=np.float32))
+    f = faces if torch.is_tensor(faces) else torch.from_numpy(np.ascontiguousarray(faces, dtype=np.int64))
+    v, f = v.reshape(-1, 3), f.reshape(-1, 3)
+    if f.numel() == 0 or v.numel() == 0:
+        raise ValueError('empty mesh')
+    if f.dtype != torch.int32:
+        if int(f.abs().max()) >= 2 ** 31:
+            raise ops.hip.PsiHipError('a face index lies outside [0, nv)')
+        f = f.to(torch.int32)
+    return ops.mesh_cloud(v.to(dev, torch.float32).contiguous(), f.to(dev).contiguous(), float(spacing))
+
+
+def surface_cloud(verts, faces, spacing, device='cuda', return_tri=False):
+    """Points on the surface of the mesh, [m,3] fp32 (NumPy, like ``scene_cloud``): about one per cell of a ``spacing``-sized lattice,
+    the candidate of a row-by-row sampling of every triangle that lies nearest to the cell's centre, so the density follows the area and
+    not the tessellation; every surface point is within 2.3 x ``spacing`` of one (measured: within about one ``spacing``).  Deterministic
+    and computed on the GPU.  ``faces`` are the caller's, unwelded: with ``return_tri`` the face index of every point comes along
+    ([m] int32), which gives access to normals, labels and colours.  A mesh with more than 2^31 - 1 candidates at this spacing is a
+    ``ValueError``."""
+    points, tri = surface_cloud_device(verts, faces, spacing, device=device)
+    points = points.cpu().numpy()
+    return (points, tri.cpu().numpy()) if return_tri else points
+
+
+CLOUDS = ('vertices', 'surface')
+
+
+def check_cloud_args(cloud, voxel, spacing):
+    """The argument rules of ``scene_from_mesh``'s two clouds (``ValueError``), checked before any work."""
+    if cloud not in CLOUDS:
+        raise ValueError("cloud is 'vertices' or 'surface'")
+    if cloud == 'surface':
+        if voxel is not None:
+            raise ValueError("voxel thins the vertex cloud: with cloud='surface' pass spacing instead")
+        if spacing is None or not (float(spacing) > 0 and np.isfinite(float(spacing))):
+            raise ValueError("cloud='surface' needs a positive, finite spacing")
+    elif spacing is not None:
+        raise ValueError("spacing belongs to cloud='surface'")
+
+
 def check_engine_dim(dim):
     if dim % 4 != 0 or dim > ENGINE_MAX_DIM or dim < 4:
         raise ValueError('dim = %d: the fitting engine needs a multiple of 4, at most %d (pass check_engine=False for a volume that is '
@@ -121,12 +172,14 @@ def grid_box(verts, margin):
 
 
 def scene_from_mesh(verts, faces, dim=256, margin=0.5, voxel=None, contact_parts=None, check_engine=True, device='cuda', sign='pseudonormal',
-                    exterior='solid', beta=3.0) -> synth.SceneData:
+                    exterior='solid', beta=3.0, cloud='vertices', spacing=None) -> synth.SceneData:
     """The ``synth.SceneData`` of a scene mesh: ``sdf`` [D,D,D] computed on the GPU over the mesh's box grown by ``margin`` on every side,
     ``verts`` = ``scene_cloud(verts, voxel)``.  ``FittingOP(scene=...)``, ``scenes=[...]`` and ``SceneData.write_prox_layout`` take it as
     is.  The several-scenes engine refuses D % 4 != 0 and D > 480: the same ``ValueError`` is raised here, before any work, unless
-    ``check_engine=False``.  ``sign``, ``exterior`` and ``beta`` are those of ``MeshSDF.compute``."""
+    ``check_engine=False``.  ``sign``, ``exterior`` and ``beta`` are those of ``MeshSDF.compute``.  ``cloud='surface'`` with a ``spacing``
+    puts ``surface_cloud(verts, faces, spacing)`` into ``verts`` instead (``voxel`` then is a ``ValueError``: it thins vertices)."""
     dim = int(dim)
+    check_cloud_args(cloud, voxel, spacing)
     if check_engine:
         check_engine_dim(dim)
     if not margin >= 0:
@@ -136,4 +189,5 @@ def scene_from_mesh(verts, faces, dim=256, margin=0.5, voxel=None, contact_parts
     mesh = MeshSDF(verts, faces, device=device)
     lo, hi = grid_box(verts, margin)
     sdf = mesh.compute(lo, hi, dim, sign=sign, exterior=exterior, beta=beta).cpu().numpy()
-    return synth.SceneData(scene_cloud(verts, voxel), sdf, lo, hi, dim, dict(contact_parts or {}))
+    points = scene_cloud(verts, voxel) if cloud == 'vertices' else surface_cloud(verts, faces, spacing, device=device)
+    return synth.SceneData(points, sdf, lo, hi, dim, dict(contact_parts or {}))

@@ -1,9 +1,11 @@
 #!/usr/bin/env python
-"""python utils_scene_sdf.py SCENE_PLY OUT_ROOT --name N [--dim 256 --margin 0.5 --voxel V --sign winding]     (or: OUT_ROOT --name N --synthetic)
+"""python utils_scene_sdf.py SCENE_PLY OUT_ROOT --name N [--dim 256 --margin 0.5 --voxel V --sign winding --cloud surface --spacing S]
+                                                                                                   (or: OUT_ROOT --name N --synthetic)
 
 From a scene mesh to the two scene files of the fitting and evaluation scripts, on the GPU: OUT_ROOT/scenes_sdf/N.json + N_sdf.npy (the
 signed distance volume over the mesh's box grown by --margin, [ix][iy][iz], positive in free space) and OUT_ROOT/scenes_downsampled/N.ply
-(the welded vertices, one per --voxel cell when given).  The reference ships these as downloads.  Triangles must face free space; with
+(the welded vertices, one per --voxel cell when given; with --cloud surface --spacing S points on the surface instead, about one per
+S-sized cell whatever the tessellation: for CAD, synthetic and decimated meshes).  The reference ships these as downloads.  Triangles must face free space; with
 the default --sign pseudonormal an open mesh gets its sign from the orientation of the nearest triangle, --sign winding takes it from the
 generalised winding number (open scans, furniture that touches or enters the floor).  Prints the three config paths of the fitting scripts."""
 import argparse
@@ -22,6 +24,9 @@ def parse(argv=None):
     ap.add_argument('--dim', type=int, default=256, help='nodes per axis (a multiple of 4, at most 480: what the fitting engine samples)')
     ap.add_argument('--margin', type=float, default=0.5, help='the grid box is the mesh box grown by this on every side (m)')
     ap.add_argument('--voxel', type=float, default=None, help='keep one vertex per cell of this size in the point cloud')
+    ap.add_argument('--cloud', choices=scene_sdf.CLOUDS, default='vertices', help='the point cloud: the welded vertices of the mesh, or even '
+                    'samples of its surface (needs --spacing)')
+    ap.add_argument('--spacing', type=float, default=None, help='--cloud surface: about one point per cell of this size (m)')
     ap.add_argument('--sign', choices=scene_sdf.SIGNS, default='pseudonormal', help='where the sign comes from: the pseudonormal of the nearest '
                     'feature (closed, clean meshes) or the generalised winding number (open, touching or interpenetrating meshes)')
     ap.add_argument('--exterior', choices=sorted(scene_sdf.LEVELS), default='solid', help='--sign winding: what lies outside the mesh, solid '
@@ -45,6 +50,10 @@ def parse(argv=None):
         ap.error('--beta must be finite and not negative')
     if a.margin < 0 or (a.voxel is not None and a.voxel <= 0):
         ap.error('--margin must not be negative and --voxel must be positive')
+    try:
+        scene_sdf.check_cloud_args(a.cloud, a.voxel, a.spacing)
+    except ValueError as e:
+        ap.error(str(e))
     return a
 
 
@@ -58,7 +67,7 @@ def main(argv=None):
     else:
         verts, faces, _ = read_ply_mesh(a.scene_ply)
     scene = scene_sdf.scene_from_mesh(verts, faces, dim=a.dim, margin=a.margin, voxel=a.voxel, contact_parts=parts, sign=a.sign, exterior=a.exterior,
-                                      beta=a.beta)
+                                      beta=a.beta, cloud=a.cloud, spacing=a.spacing)
     paths = scene.write_prox_layout(a.out_root, a.name)
     print('[INFO] %d triangles -> %d^3 volume, %d cloud points' % (len(faces), a.dim, len(scene.verts)))
     for k in ('scene_verts_path', 'scene_sdf_path', 'contact_id_folder'):
