@@ -688,6 +688,30 @@ int psi_mesh_cloud_winners(const int64_t *d_cell_sorted, const int64_t *d_perm, 
 int psi_mesh_cloud_compact(const float *d_pos, const int32_t *d_tri, const int32_t *d_keep, const int64_t *d_keep_scan, long long n,
                            long long n_out, float *d_points, int32_t *d_out_tri, void *stream);
 
+/* ---- orienting a scene mesh towards free space: the two device steps of scene_sdf.orient_faces ----
+ * psi_flood_fill: d_free (device, u8 [Dx,Dy,Dz], element [ix][iy][iz], overwritten) becomes 1 at the nodes of d_open (same shape, non-zero =
+ * open, only read) that are 6-connected through open nodes to one of the n seed nodes d_seed_nodes [n,3] int32 (ix, iy, iz), 0 elsewhere.  A
+ * seed node outside the grid or on a node that is not open contributes nothing.  One wave owns an 8 x 8 x 8 brick of nodes, keeps it and a
+ * one-node apron as bits in LDS, floods it to convergence locally, writes the nodes it gained and raises the launch's word (integer
+ * atomicOr) when it gained one.  The call launches the kernel until a launch raises nothing, reads the words of 8 launches back at a time
+ * (it synchronises `stream` once per 8 launches) and stores in *h_rounds (host, may be NULL) the number of launches up to and including the
+ * first that gained nothing.  A launch reads what the launch before it left, never what another workgroup of the same launch writes: the
+ * set and *h_rounds are the same from run to run.  The words come from the library's per-stream scratch.
+ * PSI_EINVAL: an edge outside 2 .. 1024, n < 1, d_open == d_free.
+ *
+ * psi_mesh_orient_votes: for sample i < n (d_points [n,3] fp32 on triangle d_tri[i] of d_faces [nf,3] int32 over d_verts [nv,3] fp32), in
+ * fp32, not contracted, IEEE division and square root: u = b - a, v = c - a, cr = u x v (each component one product minus the other),
+ * len = sqrtf((cr.x cr.x + cr.y cr.y) + cr.z cr.z); a sample whose len is not > 0 casts no vote; q = p +- delta * (cr / len) per axis;
+ * the node of q is rintf((q - gmin) / step) per axis, step = (gmax - gmin) / (float)(D - 1), the nodes of psi_mesh_sdf_compute; a probe
+ * whose node lies outside [0, D - 1] on an axis is not free.  d_votes [nf,2] int32 (zeroed by the call) counts per triangle the samples
+ * whose front probe (+) and whose back probe (-) hit a free node of d_free (u8 [D,D,D]), by integer atomicAdd.  One lane per sample; a
+ * sample whose triangle lies outside [0, nf) or whose triangle refers to a vertex outside [0, nv) casts no vote.  One memset and one kernel
+ * on `stream`, no host synchronisation.  PSI_EINVAL: D outside 2 .. 1024, bounds as psi_mesh_sdf_compute, delta not positive and finite,
+ * n outside 0 .. 2^31 - 1. */
+int psi_flood_fill(const uint8_t *d_open, int Dx, int Dy, int Dz, const int32_t *d_seed_nodes, int n, uint8_t *d_free, int *h_rounds, void *stream);
+int psi_mesh_orient_votes(const float *d_points, const int32_t *d_tri, long long n, const float *d_verts, int nv, const int32_t *d_faces, int nf,
+                          const uint8_t *d_free, const float gmin[3], const float gmax[3], int D, float delta, int32_t *d_votes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

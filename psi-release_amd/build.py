@@ -35,6 +35,7 @@ PER_FILE = {'chamfer.hip': ['-ffp-contract=off', '-fno-slp-vectorize'], 'nnindex
             'mesh_sdf.hip': ['-ffp-contract=off'],      # pruned and brute-force search must give the same bits
             'canvas.hip': ['-ffp-contract=off'],        # the scale and the interpolation as written
             'mesh_cloud.hip': ['-ffp-contract=off'],    # the rule of the surface cloud, operation by operation
+            'mesh_orient.hip': ['-ffp-contract=off'],   # the probes of the votes, operation by operation
             'mesh_winding.hip': []}               # default contraction: its contract is a tolerance; the node positions and the far
                                                         # test switch contraction off in their own statements
 

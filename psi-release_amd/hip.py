@@ -143,6 +143,9 @@ SIGNATURES = {
     'psi_mesh_cloud_emit': (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_float] + [c_void_p] * 4 + [ctypes.c_longlong] * 2 + [c_void_p] * 5),
     'psi_mesh_cloud_winners': (c_int, [c_void_p] * 3 + [ctypes.c_longlong] + [c_void_p] * 2),
     'psi_mesh_cloud_compact': (c_int, [c_void_p] * 4 + [ctypes.c_longlong] * 2 + [c_void_p] * 3),
+    'psi_flood_fill': (c_int, [c_void_p] + [c_int] * 3 + [c_void_p, c_int] + [c_void_p] * 3),
+    'psi_mesh_orient_votes': (c_int, [c_void_p] * 2 + [ctypes.c_longlong, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 3 + [c_int, c_float]
+                              + [c_void_p] * 2),
 }
 
 

@@ -1284,3 +1284,77 @@ def mesh_cloud(verts, faces, spacing, out=None, return_counts=False):
     if return_counts:
         return points, tri_out, (n_cands, n_rows)
     return points, tri_out
+
+
+# ------------------------------------------------------------------------------------------
+# Orienting a mesh towards free space: flood fill of a node mask and the votes of the triangles (psi_flood_fill, psi_mesh_orient_votes)
+# ------------------------------------------------------------------------------------------
+FLOOD_MIN_EDGE, FLOOD_MAX_EDGE = 2, 1024
+
+
+def flood_fill(open_mask, seed_nodes, return_rounds=False):
+    """The nodes of ``open_mask`` [Dx,Dy,Dz] (bool or uint8 on the GPU, non-zero = open) that are 6-connected through open nodes to one of
+    ``seed_nodes`` [n,3] (ix, iy, iz; a tensor or anything ``torch.as_tensor`` takes): a bool tensor of the same shape (include/psi_hip.h:
+    psi_flood_fill).  With ``return_rounds`` also the number of launches up to and including the first that gained
+    nothing.  ``ValueError``: an edge outside 2 .. 1024, no seed, a seed node outside the grid or on a node that is not open (the message
+    names the seed).  The call synchronises the stream once per 8 launches, and once before them for the seeds' verdict."""
+    import ctypes
+    if not torch.is_tensor(open_mask) or open_mask.dim() != 3 or open_mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError('expected open_mask [Dx,Dy,Dz] bool or uint8')
+    hip.ptr(open_mask)
+    dims = tuple(int(d) for d in open_mask.shape)
+    if min(dims) < FLOOD_MIN_EDGE or max(dims) > FLOOD_MAX_EDGE:
+        raise ValueError('psi_flood_fill: every edge lies in %d .. %d (got %r)' % (FLOOD_MIN_EDGE, FLOOD_MAX_EDGE, dims))
+    dev = open_mask.device
+    seeds = torch.as_tensor(seed_nodes).reshape(-1, 3)
+    if seeds.is_floating_point() or seeds.shape[0] < 1:
+        raise ValueError('expected at least one seed node [n,3] of integers')
+    seeds = seeds.to(dev, torch.int64)
+    mask = open_mask.view(torch.uint8) if open_mask.dtype == torch.bool else open_mask
+    hi = torch.tensor(dims, device=dev)
+    inside = ((seeds >= 0) & (seeds < hi)).all(1)
+    clamped = torch.minimum(seeds.clamp(min=0), hi - 1)
+    is_open = mask[clamped[:, 0], clamped[:, 1], clamped[:, 2]] != 0
+    verdict = torch.stack([inside, is_open], 1).cpu().numpy()                   # the one read before the launches
+    for i, (ins, opn) in enumerate(verdict):
+        if not ins:
+            raise ValueError('seed %d: node %r lies outside the %r grid' % (i, tuple(seeds[i].tolist()), dims))
+        if not opn:
+            raise ValueError('seed %d: node %r is not open' % (i, tuple(seeds[i].tolist())))
+    seeds32 = seeds.to(torch.int32).contiguous()
+    free = torch.empty(dims, dtype=torch.uint8, device=dev)
+    rounds = ctypes.c_int(0)
+    with torch.cuda.device(dev):
+        hip.check(hip.lib().psi_flood_fill(hip.ptr(mask), dims[0], dims[1], dims[2], hip.ptr(seeds32), int(seeds32.shape[0]), hip.ptr(free),
+                                           ctypes.byref(rounds), hip.stream()), 'psi_flood_fill')
+    free = free.view(torch.bool)
+    return (free, rounds.value) if return_rounds else free
+
+
+def mesh_orient_votes(points, tri, verts, faces, free, grid_min, grid_max, delta):
+    """votes [nf,2] int32 on the GPU: per triangle the samples whose probe ``p + delta n`` (column 0) and ``p - delta n`` (column 1) has a
+    free nearest node (include/psi_hip.h: psi_mesh_orient_votes).  points [n,3] fp32 and tri [n] int32 are the
+    samples and their triangles, verts [nv,3] fp32 and faces [nf,3] int32 the caller's mesh, free [D,D,D] bool or uint8 the free nodes of
+    the grid grid_min .. grid_max (host values), all on one GPU."""
+    import math
+    pp, pt, pv, pf = hip.ptr(points), hip.ptr(tri), hip.ptr(verts), hip.ptr(faces)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or tri.dtype != torch.int32 or tri.dim() != 1 \
+            or tri.shape[0] != points.shape[0]:
+        raise ValueError('expected points [n,3] float32 and tri [n] int32')
+    if verts.dtype != torch.float32 or faces.dtype != torch.int32 or verts.dim() != 2 or faces.dim() != 2 or verts.shape[1] != 3 or faces.shape[1] != 3:
+        raise ValueError('expected verts [nv,3] float32 and faces [nf,3] int32')
+    if free.dtype not in (torch.bool, torch.uint8) or free.dim() != 3 or free.shape[0] != free.shape[1] or free.shape[1] != free.shape[2]:
+        raise ValueError('expected free [D,D,D] bool or uint8')
+    if len({t.device for t in (points, tri, verts, faces, free)}) != 1:
+        raise ValueError('the tensors lie on different devices')
+    dim, nv, nf = int(free.shape[0]), int(verts.shape[0]), int(faces.shape[0])
+    delta = float(delta)
+    if dim < FLOOD_MIN_EDGE or dim > FLOOD_MAX_EDGE or nv < 1 or nf < 1 or not (math.isfinite(delta) and delta > 0):
+        raise hip.PsiHipError('psi_mesh_orient_votes: 2 <= D <= 1024, nv >= 1, nf >= 1, delta positive and finite')
+    lo, hi = _mesh_sdf_bounds(grid_min, grid_max)
+    mask = free.view(torch.uint8) if free.dtype == torch.bool else free
+    votes = torch.empty(nf, 2, dtype=torch.int32, device=verts.device)
+    with torch.cuda.device(verts.device):
+        hip.check(hip.lib().psi_mesh_orient_votes(pp, pt, int(points.shape[0]), pv, nv, pf, nf, hip.ptr(mask), lo, hi, dim, delta, hip.ptr(votes),
+                                                  hip.stream()), 'psi_mesh_orient_votes')
+    return votes

@@ -8,6 +8,8 @@ volume" states the contract).
 * ``surface_cloud``    points ON the surface, about one per ``spacing`` cell whatever the tessellation (csrc/mesh_cloud.hip through
                        ``ops.mesh_cloud``): for CAD, synthetic and decimated meshes, whose vertices say little
                        about where their floors and walls are
+* ``orient_faces``     the faces wound so that every triangle faces free space, from one point known to be free (csrc/mesh_orient.hip
+                       through ``ops.flood_fill`` and ``ops.mesh_orient_votes``): for meshes with mixed winding
 * ``scene_from_mesh``  both, as the ``synth.SceneData`` that ``FittingOP(scene=...)``, ``scenes=[...]`` and ``write_prox_layout`` take
 
 Convention: triangles face free space, so free space is positive and solid is negative — what the collision term and
@@ -19,6 +21,7 @@ ambiguous.  ``sign='winding'`` takes the sign from the generalised winding numbe
 from __future__ import annotations
 
 import warnings
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -172,12 +175,13 @@ def grid_box(verts, margin):
 
 
 def scene_from_mesh(verts, faces, dim=256, margin=0.5, voxel=None, contact_parts=None, check_engine=True, device='cuda', sign='pseudonormal',
-                    exterior='solid', beta=3.0, cloud='vertices', spacing=None) -> synth.SceneData:
+                    exterior='solid', beta=3.0, cloud='vertices', spacing=None, orient_seeds=None) -> synth.SceneData:
     """The ``synth.SceneData`` of a scene mesh: ``sdf`` [D,D,D] computed on the GPU over the mesh's box grown by ``margin`` on every side,
     ``verts`` = ``scene_cloud(verts, voxel)``.  ``FittingOP(scene=...)``, ``scenes=[...]`` and ``SceneData.write_prox_layout`` take it as
     is.  The several-scenes engine refuses D % 4 != 0 and D > 480: the same ``ValueError`` is raised here, before any work, unless
     ``check_engine=False``.  ``sign``, ``exterior`` and ``beta`` are those of ``MeshSDF.compute``.  ``cloud='surface'`` with a ``spacing``
-    puts ``surface_cloud(verts, faces, spacing)`` into ``verts`` instead (``voxel`` then is a ``ValueError``: it thins vertices)."""
+    puts ``surface_cloud(verts, faces, spacing)`` into ``verts`` instead (``voxel`` then is a ``ValueError``: it thins vertices).
+    ``orient_seeds`` [n,3], points known to lie in free space: the faces go through ``orient_faces(verts, faces, orient_seeds)`` first."""
     dim = int(dim)
     check_cloud_args(cloud, voxel, spacing)
     if check_engine:
@@ -186,8 +190,171 @@ def scene_from_mesh(verts, faces, dim=256, margin=0.5, voxel=None, contact_parts
         raise ValueError('margin must not be negative')
     if sign not in SIGNS or exterior not in LEVELS:
         raise ValueError("sign is 'pseudonormal' or 'winding', exterior is 'solid' or 'free'")
+    if orient_seeds is not None:
+        faces = orient_faces(verts, faces, orient_seeds, device=device).faces
     mesh = MeshSDF(verts, faces, device=device)
     lo, hi = grid_box(verts, margin)
     sdf = mesh.compute(lo, hi, dim, sign=sign, exterior=exterior, beta=beta).cpu().numpy()
     points = scene_cloud(verts, voxel) if cloud == 'vertices' else surface_cloud(verts, faces, spacing, device=device)
     return synth.SceneData(points, sdf, lo, hi, dim, dict(contact_parts or {}))
+
+
+# ---- orienting a mesh towards free space ----
+DECIDED_BY_VOTE, DECIDED_BY_PROPAGATION, UNDECIDED, ZERO_AREA = 0, 1, -1, -2
+
+
+@dataclass
+class OrientResult:
+    faces: np.ndarray        # the input's dtype and shape; columns 1 and 2 swapped where ``flipped``
+    flipped: np.ndarray      # [nf] bool
+    votes: np.ndarray        # [nf,2] int32: samples whose front / back probe reached a free node
+    decided_by: np.ndarray   # [nf] int8: 0 vote, 1 propagation, -1 undecided, -2 zero area
+    free_nodes: int          # free nodes of the grid
+    rounds: int              # launches of the flood fill up to and including the first that gained nothing
+
+
+def _orient_mesh(verts, faces):
+    as_np = lambda a, dt: np.ascontiguousarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=dt)
+    v, f = as_np(verts, np.float32).reshape(-1, 3), as_np(faces, np.int64).reshape(-1, 3)
+    if len(f) == 0 or len(v) == 0:
+        raise ValueError('empty mesh')
+    if f.min() < 0 or f.max() >= len(v):
+        raise ops.hip.PsiHipError('a face index lies outside [0, nv)')
+    return v, f
+
+
+def _free_space(v, f, seeds, dim, margin, device):
+    """(free [D,D,D] bool on the device, grid_min, grid_max, h fp32, rounds) of a mesh already checked by ``_orient_mesh``."""
+    dim = int(dim)
+    if dim < ops.FLOOD_MIN_EDGE or dim > ops.FLOOD_MAX_EDGE:
+        raise ValueError('dim = %d: an edge of the grid lies in %d .. %d' % (dim, ops.FLOOD_MIN_EDGE, ops.FLOOD_MAX_EDGE))
+    if not margin >= 0:
+        raise ValueError('margin must not be negative')
+    p = np.asarray(seeds, dtype=np.float32).reshape(-1, 3)
+    if len(p) == 0:
+        raise ValueError('at least one seed: a point known to lie in free space')
+    lo, hi = grid_box(v, margin)
+    step = (hi - lo) / np.float32(dim - 1)
+    if not (step > 0).all():
+        raise ValueError('the mesh is flat along an axis: pass a margin')
+    with np.errstate(invalid='ignore'):
+        node = np.rint((p - lo[None]) / step[None])
+    for i in range(len(p)):
+        if not ((node[i] >= 0) & (node[i] <= dim - 1)).all():
+            raise ValueError('seed %d = %r lies outside the grid %r .. %r' % (i, p[i].tolist(), lo.tolist(), hi.tolist()))
+    h = step.max()
+    mesh = MeshSDF(v, f, device=device)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')                            # only the magnitude is used: an open mesh is no concern here
+        U = mesh.compute(lo, hi, dim, sign='pseudonormal').abs_()
+    open_mask = U > float(np.float32(0.5) * h)
+    try:
+        free, rounds = ops.flood_fill(open_mask, node.astype(np.int64), return_rounds=True)
+    except ValueError as e:
+        msg = str(e)
+        if 'is not open' in msg:
+            i = int(msg.split()[1].rstrip(':'))
+            raise ValueError('seed %d = %r lies on a node that is not open: within %g of the surface' % (i, p[i].tolist(), 0.5 * h)) from None
+        raise
+    return free, lo, hi, h, rounds
+
+
+def free_space(verts, faces, seeds, dim=128, margin=0.0, device='cuda'):
+    """(free [D,D,D] bool on the device, grid_min, grid_max): the nodes of the grid ``grid_box(verts, margin)`` with ``dim`` nodes per axis
+    that a point could reach from one of ``seeds`` [n,3] without coming within half a node spacing of the surface.
+    ``ValueError``: a seed outside the grid or on a node that is not open (the message names it), ``dim`` outside 2 .. 1024."""
+    v, f = _orient_mesh(verts, faces)
+    free, lo, hi, _, _ = _free_space(v, f, seeds, dim, margin, device)
+    return free, lo, hi
+
+
+def _edge_pairs(v, f, with_area):
+    """(t, u, consistent) of every ordered pair of triangles with area that share an edge no third one uses; positions identify vertices."""
+    _, inv = np.unique((v + np.float32(0.0)).view(np.uint32).reshape(-1, 3), axis=0, return_inverse=True)
+    tri = np.nonzero(with_area)[0]
+    W = inv.reshape(-1)[f[tri]]
+    a, b = W.reshape(-1), np.roll(W, -1, axis=1).reshape(-1)        # edge k of a triangle runs from corner k to corner k + 1
+    t = np.repeat(tri, 3)
+    key = np.minimum(a, b) * (int(W.max()) + 1) + np.maximum(a, b)
+    order = np.argsort(key, kind='stable')
+    key, t, fwd = key[order], t[order], (a < b)[order]
+    start = np.nonzero(np.r_[True, key[1:] != key[:-1]])[0]
+    count = np.diff(np.r_[start, len(key)])
+    i = start[count == 2]
+    i = i[t[i] != t[i + 1]]
+    same = fwd[i] != fwd[i + 1]                                    # opposite directions along the edge: consistently wound
+    return np.r_[t[i], t[i + 1]], np.r_[t[i + 1], t[i]], np.r_[same, same]
+
+
+def _propagate(v, f, flip, by):
+    t, u, same = _edge_pairs(v, f, by != ZERO_AREA)
+    flip, by = flip.copy(), by.copy()
+    level = by == DECIDED_BY_VOTE
+    while level.any():
+        k = np.nonzero(level[t] & (by[u] == UNDECIDED))[0]
+        if not len(k):
+            break
+        k = k[np.lexsort((t[k], u[k]))]                             # per undecided triangle its neighbours of this level, lowest index first
+        k = k[np.r_[True, u[k][1:] != u[k][:-1]]]
+        flip[u[k]] = np.where(same[k], flip[t[k]], ~flip[t[k]])
+        by[u[k]] = DECIDED_BY_PROPAGATION
+        level = np.zeros(len(by), bool)
+        level[u[k]] = True
+    return flip, by
+
+
+def _with_area(v, f):
+    """[nf] bool: the fp32 length of (b - a) x (c - a), with the association of csrc/mesh_orient.hip, is > 0."""
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    e1, e2 = b - a, c - a
+    cr = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2], e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
+    with np.errstate(over='ignore', invalid='ignore'):
+        return np.sqrt((cr[:, 0] * cr[:, 0] + cr[:, 1] * cr[:, 1]) + cr[:, 2] * cr[:, 2]) > 0
+
+
+def orient_samples(verts, faces, h, device='cuda'):
+    """(points [n,3] fp32, tri [n] int32) on the device: where ``orient_faces`` probes a mesh at node spacing ``h``.  The centroid
+    ((a + b) + c) / 3 of every triangle with area, then ``surface_cloud_device(verts, faces, spacing=h)``: a floor of two triangles is
+    probed everywhere, not once."""
+    dev = torch.device(device)
+    v, f = _orient_mesh(verts, faces)
+    with_area = _with_area(v, f)
+    centre = (((v[f[:, 0]] + v[f[:, 1]]) + v[f[:, 2]]) / np.float32(3))[with_area]
+    cloud_p, cloud_t = surface_cloud_device(torch.from_numpy(v).to(dev), torch.from_numpy(f.astype(np.int32)).to(dev), float(h), device=dev)
+    return (torch.cat([torch.from_numpy(centre).to(dev), cloud_p]).contiguous(),
+            torch.cat([torch.from_numpy(np.nonzero(with_area)[0].astype(np.int32)).to(dev), cloud_t]).contiguous())
+
+
+def orient_faces(verts, faces, seeds, dim=128, margin=0.0, ratio=4, propagate=True, device='cuda') -> OrientResult:
+    """The faces with every triangle wound so that its normal (b - a) x (c - a) points into free space, given ``seeds`` [n,3]: points known
+    to be free (one is enough).  The rule is DESIGN.md section 10c: nodes farther than half a spacing from the surface are open, the open
+    nodes connected to a seed are free (``free_space``), every triangle is probed 1.5 spacings in front of and behind its centroid and
+    its ``surface_cloud`` samples, and a side wins with ``ratio`` times the votes of the other; triangles the votes leave undecided take
+    their orientation from decided neighbours across edges shared by exactly two triangles (``propagate``).  What is still undecided, and
+    triangles without area, stay as they are and are counted in ``decided_by``.  Bit-identical from run to run."""
+    if not ratio >= 1:
+        raise ValueError('ratio must be at least 1')
+    dev = torch.device(device)
+    v, f = _orient_mesh(verts, faces)
+    free, lo, hi, h, rounds = _free_space(v, f, seeds, dim, margin, dev)
+    with_area = _with_area(v, f)
+    if not with_area.any():
+        raise ValueError('no triangle with area')
+    dv, df = torch.from_numpy(v).to(dev), torch.from_numpy(f.astype(np.int32)).to(dev)
+    points, tri = orient_samples(v, f, h, device=dev)
+    votes = ops.mesh_orient_votes(points, tri, dv, df, free, lo, hi, float(np.float32(1.5) * h)).cpu().numpy()
+    F, B = votes[:, 0].astype(np.int64), votes[:, 1].astype(np.int64)
+    keep = (F > 0) & (F >= ratio * B)
+    flip = (B > 0) & (B >= ratio * F) & ~keep
+    by = np.full(len(f), UNDECIDED, np.int8)
+    by[keep | flip] = DECIDED_BY_VOTE
+    by[~with_area] = ZERO_AREA
+    flip &= with_area
+    if propagate:
+        flip, by = _propagate(v, f, flip, by)
+    flip &= by >= 0
+    src = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
+    out = np.array(src, copy=True)
+    rows = out.reshape(-1, 3)
+    rows[flip] = rows[flip][:, [0, 2, 1]]
+    return OrientResult(out, flip, votes, by, int(free.sum().item()), int(rounds))

@@ -446,3 +446,15 @@ def make_open_room(subdiv: int = 2, drop_ceiling: bool = True, sink: float = 0.0
     if drop_ceiling:                                             # the sixth face of the room box: axis 2, upper side
         faces = np.ascontiguousarray(np.concatenate([faces[:5 * nt], faces[6 * nt:]]))
     return OrientedRoom(verts, faces, room.box_min, room.box_max, [moved] + list(room.boxes[1:]))
+
+
+def flip_faces(faces, fraction: float, seed: int = 0):
+    """(faces, mask): a copy of ``faces`` [nf,3] with columns 1 and 2 swapped in a seeded subset of round(fraction * nf) triangles (their
+    normals reversed), and the bool mask [nf] of that subset: a mesh with mixed winding, the input of ``scene_sdf.orient_faces``."""
+    f = np.array(faces, copy=True).reshape(-1, 3)
+    if not 0.0 <= fraction <= 1.0:
+        raise ValueError('fraction lies in [0, 1]')
+    mask = np.zeros(len(f), bool)
+    mask[np.random.RandomState(seed).permutation(len(f))[:int(round(fraction * len(f)))]] = True
+    f[mask] = f[mask][:, [0, 2, 1]]
+    return f, mask
