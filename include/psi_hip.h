@@ -278,7 +278,7 @@ int psi_stream_wait(void *stream, int timeout_ms);
  * optimisation by n_rep steps.  h_names: [max_stages][name_stride] chars, h_ms: [max_stages] milliseconds. */
 int psi_fit_profile(psi_fit_engine *engine, int n_rep, char *h_names, int name_stride, float *h_ms, int max_stages,
                     int *h_n_stages, void *stream);
-/* Test/diagnostic copy of an engine-owned device buffer by name ("verts" [B,V,3], "g_verts", "pose" [B,165],
+/* Test/diagnostic copy of an engine-owned device buffer by name ("verts" [B,V,3], "pose" [B,165],
  * "g_pose", "g_rot" [B,55,9], "stats" [8], "adam_m"/"adam_v" [B,75]; the backward's intermediates "gA" [B,64,16], "gfeat" [B,Kpad],
  * "g_transl" [B,3], "gl" / "g_vp" / "v_posed" [B,Npad], and — engines whose per-vertex backward runs inside the scene launch — the
  * contact class of rows "glc" / "gvpc" / "vpc" [B,3 ncp] in slot order, and "penmask" [B][Vpad/64] 64-bit words = 2 floats' worth of bits

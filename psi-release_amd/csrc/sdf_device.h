@@ -13,13 +13,18 @@ struct PsiAxis {
 
 __device__ __forceinline__ PsiAxis psi_axis_setup(float v, float mn, float mx, int D, int align_corners)
 {
-    float nrm = (v - mn) / (mx - mn) * 2.0f - 1.0f;     // fitting_proxe.py:147, in this operation order
+    // Which products are fused into the following add is WRITTEN here and in psi_trilinear, not left to the compiler: the function is
+    // inlined into several kernels (the operator, the fitting engine's plain-volume arm, the evaluation), and with the default
+    // contraction each of them got its own choice — the engine's rows differed from the operator's in the last bits on the same inputs
+    // (tests/test_sdf_lookup_gpu.py::test_plain_volume_arms).  The choices are those the operator's kernel was compiled to.
+#pragma clang fp contract(off)
+    float nrm = __builtin_fmaf((v - mn) / (mx - mn), 2.0f, -1.0f);     // fitting_proxe.py:147, in this operation order (the doubling is exact)
     float u, scale;
     if (align_corners) {
         u = (nrm + 1.0f) / 2.0f * (float)(D - 1);
         scale = (float)(D - 1) / 2.0f;
     } else {
-        u = ((nrm + 1.0f) * (float)D - 1.0f) / 2.0f;
+        u = __builtin_fmaf(nrm + 1.0f, (float)D, -1.0f) / 2.0f;
         scale = (float)D / 2.0f;
     }
     float g = scale;                                    // border: clip to [0, D-1], clipped coordinate has zero gradient
@@ -39,6 +44,7 @@ __device__ __forceinline__ float psi_trilinear(const float *__restrict__ vol, co
                                                const float *__restrict__ gmax, float x, float y, float z, int D,
                                                int align_corners, float *grad)
 {
+#pragma clang fp contract(off)
     PsiAxis ax = psi_axis_setup(x, gmin[0], gmax[0], D, align_corners);
     PsiAxis ay = psi_axis_setup(y, gmin[1], gmax[1], D, align_corners);
     PsiAxis az = psi_axis_setup(z, gmin[2], gmax[2], D, align_corners);
@@ -58,14 +64,15 @@ __device__ __forceinline__ float psi_trilinear(const float *__restrict__ vol, co
     const float wx1 = ax.w1, wx0 = 1.0f - ax.w1;
     const float wy1 = ay.w1, wy0 = 1.0f - ay.w1;
     const float wz1 = az.w1, wz0 = 1.0f - az.w1;
-    float c00 = c000 * wz0 + c001 * wz1, c01 = c010 * wz0 + c011 * wz1;
-    float c10 = c100 * wz0 + c101 * wz1, c11 = c110 * wz0 + c111 * wz1;
-    float c0 = c00 * wy0 + c01 * wy1, c1 = c10 * wy0 + c11 * wy1;
+    // (see psi_axis_setup: one product of each pair is rounded, the other fused into the sum; the last stage rounds both)
+    float c00 = __builtin_fmaf(c001, wz1, c000 * wz0), c01 = __builtin_fmaf(c011, wz1, c010 * wz0);
+    float c10 = __builtin_fmaf(c101, wz1, c100 * wz0), c11 = __builtin_fmaf(c111, wz1, c110 * wz0);
+    float c0 = __builtin_fmaf(c00, wy0, c01 * wy1), c1 = __builtin_fmaf(c10, wy0, c11 * wy1);
     if (grad) {
         float gx = c1 - c0;
         float gy = (c01 - c00) * wx0 + (c11 - c10) * wx1;
         float d00 = c001 - c000, d01 = c011 - c010, d10 = c101 - c100, d11 = c111 - c110;
-        float gz = (d00 * wy0 + d01 * wy1) * wx0 + (d10 * wy0 + d11 * wy1) * wx1;
+        float gz = __builtin_fmaf(d00, wy0, d01 * wy1) * wx0 + __builtin_fmaf(d10, wy0, d11 * wy1) * wx1;
         grad[0] = gx * ax.du;
         grad[1] = gy * ay.du;
         grad[2] = gz * az.du;
