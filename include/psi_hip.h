@@ -281,9 +281,10 @@ int psi_fit_profile(psi_fit_engine *engine, int n_rep, char *h_names, int name_s
 /* Test/diagnostic copy of an engine-owned device buffer by name ("verts" [B,V,3], "pose" [B,165],
  * "g_pose", "g_rot" [B,55,9], "stats" [8], "adam_m"/"adam_v" [B,75]; the backward's intermediates "gA" [B,64,16], "gfeat" [B,Kpad],
  * "g_transl" [B,3], "gl" / "g_vp" / "v_posed" [B,Npad], and — engines whose per-vertex backward runs inside the scene launch — the
- * contact class of rows "glc" / "gvpc" / "vpc" [B,3 ncp] in slot order, and "penmask" [B][Vpad/64] 64-bit words = 2 floats' worth of bits
+ * contact class of rows "glc" / "gvpc" / "vpc" [B,3 ncp] in slot order (ncp = n_contact rounded up to 256), "spb" [B] (independent
+ * bodies: each body's penetration factor -w_collision / N_b), and "penmask" [B][Vpad/64] 64-bit words = 2 floats' worth of bits
  * each, Vpad = V rounded up to 256: bit v % 64 of word v / 64 is set when vertex v of the body had sdf < 0 in the last forward, i.e. when
- * its rows of "gl" / "g_vp" may be non-zero) into d_out (device). */
+ * its rows of "gl" / "g_vp" may be non-zero) into d_out (device).  n_floats above a buffer's size, or an unknown name: PSI_EINVAL. */
 int psi_fit_copy_buffer(psi_fit_engine *engine, const char *name, float *d_out, long n_floats, void *stream);
 
 /* ---------------------------------------------------------------------------------------------

@@ -3,25 +3,35 @@
 //                                                                                        source/fitting_proxe.py:101-162,177-189
 // as a fixed sequence of HIP kernels with a hand-derived backward, replayable as a hipGraph (no host sync, no autograd).
 //
-// Seven launches per iteration (single process, B <= 128: skin_fwd<SdfPen> and kd_query<CONTACT> share ONE launch, fwd_scene_kernel,
-// in which the NN-search workgroups skin their own contact vertices; eight launches above that):
+// Six launches per iteration by default (single process, kd-tree search, B <= 128: FitModes::fused_bwd):
 //   head_fwd          per body: L1 / latent-prior partial sums (fitting_proxe.py:105-110); convert_to_3D_rot (cvae.py:128-137);
 //                     VPoser.decode 32->512->512->126 -> 21 x (6D -> R -> angle-axis) (vposer_smpl.py:107-121,152-161);
 //                     SMPL-X hand PCA + pose_mean (smplx 0.1.13 forward); then the LBS pose stage of the
 //                     body (Rodrigues, joints, kinematic chain: lbs_device.h)
 //   blend_fwd         v_posed = v_t + feat @ dirs (MFMA)                                  (lbs.hip)
-//   skin_fwd<SdfPen>  skinning incl. cam_ext, with the trilinear SDF lookup + analytic gradient + penetration partial sums
-//                     as its per-vertex epilogue (fitting_proxe.py:144-158)               (lbs_device.h template)
-//   kd_query<CONTACT> exact NN of the gathered contact vertices + contact-loss epilogue   (nnindex.hip; fitting_proxe.py:131-139;
-//                     nn_mode 0: the brute-force kernels of chamfer.hip)
-//   skin_bwd_v<Grad>  prologue: statistics stats[6] = [sum|dx|, sum z^2, sum f, sum|sdf-|, N, 0] and d loss / d verts =
-//                     penetration part (needs the GLOBAL count N) + contact part, built on the fly; then the skinning backward
-//   bwd_joint         skin_bwd_A and blend_bwd (both MFMA) as one heterogeneous grid       (lbs.hip)
-//   reduce_partials   sums of the split-contraction partials                               (lbs.hip)
+//   fwd_scene         ONE launch for both scene terms and the per-vertex backward.  Skinning workgroups: skinning incl. cam_ext, with the
+//                     trilinear SDF lookup + analytic gradient + penetration partial sums as the per-vertex epilogue
+//                     (fitting_proxe.py:144-158; skin_fwd<SdfPen>, lbs_device.h template), and the skinning backward of the penetration
+//                     rows, UNSCALED (the global count N is not known yet), with the iteration's penetration mask.  Search workgroups:
+//                     they skin their own contact vertices, exact NN + contact-loss epilogue (kd_query<CONTACT>, nnindex_device.h;
+//                     fitting_proxe.py:131-139), and the skinning backward of the contact rows, in slot order
+//   fit_bwd_joint     skin_bwd_A and blend_bwd (both MFMA) over both classes of rows — the model's vertices and the contact slots — as one
+//                     heterogeneous grid (plans: ska_plan.h), plus one statistics workgroup: stats[6] = [sum|dx|, sum z^2, sum f,
+//                     sum|sdf-|, N, 0]
+//   fit_reduce        sums of the split-contraction partials of both classes, combined as (-w_col / N) * penetration + contact
 //   head_bwd_adam     per body: LBS pose backward, Gram-Schmidt / VPoser-MLP / hand-PCA backward, + L1 and prior gradients,
 //                     Adam update (torch.optim.Adam defaults)
-// Data-parallel runs add loss_finalize after kd_query, all-reduce `stats` there (one 6-float RCCL all-reduce per iteration)
-// and skin_bwd_v reads the reduced values.  psi_fit_decode_forward/backward drive the head / LBS kernels alone (training).
+// Seven launches without the fused backward (PSI_FIT_FUSED_BWD=0, or no column slice left for the contact class: fit_decide): fwd_scene
+// only goes forward, and between it and the joint contractions runs
+//   skin_bwd_v<Grad>  prologue: the statistics, and d loss / d verts = penetration part (needs the GLOBAL count N) + contact part, built
+//                     on the fly; then the skinning backward
+// followed by bwd_joint and reduce_partials of lbs.hip over the model's rows alone.
+// Eight launches at B > 128 (or PSI_SPLIT_SCENE=1, or nn_mode 0: the brute-force search of chamfer.hip): the two scene terms are
+// throughput-bound there and run as skin_fwd_sdf and kd_query<CONTACT>, two launches in fwd_scene's place; the backward is the seven-launch
+// arm's, with loss_finalize in front of it from B = 128 on (fit_stats_source).
+// Data-parallel runs all-reduce `stats` (one 6-float RCCL all-reduce per iteration) where it is complete and not yet read: behind
+// fit_bwd_joint on a fused engine, whose fit_reduce reads the reduced values; on the other arms behind loss_finalize, which then ends the
+// forward, with skin_bwd_v reading them.  psi_fit_decode_forward/backward drive the head / LBS kernels alone (training).
 //
 // Gradient through "6D -> R -> angle-axis -> Rodrigues -> R'": the forward evaluates the reference's chain literally;
 // the backward uses that R' == R on SO(3) and that Gram-Schmidt only moves along SO(3), so J_GS^T dL/dR' is the exact
@@ -1594,7 +1604,8 @@ __global__ void adam_reset_kernel(float *m, float *v, int *step, int n)
 #endif
 constexpr int GRAPH_UNROLL = PSI_GRAPH_UNROLL;
 
-// ---- host-only state of an engine: development switches, launch plan, graph caches.  Plain data: the engine is zero-filled on allocation.
+// ---- host-only state of an engine: development switches, mode decisions, the blob's table, launch plan, graph caches.  Plain data but for
+// the table's vector: the engine is value-initialised (all zero) on allocation.
 // Every development switch of the engine, read ONCE per engine at psi_fit_create (README, "Environment knobs"); a value that is not
 // accepted leaves the default (0 in the int fields)
 struct FitKnobs {
@@ -1629,6 +1640,80 @@ static FitKnobs fit_read_knobs()
 #endif
     return k;
 }
+
+// The mode decisions of an engine, taken in ONE place (fit_decide, at psi_fit_create) before any buffer is sized
+struct FitModes {
+    bool self_skin;               // the NN search can skin its own contact vertices (ContactSkinSrc): it does not read `verts`
+    bool merged_scene;            // skinning + SDF and the NN search in one launch (kd-tree mode, J <= 56, 4 lanes per query)
+    bool keep_verts;              // the forward skinning kernel stores the camera-frame vertices (only needed when !self_skin)
+    bool fused_bwd;               // the skinning backward rides on fwd_scene (see fit_bwd_joint_kernel): six launches per iteration, no per-vertex backward launch
+    int skin_nb;                  // bodies per workgroup of the forward skinning + SDF kernel (1 or 2: lbs_device.h)
+    int hc;                       // workgroups per body in the head / tail kernels (FitDev::hc)
+    int gv_sps;                   // slots per body and class of the rows' maxima (FitDev::gv_sps)
+    PsiStreamSplit split;         // column slices of the stream workgroups of fit_bwd_joint_kernel per row class, steps per slice (ska_plan.h)
+};
+
+// ncp3: the columns of the contact class (3 x n_c padded to whole 256-slot slices); mc: the model's counts at cfg->B (psi_lbs_counts)
+static FitModes fit_decide(const psi_fit_config *cfg, const FitKnobs &knobs, int J, int ncp3, const PsiLbsCounts &mc)
+{
+    FitModes d = {};
+    // one launch for both scene terms up to B = 128 (measured: 0.1695 -> 0.1611 ms per iteration at B = 32, 0.2342 -> 0.2258 at 64, 0.3957 ->
+    // 0.3922 at 128; at 256 and above both parts are throughput-bound and the shared launch is 1-2 % slower); PSI_SPLIT_SCENE=1: two launches.
+    // (Round 3 also tried the opposite arrangement — no search workgroups at all, every skinning workgroup answering the contact queries of
+    // its own 256 vertices from LDS after the SDF lookup: 1312 workgroups = one occupancy round instead of two, no second skinning of the
+    // query vertices.  It measured 42 us against 33: the search became a serial tail of every workgroup instead of running beside them.)
+    d.self_skin = cfg->nn_mode == 1 && J <= PSI_JP - 8 && psikd::LPQ == 4;      // the search lanes can skin their own contact vertex
+    d.merged_scene = d.self_skin && cfg->B <= 128 && !knobs.split_scene;
+    // the vertices themselves are an output nobody reads when the search skins its own queries (the shared launch): not stored there
+    // (psi_fit_copy_buffer("verts") produces them on demand); with separate launches the search reads its contact rows, which are the
+    // only ones stored (fit_forward); PSI_KEEP_VERTS=1 stores all of them in every iteration
+    d.keep_verts = !d.merged_scene || knobs.keep_verts;
+    // workgroups per body in the head / tail kernels: enough to put ~256 workgroups on the chip, none once the bodies alone do
+    const long bodies = (long)cfg->B * (cfg->concurrent_engines > 1 ? cfg->concurrent_engines : 1);
+    d.hc = bodies <= 32 ? 8 : bodies <= 64 ? 4 : bodies <= 128 ? 2 : 1;
+    if (knobs.head_cluster) d.hc = knobs.head_cluster;
+    // per-body slots of the rows' maxima: up to 16 per body (a body's rows come from one skinning workgroup per 256 vertices and a few
+    // search workgroups: a few producers per address, where one address for a whole class cost 6 us), all inside the class's PSI_GV_SLOTS
+    d.gv_sps = 16;
+    while (d.gv_sps > 1 && (long)d.gv_sps * cfg->B > PSI_GV_SLOTS) d.gv_sps >>= 1;
+    // column slices of the stream workgroups, split between the two classes so that the LONGEST slice is as short as possible (the rule and
+    // its reason: ska_plan.h)
+    d.split = psi_stream_split(mc.Npad / 16, ncp3 / 16, mc.nsn);
+    // the contact slots as a second class of rows of the joint-side contractions — unless the split leaves that class no column slice
+    d.fused_bwd = d.merged_scene && !knobs.no_fused_bwd && d.split.nsn_c > 0;
+    // two bodies per skinning workgroup share one pass over the vertex's weight row: from the batch size at which the kernel is
+    // throughput-bound (its own launch, B > 128); PSI_SKIN_NB=1|2 overrides
+    // (compressed rows are read once per lane either way and measured 2-3 % slower with two bodies: 114.7 vs 112.3 us at B = 512)
+    d.skin_nb = cfg->B > 128 && !mc.compressed_weights ? 2 : 1;
+    if (knobs.skin_nb) d.skin_nb = knobs.skin_nb;
+    return d;
+}
+
+// The engine's blob: one device allocation for every buffer the engine owns.  A buffer is declared ONCE (fit_create) — the pointer field it
+// binds, its size, how it starts, and the name under which psi_fit_copy_buffer exposes it — and takes the next 256-byte-aligned offset.
+// After the allocation one loop binds the fields and does the uploads and the fills (fit_create); psi_fit_copy_buffer looks names and
+// capacities up here.
+struct FitBuf {
+    void *field;                  // address of the pointer field (of FitDev or of the engine) that points at the buffer
+    size_t off, bytes;
+    const void *src;              // uploaded from this host array (only until fit_create has done so); nullptr: filled
+    int fill;                     // byte the buffer starts as when it is not uploaded: 0, or 0xff
+    const char *name;             // psi_fit_copy_buffer's name for it, capacity bytes / 4 floats; nullptr: not exposed
+};
+struct FitBlob {
+    std::vector<FitBuf> bufs;
+    size_t size;                  // bytes declared so far
+    size_t zero_begin;            // the constants end here; everything behind is zeroed in one go before the other fills
+    template <class T>
+    void add(T *&field, size_t bytes, const void *src, int fill, const char *name)
+    {
+        bufs.push_back({&field, size, bytes, src, fill, name});
+        size += (bytes + 255) & ~(size_t)255;
+    }
+    template <class T> void upload(T *&field, const void *src, size_t bytes) { add(field, bytes, src, 0, nullptr); }
+    template <class T> void zero(T *&field, size_t bytes, const char *name = nullptr) { add(field, bytes, nullptr, 0, name); }
+    template <class T> void ones(T *&field, size_t bytes) { add(field, bytes, nullptr, 0xff, nullptr); }
+};
 
 // Launch geometry of fit_bwd_joint_kernel: fixed by the model and the batch size, so derived once (fit_plan_make, at psi_fit_create)
 struct FitPlan {
@@ -1758,14 +1843,11 @@ struct psi_fit_engine {
     PsiLbsView lv;                // pointers into lbs_ws for the pose stages fused into the head / tail kernels
     void *nn_ws;
     char *blob;
+    FitBlob table;                // what the blob holds (the declarations of fit_create)
     float *stats_local;           // engine-owned stats buffer (single-GPU path)
     FitKnobs knobs;
+    FitModes mode;
     FitPlan plan;
-    bool merged_scene;            // skinning + SDF and the NN search in one launch (kd-tree mode, J <= 56, 4 lanes per query)
-    bool self_skin;               // the NN search can skin its own contact vertices (ContactSkinSrc): it does not read `verts`
-    bool keep_verts;              // the forward skinning kernel stores the camera-frame vertices (only needed when !self_skin)
-    bool fused_bwd;               // the skinning backward rides on fwd_scene (see fit_bwd_joint_kernel): six launches per iteration, no per-vertex backward launch
-    int skin_nb;                  // bodies per workgroup of the forward skinning + SDF kernel (1 or 2: lbs_device.h)
     // ---- several scenes (psi_fit_create_scenes; all null / 0 in a psi_fit_create engine): per scene slot an NN index and a re-ordered copy of
     // the volume, both owned by the engine; their device descriptors as tables indexed by slot; the bodies' slots.  nn_index is scene 0's.
     int n_scenes;                 // 0: a psi_fit_create engine (one scene, the single-scene kernels)
@@ -1828,7 +1910,7 @@ enum class FitStats {
 //   psi_fit_backward_step                                 Caller     Caller       Caller                 Caller
 static inline FitStats fit_stats_source(const psi_fit_engine *e, FitStats wish)
 {
-    return wish == FitStats::Backward && !e->fused_bwd && e->d.B >= PSI_SKIN_MB_MIN_B ? FitStats::Finalize : wish;
+    return wish == FitStats::Backward && !e->mode.fused_bwd && e->d.B >= PSI_SKIN_MB_MIN_B ? FitStats::Finalize : wish;
 }
 
 static int fit_launch_stats(psi_fit_engine *e, float *stats, hipStream_t st)
@@ -1848,8 +1930,8 @@ static void launch_fwd_scene(const psi_fit_engine *e, float gscale, hipStream_t 
     const int nqb = f.nfp, n_kd = nqb * f.B, skin_first = e->knobs.scene_skin_first ? 1 : 0;
     const dim3 grid(n_kd + f.nsdfblk * psi_cdiv(f.B, NB));
     FitDev fk = f;
-    if (!e->keep_verts) fk.verts = nullptr;
-    const auto epi = make_sdf_epilogue<SCENES>(f, e->grid, false, e->fused_bwd ? &e->lv : nullptr, e->d_grid_tab, e->d_slot);
+    if (!e->mode.keep_verts) fk.verts = nullptr;
+    const auto epi = make_sdf_epilogue<SCENES>(f, e->grid, false, e->mode.fused_bwd ? &e->lv : nullptr, e->d_grid_tab, e->d_slot);
     SceneTrees<SCENES> T;
     int rows;                                                    // traversal stack of the search (its LDS): the tree's, or the largest of the set
     if constexpr (SCENES) {
@@ -1877,7 +1959,7 @@ static void fit_scene_dispatch(const psi_fit_engine *e, L &&launch)
 {
     using One = std::integral_constant<int, 1>;
     using Two = std::integral_constant<int, 2>;
-    switch ((e->n_scenes ? 2 : 0) | (e->skin_nb == 2 ? 1 : 0)) {
+    switch ((e->n_scenes ? 2 : 0) | (e->mode.skin_nb == 2 ? 1 : 0)) {
     case 0: launch(One{}, std::false_type{}); break;
     case 1: launch(Two{}, std::false_type{}); break;
     case 2: launch(One{}, std::true_type{}); break;
@@ -1894,7 +1976,7 @@ static int fit_forward(psi_fit_engine *e, float *stats, hipStream_t st, FitStats
     int rc = psi_lbs_blend_forward(e->lbs, f.B, e->lbs_ws, st);
     if (rc) return rc;
     float gscale = f.w_contact / ((f.indep ? 1.0f : (float)f.B * (float)f.world) * (float)f.n_c);
-    if (e->nn_index && e->merged_scene) {
+    if (e->nn_index && e->mode.merged_scene) {
         // skinning + SDF and the NN search of the contact vertices as ONE launch (fwd_scene_kernel)
         fit_scene_dispatch(e, [&](auto nb, auto scenes) { launch_fwd_scene<decltype(nb)::value, decltype(scenes)::value>(e, gscale, st); });
         PSI_CHECK_LAUNCH("fwd_scene_kernel");
@@ -1966,7 +2048,7 @@ static int fit_backward_tail(psi_fit_engine *e, float *stats, hipStream_t st)
 static int fit_backward(psi_fit_engine *e, float *stats, hipStream_t st, FitStats who)
 {
     FitDev &f = e->d;
-    if (e->fused_bwd) {
+    if (e->mode.fused_bwd) {
         int rc = fit_backward_joint(e, stats, st, who);
         return rc ? rc : fit_backward_tail(e, stats, st);
     }
@@ -2000,6 +2082,13 @@ static int fit_backward(psi_fit_engine *e, float *stats, hipStream_t st, FitStat
 }
 
 static int fit_build_scenes(psi_fit_engine *e, const psi_fit_scene *h_scenes, int S);
+
+// sizes of the buffers that are also copied or refilled after creation, for their declarations (fit_create) and those calls alike
+static inline size_t fit_x_bytes(const FitDev &f) { return (size_t)f.B * XD * 4; }               // x, xhr and the Adam moments: [B][75]
+static inline size_t fit_cam_bytes(const FitDev &f) { return (size_t)f.B * 16 * 4; }             // cam: [B][4][4]
+static inline size_t fit_hint_bytes(const FitDev &f) { return (size_t)f.B * f.n_c * 4; }         // nn_hint: [B][n_c]
+// no warm start for the next search: -1 in every hint
+static inline hipError_t fit_hints_reset(const FitDev &f, hipStream_t st) { return hipMemsetAsync(f.nn_hint, 0xff, fit_hint_bytes(f), st); }
 
 // the engine's cell-major copy of a [D][D][D] volume (sdf_device.h; psi_sdf_cells_fit(D) holds): its size, and the one-off re-layout into it
 // (NULL stream: the caller synchronises)
@@ -2036,8 +2125,9 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     PSI_REQUIRE(!(cfg->independent_bodies && cfg->world_size > 1), "independent bodies have no cross-rank coupling: use world_size 1");
     for (int i = 0; i < 66; i++) PSI_REQUIRE(h_pose_mean[i] == 0.0f, "pose_mean must be zero for global_orient/body joints");
     for (int i = 0; i < cfg->n_contact; i++) PSI_REQUIRE(h_contact_ids[i] >= 0 && h_contact_ids[i] < V, "contact id out of range");
-    psi_fit_engine *e = new psi_fit_engine;
-    memset(e, 0, sizeof(*e));
+    PsiLbsCounts mc;
+    if (int rcv = psi_lbs_counts(lbs, cfg->B, &mc)) return rcv;
+    psi_fit_engine *e = new psi_fit_engine();
     // the one way out of every failure below: psi_fit_destroy copes with each partially built engine (no blob yet; blob but no NN index)
     // and sets no error message of its own, so the caller reads the failing call's
     std::unique_ptr<psi_fit_engine, void (*)(psi_fit_engine *)> owner(e, psi_fit_destroy);
@@ -2055,37 +2145,31 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     f.beta2_d = cfg->beta2_d != 0.0 ? cfg->beta2_d : (double)cfg->beta2;
     f.one_m_beta1 = (float)(1.0 - f.beta1_d);
     f.one_m_beta2 = (float)(1.0 - f.beta2_d);
-    // one launch for both scene terms up to B = 128 (measured: 0.1695 -> 0.1611 ms per iteration at B = 32, 0.2342 -> 0.2258 at 64, 0.3957 ->
-    // 0.3922 at 128; at 256 and above both parts are throughput-bound and the shared launch is 1-2 % slower); PSI_SPLIT_SCENE=1: two launches.
-    // (Round 3 also tried the opposite arrangement — no search workgroups at all, every skinning workgroup answering the contact queries of
-    // its own 256 vertices from LDS after the SDF lookup: 1312 workgroups = one occupancy round instead of two, no second skinning of the
-    // query vertices.  It measured 42 us against 33: the search became a serial tail of every workgroup instead of running beside them.)
-    e->self_skin = cfg->nn_mode == 1 && J <= PSI_JP - 8 && psikd::LPQ == 4;      // the search lanes can skin their own contact vertex
-    e->merged_scene = e->self_skin && cfg->B <= 128 && !knobs.split_scene;
-    // the vertices themselves are an output nobody reads when the search skins its own queries (the shared launch): not stored there
-    // (psi_fit_copy_buffer("verts") produces them on demand); with separate launches the search reads its contact rows, which are the
-    // only ones stored (fit_forward); PSI_KEEP_VERTS=1 stores all of them in every iteration
-    e->keep_verts = !e->merged_scene || knobs.keep_verts;
     f.nsdfblk = psi_cdiv(V, 256);
     f.Vpad = f.nsdfblk * 256;
     f.nfp = cfg->nn_mode == 1 ? psi_nn_index_fparts(f.n_c) : psi_nn_contact_fparts(f.n_c);
     f.max_hist = cfg->max_history > 0 ? cfg->max_history : 1024;
-    // workgroups per body in the head / tail kernels: enough to put ~256 workgroups on the chip, none once the bodies alone do
-    {
-        const long bodies = (long)cfg->B * (cfg->concurrent_engines > 1 ? cfg->concurrent_engines : 1);
-        f.hc = bodies <= 32 ? 8 : bodies <= 64 ? 4 : bodies <= 128 ? 2 : 1;
-    }
+    f.ncp = psi_cdiv(f.n_c, 256) * 256;
+    f.ncp3 = 3 * f.ncp;
+    f.nsv = mc.nsv;
+    f.nsv_c = f.ncp / 256;
+    f.scene = d_scene_verts;
+    f.sdf = d_sdf;
+    // ---- the decisions, and their copies where the kernels read them
+    const FitModes &mode = e->mode = fit_decide(cfg, knobs, J, f.ncp3, mc);
+    f.hc = mode.hc;
+    f.gv_sps = mode.gv_sps;
+    f.fused_bwd = mode.fused_bwd ? 1 : 0;
+    f.pen_skip = mode.fused_bwd && !knobs.no_pen_skip ? 1 : 0;
+    f.nsn_m = mode.split.nsn_m; f.nsn_c = mode.split.nsn_c; f.spm = mode.split.spm; f.spc = mode.split.spc;
 #ifdef PSI_HEAD_STOPS
     f.stop_h = knobs.head_stop;
     f.stop_t = knobs.tail_stop;
     (void)hipMemcpyToSymbol(HIP_SYMBOL(psi_dbg_sstop), &knobs.skin_stop, sizeof(int));
     (void)hipMemcpyToSymbol(HIP_SYMBOL(psi_dbg_pstop), &f.stop_t, sizeof(int));
 #endif
-    if (knobs.head_cluster) f.hc = knobs.head_cluster;
-    f.scene = d_scene_verts;
-    f.sdf = d_sdf;
-    const int B = f.B;
-    // host staging of constants
+    const size_t B = (size_t)f.B;                                // (as size_t: the sizes below are products in bytes)
+    // ---- host staging of constants
     std::vector<float> W1T((size_t)NZ * NH), W2T((size_t)NH * NH), W3T((size_t)NH * 128, 0.0f), b3p(128, 0.0f);
     memcpy(b3p.data(), h_b3, NJ6 * 4);
     for (int o = 0; o < NH; o++) for (int k = 0; k < NZ; k++) W1T[(size_t)k * NH + o] = h_w1[(size_t)o * NZ + k];
@@ -2100,123 +2184,116 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
         for (int v = 0; v < V; v++)
             if (cs_ptr[v + 1] > cs_ptr[v]) cs_first[v] = cs_idx[cs_ptr[v]] | (std::min(cs_ptr[v + 1] - cs_ptr[v], 127) << 24);
     }
-    struct Item { const void *src; size_t bytes; size_t off; };
-    std::vector<Item> items;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
-    auto cst = [&](const void *src, size_t bytes) { size_t r = take(bytes); items.push_back({src, bytes, r}); return r; };
-    size_t o_w1t = cst(W1T.data(), W1T.size() * 4), o_b1 = cst(h_b1, NH * 4), o_w2t = cst(W2T.data(), W2T.size() * 4), o_b2 = cst(h_b2, NH * 4),
-           o_w3t = cst(W3T.data(), W3T.size() * 4), o_b3 = cst(b3p.data(), 128 * 4), o_w1 = cst(h_w1, (size_t)NH * NZ * 4),
-           o_w2 = cst(h_w2, (size_t)NH * NH * 4), o_w3 = cst(h_w3, (size_t)NJ6 * NH * 4), o_lh = cst(h_lh_comp, (size_t)f.ncomp * 45 * 4),
-           o_rh = cst(h_rh_comp, (size_t)f.ncomp * 45 * 4), o_pm = cst(h_pose_mean, (size_t)J * 3 * 4), o_vid = cst(h_contact_ids, (size_t)f.n_c * 4),
-           o_cp = cst(cs_ptr.data(), cs_ptr.size() * 4), o_ci = cst(cs_idx.data(), cs_idx.size() * 4), o_cf = cst(cs_first.data(), cs_first.size() * 4), o_gmin = cst(h_gmin, 12), o_gmax = cst(h_gmax, 12);
-    size_t zero_begin = o;
-    size_t o_x = take((size_t)B * XD * 4), o_xhr = take((size_t)B * XD * 4), o_cam = take((size_t)B * 16 * 4), o_am = take((size_t)B * XD * 4),
-           o_av = take((size_t)B * XD * 4), o_step = take(256), o_h1 = take((size_t)B * NH * 4), o_h2 = take((size_t)B * NH * 4),
-           o_o6 = take((size_t)B * 128 * 4), o_b20 = take((size_t)B * NB * 4), o_pose = take((size_t)B * J * 3 * 4), o_tr = take((size_t)B * 3 * 4),
-           o_verts = take((size_t)B * V * 3 * 4), o_cv = take((size_t)B * f.n_c * 3 * 4), o_og = take((size_t)B * psi_cdiv(V, 256) * 256 * 4 * 4),
-           o_gq = take((size_t)B * f.n_c * 3 * 4), o_fp = take((size_t)B * f.nfp * 4), o_pp = take((size_t)B * f.nsdfblk * 2 * 4),
-           o_rp = take((size_t)B * 4), o_vp = take((size_t)B * 4), o_gb = take((size_t)B * NB * 4), o_gp = take((size_t)B * J * 3 * 4),
-           o_gt = take((size_t)B * 3 * 4), o_gr = take((size_t)B * J * 9 * 4), o_hist = take((size_t)f.max_hist * 4 * 4), o_stats = take(256), o_hint = take((size_t)B * f.n_c * 4);
-    size_t o_hxo = take((size_t)B * f.hc * 128 * 8), o_hxg = take((size_t)B * f.hc * NH * 8), o_hxc = take((size_t)2 * B * 4);
-    size_t o_wct = take((size_t)f.n_c * PSI_JP * 4);
-    // the contact slots as a second class of rows of the joint-side contractions (fused_bwd)
-    e->fused_bwd = e->merged_scene && !knobs.no_fused_bwd;
-    f.fused_bwd = e->fused_bwd ? 1 : 0;
-    f.ncp = psi_cdiv(f.n_c, 256) * 256;
-    f.ncp3 = 3 * f.ncp;
-    // per-body slots of the rows' maxima: up to 16 per body (a body's rows come from one skinning workgroup per 256 vertices and a few
-    // search workgroups: a few producers per address, where one address for a whole class cost 6 us), all inside the class's PSI_GV_SLOTS
-    f.gv_sps = 16;
-    while (f.gv_sps > 1 && (long)f.gv_sps * B > PSI_GV_SLOTS) f.gv_sps >>= 1;
-    size_t o_glc = 0, o_gvpc = 0, o_vpc = 0, o_gtc = 0, o_gvb = 0, o_wttc = 0, o_dirsc = 0, o_gap = 0, o_gfp = 0, o_spb = 0, o_pmask = 0;
-    {
-        // slice counts of the model's own rows: from the LBS workspace layout (offsets only: no memory is touched through this view)
-        PsiLbsView lv0;
-        if (int rcv = psi_lbs_view(lbs, B, reinterpret_cast<float *>((uintptr_t)4096), &lv0)) return rcv;
-        const int Kpad = lv0.m.Kpad, Npad = lv0.m.Npad, nsn = lv0.nsn;
-        const int SM = Npad / 16, SC = f.ncp3 / 16;
-        f.nsv = lv0.nsv;
-        f.nsv_c = f.ncp / 256;
-        // column slices of the stream workgroups, split between the two classes so that the LONGEST slice is as short as possible (a
-        // proportional split left a 512-slot contact set with one 96-step slice beside 64-step ones: bwd_joint 42 us instead of 28)
-        f.nsn_c = 0;
-        for (int c = 1, best = INT_MAX; c < nsn; c++) {
-            const int longest = std::max(psi_cdiv(SM, nsn - c), psi_cdiv(SC, c));
-            if (longest < best) { best = longest; f.nsn_c = c; }
-        }
-        f.nsn_m = nsn - f.nsn_c;
-        f.spm = psi_cdiv(SM, f.nsn_m);
-        f.spc = f.nsn_c ? psi_cdiv(SC, f.nsn_c) : 0;
-        if (e->fused_bwd && !f.nsn_c) { e->fused_bwd = false; f.fused_bwd = 0; }
-        if (e->fused_bwd) {
-            o_glc = take((size_t)B * f.ncp3 * 4); o_gvpc = take((size_t)B * f.ncp3 * 4); o_vpc = take((size_t)B * f.ncp3 * 4);
-            o_gtc = take((size_t)B * f.nfp * 4 * 4); o_gvb = take(2 * PSI_GV_SLOTS * 4); o_wttc = take((size_t)f.ncp * PSI_JP * 4); o_dirsc = take((size_t)f.ncp3 * Kpad * 4);
-            o_gap = take((size_t)(f.nsv + f.nsv_c) * B * PSI_JP * 16 * 4); o_gfp = take((size_t)(f.nsn_m + f.nsn_c) * B * Kpad * 4);
-            o_spb = take((size_t)B * 4);
-            o_pmask = take((size_t)B * (f.Vpad / 64) * 8);
-        }
+    // ---- the blob, buffer by buffer.  The ORDER is the layout: placement in memory is part of the measured performance.
+    // (sizes in bytes that several buffers share)
+    const size_t hand_pca = (size_t)f.ncomp * 45 * 4, hidden = B * NH * 4, betas = B * NB * 4, pose = B * J * 3 * 4, transl = B * 3 * 4,
+                 crows = B * f.n_c * 3 * 4, per_body = B * 4, slot_rows = B * f.ncp3 * 4;
+    FitBlob &T = e->table;
+    // constants
+    T.upload(f.W1T, W1T.data(), W1T.size() * 4);
+    T.upload(f.b1, h_b1, NH * 4);
+    T.upload(f.W2T, W2T.data(), W2T.size() * 4);
+    T.upload(f.b2, h_b2, NH * 4);
+    T.upload(f.W3T, W3T.data(), W3T.size() * 4);
+    T.upload(f.b3, b3p.data(), 128 * 4);
+    T.upload(f.W1, h_w1, (size_t)NH * NZ * 4);
+    T.upload(f.W2, h_w2, (size_t)NH * NH * 4);
+    T.upload(f.W3, h_w3, (size_t)NJ6 * NH * 4);
+    T.upload(f.lhc, h_lh_comp, hand_pca);
+    T.upload(f.rhc, h_rh_comp, hand_pca);
+    T.upload(f.pose_mean, h_pose_mean, (size_t)J * 3 * 4);
+    T.upload(f.vid, h_contact_ids, (size_t)f.n_c * sizeof(int32_t));
+    T.upload(f.cs_ptr, cs_ptr.data(), cs_ptr.size() * sizeof(int));
+    T.upload(f.cs_idx, cs_idx.data(), cs_idx.size() * sizeof(int));
+    T.upload(f.cs_first, cs_first.data(), cs_first.size() * sizeof(int));
+    T.upload(f.gmin, h_gmin, 12);
+    T.upload(f.gmax, h_gmax, 12);
+    T.zero_begin = T.size;
+    // state
+    T.zero(f.x, fit_x_bytes(f));
+    T.zero(f.xhr, fit_x_bytes(f));
+    T.zero(f.cam, fit_cam_bytes(f));
+    T.zero(f.adam_m, fit_x_bytes(f), "adam_m");
+    T.zero(f.adam_v, fit_x_bytes(f), "adam_v");
+    T.zero(f.step, 256);                                         // {Adam step, cluster-exchange error word (hx_err)}
+    // per-iteration buffers
+    T.zero(f.h1, hidden);
+    T.zero(f.h2, hidden);
+    T.zero(f.o6, B * 128 * 4);
+    T.zero(f.betas20, betas);
+    T.zero(f.pose, pose, "pose");
+    T.zero(f.transl, transl);
+    T.zero(f.verts, B * V * 3 * 4, "verts");
+    T.zero(f.cverts, crows);
+    T.zero(f.og, B * f.Vpad * 4 * 4);
+    T.zero(f.gq, crows);
+    T.zero(f.fpart, B * f.nfp * 4);
+    T.zero(f.penpart, B * f.nsdfblk * 2 * 4);
+    T.zero(f.recpart, per_body);
+    T.zero(f.vppart, per_body);
+    T.zero(f.g_betas, betas);
+    T.zero(f.g_pose, pose, "g_pose");
+    T.zero(f.g_transl, transl, "g_transl");
+    T.zero(f.g_rot, B * J * 9 * 4, "g_rot");
+    T.zero(f.history, (size_t)f.max_hist * 4 * 4);
+    T.zero(e->stats_local, 256);
+    T.ones(f.nn_hint, fit_hint_bytes(f));                        // -1 = no hint
+    T.zero(f.hx_o6, B * f.hc * 128 * 8);
+    T.zero(f.hx_gh1, B * f.hc * NH * 8);
+    T.zero(f.hx_epoch, 2 * B * 4);
+    T.zero(f.Wct, (size_t)f.n_c * PSI_JP * 4);
+    if (mode.fused_bwd) {
+        // the contact slots as a second class of rows of the joint-side contractions; "glc" / "gvpc": the contact part of the per-vertex rows
+        // of the skinning backward in slot order (the UNSCALED penetration part is in the LBS workspace's gl / g_vp)
+        T.zero(f.glc, slot_rows, "glc");
+        T.zero(f.gvpc, slot_rows, "gvpc");
+        T.zero(f.vpc, slot_rows, "vpc");
+        T.zero(f.gtc_part, B * f.nfp * 4 * 4);
+        T.zero(f.gvbits, 2 * PSI_GV_SLOTS * 4);
+        T.zero(f.WTt_c, (size_t)f.ncp * PSI_JP * 4);
+        T.zero(f.dirs_ch, (size_t)f.ncp3 * mc.Kpad * 4);
+        T.zero(f.gA_part, (size_t)(f.nsv + f.nsv_c) * B * PSI_JP * 16 * 4);
+        T.zero(f.gfeat_part, (size_t)(f.nsn_m + f.nsn_c) * B * mc.Kpad * 4);
+        T.zero(f.spb, per_body, "spb");                             // independent bodies: each body's penetration factor -w / N_b
+        // the penetration mask of the last forward, [B][Vpad / 64] 64-bit words as pairs of floats' worth of bits
+        T.zero(f.penmask, B * (f.Vpad / 64) * 8, "penmask");
     }
     // the cell-major copy of the one scene's volume; without it (a D it cannot hold, PSI_SDF_LINEAR=1) the plain volume is sampled
     // (several scenes: one copy per scene, allocated by fit_build_scenes)
     const bool cells = !h_scenes && psi_sdf_cells_fit(f.D) && !knobs.sdf_linear;
-    size_t o_cells = cells ? take(sdf_cells_bytes(f.D)) : 0;
-    size_t lbs_floats = psi_lbs_workspace_floats(lbs, B);
-    size_t o_lws = take(lbs_floats * 4), o_nws = take(psi_nn_ws_bytes(B, f.n_c, f.m));
-    hipError_t err = hipMalloc((void **)&e->blob, o);
+    if (cells) T.zero(f.sdf_cells, sdf_cells_bytes(f.D));
+    T.zero(e->lbs_ws, psi_lbs_workspace_floats(lbs, f.B) * 4);
+    T.zero(e->nn_ws, psi_nn_ws_bytes(f.B, f.n_c, f.m));
+    // ---- allocate, bind, upload, fill
+    hipError_t err = hipMalloc((void **)&e->blob, T.size);
     if (err != hipSuccess) {
-        psi_set_error("psi_fit_create: hipMalloc(%zu) failed: %s", o, hipGetErrorString(err));
+        psi_set_error("psi_fit_create: hipMalloc(%zu) failed: %s", T.size, hipGetErrorString(err));
         return (int)err;
     }
-    err = hipMemset(e->blob + zero_begin, 0, o - zero_begin);
-    if (err == hipSuccess) err = hipMemset(e->blob + o_hint, 0xff, (size_t)B * f.n_c * 4);   // -1 = no hint
-    for (auto &it : items)
-        if (err == hipSuccess) err = hipMemcpy(e->blob + it.off, it.src, it.bytes, hipMemcpyHostToDevice);
+    err = hipMemset(e->blob + T.zero_begin, 0, T.size - T.zero_begin);
+    for (FitBuf &b : T.bufs) {
+        char *p = e->blob + b.off;
+        memcpy(b.field, &p, sizeof(p));                          // (the fields are object pointers of several types: one representation)
+        if (err == hipSuccess && b.src) err = hipMemcpy(p, b.src, b.bytes, hipMemcpyHostToDevice);
+        else if (err == hipSuccess && b.fill) err = hipMemset(p, b.fill, b.bytes);
+        b.src = nullptr;                                         // the host arrays do not outlive this call
+    }
     if (err != hipSuccess) {
         psi_set_error("psi_fit_create: upload failed: %s", hipGetErrorString(err));
         return (int)err;
     }
-    char *bl = e->blob;
-    auto F = [&](size_t off) { return (float *)(bl + off); };
-    f.W1T = F(o_w1t); f.b1 = F(o_b1); f.W2T = F(o_w2t); f.b2 = F(o_b2); f.W3T = F(o_w3t); f.b3 = F(o_b3);
-    f.W1 = F(o_w1); f.W2 = F(o_w2); f.W3 = F(o_w3); f.lhc = F(o_lh); f.rhc = F(o_rh); f.pose_mean = F(o_pm);
-    f.vid = (const int *)(bl + o_vid); f.cs_ptr = (const int *)(bl + o_cp); f.cs_idx = (const int *)(bl + o_ci); f.cs_first = (const int *)(bl + o_cf);
-    f.gmin = F(o_gmin); f.gmax = F(o_gmax);
-    f.x = F(o_x); f.xhr = F(o_xhr); f.cam = F(o_cam); f.adam_m = F(o_am); f.adam_v = F(o_av); f.step = (int *)(bl + o_step); f.hx_err = f.step + 1;
-    f.h1 = F(o_h1); f.h2 = F(o_h2); f.o6 = F(o_o6); f.betas20 = F(o_b20); f.pose = F(o_pose); f.transl = F(o_tr);
-    f.verts = F(o_verts); f.cverts = F(o_cv); f.og = F(o_og); f.gq = F(o_gq); f.fpart = F(o_fp); f.penpart = F(o_pp);
-    f.recpart = F(o_rp); f.vppart = F(o_vp); f.g_betas = F(o_gb); f.g_pose = F(o_gp); f.g_transl = F(o_gt); f.g_rot = F(o_gr);
-    f.history = F(o_hist);
-    f.nn_hint = (int *)(bl + o_hint);
-    f.hx_o6 = (unsigned long long *)(bl + o_hxo); f.hx_gh1 = (unsigned long long *)(bl + o_hxg); f.hx_epoch = (unsigned *)(bl + o_hxc);
-    e->stats_local = F(o_stats);
-    e->lbs_ws = F(o_lws);
-    if (int rcv = psi_lbs_view(lbs, B, e->lbs_ws, &e->lv)) return rcv;
+    f.hx_err = f.step + 1;
+    if (int rcv = psi_lbs_view(lbs, f.B, e->lbs_ws, &e->lv)) return rcv;
     e->plan = fit_plan_make(f, e->lv.m, knobs.ska_nbody, knobs.bwd_pf1);
-    f.Wct = F(o_wct);
-    if (e->fused_bwd) {
-        f.glc = F(o_glc); f.gvpc = F(o_gvpc); f.vpc = F(o_vpc); f.gtc_part = F(o_gtc); f.WTt_c = F(o_wttc); f.dirs_ch = F(o_dirsc); f.gvbits = (unsigned *)(bl + o_gvb);
-        f.gA_part = F(o_gap); f.gfeat_part = F(o_gfp); f.spb = F(o_spb);
-        f.penmask = (unsigned long long *)(bl + o_pmask);
-        f.pen_skip = knobs.no_pen_skip ? 0 : 1;
-    }
-    // two bodies per skinning workgroup share one pass over the vertex's weight row: from the batch size at which the kernel is
-    // throughput-bound (its own launch, B > 128); PSI_SKIN_NB=1|2 overrides
-    // (compressed rows are read once per lane either way and measured 2-3 % slower with two bodies: 114.7 vs 112.3 us at B = 512)
-    e->skin_nb = cfg->B > 128 && !e->lv.m.Wc ? 2 : 1;
-    if (knobs.skin_nb) e->skin_nb = knobs.skin_nb;
+    // ---- the one-off layout kernels, on the NULL stream
     hipLaunchKernelGGL(contact_weight_table_kernel, dim3(psi_cdiv((long)f.n_c * PSI_JP, 256)), dim3(256), 0, 0, e->lv.m.WT, e->lv.m.Vpad, f.vid,
                        f.n_c, J, (float *)f.Wct);
-    if (e->fused_bwd) {
+    if (mode.fused_bwd) {
         hipLaunchKernelGGL(contact_weight_tiles_kernel, dim3(psi_cdiv((long)f.ncp * PSI_JP, 256)), dim3(256), 0, 0, f.Wct, f.n_c, f.ncp, (float *)f.WTt_c);
         hipLaunchKernelGGL(contact_dirs_h_kernel, dim3(psi_cdiv((long)f.ncp3 * e->lv.m.Kpad, 256)), dim3(256), 0, 0, e->lv.m.dirs_bh, e->lv.m.Kpad, f.vid,
                            f.n_c, f.ncp3, (float *)f.dirs_ch);
     }
-    f.sdf_cells = nullptr;
-    if (cells) {
-        sdf_cells_fill(d_sdf, F(o_cells), f.D);
-        f.sdf_cells = F(o_cells);
-    }
+    if (cells) sdf_cells_fill(d_sdf, (float *)f.sdf_cells, f.D);
     e->grid = psi_sdf_grid_make(f.sdf_cells, h_gmin, h_gmax, f.D, f.align_corners);
     err = hipDeviceSynchronize();                                // the one-off layout kernels above ran on the NULL stream
     if (err == hipSuccess) err = hipGetLastError();
@@ -2224,7 +2301,6 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
         psi_set_error("psi_fit_create: layout kernels failed: %s", hipGetErrorString(err));
         return (int)err;
     }
-    e->nn_ws = bl + o_nws;
     if (h_scenes) {
         if (int rc = fit_build_scenes(e, h_scenes, S)) return rc;
     } else if (cfg->nn_mode == 1) {
@@ -2342,7 +2418,7 @@ extern "C" int psi_fit_set_scene_slots(psi_fit_engine *e, const int32_t *d_slot,
         PSI_CHECK_LAUNCH("scene_slots_kernel");
     }
     // a hint is an index into ONE scene's cloud: against another scene it would be a wrong candidate
-    PSI_CHECK_HIP(hipMemsetAsync(f.nn_hint, 0xff, (size_t)f.B * f.n_c * 4, st));
+    PSI_CHECK_HIP(fit_hints_reset(f, st));
     return 0;
 }
 
@@ -2372,11 +2448,10 @@ extern "C" int psi_fit_set_problem(psi_fit_engine *e, const float *d_xhr, const 
     PSI_REQUIRE(e && d_xhr && d_cam_ext, "null pointer");
     FitDev &f = e->d;
     hipStream_t st = (hipStream_t)stream;
-    size_t nb = (size_t)f.B * XD * 4;
-    PSI_CHECK_HIP(hipMemcpyAsync(f.xhr, d_xhr, nb, hipMemcpyDeviceToDevice, st));
-    PSI_CHECK_HIP(hipMemcpyAsync(f.x, d_x_init ? d_x_init : d_xhr, nb, hipMemcpyDeviceToDevice, st));
-    PSI_CHECK_HIP(hipMemcpyAsync(f.cam, d_cam_ext, (size_t)f.B * 16 * 4, hipMemcpyDeviceToDevice, st));
-    PSI_CHECK_HIP(hipMemsetAsync(f.nn_hint, 0xff, (size_t)f.B * f.n_c * 4, st));
+    PSI_CHECK_HIP(hipMemcpyAsync(f.xhr, d_xhr, fit_x_bytes(f), hipMemcpyDeviceToDevice, st));
+    PSI_CHECK_HIP(hipMemcpyAsync(f.x, d_x_init ? d_x_init : d_xhr, fit_x_bytes(f), hipMemcpyDeviceToDevice, st));
+    PSI_CHECK_HIP(hipMemcpyAsync(f.cam, d_cam_ext, fit_cam_bytes(f), hipMemcpyDeviceToDevice, st));
+    PSI_CHECK_HIP(fit_hints_reset(f, st));
     if (reset_optimizer) {
         hipLaunchKernelGGL(adam_reset_kernel, dim3(psi_cdiv((long)f.B * XD, 256)), dim3(256), 0, st, f.adam_m, f.adam_v, f.step, f.B * XD);
         PSI_CHECK_LAUNCH("adam_reset_kernel");
@@ -2447,7 +2522,7 @@ extern "C" int psi_fit_iterate_dp(psi_fit_engine *e, psi_dp_comm *comm, int n_it
     hipStream_t st = (hipStream_t)stream;
     float *stats = d_stats ? d_stats : e->stats_local;
     auto one = [&]() -> int {
-        if (e->fused_bwd) {
+        if (e->mode.fused_bwd) {
             // The global penetration count is needed only where the slices are summed (fit_reduce_kernel), so the statistics come from the joint
             // kernel's statistics workgroup (no separate launch) and the ONE collective of the iteration sits between the joint kernel and the
             // reduction: forward -> joint kernel -> ncclAllReduce(stats) -> reduction -> tail, all on one stream / one chain of the graph.
@@ -2507,8 +2582,8 @@ extern "C" int psi_fit_decode_forward(psi_fit_engine *e, const float *d_x75, con
     PSI_REQUIRE(e && d_x75 && d_cam_ext && d_verts, "null pointer");
     FitDev &f = e->d;
     hipStream_t st = (hipStream_t)stream;
-    PSI_CHECK_HIP(hipMemcpyAsync(f.x, d_x75, (size_t)f.B * XD * 4, hipMemcpyDeviceToDevice, st));
-    PSI_CHECK_HIP(hipMemcpyAsync(f.cam, d_cam_ext, (size_t)f.B * 16 * 4, hipMemcpyDeviceToDevice, st));
+    PSI_CHECK_HIP(hipMemcpyAsync(f.x, d_x75, fit_x_bytes(f), hipMemcpyDeviceToDevice, st));
+    PSI_CHECK_HIP(hipMemcpyAsync(f.cam, d_cam_ext, fit_cam_bytes(f), hipMemcpyDeviceToDevice, st));
     launch_head_fwd(f, e->lv, st);
     PSI_CHECK_LAUNCH("head_fwd_kernel");
     int rc = psi_lbs_blend_forward(e->lbs, f.B, e->lbs_ws, st);
@@ -2584,7 +2659,7 @@ extern "C" int psi_fit_read(psi_fit_engine *e, float *d_x_out, float *d_history_
     PSI_REQUIRE(e, "null engine");
     FitDev &f = e->d;
     hipStream_t st = (hipStream_t)stream;
-    if (d_x_out) PSI_CHECK_HIP(hipMemcpyAsync(d_x_out, f.x, (size_t)f.B * XD * 4, hipMemcpyDeviceToDevice, st));
+    if (d_x_out) PSI_CHECK_HIP(hipMemcpyAsync(d_x_out, f.x, fit_x_bytes(f), hipMemcpyDeviceToDevice, st));
     if (d_history_out && n_hist > 0) {
         if (n_hist > f.max_hist) n_hist = f.max_hist;
         PSI_CHECK_HIP(hipMemcpyAsync(d_history_out, f.history, (size_t)n_hist * 16, hipMemcpyDeviceToDevice, st));
@@ -2616,36 +2691,29 @@ extern "C" int psi_fit_copy_buffer(psi_fit_engine *e, const char *name, float *d
 {
     PSI_REQUIRE(e && name && d_out && n_floats >= 0, "bad arguments");
     FitDev &f = e->d;
+    const PsiLbsView &lv = e->lv;
     const float *src = nullptr;
     long cap = 0;
-    if (!strcmp(name, "verts")) {
-        src = f.verts; cap = (long)f.B * f.V * 3;
-        if (e->nn_index) {           // not (or only partly) stored by the iteration: skinned on demand from the last forward's v_posed and transforms
-            hipLaunchKernelGGL(psi_skin_fwd_kernel<PsiSkinNoEpilogue>, dim3(f.nsdfblk, f.B), dim3(PSI_SKIN_BLK), 0, (hipStream_t)stream, e->lv.m, e->lv.A,
-                               e->lv.v_posed, f.transl, f.cam, f.B, f.verts, PsiSkinNoEpilogue());
-            PSI_CHECK_LAUNCH("skin_fwd_kernel");
-        }
+    // the blob's named buffers (fit_create: the names of a fused_bwd engine's own buffers exist only there) ...
+    for (const FitBuf &b : e->table.bufs)
+        if (b.name && !strcmp(name, b.name)) { src = (const float *)(e->blob + b.off); cap = (long)(b.bytes / 4); }
+    // ... the statistics, and what lives in the LBS workspace: the reduced gradients the tail kernel reads, the per-vertex rows of the
+    // skinning backward (fused_bwd: the UNSCALED penetration part) and the posed vertices
+    const struct { const char *name; const float *src; long cap; } more[] = {
+        {"stats", e->stats_local, 8},
+        {"gA", lv.gA, (long)f.B * PSI_JP * 16},
+        {"gfeat", lv.gfeat, (long)f.B * lv.m.Kpad},
+        {"gl", lv.gl, (long)f.B * lv.m.Npad},
+        {"g_vp", lv.g_vp, (long)f.B * lv.m.Npad},
+        {"v_posed", lv.v_posed, (long)f.B * lv.m.Npad},
+    };
+    for (const auto &b : more)
+        if (!strcmp(name, b.name)) { src = b.src; cap = b.cap; }
+    if (!strcmp(name, "verts") && e->nn_index) {   // not (or only partly) stored by the iteration: skinned on demand from the last forward's v_posed and transforms
+        hipLaunchKernelGGL(psi_skin_fwd_kernel<PsiSkinNoEpilogue>, dim3(f.nsdfblk, f.B), dim3(PSI_SKIN_BLK), 0, (hipStream_t)stream, lv.m, lv.A,
+                           lv.v_posed, f.transl, f.cam, f.B, f.verts, PsiSkinNoEpilogue());
+        PSI_CHECK_LAUNCH("skin_fwd_kernel");
     }
-    else if (!strcmp(name, "pose")) { src = f.pose; cap = (long)f.B * f.J * 3; }
-    else if (!strcmp(name, "g_pose")) { src = f.g_pose; cap = (long)f.B * f.J * 3; }
-    else if (!strcmp(name, "g_rot")) { src = f.g_rot; cap = (long)f.B * f.J * 9; }
-    else if (!strcmp(name, "stats")) { src = e->stats_local; cap = 8; }
-    else if (!strcmp(name, "adam_m")) { src = f.adam_m; cap = (long)f.B * XD; }
-    else if (!strcmp(name, "adam_v")) { src = f.adam_v; cap = (long)f.B * XD; }
-    // the reduced gradients the tail kernel reads, and the per-vertex rows of the skinning backward (fused_bwd: the UNSCALED penetration part in
-    // gl / g_vp, the contact part in slot order in glc / gvpc)
-    else if (!strcmp(name, "gA")) { src = e->lv.gA; cap = (long)f.B * PSI_JP * 16; }
-    else if (!strcmp(name, "gfeat")) { src = e->lv.gfeat; cap = (long)f.B * e->lv.m.Kpad; }
-    else if (!strcmp(name, "g_transl")) { src = f.g_transl; cap = (long)f.B * 3; }
-    else if (!strcmp(name, "gl")) { src = e->lv.gl; cap = (long)f.B * e->lv.m.Npad; }
-    else if (!strcmp(name, "g_vp")) { src = e->lv.g_vp; cap = (long)f.B * e->lv.m.Npad; }
-    else if (!strcmp(name, "v_posed")) { src = e->lv.v_posed; cap = (long)f.B * e->lv.m.Npad; }
-    else if (!strcmp(name, "glc") && e->fused_bwd) { src = f.glc; cap = (long)f.B * f.ncp3; }
-    else if (!strcmp(name, "gvpc") && e->fused_bwd) { src = f.gvpc; cap = (long)f.B * f.ncp3; }
-    else if (!strcmp(name, "vpc") && e->fused_bwd) { src = f.vpc; cap = (long)f.B * f.ncp3; }
-    else if (!strcmp(name, "spb") && e->fused_bwd) { src = f.spb; cap = f.B; }      // independent bodies: each body's penetration factor -w / N_b
-    // the penetration mask of the last forward, [B][Vpad / 64] 64-bit words as pairs of floats' worth of bits
-    else if (!strcmp(name, "penmask") && e->fused_bwd) { src = (const float *)f.penmask; cap = (long)f.B * (f.Vpad / 64) * 2; }
     PSI_REQUIRE(src != nullptr, "unknown buffer name");
     PSI_REQUIRE(n_floats <= cap, "buffer is smaller than requested");
     PSI_CHECK_HIP(hipMemcpyAsync(d_out, src, (size_t)n_floats * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));

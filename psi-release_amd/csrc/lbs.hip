@@ -652,6 +652,15 @@ int psi_lbs_view(const psi_lbs_model *mdl, int B, float *ws, PsiLbsView *out)
     return 0;
 }
 
+int psi_lbs_counts(const psi_lbs_model *mdl, int B, PsiLbsCounts *out)
+{
+    PSI_REQUIRE(mdl && out && B > 0, "bad arguments");
+    const LbsDev &m = mdl->d;
+    const WsLayout L = ws_layout(m, B);
+    *out = PsiLbsCounts{L.nsv, L.nsn, m.Kpad, m.Npad, m.Wc != nullptr};
+    return 0;
+}
+
 int psi_lbs_blend_forward(const psi_lbs_model *mdl, int B, float *ws, hipStream_t st)
 {
     const LbsDev &m = mdl->d;

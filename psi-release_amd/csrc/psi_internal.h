@@ -57,6 +57,11 @@ static inline int psi_ska_nbody(int rule, int limit, int override_) { return ove
 // the fused fitting engine runs the per-body pose stages inside its own kernels (lbs_device.h) and calls these for the rest
 struct PsiLbsView;
 int psi_lbs_view(const psi_lbs_model *mdl, int B, float *ws, PsiLbsView *out);
+// what the engine sizes its own buffers with before it has a workspace: the slice counts of the workspace layout at batch size B (256-vertex
+// slices of skin_bwd_A, column slices of blend_bwd), the padded feature and column counts, and whether the skinning weights are stored
+// as compressed rows (LbsDev::Wc)
+struct PsiLbsCounts { int nsv, nsn, Kpad, Npad; bool compressed_weights; };
+int psi_lbs_counts(const psi_lbs_model *mdl, int B, PsiLbsCounts *out);
 int psi_lbs_blend_forward(const psi_lbs_model *mdl, int B, float *ws, hipStream_t st);          // v_posed = v_t + feat @ dirs
 // pose_fwd + blend_fwd of psi_lbs_forward for given betas / pose: A and v_posed in the workspace, no vertices (eval.hip skins with its own epilogue)
 int psi_lbs_pose_blend_forward(const psi_lbs_model *mdl, const float *betas, const float *pose, const float *transl, int B, float *ws,

@@ -1,7 +1,12 @@
-// The skin_bwd_A workgroups of fit_bwd_joint_kernel (fit.hip): how many bodies a workgroup of each row class takes, and which (slice, body
-// group) workgroup `bid` is.  The launcher (fit_plan_make) and the kernel both go through these functions, so they cannot disagree.
-// No dependencies: tools/fit_plan_host_check.hip walks every workgroup of every plan on the host.
+// The launch plans of fit_bwd_joint_kernel (fit.hip), as functions without dependencies that both the host code and the kernel go through,
+// so they cannot disagree; tools/fit_plan_host_check.hip walks every workgroup and every slice of every plan on the host.
+//   * psi_ska_plan / psi_ska_map: the skin_bwd_A workgroups — how many bodies a workgroup of each row class takes, and which (slice, body
+//     group) workgroup `bid` is.  The launcher (fit_plan_make) calls the first, the kernel the second.
+//   * psi_stream_split: the stream (blend_bwd) workgroups — how the column slices are divided between the two row classes and how many
+//     16-column steps a slice of each class holds.  fit_decide calls it at psi_fit_create; the kernel reads the four numbers from FitDev
+//     and gives slice i of a class the steps [i * sp, (i + 1) * sp), clipped to the class's step count.
 //
+// skin_bwd_A.
 // A workgroup is one 256-vertex slice x nbody bodies = ceil(12 nbody / 16) column tiles of the fp32 MFMA, 64 instructions per tile and wave.
 // The two classes differ: the model's 41 slices are almost all skipped once the fit is under way (penetration mask), the contact slots'
 // few slices never are, and their workgroups are then what the launch waits for.  So
@@ -79,4 +84,27 @@ PSI_SKA_HD inline void psi_ska_map(const PsiSkaPlan &p, int bid, int &sl, int &b
         b0 = (i / p.nsv) * p.nb_m;
         nbody = p.nb_m;
     }
+}
+
+// ---- the stream workgroups' column slices.  SM >= 1 / SC >= 0 steps of 16 columns of the model / the contact class, nsn >= 1 slices for
+// both.  The slices are split between the two classes so that the LONGEST slice is as short as possible (a proportional split left a
+// 512-slot contact set with one 96-step slice beside 64-step ones: bwd_joint 42 us instead of 28); ties go to the smaller contact count.
+// nsn_c == 0 (nsn == 1: no slice to spare): the contact class cannot be streamed, the engine runs without the fused backward.
+struct PsiStreamSplit {
+    int nsn_m, nsn_c;             // column slices of the model / of the contact slots
+    int spm, spc;                 // steps per slice of each class (spc == 0 without contact slices)
+};
+
+PSI_SKA_HD inline PsiStreamSplit psi_stream_split(int SM, int SC, int nsn)
+{
+    PsiStreamSplit s;
+    s.nsn_c = 0;
+    for (int c = 1, best = 0x7fffffff; c < nsn; c++) {
+        const int lm = psi_ska_cdiv(SM, nsn - c), lc = psi_ska_cdiv(SC, c), longest = lm > lc ? lm : lc;
+        if (longest < best) { best = longest; s.nsn_c = c; }
+    }
+    s.nsn_m = nsn - s.nsn_c;
+    s.spm = psi_ska_cdiv(SM, s.nsn_m);
+    s.spc = s.nsn_c ? psi_ska_cdiv(SC, s.nsn_c) : 0;
+    return s;
 }

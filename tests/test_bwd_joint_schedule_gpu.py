@@ -7,7 +7,8 @@ engines compared here must agree BIT FOR BIT in gA, gfeat, g_transl, x, the Adam
 
 Shapes: the J = 55 model with V = 500, 1100 and 2000, n_c = 64 / 1024, m = 512, D = 16 / 32, B in {1, 3, 17, 33} (16-body tiles per
 stream workgroup 1, 1, 2, 4); one case at the production V = 10475, n_c = 2048, B = 2.
-The contact class's column slices, steps per wave (stream_plan below restates fit.hip's rule):
+The contact class's column slices, steps per wave (stream_plan below restates the rule of csrc/ska_plan.h, psi_stream_split;
+tests/test_fit_plan_cpu.py compares the two):
   V = 1100, n_c = 64:      48 steps, 5 slices of 10 (last 8)           -> 3/3/2/2 and 2/2/2/2 per wave
   V = 1100, n_c = 1024:   192 steps, 14 slices of 14 (last 10)         -> 4/4/3/3 and 3/3/2/2
   V = 2000, n_c = 1024:   192 steps, 11 slices of 18 (last 12)         -> 5/5/4/4 and 3/3/3/3
@@ -34,7 +35,7 @@ SMALL = [(1100, 64, B) for B in (1, 3, 17, 33)]
 SHAPES = SMALL + [(1100, 1024, 3), (1100, 1024, 17), (1100, 1024, 33), (2000, 1024, 3), (500, 64, 3), (10475, 2048, 2)]
 
 
-# ---- the stream plan of a shape, restated from fit.hip (psi_fit_create) and lbs.hip (the workspace layout) ---------------------------
+# ---- the stream plan of a shape, restated from ska_plan.h (psi_stream_split) and lbs.hip (the workspace layout) ----------------------
 def stream_plan(V, n_c, B):
     """-> (depth of the contact class, [per-wave step counts of each contact column slice])"""
     cdiv = lambda a, b: -(-a // b)

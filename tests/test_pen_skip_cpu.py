@@ -22,9 +22,13 @@ def test_step_mask_equals_brute_force(tmp_path):
 
 
 def test_knob_and_buffer_are_declared():
-    """PSI_FIT_PEN_SKIP is read with the engine's other switches and documented; "penmask" is a buffer of psi_fit_copy_buffer."""
+    """PSI_FIT_PEN_SKIP is read with the engine's other switches and documented; "penmask" is a buffer of psi_fit_copy_buffer: a name in
+    the blob's table (declared in fit_create, on engines with the fused backward only), which psi_fit_copy_buffer looks names up in."""
     src = open(os.path.join(ROOT, 'psi-release_amd', 'csrc', 'fit.hip')).read()
     assert 'is("PSI_FIT_PEN_SKIP", \'0\')' in src.split('static FitKnobs fit_read_knobs()')[1].split('return k;')[0]
-    assert '"penmask"' in src.split('extern "C" int psi_fit_copy_buffer')[1]
+    create = src.split('static int fit_create(')[1].split('extern "C" int psi_fit_create(')[0]
+    assert 'T.zero(f.penmask, ' in create.split('if (mode.fused_bwd) {')[1].split('}')[0] and '"penmask");' in create
+    copy = src.split('extern "C" int psi_fit_copy_buffer')[1]
+    assert 'e->table.bufs' in copy and '!strcmp(name, b.name)' in copy
     assert 'PSI_FIT_PEN_SKIP' in open(os.path.join(ROOT, 'README.md')).read()
     assert 'penmask' in open(os.path.join(ROOT, 'include', 'psi_hip.h')).read()

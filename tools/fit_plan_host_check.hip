@@ -9,7 +9,13 @@
 // heap array of exactly (nsv + nsv_c) x B entries: a slice or body outside it is a sanitizer error), that no workgroup holds more than
 // SKA_NBODY bodies, that an override is obeyed, and that the plan never has more workgroups than the single-count rule it replaced gives
 // for the same input; at the production shape (B = 32, V = 10475, n_c = 2048: 256 stream workgroups and the statistics workgroup) the
-// grid is at most 512, one occupancy round.  Exit status 1 at the first failure.
+// grid is at most 512, one occupancy round.
+// The stream workgroups' column slices (psi_stream_split) for the same V and n_c, with 64, 32 (the SMPL-X-shaped model), 21, 2 slices and
+// one: every 16-column step of the model class and of the contact class lies in exactly one slice's [slice * sp, (slice + 1) * sp) clipped
+// to the class's step count — the arithmetic of fit_bwd_joint_kernel — the two classes' slices are exactly the nsn the partial table is
+// sized for, and the longest slice is the minimum over all splits by brute force (ties: the fewest contact slices); at the production
+// shape 384 contact steps in 6 slices of 64.  With arguments `V n_c ...` it only prints the split of those shapes (Kpad = 512).
+// Exit status 1 at the first failure.
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
@@ -74,14 +80,85 @@ static int check(int B, int V, int n_c, int override_)
     return 0;
 }
 
-int main()
+static long splits = 0, steps = 0;
+
+// every step of a class of S steps in exactly one slice's [slice * sp, (slice + 1) * sp) clipped to S (blend_bwd_h_body's own clipping); the
+// table is a heap array of exactly S entries
+static int check_class(const char *cls, int V, int n_c, int nsn, int S, int nslices, int sp)
 {
-    const int ncs[] = {1, 16, 64, 256, 257, 1024, 2048, 4096}, Vs[] = {1100, 10475};
+    int *cover = (int *)calloc((size_t)(S > 0 ? S : 1), sizeof(int));
+    int rc = 0;
+    for (int slice = 0; slice < nslices; slice++) {
+        const int lo = slice * sp, hi = (slice + 1) * sp < S ? (slice + 1) * sp : S;
+        for (int s = lo; s < hi; s++) cover[s]++;
+    }
+    for (int s = 0; s < S && !rc; s++) {
+        steps++;
+        if (cover[s] != 1) {
+            printf("V %d n_c %d nsn %d: %s step %d in %d slices\n", V, n_c, nsn, cls, s, cover[s]);
+            rc = 1;
+        }
+    }
+    free(cover);
+    return rc;
+}
+
+// the stream workgroups' column slices (psi_stream_split) as fit_bwd_joint_kernel applies them: slice < nsn_m is the model's slice with
+// steps of spm, slice - nsn_m the contact class's with steps of spc, nsn_m + nsn_c slices in all.  kpad: the model's padded feature count,
+// which decides the number of slices as the workspace layout of lbs.hip does
+static int check_split(int V, int n_c, int kpad)
+{
+    const int SM = 3 * cdiv(V, 256) * 256 / 16, SC = 3 * cdiv(n_c, 256) * 256 / 16;
+    int nsn = 256 / (kpad / 64) > 0 ? 256 / (kpad / 64) : 1;
+    if (nsn > SM) nsn = SM;
+    const PsiStreamSplit s = psi_stream_split(SM, SC, nsn);
+    splits++;
+#define FAIL(...) do { printf("V %d n_c %d nsn %d: ", V, n_c, nsn); printf(__VA_ARGS__); printf("\n"); return 1; } while (0)
+    if (s.nsn_m < 1 || s.nsn_c < 0 || s.nsn_m + s.nsn_c != nsn) FAIL("%d + %d slices", s.nsn_m, s.nsn_c);
+    if (s.spm != cdiv(SM, s.nsn_m) || s.spc != (s.nsn_c ? cdiv(SC, s.nsn_c) : 0)) FAIL("steps per slice %d / %d", s.spm, s.spc);
+    if (check_class("model", V, n_c, nsn, SM, s.nsn_m, s.spm)) return 1;
+    if (s.nsn_c && check_class("contact", V, n_c, nsn, SC, s.nsn_c, s.spc)) return 1;
+    // the longest slice is the shortest any split gives; among equals, the fewest contact slices
+    int best = 0x7fffffff, best_c = 0;
+    for (int c = 1; c < nsn; c++) {
+        const int longest = cdiv(SM, nsn - c) > cdiv(SC, c) ? cdiv(SM, nsn - c) : cdiv(SC, c);
+        if (longest < best) { best = longest; best_c = c; }
+    }
+    if (nsn > 1) {
+        const int longest = s.spm > s.spc ? s.spm : s.spc;
+        if (longest != best || s.nsn_c != best_c) FAIL("%d contact slices, longest %d; brute force: %d, longest %d", s.nsn_c, longest, best_c, best);
+    } else if (s.nsn_c) FAIL("a contact slice out of one");
+    if (V == 10475 && n_c == 2048 && kpad == 512) {
+        printf("V 10475, n_c 2048: %d contact steps, %d slices of %d; %d model steps, %d slices of %d\n", SC, s.nsn_c, s.spc, SM, s.nsn_m, s.spm);
+        if (SC != 384 || s.nsn_c != 6 || s.spc != 64) FAIL("not the production table");
+    }
+#undef FAIL
+    return 0;
+}
+
+// argv: V n_c pairs — print the stream split of each shape of the SMPL-X-shaped model (Kpad = 512) and leave
+int main(int argc, char **argv)
+{
+    if (argc > 1) {
+        for (int i = 1; i + 1 < argc; i += 2) {
+            const int V = atoi(argv[i]), n_c = atoi(argv[i + 1]);
+            const int SM = 3 * cdiv(V, 256) * 256 / 16, SC = 3 * cdiv(n_c, 256) * 256 / 16;
+            const PsiStreamSplit s = psi_stream_split(SM, SC, 32 < SM ? 32 : SM);
+            printf("split V %d n_c %d: nsn_m %d nsn_c %d spm %d spc %d SM %d SC %d\n", V, n_c, s.nsn_m, s.nsn_c, s.spm, s.spc, SM, SC);
+        }
+        return 0;
+    }
+    const int ncs[] = {1, 16, 64, 256, 257, 1024, 2048, 4096}, Vs[] = {1100, 10475}, kpads[] = {256, 512, 768, 8192, 16384};
     for (int V : Vs)
         for (int n_c : ncs)
             for (int B = 1; B <= 128; B++)
                 for (int ov = 0; ov <= LIMIT; ov++)
                     if (check(B, V, n_c, ov)) return 1;
     printf("fit plan: %ld plans, %ld workgroups: every (slice, body) covered exactly once\n", plans, workgroups);
+    for (int V : Vs)
+        for (int n_c : ncs)
+            for (int kpad : kpads)                               // 64, 32 (SMPL-X), 21, 2 slices and 1
+                if (check_split(V, n_c, kpad)) return 1;
+    printf("stream split: %ld splits, %ld steps: every step in exactly one slice, the longest slice minimal\n", splits, steps);
     return 0;
 }
