@@ -713,6 +713,52 @@ int psi_flood_fill(const uint8_t *d_open, int Dx, int Dy, int Dz, const int32_t 
 int psi_mesh_orient_votes(const float *d_points, const int32_t *d_tri, long long n, const float *d_verts, int nv, const int32_t *d_faces, int nf,
                           const uint8_t *d_free, const float gmin[3], const float gmax[3], int D, float delta, int32_t *d_votes, void *stream);
 
+/* ---- body against body: which vertices of one body of a batch lie inside another body of the batch ----
+ * Contract (csrc/body_overlap_shared.h holds the statements).  d_verts [B,V,3] fp32, world frame; the faces [F,3] int32 of the handle are
+ * shared by all bodies and wound outwards; d_group [B] int32 or NULL (all bodies in one group):
+ *   box        of body j: the exact min / max of its V vertices per axis
+ *   candidate  an ordered triple (i, j, v) with i != j, group[i] == group[j] and vertex v of body i inside the closed box of j (comparisons
+ *              only); a vertex outside the box is outside the body.  The list is in ascending (i, j, v) order
+ *   w          (sum over the F triangles of body j, in face order, of atan2(a . n, |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|)) / 2 pi with
+ *              a = A - p, b = B - p, c = C - p and n = (B - A) x (C - A) in fp32 from the body's current vertices; atan2(0, 0) = 0: the
+ *              statement of psi_mesh_winding_compute, about 1 inside and about 0 outside
+ *   sum        fp32 within a chunk of 256 consecutive faces; the chunk sums added in fp64, in order, within a slice of 2048 consecutive
+ *              faces; the slice sums added in fp64 in slice order.  256 and 2048 are constants of the contract, not launch parameters
+ *   decision   vertex v of body i is inside j iff w > 0.5
+ * No floating-point atomics: every output is bit-identical from run to run, and the w of a triple has the same bits whatever else the
+ * batch holds.  The passes of one computation; the scans between them are the caller's (ops.body_overlap):
+ *   create   h_faces: HOST [F,3] int32, copied to the device.  PSI_EINVAL: F < 1, V < 1, a face index outside [0, V)
+ *   boxes    writes d_boxes [B,6] fp32 (min xyz, max xyz) and *d_bad (device int32): the smallest index of a body with a non-finite
+ *            coordinate, a value >= B when there is none
+ *   count    writes d_pair_count [B,B] int32: the vertices of i in the closed box of j; 0 on the diagonal, across groups and where the
+ *            boxes do not meet (such a pair costs one comparison)
+ *   emit     d_cand_off, d_chunk_off [B,B] int64 = the exclusive scans of d_pair_count and of ceil(d_pair_count / 256); n_cand, n_chunks
+ *            their totals.  Writes d_cand [n_cand,3] int32 = (i, j, v) and d_chunks [n_chunks,4] int32 = (first candidate, candidates,
+ *            i, j): up to 256 candidates of ONE pair
+ *   wind     the hot pass, grid = (chunk, slice): writes the fp64 slice sums of every candidate into d_workspace
+ *            (psi_body_overlap_workspace_bytes(n_cand, F) = ceil(F / 2048) * n_cand * 8 bytes; 0 for n_cand outside [1, 2^31))
+ *   decide   writes d_w [n_cand] fp32 and adds into d_counts [B,B] int32 and d_mask [B, ceil(V / 32)] uint32 (bit v % 32 of word v / 32:
+ *            vertex v is inside another body), which the CALLER has zeroed, by integer atomics
+ * Each pass is one kernel on `stream` (boxes after one memset) with no host synchronisation; none launches an empty grid: with n_cand = 0
+ * the caller stops after count.  PSI_EINVAL: a null pointer (d_group excepted), B < 1 or B > 46340, n_cand outside [1, 2^31), n_chunks
+ * outside [1, n_cand], a workspace smaller than the query's value. */
+typedef struct psi_body_overlap psi_body_overlap;
+int psi_body_overlap_create(psi_body_overlap **out, const int32_t *h_faces, int V, int F);
+void psi_body_overlap_destroy(psi_body_overlap *h);
+/* info[0] = V, info[1] = F */
+int psi_body_overlap_info(const psi_body_overlap *h, int32_t info[2]);
+size_t psi_body_overlap_workspace_bytes(long long n_cand, int F);
+int psi_body_overlap_boxes(const psi_body_overlap *h, const float *d_verts, int B, float *d_boxes, int32_t *d_bad, void *stream);
+int psi_body_overlap_count(const psi_body_overlap *h, const float *d_verts, const int32_t *d_group, int B, const float *d_boxes,
+                           int32_t *d_pair_count, void *stream);
+int psi_body_overlap_emit(const psi_body_overlap *h, const float *d_verts, const int32_t *d_group, int B, const float *d_boxes,
+                          const int32_t *d_pair_count, const int64_t *d_cand_off, const int64_t *d_chunk_off, long long n_cand,
+                          long long n_chunks, int32_t *d_cand, int32_t *d_chunks, void *stream);
+int psi_body_overlap_wind(const psi_body_overlap *h, const float *d_verts, int B, const int32_t *d_cand, long long n_cand,
+                          const int32_t *d_chunks, long long n_chunks, void *d_workspace, size_t workspace_bytes, void *stream);
+int psi_body_overlap_decide(const psi_body_overlap *h, int B, const int32_t *d_cand, long long n_cand, const void *d_workspace,
+                            size_t workspace_bytes, float *d_w, int32_t *d_counts, uint32_t *d_mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,8 +36,10 @@ PER_FILE = {'chamfer.hip': ['-ffp-contract=off', '-fno-slp-vectorize'], 'nnindex
             'canvas.hip': ['-ffp-contract=off'],        # the scale and the interpolation as written
             'mesh_cloud.hip': ['-ffp-contract=off'],    # the rule of the surface cloud, operation by operation
             'mesh_orient.hip': ['-ffp-contract=off'],   # the probes of the votes, operation by operation
-            'mesh_winding.hip': []}               # default contraction: its contract is a tolerance; the node positions and the far
+            'mesh_winding.hip': [],               # default contraction: its contract is a tolerance; the node positions and the far
                                                         # test switch contraction off in their own statements
+            'body_overlap.hip': []}               # default contraction: the contract on w is a tolerance, and
+                                                        # everything that decides membership (box, threshold) is a comparison
 
 
 def sources():

@@ -6,6 +6,10 @@ Same SMPL-X + SDF path as fitting (HIP operators), Habitat camera flip (:160-165
 time through the operators; ``scores_many`` / ``eval_folder_batched`` / ``evaluate_scenes`` score whole folders with one fused
 skin + sign-count launch per chunk of bodies (psi_lbs_sdf_counts) and one device -> host copy.
 
+Body against body: ``BodyOverlap`` counts, per ordered pair of a batch, the vertices of one body inside the other (psi_body_overlap_*,
+DESIGN.md section 10d), and ``select_disjoint`` picks a greedy set of bodies that do not stand in each other; the reference has no
+counterpart on the path (its BodyInterpenetration needs an external CUDA package).
+
 Diversity: utils/utils_eval_diversity.py:93-104 — ``diversity_reference`` runs the reference's ``scipy.cluster.vq.kmeans`` protocol
 on the GPU (psi_kmeans_*, psi_vq); ``diversity_scores`` is the older k-means++ variant (a different algorithm, kept as it is).
 """
@@ -15,6 +19,7 @@ import os
 import pickle
 
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -171,6 +176,95 @@ class PlausibilityEvaluator:
             out[name] = (coll[lo:lo + x.shape[0]].tolist(), cont[lo:lo + x.shape[0]].tolist())
             lo += x.shape[0]
         return out
+
+
+class OverlapResult(NamedTuple):
+    counts: torch.Tensor       # [B,B] int32: counts[i,j] = vertices of body i inside body j (zero diagonal, not symmetric)
+    inside: torch.Tensor       # [B,V] bool: the vertex is inside at least one other body
+    per_body: torch.Tensor     # [B] int64: inside.sum(1)
+
+
+class BodyOverlap:
+    """Body against body: which vertices of one body of a batch lie inside another (``ops.body_overlap``).  What
+    ``BodyInterpenetration`` of the reference tree asks an external CUDA package for, as a count per ordered pair.  ``faces`` [F,3]: the
+    one topology of every body, wound outwards."""
+
+    def __init__(self, faces, device='cuda'):
+        self.device = torch.device(device)
+        f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
+        self.faces = np.ascontiguousarray(f.astype(np.int32))
+        self._handle, self._V = None, None
+
+    def _handle_for(self, V):
+        if self._handle is None or self._V != V:
+            self.close()
+            with torch.cuda.device(self.device):
+                self._handle, self._V = ops.body_overlap_create(self.faces, V), V
+        return self._handle
+
+    def close(self):
+        if getattr(self, '_handle', None):
+            ops.body_overlap_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @torch.no_grad()
+    def counts(self, verts, group=None):
+        """verts [B,V,3] fp32 on the device, world frame (``op.body_verts`` / ``BodyDecoder.verts`` / ``model(..., cam_ext=)``); ``group``
+        [B] or None: only bodies of equal group are compared (bodies of different scenes in one batch)."""
+        if group is not None:
+            group = torch.as_tensor(group, device=verts.device).to(torch.int32).contiguous()
+        counts, inside = ops.body_overlap(verts.contiguous(), self._handle_for(int(verts.shape[1])), group=group)
+        return OverlapResult(counts, inside, inside.sum(1))
+
+    @torch.no_grad()
+    def counts_of_records(self, xh72, cam_ext, evaluator_or_decoder, chunk=512, group=None):
+        """The bodies ``xh72`` [N,72] with cameras ``cam_ext`` [N,4,4] or [1,4,4], skinned in chunks of ``chunk`` as ``scores_many`` does,
+        then ONE overlap call over all N.  ``evaluator_or_decoder``: a ``PlausibilityEvaluator`` (its Habitat flip applies, as in its
+        scores) or an object with ``verts(xh72, pose)`` (the ``BodyDecoder`` of utils_show_test_results.py: ``cam_ext`` is then the pose
+        the bodies are placed with, as given)."""
+        if chunk < 1:
+            raise ValueError('counts_of_records: chunk must be >= 1')
+        src = evaluator_or_decoder
+        xh = torch.as_tensor(xh72, dtype=torch.float32, device=self.device).reshape(-1, 72)
+        cam = torch.as_tensor(np.asarray(cam_ext, np.float32) if not torch.is_tensor(cam_ext) else cam_ext, dtype=torch.float32,
+                              device=self.device).reshape(-1, 4, 4)
+        N = xh.shape[0]
+        if N < 1 or cam.shape[0] not in (1, N):
+            raise ValueError('counts_of_records: N >= 1 bodies and cam_ext [N,4,4] or [1,4,4], got %d and %s' % (N, tuple(cam.shape)))
+        if isinstance(src, PlausibilityEvaluator):
+            if src.flip:
+                cam = torch.matmul(cam, torch.diag(torch.tensor([1.0, -1.0, -1.0, 1.0], device=self.device)).unsqueeze(0))
+            xh_rec = GeometryTransformer.convert_to_3D_rot(GeometryTransformer.convert_to_6D_rot(xh))
+            skin = lambda lo, hi, c: src.op.body_verts(xh_rec[lo:hi], c)
+        else:
+            skin = lambda lo, hi, c: src.verts(xh[lo:hi], c.cpu().numpy())
+        cam = cam.expand(N, 4, 4).contiguous()
+        verts = torch.cat([skin(lo, min(N, lo + chunk), cam[lo:min(N, lo + chunk)]) for lo in range(0, N, chunk)])
+        return self.counts(verts, group)
+
+
+def select_disjoint(order, counts, max_inside=0):
+    """A greedy set of mutually compatible bodies, on the host: walk the bodies in ``order`` (e.g. best plausibility first) and keep body i
+    iff counts[i,k] + counts[k,i] <= max_inside for every body k already kept.  ``counts`` [B,B]: ``OverlapResult.counts`` (a tensor or an
+    array).  Returns the kept indices in ``order``'s order."""
+    c = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+    if c.ndim != 2 or c.shape[0] != c.shape[1]:
+        raise ValueError('select_disjoint: counts is [B,B], got %s' % (c.shape,))
+    c = c.astype(np.int64)
+    kept = []
+    for i in order:
+        i = int(i)
+        if not 0 <= i < c.shape[0]:
+            raise ValueError('select_disjoint: body %d outside [0, %d)' % (i, c.shape[0]))
+        if i not in kept and all(c[i, k] + c[k, i] <= max_inside for k in kept):
+            kept.append(i)
+    return kept
 
 
 class KMeansRestarts:

@@ -146,6 +146,15 @@ SIGNATURES = {
     'psi_flood_fill': (c_int, [c_void_p] + [c_int] * 3 + [c_void_p, c_int] + [c_void_p] * 3),
     'psi_mesh_orient_votes': (c_int, [c_void_p] * 2 + [ctypes.c_longlong, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 3 + [c_int, c_float]
                               + [c_void_p] * 2),
+    'psi_body_overlap_create': (c_int, [c_void_p] * 2 + [c_int] * 2),
+    'psi_body_overlap_destroy': (None, [c_void_p]),
+    'psi_body_overlap_info': (c_int, [c_void_p] * 2),
+    'psi_body_overlap_workspace_bytes': (c_size_t, [ctypes.c_longlong, c_int]),
+    'psi_body_overlap_boxes': (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 3),
+    'psi_body_overlap_count': (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 3),
+    'psi_body_overlap_emit': (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 4 + [ctypes.c_longlong] * 2 + [c_void_p] * 3),
+    'psi_body_overlap_wind': (c_int, [c_void_p] * 2 + [c_int, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_size_t, c_void_p]),
+    'psi_body_overlap_decide': (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_size_t] + [c_void_p] * 4),
 }
 
 

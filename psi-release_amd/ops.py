@@ -1358,3 +1358,103 @@ def mesh_orient_votes(points, tri, verts, faces, free, grid_min, grid_max, delta
         hip.check(hip.lib().psi_mesh_orient_votes(pp, pt, int(points.shape[0]), pv, nv, pf, nf, hip.ptr(mask), lo, hi, dim, delta, hip.ptr(votes),
                                                   hip.stream()), 'psi_mesh_orient_votes')
     return votes
+
+
+# ------------------------------------------------------------------------------------------
+# Body against body: interpenetration counts of a batch (psi_body_overlap_*)
+# ------------------------------------------------------------------------------------------
+BODY_OVERLAP_CHUNK = 256
+BODY_OVERLAP_MAX_CANDIDATES = 2 ** 31 - 1
+
+
+def body_overlap_create(faces, V):
+    """faces [F,3] int32 (a tensor on any device, or an array), the one topology of every body, wound outwards; V vertices per body.  Returns
+    the ``psi_body_overlap`` handle (free it with ``body_overlap_destroy``).  ``ValueError`` for a wrong dtype or shape; ``PsiHipError``
+    for what the library refuses: F < 1, a face index outside [0, V)."""
+    import ctypes
+    import numpy as np
+    f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
+    if f.dtype != np.int32 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError('expected faces [F,3] int32')
+    f = np.ascontiguousarray(f)
+    h = ctypes.c_void_p()
+    hip.check(hip.lib().psi_body_overlap_create(ctypes.byref(h), f.ctypes.data_as(ctypes.c_void_p), int(V), int(f.shape[0])),
+              'psi_body_overlap_create')
+    return h
+
+
+def body_overlap_destroy(handle):
+    if handle:
+        hip.lib().psi_body_overlap_destroy(handle)
+
+
+def body_overlap(verts, faces_handle_or_tensor, group=None, return_candidates=False):
+    """Which vertices of one body of a batch lie inside another body of the batch (include/psi_hip.h: psi_body_overlap_*; DESIGN.md
+    section 10d).  verts [B,V,3] fp32 on the GPU, world frame; ``faces_handle_or_tensor``: a handle of ``body_overlap_create`` or faces
+    [F,3] int32 (a handle is then made and freed by the call); ``group`` [B] int32 on the GPU or None: only bodies of equal group are
+    compared.  Returns counts [B,B] int32 (counts[i,j] = vertices of i inside j; zero diagonal, not symmetric) and inside [B,V] bool
+    (inside at least one other body), with ``return_candidates`` also cand [n,3] int32 in ascending (i, j, v) order and w [n] fp32: all
+    on the device.
+
+    The kernels run on the current stream; the two scans (``torch.cumsum``, int64) are plumbing, and one read-back returns the number of
+    candidates, the number of 256-candidate chunks and the non-finite flag: the call's only host synchronisation.  ``ValueError`` for
+    wrong dtypes, shapes or devices, for a non-finite vertex (it names the first such body) and for more than 2^31 - 1 candidates;
+    ``PsiHipError`` for what the library refuses, CPU tensors included."""
+    import ctypes
+    if not torch.is_tensor(verts) or verts.dtype != torch.float32 or verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
+        raise ValueError('expected verts [B,V,3] float32')
+    B, V = int(verts.shape[0]), int(verts.shape[1])
+    dev = verts.device
+    if group is not None and (not torch.is_tensor(group) or group.dtype != torch.int32 or tuple(group.shape) != (B,) or group.device != dev):
+        raise ValueError('expected group [%d] int32 on the device of verts' % B)
+    pv, pg = hip.ptr(verts), hip.ptr(group)
+    if B < 1:
+        raise hip.PsiHipError('psi_body_overlap: B >= 1')
+    L = hip.lib()
+    own = torch.is_tensor(faces_handle_or_tensor)
+    with torch.cuda.device(dev):
+        handle = body_overlap_create(faces_handle_or_tensor, V) if own else faces_handle_or_tensor
+        try:
+            info = (ctypes.c_int32 * 2)()
+            hip.check(L.psi_body_overlap_info(handle, info), 'psi_body_overlap_info')
+            if info[0] != V:
+                raise ValueError('the handle was made for %d vertices per body, verts has %d' % (info[0], V))
+            F = int(info[1])
+            st = hip.stream()
+            boxes = torch.empty(B, 6, dtype=torch.float32, device=dev)
+            bad = torch.empty(1, dtype=torch.int32, device=dev)
+            pair_count = torch.empty(B * B, dtype=torch.int32, device=dev)
+            hip.check(L.psi_body_overlap_boxes(handle, pv, B, hip.ptr(boxes), hip.ptr(bad), st), 'psi_body_overlap_boxes')
+            hip.check(L.psi_body_overlap_count(handle, pv, pg, B, hip.ptr(boxes), hip.ptr(pair_count), st), 'psi_body_overlap_count')
+            pair_chunks = (pair_count + (BODY_OVERLAP_CHUNK - 1)) // BODY_OVERLAP_CHUNK
+            cand_inc = torch.cumsum(pair_count, 0, dtype=torch.int64)
+            chunk_inc = torch.cumsum(pair_chunks, 0, dtype=torch.int64)
+            n_cand, n_chunks, first_bad = torch.stack([cand_inc[-1], chunk_inc[-1], bad[0].to(torch.int64)]).cpu().tolist()
+            if first_bad < B:
+                raise ValueError('body %d has a non-finite vertex coordinate' % first_bad)
+            if n_cand > BODY_OVERLAP_MAX_CANDIDATES:
+                raise ValueError('the batch has %d candidates: more than 2^31 - 1' % n_cand)
+            counts = torch.zeros(B, B, dtype=torch.int32, device=dev)
+            words = (V + 31) // 32
+            mask = torch.zeros(B, words, dtype=torch.int32, device=dev)
+            cand = torch.empty(n_cand, 3, dtype=torch.int32, device=dev)
+            w = torch.empty(n_cand, dtype=torch.float32, device=dev)
+            if n_cand > 0:                      # never an empty grid
+                cand_off, chunk_off = cand_inc - pair_count, chunk_inc - pair_chunks
+                chunks = torch.empty(n_chunks, 4, dtype=torch.int32, device=dev)
+                hip.check(L.psi_body_overlap_emit(handle, pv, pg, B, hip.ptr(boxes), hip.ptr(pair_count), hip.ptr(cand_off), hip.ptr(chunk_off),
+                                                  n_cand, n_chunks, hip.ptr(cand), hip.ptr(chunks), st), 'psi_body_overlap_emit')
+                ws_bytes = int(L.psi_body_overlap_workspace_bytes(n_cand, F))
+                ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+                hip.check(L.psi_body_overlap_wind(handle, pv, B, hip.ptr(cand), n_cand, hip.ptr(chunks), n_chunks, hip.ptr(ws), ws_bytes, st),
+                          'psi_body_overlap_wind')
+                hip.check(L.psi_body_overlap_decide(handle, B, hip.ptr(cand), n_cand, hip.ptr(ws), ws_bytes, hip.ptr(w), hip.ptr(counts),
+                                                    hip.ptr(mask), st), 'psi_body_overlap_decide')
+        finally:
+            if own:
+                body_overlap_destroy(handle)
+        bit = torch.arange(V, device=dev)
+        inside = ((mask[:, bit >> 5] >> (bit & 31).to(torch.int32)) & 1).bool()
+    if return_candidates:
+        return counts, inside, cand, w
+    return counts, inside

@@ -6,7 +6,10 @@ body of GEN_FOLDER/body_gen_*.pkl drawn, shaded, into the scene mesh SCENE_PLY (
 OUT_DIR/img_%06d_cam1.png from the body's own camera — the matrix the reference transforms the body with, cam_ext . T_mat for Habitat
 trees (utils_show_test_results_habitat.py:261-265, 289), cam_ext with --no_flip for PROX-E — and with --fixed_cam as img_%06d_cam2.png
 from that overview camera; --together adds img_together.png, all bodies from the fixed camera.  OUT_DIR/visibility.json lists, per
-body, the pixels it covers and the pixels of those that the scene does not hide.  The reference's interactive window is not included."""
+body, the pixels it covers and the pixels of those that the scene does not hide.  With --disjoint [MAX_INSIDE] (it needs --together)
+img_together.png draws only the greedy set of bodies that do not stand in each other (evaluation.BodyOverlap and select_disjoint in file
+order; MAX_INSIDE vertices, default 0, are tolerated per pair), and every row of visibility.json gains ``inside_others``, the number of
+the body's vertices inside other bodies, and ``disjoint``, whether it was drawn.  The reference's interactive window is not included."""
 import argparse
 import json
 import os
@@ -45,6 +48,8 @@ def parse_args(argv=None):
     ap.add_argument('--size', type=int, nargs=2, default=[540, 960], metavar=('H', 'W'))
     ap.add_argument('--fixed_cam', nargs='+', default=None, metavar='M', help='camera-to-world pose of the overview camera: 16 numbers or a .npy')
     ap.add_argument('--together', action='store_true', help='also one image of all bodies from the fixed camera')
+    ap.add_argument('--disjoint', type=int, nargs='?', const=0, default=None, metavar='MAX_INSIDE',
+                    help='with --together: draw only bodies that do not stand in each other; MAX_INSIDE vertices are tolerated per pair')
     ap.add_argument('--no_flip', action='store_true', help='PROX-E trees: no Habitat camera flip')
     ap.add_argument('--pack', type=int, default=64, help='bodies per render call')
     ap.add_argument('--near', type=float, default=0.05)
@@ -57,6 +62,10 @@ def parse_args(argv=None):
         ap.error('--fixed_cam takes 16 numbers or one .npy file')
     if a.together and a.fixed_cam is None:
         ap.error('--together needs --fixed_cam')
+    if a.disjoint is not None and not a.together:
+        ap.error('--disjoint needs --together')
+    if a.disjoint is not None and a.disjoint < 0:
+        ap.error('--disjoint MAX_INSIDE must not be negative')
     if a.pack < 1:
         ap.error('--pack must be at least 1')
     return a
@@ -133,10 +142,17 @@ def main(argv=None):
         report += rows
     if a.together:
         verts = torch.cat(all_verts)
-        res = renderer.render(verts, fixed[None], K, (H, W), draw_body=np.arange(len(verts)), draw_view=np.zeros(len(verts), np.int64), near=a.near)
+        drawn = np.arange(len(verts))
+        if a.disjoint is not None:
+            from psi_release_amd.evaluation import BodyOverlap, select_disjoint
+            overlap = BodyOverlap(decoder.faces, device).counts(verts)
+            drawn = np.array(select_disjoint(range(len(verts)), overlap.counts, a.disjoint), np.int64)
+            for row, n_in in zip(report, overlap.per_body.cpu().tolist()):
+                row['inside_others'], row['disjoint'] = int(n_in), bool(row['body'] in drawn)
+        res = renderer.render(verts, fixed[None], K, (H, W), draw_body=drawn, draw_view=np.zeros(len(drawn), np.int64), near=a.near)
         rendering.write_png(os.path.join(a.out_dir, 'img_together.png'), res.rgb[0])
-        for row, c in zip(report, res.counts.cpu().numpy()):
-            row['together'] = {'covered': int(c[0]), 'visible': int(c[1])}
+        for b, c in zip(drawn.tolist(), res.counts.cpu().numpy()):
+            report[b]['together'] = {'covered': int(c[0]), 'visible': int(c[1])}
     with open(os.path.join(a.out_dir, 'visibility.json'), 'w') as fjson:
         json.dump(report, fjson, indent=1)
     print('[INFO] wrote %d bodies to %s' % (len(report), a.out_dir))
