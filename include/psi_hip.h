@@ -284,7 +284,9 @@ int psi_fit_profile(psi_fit_engine *engine, int n_rep, char *h_names, int name_s
  * contact class of rows "glc" / "gvpc" / "vpc" [B,3 ncp] in slot order (ncp = n_contact rounded up to 256), "spb" [B] (independent
  * bodies: each body's penetration factor -w_collision / N_b), and "penmask" [B][Vpad/64] 64-bit words = 2 floats' worth of bits
  * each, Vpad = V rounded up to 256: bit v % 64 of word v / 64 is set when vertex v of the body had sdf < 0 in the last forward, i.e. when
- * its rows of "gl" / "g_vp" may be non-zero) into d_out (device).  n_floats above a buffer's size, or an unknown name: PSI_EINVAL. */
+ * its rows of "gl" / "g_vp" may be non-zero; "gtc_part" [B, nfp, 4]: the translation gradient's contact part per 64-query slice, nfp =
+ * ceil(n_contact / 64)) — and, on every engine, the contact term's slices "fpart" [B, nfp] and the search's warm-start hints "nn_hint"
+ * (int32 bits; at least [B, n_contact], -1 = none) — into d_out (device).  n_floats above a buffer's size, or an unknown name: PSI_EINVAL. */
 int psi_fit_copy_buffer(psi_fit_engine *engine, const char *name, float *d_out, long n_floats, void *stream);
 
 /* ---------------------------------------------------------------------------------------------

@@ -689,6 +689,22 @@ static inline SdfEpilogue<SCENES> make_sdf_epilogue(const FitDev &f, const PsiSd
     return e;
 }
 
+// The per-part sums of a wave in the pair tree of search_sum_order.h (LPQ = 4: one part, psi_wave_sum's very steps; LPQ = 2: the two halves,
+// without the step across lane 32)
+template <int LPQ>
+__device__ __forceinline__ void psi_contact_part_sums(float x, float (&out)[psi_sum_parts_per_wave(LPQ)])
+{
+    x += psi_dpp<0xB1, 0xf>(x);      // quad_perm [1,0,3,2]
+    x += psi_dpp<0x4E, 0xf>(x);      // quad_perm [2,3,0,1]
+    x += psi_dpp<0x124, 0xf>(x);     // row_ror 4
+    x += psi_dpp<0x128, 0xf>(x);     // row_ror 8: every lane holds its row's total
+    x += psi_dpp<0x142, 0xa>(x);     // row_bcast 15 into rows 1 and 3: lanes 31 and 63 hold their half's total
+    if (psi_sum_part_lanes(LPQ) == 64) x += psi_dpp<0x143, 0xc>(x);     // row_bcast 31 into rows 2 and 3: lane 63 holds the wave's total
+#pragma unroll
+    for (int p = 0; p < psi_sum_parts_per_wave(LPQ); p++)
+        out[p] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), psi_sum_last_lane(LPQ, p)));
+}
+
 // ------------------------------------------------------------------------------------------------
 // Query source of the NN search inside the fused forward launch: the contact vertex is SKINNED HERE, by the query's own lane group,
 // instead of being read from `verts` — so the search does not depend on the skinning kernel and both run in ONE launch
@@ -696,21 +712,29 @@ static inline SdfEpilogue<SCENES> make_sdf_epilogue(const FitDev &f, const PsiSd
 // same packed fma as psi_blend_transforms: bit-identical to the vertex the skinning workgroups write), the three coordinates are
 // exchanged with shuffles and every lane applies translation and camera.  Weights come from a compact [n_c][64] table (one
 // contiguous 256-byte row per contact slot; zero beyond J), the body's joint transforms from LDS.
+//   LPQ = 2 (two lanes per query, 128 threads of the workgroup: nnindex_device.h): lane 0 builds rows 0 AND 2, lane 1 row 1 — the same
+// ascending-joint chains, so the query point, the gradient rows and the hints are bit-identical to the 4-lane form; the 128 threads stage the
+// transforms in three pieces each.
+template <int LPQ>
 struct ContactSkinSrc {
+    static_assert(LPQ == 2 || LPQ == 4, "the query's lane group skins its own vertex with 2 or 4 lanes");
+    static constexpr int NT = psikd::kd_threads(LPQ);             // threads of the workgroup that are present
+    static constexpr int NST = (PSI_JP * 6 + NT - 1) / NT;        // pieces of the body's transforms per thread: 2 (256 threads) or 3 (128)
+    static constexpr int CT0 = LPQ == 2 ? 80 : 128;               // first of the 15 threads that fetch the camera / translation: their last piece is beyond J <= 56
     FitDev f;
     LbsDev m;
     const float *As, *v_posed;
     psi_f2 (*sA)[6];
     // The source's loads in TWO dependent rounds (round 3 had six in a row in front of the search: winner index, winner coordinates, two
     // load -> LDS-store trips of the transform staging loop, then contact id + weight row, then posed vertex + translation + camera):
-    //   issue()   this thread's two pieces of the body's transforms, the slot's vertex id            (with the caller's hint load)
-    //             + one entry of the body's camera / translation per thread 128 .. 142
+    //   issue()   this thread's two (three) pieces of the body's transforms, the slot's vertex id    (with the caller's hint load)
+    //             + one entry of the body's camera / translation per thread CT0 .. CT0 + 14
     //   fetch()   the posed vertex (needs the id)                                                    (with the caller's winner coordinates)
     //   prepare() transforms, camera, translation -> LDS, barrier;   point() the weight row (slot-indexed) and the arithmetic
     // = two rounds + the weight row in front of the search where there were six (camera and translation come back from LDS: as per-lane
     // loads the scheduler sank them behind the blend, as scalar loads the kernel spilled 221 registers).
-    psi_f2 st[2];
-    float ct;                     // threads 128 .. 142 of the workgroup: one entry of the body's camera (12) / translation (3), staged with the transforms
+    psi_f2 st[NST];
+    float ct;                     // threads CT0 .. CT0 + 14 of the workgroup: one entry of the body's camera (12) / translation (3), staged with the transforms
     int v;
     float px, py, pz;
     float *sCT;
@@ -724,16 +748,18 @@ struct ContactSkinSrc {
     float gvm = 0.0f;                     // max |g_vposed entry| of this lane's contact row
     float gs[3] = {0.0f, 0.0f, 0.0f};     // this lane's g_local (lane 0 of a group with a query; 0 elsewhere): summed per workgroup for the translation gradient
     int bq = 0;
-    __device__ __forceinline__ void issue(int b, int j)
+    bool live = false;                    // the group has a query (issue); only the 2-lane form looks at it
+    __device__ __forceinline__ void issue(int b, int j, bool active)
     {
         jslot = j;
         bq = b;
+        live = active;
 #pragma unroll
-        for (int q = 0; q < 2; q++) {
-            const int idx = threadIdx.x + q * 256;
+        for (int q = 0; q < NST; q++) {
+            const int idx = threadIdx.x + q * NT;
             st[q] = idx < m.J * 6 ? psi_ld<psi_f2>(As + (size_t)b * m.J * 12, (unsigned)idx * 8u) : (psi_f2){0.0f, 0.0f};
         }
-        const int k = (int)threadIdx.x - 128;                // (the second transform piece of these threads is beyond J: they have a load slot free)
+        const int k = (int)threadIdx.x - CT0;                // (the last transform piece of these threads is beyond J: they have a load slot free)
         ct = 0.0f;
         if (k >= 0 && k < 12) ct = f.cam[(size_t)b * 16 + k];
         else if (k >= 12 && k < 15) ct = f.transl[(size_t)b * 3 + (k - 12)];
@@ -753,13 +779,13 @@ struct ContactSkinSrc {
     {
         psi_f2 (*sA_)[6] = psi_transform_stage<1>()[0];           // (shared with the skinning workgroups of the launch: lbs_device.h)
         __shared__ float sCT_[16];
-        __shared__ float sTR_[psikd::QPB][9];
+        __shared__ float sTR_[psikd::kd_qpb(LPQ)][9];
 #pragma unroll
-        for (int q = 0; q < 2; q++) {
-            const int idx = threadIdx.x + q * 256;
+        for (int q = 0; q < NST; q++) {
+            const int idx = threadIdx.x + q * NT;
             if (idx < PSI_JP * 6) (&sA_[0][0])[idx] = st[q];             // rows beyond J: zeros (issue)
         }
-        const int k = (int)threadIdx.x - 128;
+        const int k = (int)threadIdx.x - CT0;
         if (k >= 0 && k < 16) sCT_[k] = ct;
         __syncthreads();
         sA = sA_;
@@ -768,6 +794,40 @@ struct ContactSkinSrc {
     }
     __device__ __forceinline__ void point(int b, int j, int c, float &qx, float &qy, float &qz) const
     {
+        if constexpr (LPQ == 2) {
+            // lane c: row c in (T0, T1); both lanes: row 2 in (U0, U1) — lane 1's copy is not used
+            const f4 *wrow = (const f4 *)(f.Wct + (size_t)j * PSI_JP);
+            psi_f2 T0 = {0.0f, 0.0f}, T1 = {0.0f, 0.0f}, U0 = {0.0f, 0.0f}, U1 = {0.0f, 0.0f};
+#pragma unroll
+            for (int q = 0; q < NWQ; q++) {
+                const f4 w4 = q < NWE ? wq[q] : wrow[q];
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    const psi_f2 w2 = {w4[t], w4[t]};
+                    T0 = __builtin_elementwise_fma(w2, sA[q * 4 + t][2 * c], T0);
+                    T1 = __builtin_elementwise_fma(w2, sA[q * 4 + t][2 * c + 1], T1);
+                    U0 = __builtin_elementwise_fma(w2, sA[q * 4 + t][4], U0);
+                    U1 = __builtin_elementwise_fma(w2, sA[q * 4 + t][5], U1);
+                }
+            }
+            if (f.fused_bwd) {
+                float *tr = sTR[threadIdx.x / LPQ];
+                tr[3 * c] = T0.x; tr[3 * c + 1] = T0.y; tr[3 * c + 2] = T1.x;
+                if (c == 0) { tr[6] = U0.x; tr[7] = U0.y; tr[8] = U1.x; }
+                // the posed vertex's copy in slot order (contact_post's third store in the 4-lane form) leaves HERE: held across the search
+                // its three registers were the kernel's only spill
+                if (c == 0 && live) psi_st(f.vpc + (size_t)b * f.ncp3, (unsigned)j * 12u, psi_p3{px, py, pz});
+            }
+            const float xr = psi_dot3p(T0.x, T0.y, T1.x, T1.y, px, py, pz) + sCT[12 + c];
+            const float xr2 = psi_dot3p(U0.x, U0.y, U1.x, U1.y, px, py, pz) + sCT[14];
+            const int base = (threadIdx.x & 63) & ~1;
+            const float x = __shfl(xr, base, 64), y = __shfl(xr, base + 1, 64), z = __shfl(xr2, base, 64);
+            const float *C = sCT;
+            qx = psi_dot3p(C[0], C[1], C[2], C[3], x, y, z);
+            qy = psi_dot3p(C[4], C[5], C[6], C[7], x, y, z);
+            qz = psi_dot3p(C[8], C[9], C[10], C[11], x, y, z);
+            return;
+        }
         const int r = c < 2 ? c : 2;                          // lane 3 repeats row 2 (its result is not used)
         const f4 *wrow = (const f4 *)(f.Wct + (size_t)j * PSI_JP);
         psi_f2 T0 = {0.0f, 0.0f}, T1 = {0.0f, 0.0f};
@@ -782,7 +842,7 @@ struct ContactSkinSrc {
             }
         }
         if (f.fused_bwd && c < 3) {
-            float *tr = &sTR[threadIdx.x / psikd::LPQ][3 * c];
+            float *tr = &sTR[threadIdx.x / LPQ][3 * c];
             tr[0] = T0.x; tr[1] = T0.y; tr[2] = T1.x;
         }
         float xr = psi_dot3p(T0.x, T0.y, T1.x, T1.y, px, py, pz) + sCT[12 + r];
@@ -802,42 +862,50 @@ struct ContactSkinSrc {
         if (!f.fused_bwd) return;
         const float *C = sCT;
         const float lx = psi_dot3(C[0], C[4], C[8], gx, gy, gz), ly = psi_dot3(C[1], C[5], C[9], gx, gy, gz), lz = psi_dot3(C[2], C[6], C[10], gx, gy, gz);
-        const float *R = sTR[threadIdx.x / psikd::LPQ];
+        const float *R = sTR[threadIdx.x / LPQ];
         const size_t row = (size_t)bq * f.ncp3;
         const unsigned off = (unsigned)jslot * 12u;
         psi_st(f.glc + row, off, psi_p3{lx, ly, lz});
         const float vx = psi_dot3(R[0], R[3], R[6], lx, ly, lz), vy = psi_dot3(R[1], R[4], R[7], lx, ly, lz), vz = psi_dot3(R[2], R[5], R[8], lx, ly, lz);
         psi_st(f.gvpc + row, off, psi_p3{vx, vy, vz});
         gvm = fmaxf(fabsf(vx), fmaxf(fabsf(vy), fabsf(vz)));
-        psi_st(f.vpc + row, off, psi_p3{px, py, pz});
+        if constexpr (LPQ != 2) psi_st(f.vpc + row, off, psi_p3{px, py, pz});
         gs[0] = lx; gs[1] = ly; gs[2] = lz;
     }
     __device__ __forceinline__ void contact_finish(int b, int bx, int nbx)
     {
         if (!f.fused_bwd) return;
-        __shared__ float wsum3[psikd::QBLK / 64][3];
-        __shared__ float wmax[psikd::QBLK / 64];
-        const float sx = psi_wave_sum(gs[0]), sy = psi_wave_sum(gs[1]), sz = psi_wave_sum(gs[2]);
+        // the three sums per part and slot of search_sum_order.h (the slice's value does not depend on LPQ); the maximum in any order
+        constexpr int PPW = psi_sum_parts_per_wave(LPQ);
+        __shared__ float wsum3[psi_sum_parts(LPQ)][3];
+        __shared__ float wmax[psi_sum_waves(LPQ)];
+        float sx[PPW], sy[PPW], sz[PPW];
+        psi_contact_part_sums<LPQ>(gs[0], sx);
+        psi_contact_part_sums<LPQ>(gs[1], sy);
+        psi_contact_part_sums<LPQ>(gs[2], sz);
         float mx = gvm;
 #pragma unroll
         for (int o2 = 32; o2 > 0; o2 >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o2, 64));
         if ((threadIdx.x & 63) == 0) {
-            wsum3[threadIdx.x >> 6][0] = sx;
-            wsum3[threadIdx.x >> 6][1] = sy;
-            wsum3[threadIdx.x >> 6][2] = sz;
+#pragma unroll
+            for (int p = 0; p < PPW; p++) {
+                wsum3[psi_sum_slot(LPQ, threadIdx.x >> 6, p)][0] = sx[p];
+                wsum3[psi_sum_slot(LPQ, threadIdx.x >> 6, p)][1] = sy[p];
+                wsum3[psi_sum_slot(LPQ, threadIdx.x >> 6, p)][2] = sz[p];
+            }
             wmax[threadIdx.x >> 6] = mx;
         }
         __syncthreads();
         if (threadIdx.x == 64) {
             float m2 = wmax[0];
 #pragma unroll
-            for (int w = 1; w < psikd::QBLK / 64; w++) m2 = fmaxf(m2, wmax[w]);
+            for (int w = 1; w < psi_sum_waves(LPQ); w++) m2 = fmaxf(m2, wmax[w]);
             if (m2 > 0.0f) atomicMax(f.gvbits + PSI_GV_SLOTS + (size_t)b * f.gv_sps + (bx & (f.gv_sps - 1)), __float_as_uint(m2));
         }
         if (threadIdx.x < 3) {
             float a = 0.0f;
 #pragma unroll
-            for (int w = 0; w < psikd::QBLK / 64; w++) a += wsum3[w][threadIdx.x];
+            for (int w = 0; w < psi_sum_parts(LPQ); w++) a += wsum3[w][threadIdx.x];
             f.gtc_part[((size_t)b * nbx + bx) * 4 + threadIdx.x] = a;
         }
     }
@@ -867,7 +935,8 @@ extern "C" int psi_dbg_kd_stat(int *out, int nblocks)
 template <bool SCENES>
 using SceneTrees = std::conditional_t<SCENES, const psikd::KdDev *__restrict__, psikd::KdDev>;      // one tree in the arguments / a table on the device
 
-template <int NB, bool SCENES>
+// LPQ: lanes per contact query of the search role (2 or 4: fit_decide)
+template <int NB, bool SCENES, int LPQ>
 __global__ __launch_bounds__(256, 6) void fwd_scene_kernel(FitDev f, LbsDev m, const float *__restrict__ As, const float *__restrict__ v_posed,
                                                            SceneTrees<SCENES> T, int n_kd, int nqb, int rows, float gscale, int skin_first, SdfEpilogue<SCENES> epi)
 {
@@ -902,7 +971,7 @@ __global__ __launch_bounds__(256, 6) void fwd_scene_kernel(FitDev f, LbsDev m, c
             tab = T;
             slot = epi.slot;
         } else tree = T;
-        psikd::kd_query_body<true, SCENES>(tree, ContactSkinSrc{f, m, As, v_posed, nullptr, {}, 0.0f, 0, 0.0f, 0.0f, 0.0f, nullptr, {}, 0}, f.n_c, (float *)nullptr, (int *)nullptr,
+        psikd::kd_query_body<LPQ, true, SCENES>(tree, ContactSkinSrc<LPQ>{f, m, As, v_posed, nullptr, {}, 0.0f, 0, 0.0f, 0.0f, 0.0f, nullptr, {}, 0}, f.n_c, (float *)nullptr, (int *)nullptr,
                                            f.cconst, gscale, f.fused_bwd ? (float *)nullptr : f.gq, f.fpart, f.nn_hint, rows, tab, slot, bx, b, nqb, smem_i);
     } else {
         const int i = bid;
@@ -1599,6 +1668,9 @@ __global__ void adam_reset_kernel(float *m, float *v, int *step, int n)
 
 }  // namespace
 
+#ifndef PSI_FIT_SEARCH_LANES_DEFAULT
+#define PSI_FIT_SEARCH_LANES_DEFAULT 2
+#endif
 #ifndef PSI_GRAPH_UNROLL
 #define PSI_GRAPH_UNROLL 10
 #endif
@@ -1610,7 +1682,7 @@ constexpr int GRAPH_UNROLL = PSI_GRAPH_UNROLL;
 // accepted leaves the default (0 in the int fields)
 struct FitKnobs {
     bool split_scene, keep_verts, no_fused_bwd, sdf_linear, scene_skin_first, bwdv_mb, no_pen_skip, bwd_pf1;
-    int head_cluster, skin_nb, ska_nbody;
+    int head_cluster, skin_nb, ska_nbody, search_lanes;
 #ifdef PSI_HEAD_STOPS
     int head_stop, tail_stop, skin_stop;      // tools/head_stops.sh
 #endif
@@ -1633,6 +1705,8 @@ static FitKnobs fit_read_knobs()
     if (hc == 1 || hc == 2 || hc == 4 || hc == 8) k.head_cluster = hc;
     if (getenv("PSI_SKIN_NB")) k.skin_nb = num("PSI_SKIN_NB") == 2 ? 2 : 1;
     k.ska_nbody = psi_ska_nbody_override(SKA_NBODY);
+    const int sl = num("PSI_FIT_SEARCH_LANES");
+    if (sl == 2 || sl == 4) k.search_lanes = sl;
 #ifdef PSI_HEAD_STOPS
     k.head_stop = num("PSI_HEAD_STOP");
     k.tail_stop = num("PSI_TAIL_STOP");
@@ -1644,10 +1718,11 @@ static FitKnobs fit_read_knobs()
 // The mode decisions of an engine, taken in ONE place (fit_decide, at psi_fit_create) before any buffer is sized
 struct FitModes {
     bool self_skin;               // the NN search can skin its own contact vertices (ContactSkinSrc): it does not read `verts`
-    bool merged_scene;            // skinning + SDF and the NN search in one launch (kd-tree mode, J <= 56, 4 lanes per query)
+    bool merged_scene;            // skinning + SDF and the NN search in one launch (kd-tree mode, J <= 56)
     bool keep_verts;              // the forward skinning kernel stores the camera-frame vertices (only needed when !self_skin)
     bool fused_bwd;               // the skinning backward rides on fwd_scene (see fit_bwd_joint_kernel): six launches per iteration, no per-vertex backward launch
     int skin_nb;                  // bodies per workgroup of the forward skinning + SDF kernel (1 or 2: lbs_device.h)
+    int search_lanes;             // lanes per contact query of the search role of the shared launch (2 or 4: nnindex_device.h)
     int hc;                       // workgroups per body in the head / tail kernels (FitDev::hc)
     int gv_sps;                   // slots per body and class of the rows' maxima (FitDev::gv_sps)
     PsiStreamSplit split;         // column slices of the stream workgroups of fit_bwd_joint_kernel per row class, steps per slice (ska_plan.h)
@@ -1662,7 +1737,14 @@ static FitModes fit_decide(const psi_fit_config *cfg, const FitKnobs &knobs, int
     // (Round 3 also tried the opposite arrangement — no search workgroups at all, every skinning workgroup answering the contact queries of
     // its own 256 vertices from LDS after the SDF lookup: 1312 workgroups = one occupancy round instead of two, no second skinning of the
     // query vertices.  It measured 42 us against 33: the search became a serial tail of every workgroup instead of running beside them.)
-    d.self_skin = cfg->nn_mode == 1 && J <= PSI_JP - 8 && psikd::LPQ == 4;      // the search lanes can skin their own contact vertex
+    // the search lanes can skin their own contact vertex — with 2 or 4 lanes per query, over the slices the partial sums are sized for
+    d.self_skin = cfg->nn_mode == 1 && J <= PSI_JP - 8 && psikd::kd_qpb(psikd::LPQ_OPS) == psikd::kd_qpb(2);
+    // Lanes per contact query in the shared launch (same results bit for bit; profiles/search_width_ab.txt).  Dense weight rows: 2 — the launch
+    // is bound by what its waves issue, and two lanes issue a query's uniform part once per 32 queries instead of once per 16 (0.0884 ->
+    // 0.0857 ms per iteration).  Compressed rows (the released model's 4 weights per vertex): the skinning role is short, the launch is as long
+    // as a search workgroup's chain of dependent rounds, and the narrow group's extra scan passes lengthen it (0.0878 -> 0.0913 ms): 4.
+    // PSI_FIT_SEARCH_LANES=2|4 overrides.
+    d.search_lanes = knobs.search_lanes ? knobs.search_lanes : mc.compressed_weights ? 4 : PSI_FIT_SEARCH_LANES_DEFAULT;
     d.merged_scene = d.self_skin && cfg->B <= 128 && !knobs.split_scene;
     // the vertices themselves are an output nobody reads when the search skins its own queries (the shared launch): not stored there
     // (psi_fit_copy_buffer("verts") produces them on demand); with separate launches the search reads its contact rows, which are the
@@ -1712,7 +1794,7 @@ struct FitBlob {
     }
     template <class T> void upload(T *&field, const void *src, size_t bytes) { add(field, bytes, src, 0, nullptr); }
     template <class T> void zero(T *&field, size_t bytes, const char *name = nullptr) { add(field, bytes, nullptr, 0, name); }
-    template <class T> void ones(T *&field, size_t bytes) { add(field, bytes, nullptr, 0xff, nullptr); }
+    template <class T> void ones(T *&field, size_t bytes, const char *name = nullptr) { add(field, bytes, nullptr, 0xff, name); }
 };
 
 // Launch geometry of fit_bwd_joint_kernel: fixed by the model and the batch size, so derived once (fit_plan_make, at psi_fit_create)
@@ -1923,7 +2005,7 @@ static int fit_launch_stats(psi_fit_engine *e, float *stats, hipStream_t st)
 
 // The scene stage's two launch kinds, each for one (bodies per skinning workgroup, one scene / a table of scenes); fit_scene_dispatch
 // picks the instance of an engine
-template <int NB, bool SCENES>
+template <int NB, bool SCENES, int LPQ>
 static void launch_fwd_scene(const psi_fit_engine *e, float gscale, hipStream_t st)
 {
     const FitDev &f = e->d;
@@ -1941,7 +2023,7 @@ static void launch_fwd_scene(const psi_fit_engine *e, float gscale, hipStream_t 
         T = psi_nn_index_dev(e->nn_index);
         rows = T.rows;
     }
-    hipLaunchKernelGGL((fwd_scene_kernel<NB, SCENES>), grid, dim3(256), psikd::kd_lds_bytes(rows), st, fk, e->lv.m, e->lv.A, e->lv.v_posed, T, n_kd, nqb, rows,
+    hipLaunchKernelGGL((fwd_scene_kernel<NB, SCENES, LPQ>), grid, dim3(256), psikd::kd_lds_bytes(LPQ, rows), st, fk, e->lv.m, e->lv.A, e->lv.v_posed, T, n_kd, nqb, rows,
                        gscale, skin_first, epi);
 }
 
@@ -1978,7 +2060,10 @@ static int fit_forward(psi_fit_engine *e, float *stats, hipStream_t st, FitStats
     float gscale = f.w_contact / ((f.indep ? 1.0f : (float)f.B * (float)f.world) * (float)f.n_c);
     if (e->nn_index && e->mode.merged_scene) {
         // skinning + SDF and the NN search of the contact vertices as ONE launch (fwd_scene_kernel)
-        fit_scene_dispatch(e, [&](auto nb, auto scenes) { launch_fwd_scene<decltype(nb)::value, decltype(scenes)::value>(e, gscale, st); });
+        fit_scene_dispatch(e, [&](auto nb, auto scenes) {
+            if (e->mode.search_lanes == 2) launch_fwd_scene<decltype(nb)::value, decltype(scenes)::value, 2>(e, gscale, st);
+            else launch_fwd_scene<decltype(nb)::value, decltype(scenes)::value, 4>(e, gscale, st);
+        });
         PSI_CHECK_LAUNCH("fwd_scene_kernel");
         psi_mark("fwd_scene_kernel", st);
     } else {
@@ -2227,7 +2312,7 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     T.zero(f.cverts, crows);
     T.zero(f.og, B * f.Vpad * 4 * 4);
     T.zero(f.gq, crows);
-    T.zero(f.fpart, B * f.nfp * 4);
+    T.zero(f.fpart, B * f.nfp * 4, "fpart");
     T.zero(f.penpart, B * f.nsdfblk * 2 * 4);
     T.zero(f.recpart, per_body);
     T.zero(f.vppart, per_body);
@@ -2237,7 +2322,7 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     T.zero(f.g_rot, B * J * 9 * 4, "g_rot");
     T.zero(f.history, (size_t)f.max_hist * 4 * 4);
     T.zero(e->stats_local, 256);
-    T.ones(f.nn_hint, fit_hint_bytes(f));                        // -1 = no hint
+    T.ones(f.nn_hint, fit_hint_bytes(f), "nn_hint");             // -1 = no hint
     T.zero(f.hx_o6, B * f.hc * 128 * 8);
     T.zero(f.hx_gh1, B * f.hc * NH * 8);
     T.zero(f.hx_epoch, 2 * B * 4);
@@ -2248,7 +2333,7 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
         T.zero(f.glc, slot_rows, "glc");
         T.zero(f.gvpc, slot_rows, "gvpc");
         T.zero(f.vpc, slot_rows, "vpc");
-        T.zero(f.gtc_part, B * f.nfp * 4 * 4);
+        T.zero(f.gtc_part, B * f.nfp * 4 * 4, "gtc_part");
         T.zero(f.gvbits, 2 * PSI_GV_SLOTS * 4);
         T.zero(f.WTt_c, (size_t)f.ncp * PSI_JP * 4);
         T.zero(f.dirs_ch, (size_t)f.ncp3 * mc.Kpad * 4);

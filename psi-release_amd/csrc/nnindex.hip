@@ -7,7 +7,7 @@
 //
 //   build (host, once per scene): balanced kd-tree (median split on the widest axis) collapsed three levels at a time into
 //     8-wide nodes; leaves of <= 8 points (padded to 8 records); every internal node stores the exact AABBs of its 8 children; points are re-ordered by leaf and stored as float4 {x, y, z, bitcast(original index)}.
-//   query (a GROUP of 4 lanes per query — each takes two child boxes of a node / two points of a leaf; the traversal state is
+//   query (a GROUP of 4 lanes per query, or 2: nnindex_device.h — each takes two (four) child boxes of a node / points of a leaf; the traversal state is
 //     replicated in the group's lanes, the stack is shared in LDS): depth-first, nearer child first.  A node is skipped when
 //       d2box * 0.999999f > best,  d2box = squared distance from the query to the node's AABB evaluated in fp32.
 //     Safety: for any point p in the box, d_hat(p) >= true(p) (1 - 3e-7) >= trueBox (1 - 3e-7) >= d2box_hat (1 - 3e-7)^2,
@@ -32,7 +32,7 @@ namespace {
 
 using namespace psikd;
 
-template <bool CONTACT, bool MULTI = false>
+template <int LPQ, bool CONTACT, bool MULTI = false>
 __global__ __launch_bounds__(QBLK) void kd_query_kernel(KdDev T0, const float *__restrict__ xyz1, const int *__restrict__ qidx,
                                                         long qstride, int n, float *__restrict__ dist, int *__restrict__ idx,
                                                         float cconst, float gscale, float *__restrict__ gq, float *__restrict__ fpart,
@@ -40,10 +40,24 @@ __global__ __launch_bounds__(QBLK) void kd_query_kernel(KdDev T0, const float *_
                                                         const int *__restrict__ slot = nullptr)
 {
     extern __shared__ int smem_i[];
-    kd_query_body<CONTACT, MULTI>(T0, KdQueryFromMemory{xyz1, qidx, qstride}, n, dist, idx, cconst, gscale, gq, fpart, hint, rows, tab, slot,
+    kd_query_body<LPQ, CONTACT, MULTI>(T0, KdQueryFromMemory{xyz1, qidx, qstride}, n, dist, idx, cconst, gscale, gq, fpart, hint, rows, tab, slot,
                                   (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, smem_i);
 }
 
+// Lanes per query of the stand-alone operators: LPQ_OPS, or 2 for an index (a set) created under PSI_NN_SEARCH_LANES=2 — read once, where
+// the index is created.  Same results bit for bit; the narrow group is the fused fitting engine's (fit.hip), kept reachable here for tests
+// and measurements of the search alone.
+static int kd_lanes_from_env()
+{
+    const char *v = getenv("PSI_NN_SEARCH_LANES");
+    return v && v[0] == '2' && v[1] == 0 && kd_qpb(LPQ_OPS) == kd_qpb(2) ? 2 : LPQ_OPS;     // (never across a change of the slices)
+}
+// launch(kernel instance) for an index's width
+#define PSI_KD_LAUNCH(lanes, CONTACT, MULTI, ...)                                                          \
+    do {                                                                                                   \
+        if ((lanes) == 2) hipLaunchKernelGGL((kd_query_kernel<2, CONTACT, MULTI>), __VA_ARGS__);           \
+        else hipLaunchKernelGGL((kd_query_kernel<LPQ_OPS, CONTACT, MULTI>), __VA_ARGS__);                  \
+    } while (0)
 
 struct Builder {
     const float *p;
@@ -126,6 +140,7 @@ struct Builder {
 struct psi_nn_index {
     KdDev d;
     void *blob;
+    int lanes;              // lanes per query of this index's own launches (kd_lanes_from_env)
 };
 
 extern "C" int psi_nn_index_create(psi_nn_index **out, const float *h_points, int m)
@@ -256,6 +271,7 @@ extern "C" int psi_nn_index_create(psi_nn_index **out, const float *h_points, in
     }
     psi_nn_index *ix = new psi_nn_index;
     ix->blob = blob;
+    ix->lanes = kd_lanes_from_env();
     ix->d.nodes = (const KdNode *)blob;
     ix->d.pts = (const float4 *)(blob + off_pts);
     ix->d.opts = (const float4 *)(blob + off_opts);
@@ -284,9 +300,9 @@ extern "C" int psi_nn_index_query(const psi_nn_index *ix, const float *xyz1, int
     if (B == 0 || n == 0) return 0;
     PSI_REQUIRE(xyz1 && dist1 && idx1, "null pointer");
     PSI_REQUIRE(B <= 65535, "B exceeds grid.y");
-    hipLaunchKernelGGL(kd_query_kernel<false>, dim3(psi_cdiv(n, QPB), B), dim3(QBLK), kd_lds_bytes(ix->d.rows), (hipStream_t)stream,
+    PSI_KD_LAUNCH(ix->lanes, false, false, dim3(psi_cdiv(n, kd_qpb(ix->lanes)), B), dim3(QBLK), kd_lds_bytes(ix->lanes, ix->d.rows), (hipStream_t)stream,
                        ix->d, xyz1, (const int *)nullptr, (long)n * 3, n, dist1, idx1, 0.0f, 0.0f, (float *)nullptr, (float *)nullptr,
-                       hint, ix->d.rows);
+                       hint, ix->d.rows, (const KdDev *)nullptr, (const int *)nullptr);
     PSI_CHECK_LAUNCH("kd_query_kernel");
     psi_mark("kd_query_kernel", (hipStream_t)stream);
     return 0;
@@ -296,6 +312,7 @@ struct psi_nn_index_set {
     KdDev *tab;             // device [S]
     int S;
     int rows;               // max stack rows over the set
+    int lanes;              // as psi_nn_index::lanes
 };
 
 extern "C" int psi_nn_index_set_create(psi_nn_index_set **out, const psi_nn_index *const *indices, int S)
@@ -320,6 +337,7 @@ extern "C" int psi_nn_index_set_create(psi_nn_index_set **out, const psi_nn_inde
     st->tab = tab;
     st->S = S;
     st->rows = rows;
+    st->lanes = kd_lanes_from_env();
     *out = st;
     return 0;
 }
@@ -338,7 +356,7 @@ extern "C" int psi_nn_index_set_query(const psi_nn_index_set *set, const int32_t
     if (B == 0 || n == 0) return 0;
     PSI_REQUIRE(slot && xyz1 && dist1 && idx1, "null pointer");
     PSI_REQUIRE(B <= 65535, "B exceeds grid.y");
-    hipLaunchKernelGGL((kd_query_kernel<false, true>), dim3(psi_cdiv(n, QPB), B), dim3(QBLK), kd_lds_bytes(set->rows),
+    PSI_KD_LAUNCH(set->lanes, false, true, dim3(psi_cdiv(n, kd_qpb(set->lanes)), B), dim3(QBLK), kd_lds_bytes(set->lanes, set->rows),
                        (hipStream_t)stream, KdDev(), xyz1, (const int *)nullptr, (long)n * 3, n, dist1, idx1, 0.0f, 0.0f,
                        (float *)nullptr, (float *)nullptr, (int *)nullptr, set->rows, (const KdDev *)set->tab, (const int *)slot);
     PSI_CHECK_LAUNCH("kd_query_kernel<multi>");
@@ -350,8 +368,8 @@ extern "C" int psi_nn_index_set_query(const psi_nn_index_set *set, const int32_t
 int psi_nn_index_contact(const psi_nn_index *ix, const float *verts, long vstride, const int *vid, int B, int n, float cconst,
                          float gscale, float *gq, float *fpart, int *hint, hipStream_t st)
 {
-    hipLaunchKernelGGL(kd_query_kernel<true>, dim3(psi_cdiv(n, QPB), B), dim3(QBLK), kd_lds_bytes(ix->d.rows), st, ix->d, verts, vid,
-                       vstride, n, (float *)nullptr, (int *)nullptr, cconst, gscale, gq, fpart, hint, ix->d.rows);
+    PSI_KD_LAUNCH(ix->lanes, true, false, dim3(psi_cdiv(n, kd_qpb(ix->lanes)), B), dim3(QBLK), kd_lds_bytes(ix->lanes, ix->d.rows), st, ix->d, verts, vid,
+                       vstride, n, (float *)nullptr, (int *)nullptr, cconst, gscale, gq, fpart, hint, ix->d.rows, (const KdDev *)nullptr, (const int *)nullptr);
     PSI_CHECK_LAUNCH("kd_query_kernel<contact>");
     psi_mark("kd_query_kernel", st);
     return 0;
@@ -360,11 +378,12 @@ int psi_nn_index_contact(const psi_nn_index *ix, const float *verts, long vstrid
 int psi_nn_index_contact_set(const KdDev *tab, const int *slot, int rows, const float *verts, long vstride, const int *vid, int B, int n,
                              float cconst, float gscale, float *gq, float *fpart, int *hint, hipStream_t st)
 {
-    hipLaunchKernelGGL((kd_query_kernel<true, true>), dim3(psi_cdiv(n, QPB), B), dim3(QBLK), kd_lds_bytes(rows), st, KdDev(), verts, vid,
+    // (the fused engine's own table of trees: no index object to carry a width — the operators' width)
+    hipLaunchKernelGGL((kd_query_kernel<LPQ_OPS, true, true>), dim3(psi_cdiv(n, kd_qpb(LPQ_OPS)), B), dim3(QBLK), kd_lds_bytes(LPQ_OPS, rows), st, KdDev(), verts, vid,
                        vstride, n, (float *)nullptr, (int *)nullptr, cconst, gscale, gq, fpart, hint, rows, tab, slot);
     PSI_CHECK_LAUNCH("kd_query_kernel<contact, multi>");
     psi_mark("kd_query_kernel", st);
     return 0;
 }
-int psi_nn_index_fparts(int n) { return psi_cdiv(n, QPB); }
+int psi_nn_index_fparts(int n) { return psi_cdiv(n, kd_qpb(LPQ_OPS)); }     // (kd_qpb(2) == kd_qpb(4): the slices do not depend on the width)
 psikd::KdDev psi_nn_index_dev(const psi_nn_index *ix) { return ix->d; }

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "psi_common.h"
+#include "search_sum_order.h"
 
 #ifndef PSI_SSTOP
 #define PSI_SSTOP(k)
@@ -30,10 +31,18 @@ constexpr int QBLK = 256;           // threads per workgroup
 #ifndef PSI_KD_LPQ
 #define PSI_KD_LPQ 4
 #endif
-constexpr int LPQ = PSI_KD_LPQ;     // lanes per query (8: one child box / leaf point per lane; 4: two).  Measured at B*n_c = 65536:
-                                    // 4 lanes 28.8 us cold / 23.2 warm, 8 lanes 31.4 / 22.5; the fused iteration is 1.3 us faster with 4
-constexpr int CPL = WIDE / LPQ;     // children (leaf points) per lane
-constexpr int QPB = QBLK / LPQ;     // queries per workgroup
+// Lanes per query: a template parameter LPQ of the search (8: one child box / leaf point per lane; 4: two; 2: four).  Measured at
+// B*n_c = 65536, the search as a launch of its own: 4 lanes 28.8 us cold / 23.2 warm, 8 lanes 31.4 / 22.5; the fused iteration is 1.3 us
+// faster with 4 than with 8.  LPQ_OPS is the width of the stand-alone operators (kd_query_kernel: a cold tree walk wants the wider group)
+// unless the index was created under PSI_NN_SEARCH_LANES=2; the fused fitting engine chooses its own (fit.hip: fit_decide).
+constexpr int LPQ_OPS = PSI_KD_LPQ;
+static_assert(LPQ_OPS == 4 || LPQ_OPS == 8, "PSI_KD_LPQ: 4 or 8 (2 lanes are chosen at run time)");
+constexpr int kd_cpl(int lpq) { return WIDE / lpq; }                        // children (leaf points) per lane
+// Queries per workgroup.  With 2 lanes they are the SAME 64 as with 4 — the partial sums of a workgroup are one slice of 64 queries
+// whatever the width (search_sum_order.h) — so only waves 0 and 1 of the 256 threads carry queries and the other two retire at once.
+constexpr int kd_qpb(int lpq) { return psi_sum_slice_queries(lpq); }
+constexpr int kd_threads(int lpq) { return kd_qpb(lpq) * lpq; }              // threads of the workgroup that take part in the search
+static_assert(kd_qpb(4) == QBLK / 4 && kd_qpb(8) == QBLK / 8 && kd_qpb(2) == 64 && kd_threads(2) == 128, "workgroup shapes");
 constexpr int EMPTY = (int)0x80000000;
 
 // 8-wide node (256 bytes): per child its exact AABB and its reference, 32 bytes each, so lane c of a query's 8-lane group
@@ -66,6 +75,13 @@ struct KdDev {
 };
 
 constexpr int GRID_COLS_PER_LANE = 3;       // (x,y) cell columns of the ball a lane scans per pass over the list of surviving columns ...
+#ifndef PSI_KD_GRID_COLS_2LANE
+#define PSI_KD_GRID_COLS_2LANE 3
+#endif
+// (... as the template parameter RPL of the search.  With 2 lanes per query 3 runs make a pass 6 columns, and a ball of 7-12 surviving
+// columns takes a second pass — two more dependent rounds; 6 runs keep the pass at 12 columns and measured SLOWER, 0.0901 ms per iteration
+// against 0.0857 with 3 and 0.0884 with 4 lanes: profiles/search_width_ab.txt)
+constexpr int kd_rpl(int lpq) { return lpq == 2 ? PSI_KD_GRID_COLS_2LANE : GRID_COLS_PER_LANE; }
 #ifndef PSI_KD_GRID_LIST_MAX
 #define PSI_KD_GRID_LIST_MAX 48
 #endif
@@ -96,7 +112,7 @@ __device__ __forceinline__ kd_key kd_pack(float d, int i) { return ((kd_key)(uns
 __device__ __forceinline__ float kd_key_d(kd_key k) { return __int_as_float((int)(k >> 32)); }
 __device__ __forceinline__ int kd_key_i(kd_key k) { return (int)(unsigned)k; }
 
-// minimum of the key over the LPQ (4 or 8) lanes of a group, result in every lane
+// minimum of the key over the LPQ (2, 4 or 8) lanes of a group, result in every lane
 template <int LPQ>
 __device__ __forceinline__ kd_key group_min(kd_key k)
 {
@@ -105,8 +121,9 @@ __device__ __forceinline__ kd_key group_min(kd_key k)
         kd_key k2 = ((kd_key)(unsigned)dpp_i<CTRL>((int)(k >> 32)) << 32) | (unsigned)dpp_i<CTRL>((int)(unsigned)k); \
         k = k2 < k ? k2 : k;                                                                        \
     }
+    static_assert(LPQ == 2 || LPQ == 4 || LPQ == 8, "lanes per query");
     PSI_STEP(DPP_XOR1)
-    PSI_STEP(DPP_XOR2)
+    if (LPQ >= 4) PSI_STEP(DPP_XOR2)
     if (LPQ == 8) PSI_STEP(DPP_HALF_MIRROR)
 #undef PSI_STEP
     return k;
@@ -120,17 +137,22 @@ __device__ __forceinline__ kd_key group_min(kd_key k)
 // With the child boxes / leaf points of a visit spread over the group's lanes the per-wave instruction stream shrinks several
 // fold in the box and leaf arithmetic, there are 4096-8192 waves to overlap the dependent node loads, and a wave diverges
 // over 16 (8) queries, not 64.
+//   That was written when every query walked the tree.  Since the grid scan a warm query is a seed, a ball set-up, a column list and a few
+// rounds of pair records, and most of what a search wave issues is UNIFORM over a query's lanes (the query source, the seed, the ball set-up,
+// the contact epilogue): only the column enumeration, the z-run scan and the rare tree walk split over the group.  So the width is a template
+// parameter (LPQ), and the fused fitting engine runs its warm searches with TWO lanes per query — 32 queries per wave, 64 per workgroup in two
+// waves (fit.hip: fit_decide; profiles/search_width_ab.txt) — while a stand-alone, cold search keeps the wider group (LPQ_OPS).
 // Query source: where a query point comes from.  KdQueryFromMemory reads row qidx[j] (or j) of a [rows,3] table per body; the fused
 // fitting engine substitutes a source that SKINS the contact vertex on the spot (fit.hip), so the search does not have to wait for
 // the skinning kernel.  Three phases, so that a source's loads travel in as few DEPENDENT rounds as possible (a round trip under the load
-// of the fused launch is ~2 us, and a search workgroup's life is a chain of them): issue(b, j) = loads that depend on nothing but the
+// of the fused launch is ~2 us, and a search workgroup's life is a chain of them): issue(b, j, active) = loads that depend on nothing but the
 // query's slot, fetch(b) = loads that need issue()'s results (called after the caller has ALSO issued its own first loads), prepare(b)
 // = once per workgroup with all threads present (it may use LDS and barriers), point() = the query point.
 struct KdQueryFromMemory {
     const float *xyz1;
     const int *qidx;
     long qstride;
-    __device__ __forceinline__ void issue(int, int) {}
+    __device__ __forceinline__ void issue(int, int, bool) {}
     __device__ __forceinline__ void fetch(int) {}
     __device__ __forceinline__ void prepare(int) {}
     __device__ __forceinline__ void point(int b, int j, int, float &qx, float &qy, float &qz) const
@@ -146,20 +168,24 @@ struct KdQueryFromMemory {
     __device__ __forceinline__ void contact_finish(int, int, int) {}
 };
 
-// sum of the per-group contact terms over the workgroup (fixed order) -> *out
+// sum of the per-group contact terms over the workgroup -> *out: the halving tree and the slots of search_sum_order.h, i.e. the same
+// association for every LPQ that shares the slice (2 and 4)
+template <int LPQ>
 __device__ __forceinline__ void kd_block_fsum(float fval, float *__restrict__ out)
 {
-    __shared__ float wsum[QBLK / 64];
+    __shared__ float wsum[psi_sum_parts(LPQ)];
     const int tid = threadIdx.x;
     float v = fval;
 #pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) v += __shfl_down(v, o2, 64);
-    if ((tid & 63) == 0) wsum[tid >> 6] = v;
+    for (int o2 = psi_sum_part_lanes(LPQ) / 2; o2 > 0; o2 >>= 1) v += __shfl_down(v, o2, 64);
+#pragma unroll
+    for (int p = 0; p < psi_sum_parts_per_wave(LPQ); p++)
+        if ((tid & 63) == psi_sum_first_lane(LPQ, p)) wsum[(int)psi_sum_slot(LPQ, tid >> 6, p)] = v;
     __syncthreads();
     if (tid == 0) {
         float t = 0.0f;
 #pragma unroll
-        for (int w = 0; w < QBLK / 64; w++) t += wsum[w];
+        for (int w = 0; w < psi_sum_parts(LPQ); w++) t += wsum[w];
         *out = t;
     }
 }
@@ -176,15 +202,25 @@ __device__ __forceinline__ int kd_warm_candidate(const KdDev &T, int h, float4 &
     return h;
 }
 
+// entry (obase + jq) * K + k of a per-query table of 4-byte items, K items per query: uniform base + one 32-bit lane offset
+template <class T>
+__device__ __forceinline__ T &kd_slot(T *tab, size_t obase, int jq, int K, int k)
+{
+    return *(T *)((char *)(tab + obase * K + k) + (unsigned)jq * (unsigned)(4 * K));
+}
+
 // One round of the search: the workgroup's QPB lane groups answer one query each.  (qx,qy,qz): the group's query (the same values in
 // all LPQ lanes of the group), active: the group has a query, o: its output slot (dist / idx / hint / gq index).  Returns the contact
 // term s / (s + c) of the query in lane 0 of its group (0 elsewhere) when CONTACT.  No barriers inside: groups are independent.
-template <bool CONTACT, class QSrc>
+// o == obase + jq, obase uniform over the workgroup: with two lanes per query the outputs are addressed as (uniform base) + (32-bit lane
+// offset), so that no 64-bit lane address waits in registers across the search (kd_slot).
+template <int LPQ, int RPL, bool CONTACT, class QSrc>
 __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, float qx, float qy, float qz, bool active, size_t o, float *__restrict__ dist,
                                                 int *__restrict__ idx, float cconst, float gscale, float *__restrict__ gq, int *__restrict__ hint,
-                                                int rows, int *smem_i, int h, const float4 &hp)
+                                                int rows, int *smem_i, int h, const float4 &hp, size_t obase, int jq)
 {
 #pragma clang fp contract(off)    // the distance expression (PSI_SQ3) must not be re-contracted in translation units built with contraction on
+    constexpr int CPL = kd_cpl(LPQ);
     const int tid = threadIdx.x;
     const int c = tid & (LPQ - 1);                            // my first child / leaf slot (the others: c + LPQ, ...)
     const int g = tid / LPQ;                                  // query group inside the workgroup
@@ -242,7 +278,7 @@ __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, floa
     // (no point has u outside [0, gn]: nnindex.hip puts the origin at the cloud's minimum) — is within ru of uq; if it is, the ball reaches
     // hz = sqrt(ru^2 - dxy^2) along z in that column, i.e. cells floor(uz - hz) .. floor(uz + hz).  The lanes of the group enumerate
     // the columns of the ball's bounding rectangle, the surviving ones are numbered with a ballot and handed out round-robin through
-    // the group's (idle) stack rows, so every lane scans at most GRID_COLS_PER_LANE z-runs, each one contiguous point range.
+    // the group's (idle) stack rows, so every lane scans at most RPL z-runs per pass, each one contiguous point range.
     //   Exact for the same reason the tree is: every point with computed d <= best lies in a scanned cell, every scanned point is
     // evaluated with the identical distance expression, and the lowest index among minima wins — inside a lane by scan order (a
     // strictly smaller distance replaces; an EQUAL one raises the tie flag, and a group with a flagged lane re-does the query with
@@ -293,15 +329,15 @@ __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, floa
               float bd = INFINITY;
               int bi = 0x7fffffff;
               bool tie = false;
-              // GRID_COLS_PER_LANE z-runs per lane at a time; a ball with more columns than that (a body part outside the scene's box touches
+              // RPL z-runs per lane at a time; a ball with more columns than that (a body part outside the scene's box touches
               // it in a wide, one-cell-deep cap) takes further passes over the list — each two dependent rounds, against the 12-25 of its tree walk
-              for (int s0 = 0; s0 < nsurv; s0 += GRID_COLS_PER_LANE * LPQ) {
+              for (int s0 = 0; s0 < nsurv; s0 += RPL * LPQ) {
                 // my z-runs, as ranges of PAIR records: first pair, rounds of GRID_PAIRS pairs
-                int ps[GRID_COLS_PER_LANE], nr[GRID_COLS_PER_LANE];
-                int cs[GRID_COLS_PER_LANE], ce[GRID_COLS_PER_LANE];
+                int ps[RPL], nr[RPL];
+                int cs[RPL], ce[RPL];
                 const char *csb = (const char *)T.cell_start;
 #pragma unroll
-                for (int u = 0; u < GRID_COLS_PER_LANE; u++) {     // all ranges requested together; a slot past the list re-reads entry 0
+                for (int u = 0; u < RPL; u++) {     // all ranges requested together; a slot past the list re-reads entry 0
                     const int e = stk_n[s0 + c + u * LPQ < nsurv ? s0 + c + u * LPQ : 0];
                     const unsigned base = (unsigned)(e >> 14) * (unsigned)T.gn[2];
                     cs[u] = *(const int *)(csb + ((base + ((unsigned)e >> 7 & 127u)) << 2));
@@ -310,19 +346,28 @@ __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, floa
                 int rounds = 0;
                 PSI_KD_MARK(1);
 #pragma unroll
-                for (int u = 0; u < GRID_COLS_PER_LANE; u++) {
+                for (int u = 0; u < RPL; u++) {
                     ps[u] = cs[u] >> 1;
                     nr[u] = (ce[u] > cs[u] && s0 + c + u * LPQ < nsurv) ? (((ce[u] + 1) >> 1) - ps[u] + GRID_PAIRS - 1) / GRID_PAIRS : 0;
                     rounds += nr[u];
                 }
                 // one loop over the rounds of all my runs: round t reads pairs GRID_PAIRS t + off(t) .., off = the run's first pair minus
                 // GRID_PAIRS times the rounds before it
-                static_assert(GRID_COLS_PER_LANE == 3, "the round -> pair mapping below is written for three runs");
-                const int r01 = nr[0] + nr[1];
-                const int off1 = ps[1] - GRID_PAIRS * nr[0], off2 = ps[2] - GRID_PAIRS * r01;
+                static_assert(RPL >= 2, "the round -> pair mapping below takes at least two runs");
+                int upto[RPL - 1], off[RPL];                   // upto[u]: rounds of runs 0 .. u; run u covers rounds [upto[u - 1], upto[u])
+                upto[0] = nr[0];
+                off[0] = ps[0];
+#pragma unroll
+                for (int u = 1; u < RPL; u++) {
+                    off[u] = ps[u] - GRID_PAIRS * upto[u - 1];
+                    if (u < RPL - 1) upto[u] = upto[u - 1] + nr[u];
+                }
                 for (int t = 0; t < rounds; t++) {
                     PSI_KD_STAT(ngp += 1;)
-                    const int pr = GRID_PAIRS * t + (t < nr[0] ? ps[0] : t < r01 ? off1 : off2);
+                    int offt = off[RPL - 1];
+#pragma unroll
+                    for (int u = RPL - 2; u >= 0; u--) offt = t < upto[u] ? off[u] : offt;
+                    const int pr = GRID_PAIRS * t + offt;
                     const float4 *rp = (const float4 *)((const char *)T.gpts + ((unsigned)pr << 5));
                     float4 a[GRID_PAIRS], b[GRID_PAIRS];
 #pragma unroll
@@ -381,6 +426,9 @@ __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, floa
                 ref[u] = __float_as_int(hi.z);
                 const kd_key k = kd_pack(dc[u], c + u * LPQ);
                 km = k < km ? k : km;
+                // two lanes per query: the lane's four child boxes in two rounds of two — all eight registers quads at once are what put the
+                // fused launch (fit.hip) over its register budget, and the walk is the rare path there
+                if (CPL > 2 && u == CPL / 2 - 1) __builtin_amdgcn_sched_barrier(0);
             }
             km = group_min<LPQ>(km);
             const float dmin = kd_key_d(km);
@@ -430,9 +478,15 @@ __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, floa
     PSI_KD_MARK(3);
     if (active && c == 0) {
         const int besti = kd_key_i(bestk);
-        if (dist) dist[o] = best;
-        if (idx) idx[o] = besti;
-        if (hint) hint[o] = besti;
+        if constexpr (LPQ == 2) {
+            if (dist) kd_slot(dist, obase, jq, 1, 0) = best;
+            if (idx) kd_slot(idx, obase, jq, 1, 0) = besti;
+            if (hint) kd_slot(hint, obase, jq, 1, 0) = besti;
+        } else {
+            if (dist) dist[o] = best;
+            if (idx) idx[o] = besti;
+            if (hint) hint[o] = besti;
+        }
         if (CONTACT) {
             float4 w = hp;                                    // the winner's coordinates (same values the scan used): the warm candidate's
             if (besti != h) w = T.opts[besti];                // are here already — a load only when the winner changed since the last call
@@ -441,7 +495,11 @@ __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, floa
             fval = sq / den;
             float gg = gscale * (cconst / (2.0f * sq * den * den)) * 2.0f;
             const float gx = gg * (qx - w.x), gy = gg * (qy - w.y), gz = gg * (qz - w.z);
-            if (gq) {
+            if (LPQ == 2 && gq) {
+                kd_slot(gq, obase, jq, 3, 0) = gx;
+                kd_slot(gq, obase, jq, 3, 1) = gy;
+                kd_slot(gq, obase, jq, 3, 2) = gz;
+            } else if (gq) {
                 gq[o * 3 + 0] = gx;
                 gq[o * 3 + 1] = gy;
                 gq[o * 3 + 2] = gz;
@@ -452,14 +510,18 @@ __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, floa
     return fval;
 }
 
-// body of the search for workgroup (bx, b) of an (nbx, B) grid; smem_i: QPB * rows * 8 bytes of LDS for the traversal stacks
-template <bool CONTACT, bool MULTI, class QSrc>
+// body of the search for workgroup (bx, b) of an (nbx, B) grid; smem_i: kd_qpb(LPQ) * rows * 8 bytes of LDS for the traversal stacks
+// (launched with QBLK threads for every LPQ; the threads beyond kd_threads(LPQ) — waves 2 and 3 with 2 lanes per query — leave before the
+// source's first load: the workgroup's barriers count the waves that are left)
+template <int LPQ, bool CONTACT, bool MULTI, class QSrc>
 __device__ __forceinline__ void kd_query_body(KdDev T0, QSrc qsrc, int n, float *__restrict__ dist, int *__restrict__ idx, float cconst,
                                               float gscale, float *__restrict__ gq, float *__restrict__ fpart, int *__restrict__ hint,
                                               int rows, const KdDev *__restrict__ tab, const int *__restrict__ slot, int bx, int b, int nbx,
                                               int *smem_i)
 {
+    constexpr int QPB = kd_qpb(LPQ);
     const int tid = threadIdx.x;
+    if (kd_threads(LPQ) < QBLK && tid >= kd_threads(LPQ)) return;
     const int c = tid & (LPQ - 1), g = tid / LPQ;
     const KdDev T = MULTI ? tab[slot[b]] : T0;
     const int j = bx * QPB + g;
@@ -469,22 +531,24 @@ __device__ __forceinline__ void kd_query_body(KdDev T0, QSrc qsrc, int n, float 
     float4 hp;
     // round 1: everything that depends on the slot only (the source's own loads, last iteration's winner); round 2: what those name (the
     // winner's coordinates, the source's second-level loads) — then the workgroup phase and the arithmetic
-    qsrc.issue(b, active ? j : 0);
-    const int h0 = kd_warm_hint(hint, active, o);
+    qsrc.issue(b, active ? j : 0, active);
+    const size_t obase = (size_t)b * n;
+    const int jq = active ? j : 0;
+    const int h0 = LPQ == 2 ? ((active && hint) ? kd_slot(hint, obase, jq, 1, 0) : -1) : kd_warm_hint(hint, active, o);
     qsrc.fetch(b);
     const int h = kd_warm_candidate(T, h0, hp);
     qsrc.prepare(b);
     qsrc.point(b, active ? j : 0, c, qx, qy, qz);                // every lane of the group ends up with the same point
     PSI_SSTOP(4);                                                // (dev: differential timing — the query source alone)
     PSI_KD_MARK(0);
-    const float fval = kd_query_round<CONTACT>(T, qsrc, qx, qy, qz, active, o, dist, idx, cconst, gscale, gq, hint, rows, smem_i, h, hp);
+    const float fval = kd_query_round<LPQ, kd_rpl(LPQ), CONTACT>(T, qsrc, qx, qy, qz, active, o, dist, idx, cconst, gscale, gq, hint, rows, smem_i, h, hp, obase, jq);
     if (CONTACT) {
-        kd_block_fsum(fval, fpart + (size_t)b * nbx + bx);
+        kd_block_fsum<LPQ>(fval, fpart + (size_t)b * nbx + bx);
         qsrc.contact_finish(b, bx, nbx);
     }
 }
 
-static inline size_t kd_lds_bytes(int rows) { return (size_t)QPB * rows * 8; }
+static inline size_t kd_lds_bytes(int lpq, int rows) { return (size_t)kd_qpb(lpq) * rows * 8; }
 
 }  // namespace psikd
 
