@@ -761,6 +761,59 @@ int psi_body_overlap_wind(const psi_body_overlap *h, const float *d_verts, int B
 int psi_body_overlap_decide(const psi_body_overlap *h, int B, const int32_t *d_cand, long long n_cand, const void *d_workspace,
                             size_t workspace_bytes, float *d_w, int32_t *d_counts, uint32_t *d_mask, void *stream);
 
+/* ---- Surface crossings: which pairs of triangles of the posed body surfaces of a batch properly intersect (csrc/surface_crossings.hip) ----
+ * Contract (csrc/surface_crossings_shared.h holds the statements).  d_verts [B,V,3] fp32, world frame; the faces
+ * [F,3] int32 of the handle are shared by all bodies; d_group [B] int32 or NULL; flags = 1 (self pairs) | 2 (between bodies) | 4 (brute:
+ * no body-box and no chunk-box culling):
+ *   face box   the exact min / max of the face's three vertices
+ *   candidate  an unordered pair of faces ((i,s),(j,t)), (i,s) < (j,t): between: i < j and group[i] == group[j]; self: i == j, s < t, no
+ *              shared vertex index and part_skip[face_part[s], face_part[t]] == 0; and the two closed face boxes meet
+ *   predicate  fifteen fp32 values with fixed association (no contraction): the plane values sP, sQ and the edge values D[3][3]; edge i of
+ *              P pierces Q iff sP[i], sP[i+1] are strictly of opposite sign and D[i][0..2] are all > 0 or all < 0; Q against P alike.  The
+ *              values keep their bits when P and Q swap roles
+ *   decision   the pair crosses iff events >= 1 (events = piercing edges, 0 to 6); events == 2 is regular, and only then is length the
+ *              distance of the two piercing points x = a + t (b - a), t = s_a / (s_a - s_b) (division and square root IEEE-rounded)
+ * No floating-point atomics: every output is bit-identical from run to run and the row of a pair does not depend on the rest of the batch,
+ * on the groups or on the chunk order.  The passes of one computation; the scans and the sort between them are the caller's
+ * (ops.surface_crossings):
+ *   face_order  HOST: h_order [F] = the caller's face index at every position of the chunk order: 0..F-1 without h_order_verts, else
+ *               sorted along a Morton curve (10 bits per axis) of the face centroids of h_order_verts [V,3], ties in face order
+ *   create      h_faces HOST [F,3]; h_order_verts HOST [V,3] or NULL; h_face_part HOST [F] int32 and h_part_skip HOST [P,P] uint8
+ *               (symmetric) or both NULL with P = 0.  PSI_EINVAL: F < 1, F >= 2^21, V < 1, a face index outside [0,V), a part outside [0,P)
+ *   info        info[0..3] = V, F, chunks = ceil(F / 256), P
+ *   boxes       d_chunk_boxes [B,chunks,6] and d_body_boxes [B,6] fp32 (min xyz, max xyz), *d_bad (device int32): the smallest index of a
+ *               body with a non-finite coordinate, a value >= B when there is none
+ *   tiles       a job is (i,j), i <= j, admitted by flags and groups, whose body boxes meet; a tile is (i, j, ca, cb), ca <= cb when i == j,
+ *               whose chunk boxes meet.  Count pass (d_job_off = d_tiles = NULL, n_tiles = 0): writes d_job_tiles [B,B] int32.  Emit pass:
+ *               d_job_off [B,B] int64 = the exclusive scan of d_job_tiles, n_tiles its total; writes d_tiles [n_tiles,4] int32
+ *   test        the hot pass, one workgroup per tile.  Count pass (d_tile_off = d_keys = d_events = d_length = NULL, n_pairs = 0): writes
+ *               d_tile_hits [n_tiles] int32.  Emit pass: d_tile_off [n_tiles] int64 = its exclusive scan, n_pairs its total; writes
+ *               d_keys [n_pairs] int64 = ((i F + s) B + j) F + t, d_events, d_length, in no particular order
+ *   finish      d_keys_sorted ascending, d_order [n_pairs] int64 = where each came from, d_row_start [B+1] int64 = the first sorted row
+ *               of every body i.  Writes d_pairs [n_pairs,4] = (i,s,j,t), d_events, d_length; adds into d_counts [B,B] int32 (symmetric),
+ *               d_face_mask [B, ceil(F/32)] uint32 and *d_irregular (events != 2) by integer atomics, and writes into d_contour [B,B] fp64
+ *               the lengths of the pairs of (i,j) added sequentially in pair order, mirrored: all four ZEROED BY THE CALLER
+ * No pass launches an empty grid: with n_tiles = 0 or n_pairs = 0 the caller stops.  PSI_EINVAL: a null pointer (optional ones excepted),
+ * B < 1 or B > 46340, (B F)^2 >= 2^63 (the key is one int64), n_tiles or n_pairs outside [1, 2^31). */
+typedef struct psi_surface_crossings psi_surface_crossings;
+int psi_surface_crossings_face_order(const int32_t *h_faces, int V, int F, const float *h_order_verts, int32_t *h_order);
+int psi_surface_crossings_create(psi_surface_crossings **out, const int32_t *h_faces, int V, int F, const float *h_order_verts,
+                                 const int32_t *h_face_part, const uint8_t *h_part_skip, int P);
+void psi_surface_crossings_destroy(psi_surface_crossings *h);
+int psi_surface_crossings_info(const psi_surface_crossings *h, int32_t info[4]);
+int psi_surface_crossings_boxes(const psi_surface_crossings *h, const float *d_verts, int B, float *d_chunk_boxes, float *d_body_boxes,
+                                int32_t *d_bad, void *stream);
+int psi_surface_crossings_tiles(const psi_surface_crossings *h, const int32_t *d_group, int B, int flags, const float *d_chunk_boxes,
+                                const float *d_body_boxes, int32_t *d_job_tiles, const int64_t *d_job_off, long long n_tiles,
+                                int32_t *d_tiles, void *stream);
+int psi_surface_crossings_test(const psi_surface_crossings *h, const float *d_verts, int B, const int32_t *d_tiles, long long n_tiles,
+                               int32_t *d_tile_hits, const int64_t *d_tile_off, long long n_pairs, int64_t *d_keys, int32_t *d_events,
+                               float *d_length, void *stream);
+int psi_surface_crossings_finish(const psi_surface_crossings *h, int B, const int64_t *d_keys_sorted, const int64_t *d_order,
+                                 const int32_t *d_events_in, const float *d_length_in, long long n_pairs, const int64_t *d_row_start,
+                                 int32_t *d_pairs, int32_t *d_events, float *d_length, int32_t *d_counts, double *d_contour,
+                                 uint32_t *d_face_mask, int32_t *d_irregular, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

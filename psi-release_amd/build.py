@@ -38,6 +38,8 @@ PER_FILE = {'chamfer.hip': ['-ffp-contract=off', '-fno-slp-vectorize'], 'nnindex
             'mesh_orient.hip': ['-ffp-contract=off'],   # the probes of the votes, operation by operation
             'mesh_winding.hip': [],               # default contraction: its contract is a tolerance; the node positions and the far
                                                         # test switch contraction off in their own statements
+            # the fifteen values of a pair, the division and the square root, rounding for rounding
+            'surface_crossings.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
             'body_overlap.hip': []}               # default contraction: the contract on w is a tolerance, and
                                                         # everything that decides membership (box, threshold) is a comparison
 

@@ -1,0 +1,506 @@
+// Surface crossings: which pairs of triangles of the posed body surfaces of a batch properly intersect, for gfx950 (wave64).  The contract is
+// DESIGN.md section 10e; the per-pair statements are csrc/surface_crossings_shared.h.  This file is compiled with -ffp-contract=off.
+//
+//   candidate  an unordered pair of faces ((i, s), (j, t)), (i, s) < (j, t): bodies i < j of one group (between), or two faces s < t of one
+//              body that share no vertex index and whose parts are not skipped (self); and the closed face boxes meet
+//   decision   the pair crosses iff at least one edge of one triangle pierces the other (sc_pair); events == 2 is the regular case
+//
+// The handle keeps the faces in chunks of 256, in face order or along a Morton curve of a representative pose; results are reported in the
+// caller's face indices.  Passes: boxes (chunk boxes, body boxes, the non-finite flag), tile_count / tile_emit (a job is a pair of bodies
+// i <= j, a tile a pair of chunks of a job whose boxes meet; offsets from the caller's scan), test (the hot pass: one workgroup per tile;
+// every lane keeps one triangle of chunk ca in registers, the 256 records of chunk cb are staged in LDS and read by all lanes at the same
+// address, which broadcasts; once to count the crossing pairs of a tile, once to emit key, events and length), finish (after the caller's
+// sort of the keys: pairs, counts, face mask and irregular count by integer atomics) and contour (one workgroup per job adds the lengths
+// of its pairs in fp64, sequentially in pair order).  No floating-point atomics.
+#include "surface_crossings_shared.h"
+#include "psi_common.h"
+#include <limits.h>
+#include <algorithm>
+#include <numeric>
+#include <vector>
+
+struct psi_surface_crossings {
+    int32_t *d_faces;          // [F,3] in chunk order
+    int32_t *d_orig;           // [F] the caller's index of the face at a position
+    int32_t *d_part;           // [F] in chunk order, or null
+    uint8_t *d_skip;           // [P,P], or null
+    int V, F, P;
+};
+
+namespace psi_sc {
+
+constexpr int WG = 256;
+static_assert(WG == SC_CHUNK, "one staged record per lane");
+
+struct Tile { int i, j, ca, cb; };
+static_assert(sizeof(Tile) == 16, "the tile table is [n_tiles,4] int32");
+
+__device__ __forceinline__ int block_sum(int v, int *s_w)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int t = threadIdx.x;
+    __syncthreads();                           // s_w may still be read from an earlier call
+    if ((t & 63) == 0) s_w[t >> 6] = v;
+    __syncthreads();
+    return s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// min / max of lo / hi over the workgroup; lanes 0..2 write the six values to out
+__device__ __forceinline__ void block_box(float lo[3], float hi[3], float (*s_lo)[3], float (*s_hi)[3], float *__restrict__ out)
+{
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64));
+            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64));
+        }
+        if ((t & 63) == 0) {
+            s_lo[t >> 6][a] = lo[a];
+            s_hi[t >> 6][a] = hi[a];
+        }
+    }
+    __syncthreads();
+    if (t < 3) {
+        out[t] = fminf(fminf(s_lo[0][t], s_lo[1][t]), fminf(s_lo[2][t], s_lo[3][t]));
+        out[3 + t] = fmaxf(fmaxf(s_hi[0][t], s_hi[1][t]), fmaxf(s_hi[2][t], s_hi[3][t]));
+    }
+}
+
+__device__ __forceinline__ void load_triangle(const float *__restrict__ v, const int32_t *__restrict__ f, int id[3], float p[3][3])
+{
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        id[k] = f[k];
+#pragma unroll
+        for (int a = 0; a < 3; a++) p[k][a] = v[(size_t)id[k] * 3 + a];
+    }
+}
+
+// chunk_boxes [B, n_chunks, 6] = min xyz, max xyz of the faces of a chunk; grid = (chunk, body)
+__global__ __launch_bounds__(WG) void sc_chunk_box_kernel(const float *__restrict__ verts, const int32_t *__restrict__ faces, int V, int F,
+                                                          float *__restrict__ chunk_boxes)
+{
+    __shared__ float s_lo[WG / 64][3], s_hi[WG / 64][3];
+    const int c = blockIdx.x, b = blockIdx.y, pos = c * SC_CHUNK + threadIdx.x;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (pos < F) {
+        int id[3];
+        float p[3][3];
+        load_triangle(verts + (size_t)b * V * 3, faces + (size_t)pos * 3, id, p);
+        sc_face_box(p, lo, hi);
+    }
+    block_box(lo, hi, s_lo, s_hi, chunk_boxes + ((size_t)b * gridDim.x + c) * 6);
+}
+
+// body_boxes [B,6] over the V vertices of a body (a superset of its chunk boxes); *bad = the smallest body index with a non-finite
+// coordinate.  One workgroup per body.
+__global__ __launch_bounds__(WG) void sc_body_box_kernel(const float *__restrict__ verts, int V, float *__restrict__ body_boxes, int *__restrict__ bad)
+{
+    __shared__ float s_lo[WG / 64][3], s_hi[WG / 64][3];
+    __shared__ int s_w[WG / 64];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const float *v = verts + (size_t)b * V * 3;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    int nonfinite = 0;
+    for (int k = t; k < V; k += WG) {
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const float x = v[(size_t)k * 3 + a];
+            nonfinite |= !isfinite(x);
+            lo[a] = fminf(lo[a], x);
+            hi[a] = fmaxf(hi[a], x);
+        }
+    }
+    block_box(lo, hi, s_lo, s_hi, body_boxes + (size_t)b * 6);
+    const int any_bad = block_sum(nonfinite, s_w);
+    if (t == 0 && any_bad) atomicMin(bad, b);
+}
+
+// Is (i, j) a job: admitted by the flags and the groups, and (unless brute) with meeting body boxes?
+__device__ __forceinline__ bool job_live(const float *__restrict__ body_boxes, const int *__restrict__ group, int flags, int i, int j)
+{
+    if (i > j) return false;
+    if (i == j ? !(flags & SC_SELF) : !(flags & SC_BETWEEN)) return false;
+    if (i != j && group && group[i] != group[j]) return false;
+    if (flags & SC_BRUTE) return true;
+    return sc_boxes_meet(body_boxes + (size_t)i * 6, body_boxes + (size_t)i * 6 + 3, body_boxes + (size_t)j * 6, body_boxes + (size_t)j * 6 + 3);
+}
+
+__device__ __forceinline__ bool tile_live(const float *__restrict__ chunk_boxes, int nC, int flags, int i, int j, int ca, int cb)
+{
+    if (i == j && ca > cb) return false;
+    if (flags & SC_BRUTE) return true;
+    const float *a = chunk_boxes + ((size_t)i * nC + ca) * 6, *b = chunk_boxes + ((size_t)j * nC + cb) * 6;
+    return sc_boxes_meet(a, a + 3, b, b + 3);
+}
+
+// job_tiles [B,B]: the tiles of job (i, j); every entry is written.  With tiles != null (the emit pass) the tiles are written from
+// job_off[i,j] on, in ascending (ca, cb) order.
+__global__ __launch_bounds__(WG) void sc_tile_kernel(const float *__restrict__ chunk_boxes, const float *__restrict__ body_boxes,
+                                                     const int *__restrict__ group, int B, int nC, int flags, int *__restrict__ job_tiles,
+                                                     const long long *__restrict__ job_off, long long n_tiles, Tile *__restrict__ tiles)
+{
+    __shared__ int s_w[WG / 64];
+    const int i = blockIdx.x / B, j = blockIdx.x % B, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (!job_live(body_boxes, group, flags, i, j)) {        // the same in every lane
+        if (!tiles && t == 0) job_tiles[blockIdx.x] = 0;
+        return;
+    }
+    const int total = nC * nC;
+    if (!tiles) {
+        int n = 0;
+        for (int k = t; k < total; k += WG) n += tile_live(chunk_boxes, nC, flags, i, j, k / nC, k % nC) ? 1 : 0;
+        n = block_sum(n, s_w);
+        if (t == 0) job_tiles[blockIdx.x] = n;
+        return;
+    }
+    const int want = job_tiles[blockIdx.x];
+    if (want == 0) return;
+    const long long off = job_off[blockIdx.x];
+    int done = 0;
+    for (int k0 = 0; k0 < total; k0 += WG) {
+        const int k = k0 + t;
+        const bool in = k < total && tile_live(chunk_boxes, nC, flags, i, j, k / nC, k % nC);
+        const unsigned long long m = __ballot(in);
+        if (lane == 0) s_w[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, sum = 0;
+#pragma unroll
+        for (int w = 0; w < WG / 64; w++) {
+            const int c = s_w[w];
+            before += w < wave ? c : 0;
+            sum += c;
+        }
+        const int idx = done + before + __popcll(m & ((1ull << lane) - 1ull));
+        const long long pos = off + idx;
+        if (in && idx < want && pos < n_tiles) tiles[pos] = Tile{i, j, k / nC, k % nC};
+        done += sum;
+        __syncthreads();
+    }
+}
+
+// The hot pass.  EMIT = false: tile_hits[tile] = the crossing pairs of the tile.  EMIT = true: key, events and length of every crossing
+// pair, at tile_off[tile] + a slot taken from an LDS counter (the order within a tile is free: the keys are unique and sorted afterwards).
+template <bool EMIT>
+__global__ __launch_bounds__(WG) void sc_test_kernel(const float *__restrict__ verts, const int32_t *__restrict__ faces,
+                                                     const int32_t *__restrict__ orig, const int32_t *__restrict__ part,
+                                                     const uint8_t *__restrict__ skip, int P, int B, int V, int F,
+                                                     const Tile *__restrict__ tiles, int *__restrict__ tile_hits,
+                                                     const long long *__restrict__ tile_off, long long n_pairs, long long *__restrict__ keys,
+                                                     int *__restrict__ events, float *__restrict__ length)
+{
+    // 20 KB: per staged face lo.xyz hi.x | hi.yz id0 id1 | id2 part p0.xy | p0.z p1.xyz | p2.xyz orig
+    __shared__ float4 stage[WG * 5];
+    __shared__ int s_w[WG / 64];
+    __shared__ int s_slot;
+    const int t = threadIdx.x;
+    const Tile tl = tiles[blockIdx.x];
+    const bool self = tl.i == tl.j, diagonal = self && tl.ca == tl.cb;
+    const int nst = min(SC_CHUNK, F - tl.cb * SC_CHUNK);
+    if (EMIT && t == 0) s_slot = 0;
+    if (t < nst) {
+        const int pos = tl.cb * SC_CHUNK + t;
+        int id[3];
+        float q[3][3], lo[3], hi[3];
+        load_triangle(verts + (size_t)tl.j * V * 3, faces + (size_t)pos * 3, id, q);
+        sc_face_box(q, lo, hi);
+        stage[5 * t] = make_float4(lo[0], lo[1], lo[2], hi[0]);
+        stage[5 * t + 1] = make_float4(hi[1], hi[2], __int_as_float(id[0]), __int_as_float(id[1]));
+        stage[5 * t + 2] = make_float4(__int_as_float(id[2]), __int_as_float(part ? part[pos] : 0), q[0][0], q[0][1]);
+        stage[5 * t + 3] = make_float4(q[0][2], q[1][0], q[1][1], q[1][2]);
+        stage[5 * t + 4] = make_float4(q[2][0], q[2][1], q[2][2], __int_as_float(orig[pos]));
+    }
+    const int apos = tl.ca * SC_CHUNK + t;
+    const bool live = apos < F;
+    int aid[3] = {0, 0, 0}, apart = 0, aorig = 0;
+    float p[3][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}}, alo[3], ahi[3];
+    if (live) {
+        load_triangle(verts + (size_t)tl.i * V * 3, faces + (size_t)apos * 3, aid, p);
+        apart = part ? part[apos] : 0;
+        aorig = orig[apos];
+    }
+    sc_face_box(p, alo, ahi);
+    const long long off = EMIT ? tile_off[blockIdx.x] : 0;
+    const int want = EMIT ? tile_hits[blockIdx.x] : 0;
+    __syncthreads();
+    int hits = 0;
+    if (live) {
+        const int k0 = diagonal ? t + 1 : 0;    // on a diagonal tile every unordered pair of positions once
+        for (int k = k0; k < nst; k++) {
+            const float4 r0 = stage[5 * k], r1 = stage[5 * k + 1];
+            const float blo[3] = {r0.x, r0.y, r0.z}, bhi[3] = {r0.w, r1.x, r1.y};
+            if (!sc_boxes_meet(alo, ahi, blo, bhi)) continue;
+            const float4 r2 = stage[5 * k + 2];
+            if (self) {
+                const int bid[3] = {__float_as_int(r1.z), __float_as_int(r1.w), __float_as_int(r2.x)};
+                if (sc_share_vertex(aid, bid)) continue;
+                if (skip && skip[(size_t)apart * P + __float_as_int(r2.y)]) continue;
+            }
+            const float4 r3 = stage[5 * k + 3], r4 = stage[5 * k + 4];
+            const float q[3][3] = {{r2.z, r2.w, r3.x}, {r3.y, r3.z, r3.w}, {r4.x, r4.y, r4.z}};
+            float len;
+            const int ev = sc_pair(p, q, &len);
+            if (ev == 0) continue;
+            hits++;
+            if (EMIT) {
+                const int slot = atomicAdd(&s_slot, 1);
+                const long long at = off + slot;
+                if (slot < want && at < n_pairs) {
+                    const int borig = __float_as_int(r4.w);
+                    const int s = self ? min(aorig, borig) : aorig, u = self ? max(aorig, borig) : borig;
+                    keys[at] = sc_key(tl.i, s, tl.j, u, B, F);
+                    events[at] = ev;
+                    length[at] = len;
+                }
+            }
+        }
+    }
+    if (!EMIT) {
+        hits = block_sum(hits, s_w);
+        if (t == 0) tile_hits[blockIdx.x] = hits;
+    }
+}
+
+// One lane per pair of the sorted list: the row, and integer atomics (which commute) into counts, the face mask and the irregular count
+__global__ __launch_bounds__(WG) void sc_finish_kernel(const long long *__restrict__ keys, const long long *__restrict__ order,
+                                                       const int *__restrict__ ev_in, const float *__restrict__ len_in, long long n, int B, int F,
+                                                       int mask_words, int *__restrict__ pairs, int *__restrict__ ev_out,
+                                                       float *__restrict__ len_out, int *__restrict__ counts, unsigned int *__restrict__ mask,
+                                                       int *__restrict__ irregular)
+{
+    const long long c = (long long)blockIdx.x * WG + threadIdx.x;
+    if (c >= n) return;
+    int r[4];
+    sc_unkey(keys[c], B, F, r);
+    const long long from = order[c];
+    const int ev = ev_in[from];
+#pragma unroll
+    for (int a = 0; a < 4; a++) pairs[c * 4 + a] = r[a];
+    ev_out[c] = ev;
+    len_out[c] = len_in[from];
+    atomicAdd(counts + (size_t)r[0] * B + r[2], 1);
+    if (r[0] != r[2]) atomicAdd(counts + (size_t)r[2] * B + r[0], 1);
+    atomicOr(mask + (size_t)r[0] * mask_words + (r[1] >> 5), 1u << (r[1] & 31));
+    atomicOr(mask + (size_t)r[2] * mask_words + (r[3] >> 5), 1u << (r[3] & 31));
+    if (ev != 2) atomicAdd(irregular, 1);
+}
+
+// contour [B,B] fp64: one workgroup per job (i, j), i <= j, with pairs.  The pairs of body i are rows row_start[i] .. row_start[i+1] of the
+// sorted list; the lanes find those of body j, lane 0 adds their lengths one after the other in row order.
+__global__ __launch_bounds__(WG) void sc_contour_kernel(const int *__restrict__ pairs, const float *__restrict__ length,
+                                                        const long long *__restrict__ row_start, const int *__restrict__ counts, int B,
+                                                        double *__restrict__ contour)
+{
+    __shared__ float s_len[WG];
+    __shared__ unsigned long long s_mask[WG / 64];
+    const int i = blockIdx.x / B, j = blockIdx.x % B, t = threadIdx.x;
+    if (i > j || counts[blockIdx.x] == 0) return;
+    const long long lo = row_start[i], hi = row_start[i + 1];
+    double acc = 0.0;
+    for (long long r0 = lo; r0 < hi; r0 += WG) {
+        const long long r = r0 + t;
+        const bool mine = r < hi && pairs[r * 4 + 2] == j;
+        s_len[t] = mine ? length[r] : 0.0f;
+        const unsigned long long m = __ballot(mine);
+        if ((t & 63) == 0) s_mask[t >> 6] = m;
+        __syncthreads();
+        if (t == 0)
+            for (int w = 0; w < WG / 64; w++)
+                for (unsigned long long mm = s_mask[w]; mm; mm &= mm - 1) acc += (double)s_len[w * 64 + __ffsll((long long)mm) - 1];
+        __syncthreads();
+    }
+    if (t == 0) {
+        contour[(size_t)i * B + j] = acc;
+        contour[(size_t)j * B + i] = acc;
+    }
+}
+
+template <typename T>
+static int upload(T **out, const T *src, size_t n)
+{
+    T *d = nullptr;
+    PSI_CHECK_HIP(hipMalloc((void **)&d, n * sizeof(T)));
+    hipError_t e = hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        psi_set_error("psi_surface_crossings_create: upload failed: %s", hipGetErrorString(e));
+        (void)hipFree(d);
+        return (int)e;
+    }
+    *out = d;
+    return 0;
+}
+
+}  // namespace psi_sc
+
+extern "C" int psi_surface_crossings_face_order(const int32_t *h_faces, int V, int F, const float *h_order_verts, int32_t *h_order)
+{
+    PSI_REQUIRE(h_faces && h_order, "null pointer");
+    PSI_REQUIRE(V >= 1 && F >= 1 && F < SC_MAX_F, "V >= 1 and 1 <= F < 2^21");
+    for (long long k = 0; k < (long long)F * 3; k++)
+        if (h_faces[k] < 0 || h_faces[k] >= V) {
+            psi_set_error("invalid argument: face %lld refers to vertex %d outside [0, %d)", k / 3, (int)h_faces[k], V);
+            return PSI_EINVAL;
+        }
+    std::iota(h_order, h_order + F, 0);
+    if (!h_order_verts) return 0;
+    // centroids in fp64, quantised to 10 bits per axis of their bounding box; ties keep face order
+    std::vector<double> c((size_t)F * 3);
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int f = 0; f < F; f++)
+        for (int a = 0; a < 3; a++) {
+            double s = 0.0;
+            for (int k = 0; k < 3; k++) s += (double)h_order_verts[(size_t)h_faces[(size_t)f * 3 + k] * 3 + a];
+            PSI_REQUIRE(std::isfinite(s), "order_verts is finite");
+            c[(size_t)f * 3 + a] = s;
+            lo[a] = std::min(lo[a], s);
+            hi[a] = std::max(hi[a], s);
+        }
+    std::vector<uint32_t> code((size_t)F);
+    for (int f = 0; f < F; f++) {
+        uint32_t m = 0;
+        for (int a = 0; a < 3; a++) {
+            const double w = hi[a] - lo[a];
+            const uint32_t q = w > 0.0 ? (uint32_t)std::min(1023.0, (c[(size_t)f * 3 + a] - lo[a]) / w * 1024.0) : 0u;
+            m |= sc_spread10(q) << a;
+        }
+        code[f] = m;
+    }
+    std::stable_sort(h_order, h_order + F, [&](int32_t a, int32_t b) { return code[a] < code[b]; });
+    return 0;
+}
+
+extern "C" int psi_surface_crossings_create(psi_surface_crossings **out, const int32_t *h_faces, int V, int F, const float *h_order_verts,
+                                            const int32_t *h_face_part, const uint8_t *h_part_skip, int P)
+{
+    PSI_REQUIRE(out && h_faces, "null pointer");
+    PSI_REQUIRE((h_face_part == nullptr) == (h_part_skip == nullptr), "face_part and part_skip come together");
+    PSI_REQUIRE(h_face_part ? (P >= 1 && P <= 32768) : P == 0, "1 <= P <= 32768 with parts, P = 0 without");
+    PSI_REQUIRE(F >= 1, "F >= 1");
+    std::vector<int32_t> order((size_t)F);
+    const int rc = psi_surface_crossings_face_order(h_faces, V, F, h_order_verts, order.data());
+    if (rc) return rc;
+    std::vector<int32_t> faces((size_t)F * 3), part;
+    for (int k = 0; k < F; k++)
+        for (int a = 0; a < 3; a++) faces[(size_t)k * 3 + a] = h_faces[(size_t)order[k] * 3 + a];
+    if (h_face_part) {
+        part.resize((size_t)F);
+        for (int k = 0; k < F; k++) {
+            const int32_t pt = h_face_part[order[k]];
+            if (pt < 0 || pt >= P) {
+                psi_set_error("invalid argument: face %d has part %d outside [0, %d)", (int)order[k], (int)pt, P);
+                return PSI_EINVAL;
+            }
+            part[k] = pt;
+        }
+        for (int a = 0; a < P; a++)
+            for (int b = 0; b < P; b++)
+                PSI_REQUIRE((h_part_skip[(size_t)a * P + b] != 0) == (h_part_skip[(size_t)b * P + a] != 0), "part_skip is symmetric");
+    }
+    psi_surface_crossings h{nullptr, nullptr, nullptr, nullptr, V, F, P};
+    int e = psi_sc::upload(&h.d_faces, faces.data(), faces.size());
+    if (!e) e = psi_sc::upload(&h.d_orig, order.data(), order.size());
+    if (!e && h_face_part) e = psi_sc::upload(&h.d_part, part.data(), part.size());
+    if (!e && h_face_part) e = psi_sc::upload(&h.d_skip, h_part_skip, (size_t)P * P);
+    if (e) {
+        (void)hipFree(h.d_faces), (void)hipFree(h.d_orig), (void)hipFree(h.d_part), (void)hipFree(h.d_skip);
+        return e;
+    }
+    *out = new psi_surface_crossings(h);
+    return 0;
+}
+
+extern "C" void psi_surface_crossings_destroy(psi_surface_crossings *h)
+{
+    if (!h) return;
+    (void)hipFree(h->d_faces), (void)hipFree(h->d_orig), (void)hipFree(h->d_part), (void)hipFree(h->d_skip);
+    delete h;
+}
+
+extern "C" int psi_surface_crossings_info(const psi_surface_crossings *h, int32_t info[4])
+{
+    PSI_REQUIRE(h && info, "null pointer");
+    info[0] = h->V;
+    info[1] = h->F;
+    info[2] = (h->F + SC_CHUNK - 1) / SC_CHUNK;
+    info[3] = h->P;
+    return 0;
+}
+
+#define SC_REQUIRE_B(h, B)                                                                                          \
+    PSI_REQUIRE(B >= 1 && B <= SC_MAX_B, "1 <= B <= 46340");                                                        \
+    PSI_REQUIRE((double)B * h->F * (double)B * h->F < 9.2e18, "(B * F)^2 < 2^63: the pair key is one int64")
+
+extern "C" int psi_surface_crossings_boxes(const psi_surface_crossings *h, const float *d_verts, int B, float *d_chunk_boxes,
+                                           float *d_body_boxes, int32_t *d_bad, void *stream)
+{
+    PSI_REQUIRE(h && d_verts && d_chunk_boxes && d_body_boxes && d_bad, "null pointer");
+    SC_REQUIRE_B(h, B);
+    hipStream_t st = (hipStream_t)stream;
+    const int nC = (h->F + SC_CHUNK - 1) / SC_CHUNK;
+    PSI_CHECK_HIP(hipMemsetAsync(d_bad, 0x7f, sizeof(int32_t), st));      // 0x7f7f7f7f: above every body index
+    hipLaunchKernelGGL(psi_sc::sc_chunk_box_kernel, dim3(nC, B), dim3(psi_sc::WG), 0, st, d_verts, h->d_faces, h->V, h->F, d_chunk_boxes);
+    PSI_CHECK_LAUNCH("sc_chunk_box_kernel");
+    hipLaunchKernelGGL(psi_sc::sc_body_box_kernel, dim3(B), dim3(psi_sc::WG), 0, st, d_verts, h->V, d_body_boxes, d_bad);
+    PSI_CHECK_LAUNCH("sc_body_box_kernel");
+    return 0;
+}
+
+extern "C" int psi_surface_crossings_tiles(const psi_surface_crossings *h, const int32_t *d_group, int B, int flags, const float *d_chunk_boxes,
+                                           const float *d_body_boxes, int32_t *d_job_tiles, const int64_t *d_job_off, long long n_tiles,
+                                           int32_t *d_tiles, void *stream)
+{
+    PSI_REQUIRE(h && d_chunk_boxes && d_body_boxes && d_job_tiles, "null pointer");
+    PSI_REQUIRE((d_tiles == nullptr) == (d_job_off == nullptr), "the emit pass takes d_job_off and d_tiles, the count pass neither");
+    PSI_REQUIRE(d_tiles ? (n_tiles >= 1 && n_tiles < (1ll << 31)) : n_tiles == 0, "1 <= n_tiles < 2^31 to emit, 0 to count");
+    PSI_REQUIRE(flags >= 0 && flags < 8, "flags");
+    SC_REQUIRE_B(h, B);
+    hipLaunchKernelGGL(psi_sc::sc_tile_kernel, dim3(B * B), dim3(psi_sc::WG), 0, (hipStream_t)stream, d_chunk_boxes, d_body_boxes, d_group, B,
+                       (h->F + SC_CHUNK - 1) / SC_CHUNK, flags, d_job_tiles, (const long long *)d_job_off, n_tiles, (psi_sc::Tile *)d_tiles);
+    PSI_CHECK_LAUNCH("sc_tile_kernel");
+    return 0;
+}
+
+extern "C" int psi_surface_crossings_test(const psi_surface_crossings *h, const float *d_verts, int B, const int32_t *d_tiles, long long n_tiles,
+                                          int32_t *d_tile_hits, const int64_t *d_tile_off, long long n_pairs, int64_t *d_keys,
+                                          int32_t *d_events, float *d_length, void *stream)
+{
+    PSI_REQUIRE(h && d_verts && d_tiles && d_tile_hits, "null pointer");
+    PSI_REQUIRE(n_tiles >= 1 && n_tiles < (1ll << 31), "1 <= n_tiles < 2^31");
+    SC_REQUIRE_B(h, B);
+    const bool emit = d_keys != nullptr;
+    PSI_REQUIRE(emit ? (d_tile_off && d_events && d_length && n_pairs >= 1 && n_pairs < (1ll << 31)) : (!d_tile_off && !d_events && !d_length && n_pairs == 0),
+                "the emit pass takes d_tile_off, d_keys, d_events, d_length and 1 <= n_pairs < 2^31; the count pass none of them");
+    if (emit)
+        hipLaunchKernelGGL(psi_sc::sc_test_kernel<true>, dim3((unsigned)n_tiles), dim3(psi_sc::WG), 0, (hipStream_t)stream, d_verts, h->d_faces,
+                           h->d_orig, h->d_part, h->d_skip, h->P, B, h->V, h->F, (const psi_sc::Tile *)d_tiles, d_tile_hits,
+                           (const long long *)d_tile_off, n_pairs, (long long *)d_keys, d_events, d_length);
+    else
+        hipLaunchKernelGGL(psi_sc::sc_test_kernel<false>, dim3((unsigned)n_tiles), dim3(psi_sc::WG), 0, (hipStream_t)stream, d_verts, h->d_faces,
+                           h->d_orig, h->d_part, h->d_skip, h->P, B, h->V, h->F, (const psi_sc::Tile *)d_tiles, d_tile_hits,
+                           (const long long *)nullptr, 0ll, (long long *)nullptr, (int *)nullptr, (float *)nullptr);
+    PSI_CHECK_LAUNCH("sc_test_kernel");
+    return 0;
+}
+
+extern "C" int psi_surface_crossings_finish(const psi_surface_crossings *h, int B, const int64_t *d_keys_sorted, const int64_t *d_order,
+                                            const int32_t *d_events_in, const float *d_length_in, long long n_pairs, const int64_t *d_row_start,
+                                            int32_t *d_pairs, int32_t *d_events, float *d_length, int32_t *d_counts, double *d_contour,
+                                            uint32_t *d_face_mask, int32_t *d_irregular, void *stream)
+{
+    PSI_REQUIRE(h && d_keys_sorted && d_order && d_events_in && d_length_in && d_row_start && d_pairs && d_events && d_length && d_counts &&
+                    d_contour && d_face_mask && d_irregular, "null pointer");
+    PSI_REQUIRE(n_pairs >= 1 && n_pairs < (1ll << 31), "1 <= n_pairs < 2^31");
+    SC_REQUIRE_B(h, B);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(psi_sc::sc_finish_kernel, dim3(psi_cdiv(n_pairs, psi_sc::WG)), dim3(psi_sc::WG), 0, st, (const long long *)d_keys_sorted,
+                       (const long long *)d_order, d_events_in, d_length_in, n_pairs, B, h->F, (h->F + 31) / 32, d_pairs, d_events, d_length,
+                       d_counts, d_face_mask, d_irregular);
+    PSI_CHECK_LAUNCH("sc_finish_kernel");
+    hipLaunchKernelGGL(psi_sc::sc_contour_kernel, dim3(B * B), dim3(psi_sc::WG), 0, st, d_pairs, d_length, (const long long *)d_row_start, d_counts,
+                       B, d_contour);
+    PSI_CHECK_LAUNCH("sc_contour_kernel");
+    return 0;
+}

@@ -8,7 +8,9 @@ skin + sign-count launch per chunk of bodies (psi_lbs_sdf_counts) and one device
 
 Body against body: ``BodyOverlap`` counts, per ordered pair of a batch, the vertices of one body inside the other (psi_body_overlap_*,
 DESIGN.md section 10d), and ``select_disjoint`` picks a greedy set of bodies that do not stand in each other; the reference has no
-counterpart on the path (its BodyInterpenetration needs an external CUDA package).
+counterpart on the path (its BodyInterpenetration needs an external CUDA package).  ``SurfaceCrossings`` lists the pairs of triangles of
+the bodies' surfaces that intersect, between bodies and within one body (psi_surface_crossings_*), with
+``face_parts`` / ``part_skip_matrix`` for that class's body-part filter and ``select_uncrossed`` for the greedy choice.
 
 Diversity: utils/utils_eval_diversity.py:93-104 — ``diversity_reference`` runs the reference's ``scipy.cluster.vq.kmeans`` protocol
 on the GPU (psi_kmeans_*, psi_vq); ``diversity_scores`` is the older k-means++ variant (a different algorithm, kept as it is).
@@ -178,6 +180,30 @@ class PlausibilityEvaluator:
         return out
 
 
+def _verts_of_records(xh72, cam_ext, evaluator_or_decoder, chunk, device, what):
+    """[N,V,3] world-frame vertices of the records ``xh72`` [N,72] with cameras ``cam_ext`` [N,4,4] or [1,4,4], skinned in chunks of
+    ``chunk`` (the documentation of ``BodyOverlap.counts_of_records`` has the two kinds of ``evaluator_or_decoder``)."""
+    if chunk < 1:
+        raise ValueError(what + ': chunk must be >= 1')
+    src = evaluator_or_decoder
+    xh = torch.as_tensor(xh72, dtype=torch.float32, device=device).reshape(-1, 72)
+    cam = torch.as_tensor(np.asarray(cam_ext, np.float32) if not torch.is_tensor(cam_ext) else cam_ext, dtype=torch.float32,
+                          device=device).reshape(-1, 4, 4)
+    N = xh.shape[0]
+    if N < 1 or cam.shape[0] not in (1, N):
+        raise ValueError(what + ': N >= 1 bodies and cam_ext [N,4,4] or [1,4,4], got %d and %s' % (N, tuple(cam.shape)))
+    if isinstance(src, PlausibilityEvaluator):
+        if src.flip:
+            cam = torch.matmul(cam, torch.diag(torch.tensor([1.0, -1.0, -1.0, 1.0], device=device)).unsqueeze(0))
+        xh_rec = GeometryTransformer.convert_to_3D_rot(GeometryTransformer.convert_to_6D_rot(xh))
+        skin = lambda lo, hi, c: src.op.body_verts(xh_rec[lo:hi], c)
+    else:
+        skin = lambda lo, hi, c: src.verts(xh[lo:hi], c.cpu().numpy())
+    cam = cam.expand(N, 4, 4).contiguous()
+    verts = torch.cat([skin(lo, min(N, lo + chunk), cam[lo:min(N, lo + chunk)]) for lo in range(0, N, chunk)])
+    return verts
+
+
 class OverlapResult(NamedTuple):
     counts: torch.Tensor       # [B,B] int32: counts[i,j] = vertices of body i inside body j (zero diagonal, not symmetric)
     inside: torch.Tensor       # [B,V] bool: the vertex is inside at least one other body
@@ -228,24 +254,7 @@ class BodyOverlap:
         then ONE overlap call over all N.  ``evaluator_or_decoder``: a ``PlausibilityEvaluator`` (its Habitat flip applies, as in its
         scores) or an object with ``verts(xh72, pose)`` (the ``BodyDecoder`` of utils_show_test_results.py: ``cam_ext`` is then the pose
         the bodies are placed with, as given)."""
-        if chunk < 1:
-            raise ValueError('counts_of_records: chunk must be >= 1')
-        src = evaluator_or_decoder
-        xh = torch.as_tensor(xh72, dtype=torch.float32, device=self.device).reshape(-1, 72)
-        cam = torch.as_tensor(np.asarray(cam_ext, np.float32) if not torch.is_tensor(cam_ext) else cam_ext, dtype=torch.float32,
-                              device=self.device).reshape(-1, 4, 4)
-        N = xh.shape[0]
-        if N < 1 or cam.shape[0] not in (1, N):
-            raise ValueError('counts_of_records: N >= 1 bodies and cam_ext [N,4,4] or [1,4,4], got %d and %s' % (N, tuple(cam.shape)))
-        if isinstance(src, PlausibilityEvaluator):
-            if src.flip:
-                cam = torch.matmul(cam, torch.diag(torch.tensor([1.0, -1.0, -1.0, 1.0], device=self.device)).unsqueeze(0))
-            xh_rec = GeometryTransformer.convert_to_3D_rot(GeometryTransformer.convert_to_6D_rot(xh))
-            skin = lambda lo, hi, c: src.op.body_verts(xh_rec[lo:hi], c)
-        else:
-            skin = lambda lo, hi, c: src.verts(xh[lo:hi], c.cpu().numpy())
-        cam = cam.expand(N, 4, 4).contiguous()
-        verts = torch.cat([skin(lo, min(N, lo + chunk), cam[lo:min(N, lo + chunk)]) for lo in range(0, N, chunk)])
+        verts = _verts_of_records(xh72, cam_ext, evaluator_or_decoder, chunk, self.device, 'counts_of_records')
         return self.counts(verts, group)
 
 
@@ -263,6 +272,111 @@ def select_disjoint(order, counts, max_inside=0):
         if not 0 <= i < c.shape[0]:
             raise ValueError('select_disjoint: body %d outside [0, %d)' % (i, c.shape[0]))
         if i not in kept and all(c[i, k] + c[k, i] <= max_inside for k in kept):
+            kept.append(i)
+    return kept
+
+
+class SurfaceCrossings:
+    """Which pairs of triangles of the body surfaces of a batch properly intersect, between bodies and within one body
+    (``ops.surface_crossings``): the search and the body-part filter of the reference tree's
+    ``BodyInterpenetration`` (human_body_prior/body_model/body_model.py:460-514), without its distance-field loss.  ``faces`` [F,3]: the
+    one topology of every body; ``order_verts`` [V,3]: a representative pose (``v_template``) the faces are sorted along once;
+    ``face_part`` / ``part_skip``: ``face_parts`` and ``part_skip_matrix`` below."""
+
+    def __init__(self, faces, device='cuda', order_verts=None, face_part=None, part_skip=None):
+        self.device = torch.device(device)
+        f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
+        self.faces = np.ascontiguousarray(f.astype(np.int32))
+        as_np = lambda x, dt: None if x is None else np.ascontiguousarray((x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(dt))
+        self._order_verts, self._face_part, self._part_skip = as_np(order_verts, np.float32), as_np(face_part, np.int32), as_np(part_skip, np.uint8)
+        self._handle, self._V = None, None
+
+    def _handle_for(self, V):
+        if self._handle is None or self._V != V:
+            self.close()
+            with torch.cuda.device(self.device):
+                self._handle = ops.surface_crossings_create(self.faces, V, self._order_verts, self._face_part, self._part_skip)
+                self._V = V
+        return self._handle
+
+    def close(self):
+        if getattr(self, '_handle', None):
+            ops.surface_crossings_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @torch.no_grad()
+    def crossings(self, verts, group=None, self_pairs=True, between=True, mode='pruned'):
+        """verts [B,V,3] fp32 on the device, world frame; ``group`` [B] or None as in ``BodyOverlap.counts``.  Returns
+        ``ops.CrossingsResult``."""
+        if group is not None:
+            group = torch.as_tensor(group, device=verts.device).to(torch.int32).contiguous()
+        return ops.surface_crossings(verts.contiguous(), self._handle_for(int(verts.shape[1])), group=group, self_pairs=self_pairs,
+                                     between=between, mode=mode)
+
+    @torch.no_grad()
+    def crossings_of_records(self, xh72, cam_ext, evaluator_or_decoder, chunk=512, group=None, self_pairs=True, between=True):
+        """The bodies ``xh72`` [N,72] with cameras ``cam_ext``, skinned in chunks of ``chunk`` exactly as
+        ``BodyOverlap.counts_of_records`` skins them, then ONE crossings call over all N."""
+        verts = _verts_of_records(xh72, cam_ext, evaluator_or_decoder, chunk, self.device, 'crossings_of_records')
+        return self.crossings(verts, group, self_pairs, between)
+
+
+# the pairs of joints human_body_prior/body_model/body_model.py:488 lists for SMPL-X as additionally ignored in self contact
+SMPLX_SELF_CONTACT_PAIRS = ((9, 16), (9, 17), (6, 16), (6, 17), (1, 2), (12, 22))
+
+
+def face_parts(weights, faces):
+    """[F] int32: the part of a face is the joint with the largest sum of its three vertices' skinning weights (``weights`` [V,J], the
+    model's own), ties to the lower index."""
+    w = weights.detach().cpu().numpy() if torch.is_tensor(weights) else np.asarray(weights)
+    f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
+    if w.ndim != 2 or f.ndim != 2 or f.shape[1] != 3 or f.min() < 0 or f.max() >= w.shape[0]:
+        raise ValueError('face_parts: weights [V,J] and faces [F,3] with indices in [0, V)')
+    w = w.astype(np.float64)
+    return np.argmax(w[f[:, 0]] + w[f[:, 1]] + w[f[:, 2]], axis=1).astype(np.int32)          # argmax returns the first maximum
+
+
+def part_skip_matrix(parents, same=True, parent_child=True, extra=()):
+    """[P,P] uint8, symmetric: non-zero where self pairs of faces of the two parts are ignored: the same part, a part and its kinematic
+    parent (``parents`` [P]: the model's ``kintree_table[0]``; a root has a parent outside [0, P)), and the listed ``extra`` pairs."""
+    par = np.asarray(parents.detach().cpu().numpy() if torch.is_tensor(parents) else parents).astype(np.int64).reshape(-1)
+    P = len(par)
+    m = np.zeros((P, P), np.uint8)
+    if same:
+        m[np.arange(P), np.arange(P)] = 1
+    if parent_child:
+        for c, p in enumerate(par.tolist()):
+            if 0 <= p < P and p != c:
+                m[c, p] = m[p, c] = 1
+    for a, b in extra:
+        if not (0 <= a < P and 0 <= b < P):
+            raise ValueError('part_skip_matrix: pair (%d, %d) outside [0, %d)' % (a, b, P))
+        m[a, b] = m[b, a] = 1
+    return m
+
+
+def select_uncrossed(order, counts, max_pairs=0, max_self=None):
+    """``select_disjoint``'s walk over the crossing counts (``CrossingsResult.counts``, symmetric, self crossings on the diagonal): keep
+    body i iff counts[i,k] <= max_pairs for every body k already kept, and, with ``max_self`` given, iff counts[i,i] <= max_self.  Returns
+    the kept indices in ``order``'s order."""
+    c = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+    if c.ndim != 2 or c.shape[0] != c.shape[1]:
+        raise ValueError('select_uncrossed: counts is [B,B], got %s' % (c.shape,))
+    c = c.astype(np.int64)
+    kept = []
+    for i in order:
+        i = int(i)
+        if not 0 <= i < c.shape[0]:
+            raise ValueError('select_uncrossed: body %d outside [0, %d)' % (i, c.shape[0]))
+        if max_self is not None and c[i, i] > max_self:
+            continue
+        if i not in kept and all(c[i, k] <= max_pairs for k in kept):
             kept.append(i)
     return kept
 

@@ -155,6 +155,15 @@ SIGNATURES = {
     'psi_body_overlap_emit': (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 4 + [ctypes.c_longlong] * 2 + [c_void_p] * 3),
     'psi_body_overlap_wind': (c_int, [c_void_p] * 2 + [c_int, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_size_t, c_void_p]),
     'psi_body_overlap_decide': (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_size_t] + [c_void_p] * 4),
+    'psi_surface_crossings_face_order': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    'psi_surface_crossings_create': (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 3 + [c_int]),
+    'psi_surface_crossings_destroy': (None, [c_void_p]),
+    'psi_surface_crossings_info': (c_int, [c_void_p] * 2),
+    'psi_surface_crossings_boxes': (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 4),
+    'psi_surface_crossings_tiles': (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 4 + [ctypes.c_longlong] + [c_void_p] * 2),
+    'psi_surface_crossings_test': (c_int, [c_void_p] * 2 + [c_int, c_void_p, ctypes.c_longlong] + [c_void_p] * 2 + [ctypes.c_longlong]
+                                   + [c_void_p] * 4),
+    'psi_surface_crossings_finish': (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [ctypes.c_longlong] + [c_void_p] * 9),
 }
 
 

@@ -8,6 +8,8 @@ Inputs must live on the GPU; there is no CPU path (hip.ptr raises).
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 from torch import nn
 from torch.autograd import Function
@@ -1458,3 +1460,184 @@ def body_overlap(verts, faces_handle_or_tensor, group=None, return_candidates=Fa
     if return_candidates:
         return counts, inside, cand, w
     return counts, inside
+
+
+# ------------------------------------------------------------------------------------------
+# Surface crossings: triangle pairs of the bodies of a batch that intersect (psi_surface_crossings_*)
+# ------------------------------------------------------------------------------------------
+SURFACE_CROSSINGS_CHUNK = 256
+SURFACE_CROSSINGS_MAX = 2 ** 31 - 1             # tiles, and pairs
+SURFACE_CROSSINGS_MAX_B = 46340
+SURFACE_CROSSINGS_MAX_F = 2 ** 21
+
+
+class CrossingsResult(NamedTuple):
+    pairs: torch.Tensor        # [n,4] int32 (i, s, j, t), ascending: face s of body i crosses face t of body j
+    events: torch.Tensor       # [n] int32: piercing edges of the pair, 1 to 6; 2 is the regular case
+    length: torch.Tensor       # [n] fp32: the length of the pair's intersection segment (0 unless events == 2)
+    counts: torch.Tensor       # [B,B] int32, symmetric: crossing pairs of bodies i and j; the diagonal holds self crossings
+    contour: torch.Tensor      # [B,B] fp64, symmetric: the lengths of the pairs of (i, j) added in pair order
+    face_hit: torch.Tensor     # [B,F] bool: the face is in at least one crossing pair
+    irregular: torch.Tensor    # [] int32: pairs with events != 2
+
+
+def _host_array(x, dtype, what):
+    import numpy as np
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    if a.dtype != dtype:
+        raise ValueError('expected %s of dtype %s, got %s' % (what, np.dtype(dtype).name, a.dtype))
+    return np.ascontiguousarray(a)
+
+
+def surface_crossings_create(faces, V, order_verts=None, face_part=None, part_skip=None):
+    """faces [F,3] int32 (a tensor on any device, or an array): the one topology of every body; V vertices per body.  ``order_verts`` [V,3]
+    fp32 or None: a representative pose (``v_template``); with it the faces are sorted once along a Morton curve of their centroids into the
+    chunks of 256 the search prunes by (results are in the caller's face indices either way).  ``face_part`` [F] int32 and ``part_skip``
+    [P,P] uint8 (symmetric; non-zero: self pairs of faces of these two parts are ignored) or both None.  Returns the
+    ``psi_surface_crossings`` handle (free it with ``surface_crossings_destroy``).  ``ValueError`` for wrong dtypes or shapes, F < 1,
+    F >= 2^21, V < 1, a face index outside [0, V), a part outside [0, P), an asymmetric matrix."""
+    import ctypes
+    import numpy as np
+    f = _host_array(faces, np.int32, 'faces [F,3]')
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError('expected faces [F,3] int32')
+    F, V = int(f.shape[0]), int(V)
+    if F < 1 or F >= SURFACE_CROSSINGS_MAX_F or V < 1:
+        raise ValueError('surface_crossings_create: 1 <= F < 2^21 and V >= 1, got F = %d, V = %d' % (F, V))
+    if f.min() < 0 or f.max() >= V:
+        raise ValueError('surface_crossings_create: a face index outside [0, %d)' % V)
+    ov = fp = ps = None
+    P = 0
+    if order_verts is not None:
+        ov = _host_array(order_verts, np.float32, 'order_verts [V,3]')
+        if ov.shape != (V, 3) or not np.isfinite(ov).all():
+            raise ValueError('expected finite order_verts [%d,3] float32' % V)
+    if (face_part is None) != (part_skip is None):
+        raise ValueError('surface_crossings_create: face_part and part_skip come together')
+    if face_part is not None:
+        fp, ps = _host_array(face_part, np.int32, 'face_part [F]'), _host_array(part_skip, np.uint8, 'part_skip [P,P]')
+        P = int(ps.shape[0]) if ps.ndim == 2 else 0
+        if fp.shape != (F,) or ps.ndim != 2 or ps.shape != (P, P) or P < 1:
+            raise ValueError('expected face_part [%d] int32 and part_skip [P,P] uint8' % F)
+        if fp.min() < 0 or fp.max() >= P:
+            raise ValueError('surface_crossings_create: a face_part entry outside [0, %d)' % P)
+        if not np.array_equal(ps != 0, (ps != 0).T):
+            raise ValueError('surface_crossings_create: part_skip is not symmetric')
+    as_p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    h = ctypes.c_void_p()
+    hip.check(hip.lib().psi_surface_crossings_create(ctypes.byref(h), as_p(f), V, F, as_p(ov), as_p(fp), as_p(ps), P),
+              'psi_surface_crossings_create')
+    return h
+
+
+def surface_crossings_destroy(handle):
+    if handle:
+        hip.lib().psi_surface_crossings_destroy(handle)
+
+
+def surface_crossings(verts, handle_or_faces, group=None, self_pairs=True, between=True, mode='pruned', return_stats=False):
+    """Which pairs of triangles of the body surfaces of a batch properly intersect (include/psi_hip.h: psi_surface_crossings_*; DESIGN.md
+    section 10e).  verts [B,V,3] fp32 on the GPU, world frame; ``handle_or_faces``: a handle of ``surface_crossings_create`` or faces [F,3]
+    int32 (a handle is then made and freed by the call); ``group`` [B] int32 on the GPU or None: only bodies of equal group are compared
+    with each other; ``self_pairs``: pairs of faces of one body that share no vertex (and whose parts the handle does not skip);
+    ``between``: pairs of faces of two bodies; ``mode``: 'pruned', or 'brute', which tests every chunk pair of every admitted pair of
+    bodies and gives the same bits.  Returns a ``CrossingsResult`` on the device (with ``return_stats`` also {'tiles', 'pairs', 'box_tests'}, at the
+    price of one more read-back).
+
+    The kernels run on the current stream; two scans (``torch.cumsum``), one sort of the int64 pair keys and one ``searchsorted`` are
+    plumbing.  Two read-backs: the number of tiles with the non-finite flag, and the number of pairs.  ``ValueError`` for wrong dtypes,
+    shapes or devices, a non-finite vertex (it names the first such body), B > 46340, (B F)^2 >= 2^63 and more than 2^31 - 1 tiles or
+    pairs; ``PsiHipError`` for what the library refuses, CPU tensors included."""
+    import ctypes
+    if not torch.is_tensor(verts) or verts.dtype != torch.float32 or verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
+        raise ValueError('expected verts [B,V,3] float32')
+    if mode not in ('pruned', 'brute'):
+        raise ValueError("mode is 'pruned' or 'brute', got %r" % (mode,))
+    B, V = int(verts.shape[0]), int(verts.shape[1])
+    dev = verts.device
+    if group is not None and (not torch.is_tensor(group) or group.dtype != torch.int32 or tuple(group.shape) != (B,) or group.device != dev):
+        raise ValueError('expected group [%d] int32 on the device of verts' % B)
+    if B > SURFACE_CROSSINGS_MAX_B:
+        raise ValueError('surface_crossings: B = %d is more than %d' % (B, SURFACE_CROSSINGS_MAX_B))
+    pv, pg = hip.ptr(verts), hip.ptr(group)
+    if B < 1:
+        raise hip.PsiHipError('psi_surface_crossings: B >= 1')
+    L = hip.lib()
+    own = not isinstance(handle_or_faces, ctypes.c_void_p)
+    flags = (1 if self_pairs else 0) | (2 if between else 0) | (4 if mode == 'brute' else 0)
+    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        handle = surface_crossings_create(handle_or_faces, V) if own else handle_or_faces
+        try:
+            info = (ctypes.c_int32 * 4)()
+            hip.check(L.psi_surface_crossings_info(handle, info), 'psi_surface_crossings_info')
+            if info[0] != V:
+                raise ValueError('the handle was made for %d vertices per body, verts has %d' % (info[0], V))
+            F, nC = int(info[1]), int(info[2])
+            if (B * F) ** 2 >= 2 ** 63:
+                raise ValueError('surface_crossings: (B F)^2 = (%d x %d)^2 does not fit the int64 pair key' % (B, F))
+            st = hip.stream()
+            words = (F + 31) // 32
+            counts = torch.zeros(B, B, **i32)
+            contour = torch.zeros(B, B, dtype=torch.float64, device=dev)
+            mask = torch.zeros(B, words, **i32)
+            irregular = torch.zeros(1, **i32)
+            pairs, events = torch.empty(0, 4, **i32), torch.empty(0, **i32)
+            length = torch.empty(0, dtype=torch.float32, device=dev)
+            n_tiles = n_pairs = 0
+            if flags & 3:
+                chunk_boxes = torch.empty(B, nC, 6, dtype=torch.float32, device=dev)
+                body_boxes = torch.empty(B, 6, dtype=torch.float32, device=dev)
+                bad = torch.empty(1, **i32)
+                job_tiles = torch.empty(B * B, **i32)
+                hip.check(L.psi_surface_crossings_boxes(handle, pv, B, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(bad), st),
+                          'psi_surface_crossings_boxes')
+                hip.check(L.psi_surface_crossings_tiles(handle, pg, B, flags, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles),
+                                                        None, 0, None, st), 'psi_surface_crossings_tiles')
+                job_inc = torch.cumsum(job_tiles, 0, dtype=torch.int64)
+                n_tiles, first_bad = torch.stack([job_inc[-1], bad[0].to(torch.int64)]).cpu().tolist()          # read-back 1
+                if first_bad < B:
+                    raise ValueError('body %d has a non-finite vertex coordinate' % first_bad)
+                if n_tiles > SURFACE_CROSSINGS_MAX:
+                    raise ValueError('the batch has %d tiles: more than 2^31 - 1' % n_tiles)
+            if n_tiles > 0:                     # never an empty grid
+                tiles = torch.empty(n_tiles, 4, **i32)
+                job_off = job_inc - job_tiles
+                hip.check(L.psi_surface_crossings_tiles(handle, pg, B, flags, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles),
+                                                        hip.ptr(job_off), n_tiles, hip.ptr(tiles), st), 'psi_surface_crossings_tiles')
+                tile_hits = torch.empty(n_tiles, **i32)
+                hip.check(L.psi_surface_crossings_test(handle, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), None, 0, None, None, None, st),
+                          'psi_surface_crossings_test')
+                tile_inc = torch.cumsum(tile_hits, 0, dtype=torch.int64)
+                n_pairs = int(tile_inc[-1].item())                                                            # read-back 2
+                if n_pairs > SURFACE_CROSSINGS_MAX:
+                    raise ValueError('the batch has %d crossing pairs: more than 2^31 - 1' % n_pairs)
+            if n_pairs > 0:
+                tile_off = tile_inc - tile_hits
+                keys = torch.empty(n_pairs, **i64)
+                ev_raw = torch.empty(n_pairs, **i32)
+                len_raw = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+                hip.check(L.psi_surface_crossings_test(handle, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), hip.ptr(tile_off), n_pairs,
+                                                       hip.ptr(keys), hip.ptr(ev_raw), hip.ptr(len_raw), st), 'psi_surface_crossings_test')
+                keys_sorted, order = torch.sort(keys)
+                row_start = torch.searchsorted(keys_sorted, torch.arange(B + 1, **i64) * (F * B * F)).contiguous()
+                pairs, events = torch.empty(n_pairs, 4, **i32), torch.empty(n_pairs, **i32)
+                length = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+                hip.check(L.psi_surface_crossings_finish(handle, B, hip.ptr(keys_sorted), hip.ptr(order), hip.ptr(ev_raw), hip.ptr(len_raw), n_pairs,
+                                                         hip.ptr(row_start), hip.ptr(pairs), hip.ptr(events), hip.ptr(length), hip.ptr(counts),
+                                                         hip.ptr(contour), hip.ptr(mask), hip.ptr(irregular), st), 'psi_surface_crossings_finish')
+        finally:
+            if own:
+                surface_crossings_destroy(handle)
+        bit = torch.arange(F, device=dev)
+        face_hit = ((mask[:, bit >> 5] >> (bit & 31).to(torch.int32)) & 1).bool()
+    res = CrossingsResult(pairs, events, length, counts, contour, face_hit, irregular[0])
+    if not return_stats:
+        return res
+    box_tests = 0
+    if n_tiles > 0:                             # the (pair, box) tests the test pass executes, counted from the tile table
+        t = tiles.long()
+        na, nb = (F - t[:, 2] * SURFACE_CROSSINGS_CHUNK).clamp(max=SURFACE_CROSSINGS_CHUNK), (F - t[:, 3] * SURFACE_CROSSINGS_CHUNK).clamp(max=SURFACE_CROSSINGS_CHUNK)
+        diagonal = (t[:, 0] == t[:, 1]) & (t[:, 2] == t[:, 3])
+        box_tests = int(torch.where(diagonal, na * (na - 1) // 2, na * nb).sum().item())
+    return res, {'tiles': int(n_tiles), 'pairs': int(n_pairs), 'box_tests': box_tests}

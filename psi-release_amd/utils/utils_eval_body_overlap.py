@@ -1,13 +1,20 @@
 #!/usr/bin/env python
 """python utils_eval_body_overlap.py GEN_FOLDER [--human_model_path ... --vposer_ckpt_path ... | --synthetic DIR] [--no_flip]
-                                                 [--max_inside 0] [--out JSON]
+                                                 [--max_inside 0] [--out JSON] [--crossings [--self] [--parts]]
 
 Which bodies of GEN_FOLDER/body_gen_*.pkl stand in each other: every body is placed as utils_show_test_results.py places it (cam_ext .
 T_mat for Habitat trees, cam_ext with --no_flip for PROX-E), and every vertex of every body is tested against every other body
 (evaluation.BodyOverlap; the test is vertex-in-body and asymmetric).  Prints the number of overlapping pairs, the bodies ranked by the
 number of their vertices inside others, and the greedy set of mutually compatible bodies in file order (evaluation.select_disjoint with
 --max_inside); --out writes all of that as JSON.  The reference tree has no counterpart (its BodyInterpenetration needs an external CUDA
-package)."""
+package).
+
+--crossings adds the test of the surfaces themselves (evaluation.SurfaceCrossings: which pairs of triangles intersect): the crossing pairs
+of every pair of bodies with the length of their contour, the number of irregular pairs, and how many pairs of bodies cross although no
+vertex of either is inside the other.  --self also tests every body against itself and ranks the bodies by self crossings; --parts
+then ignores pairs of faces of the same body part, of a part and its kinematic parent and of the pairs of parts
+human_body_prior/body_model/body_model.py:488 lists, the parts taken from the model's own skinning weights and kinematic tree.  Without
+--crossings every printed line and every JSON field is what it was."""
 import argparse
 import json
 
@@ -27,7 +34,14 @@ def parse_args(argv=None):
     ap.add_argument('--max_files', type=int, default=8000)
     ap.add_argument('--chunk', type=int, default=512, help='bodies per skinning call')
     ap.add_argument('--out', default=None, metavar='JSON')
+    ap.add_argument('--crossings', action='store_true', help='also list the pairs of triangles of the surfaces that intersect')
+    ap.add_argument('--self', dest='self_pairs', action='store_true', help='with --crossings: also every body against itself')
+    ap.add_argument('--parts', action='store_true', help='with --crossings --self: ignore pairs of faces of adjacent body parts')
     a = ap.parse_args(argv)
+    if a.self_pairs and not a.crossings:
+        ap.error('--self needs --crossings')
+    if a.parts and not a.self_pairs:
+        ap.error('--parts needs --crossings --self')
     if a.max_inside < 0:
         ap.error('--max_inside must not be negative')
     if a.chunk < 1:
@@ -44,6 +58,38 @@ def report_of(counts, per_body, max_inside):
     ranked = sorted(range(B), key=lambda i: (-int(per_body[i]), i))
     return {'bodies': B, 'overlapping_pairs': len(pairs), 'pairs': pairs, 'counts': counts.tolist(), 'per_body': per_body.tolist(),
             'ranked': ranked, 'max_inside': int(max_inside), 'disjoint': select_disjoint(range(B), counts, max_inside)}
+
+
+def model_parts(smplx_src, faces):
+    """(face_part [F], part_skip [P,P]) from the model's own ``weights`` and ``kintree_table``; ``smplx_src`` as body_model.create takes it."""
+    import os
+    from psi_release_amd import body_model
+    from psi_release_amd.evaluation import SMPLX_SELF_CONTACT_PAIRS, face_parts, part_skip_matrix
+    data = smplx_src
+    if not (isinstance(data, dict) or hasattr(data, 'v_template')):
+        p = smplx_src
+        if os.path.isdir(p):
+            cand = os.path.join(p, 'smplx', 'SMPLX_NEUTRAL.npz')
+            p = cand if os.path.exists(cand) else os.path.join(p, 'SMPLX_NEUTRAL.npz')
+        data = body_model.load_smplx_npz(p)
+    g = (lambda k: np.asarray(data[k])) if not hasattr(data, 'v_template') else (lambda k: np.asarray(getattr(data, k)))
+    parents = g('kintree_table')[0].astype(np.int64).copy()
+    parents[0] = -1
+    extra = [pr for pr in SMPLX_SELF_CONTACT_PAIRS if max(pr) < len(parents)]
+    return face_parts(g('weights'), faces), part_skip_matrix(parents, extra=extra), g('v_template').astype(np.float32)
+
+
+def crossings_report(res, overlap_counts):
+    """The JSON fields of --crossings: ``res`` a CrossingsResult, ``overlap_counts`` [B,B] the vertex-in-body counts."""
+    counts, contour = res.counts.cpu().numpy().astype(np.int64), res.contour.cpu().numpy()
+    ov = np.asarray(overlap_counts, np.int64)
+    B = len(counts)
+    pairs = [[i, j, int(counts[i, j]), float(contour[i, j])] for i in range(B) for j in range(i + 1, B) if counts[i, j]]
+    own = np.diag(counts)
+    return {'crossing_pairs': pairs, 'crossing_counts': counts.tolist(), 'contour': contour.tolist(),
+            'self_crossings': own.tolist(), 'self_ranked': sorted(range(B), key=lambda i: (-int(own[i]), i)),
+            'irregular': int(res.irregular.item()), 'triangle_pairs': int(res.pairs.shape[0]),
+            'unseen_by_vertex_test': sum(1 for i, j, _, _ in pairs if ov[i, j] == 0 and ov[j, i] == 0)}
 
 
 def main(argv=None):
@@ -66,6 +112,21 @@ def main(argv=None):
     for i in rep['ranked']:
         print('body %6d: %6d vertices inside other bodies' % (i, rep['per_body'][i]))
     print('--disjoint=' + ','.join(str(i) for i in rep['disjoint']))
+    if a.crossings:
+        from psi_release_amd.evaluation import SurfaceCrossings
+        part, skip, rest = model_parts(smplx_src, decoder.faces.cpu().numpy()) if a.parts else (None, None, None)
+        sc = SurfaceCrossings(decoder.faces, device, order_verts=rest, face_part=part, part_skip=skip)
+        cres = sc.crossings_of_records(xh, camera_pose(cam, a.no_flip), decoder, chunk=a.chunk, self_pairs=a.self_pairs)
+        crep = crossings_report(cres, rep['counts'])
+        rep.update(crep)
+        print('[INFO] %d pairs of bodies cross, %d pairs of triangles (%d irregular)' % (len(crep['crossing_pairs']), crep['triangle_pairs'],
+                                                                                       crep['irregular']))
+        for i, j, n, length in crep['crossing_pairs']:
+            print('bodies %6d %6d: %6d crossing pairs, contour %.4f m' % (i, j, n, length))
+        if a.self_pairs:
+            for i in crep['self_ranked']:
+                print('body %6d: %6d self crossings' % (i, crep['self_crossings'][i]))
+        print('[INFO] %d pairs of bodies cross although no vertex of either is inside the other' % crep['unseen_by_vertex_test'])
     if a.out:
         with open(a.out, 'w') as f:
             json.dump(rep, f, indent=1)
