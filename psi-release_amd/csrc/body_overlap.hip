@@ -1,5 +1,6 @@
 // Body against body: which vertices of one body of a batch lie inside another body of the batch, for gfx950 (wave64).  The contract is
-// DESIGN.md "Body against body"; the per-triple statements are csrc/body_overlap_shared.h.
+// DESIGN.md "Body against body"; the per-triple statements are csrc/body_overlap_shared.h and csrc/geom_shared.h (boxes, normal, half_omega),
+// the workgroup sum, box and ordered rank csrc/wg_device.h.
 //
 //   box        of body j: the exact min / max of its V vertices per axis
 //   candidate  an ordered triple (i, j, v), i != j, group[i] == group[j], vertex v of body i inside the closed box of j; ascending (i, j, v)
@@ -15,6 +16,7 @@
 // lane reads every record: identical addresses broadcast), decide (the slice sums in order, w, integer atomics into counts and the bit mask).
 #include "body_overlap_shared.h"
 #include "psi_common.h"
+#include "wg_device.h"
 #include <limits.h>
 #include <vector>
 
@@ -25,59 +27,16 @@ struct psi_body_overlap {
 
 namespace psi_bo {
 
-constexpr int WG = 256;
+constexpr int WG = WG_LANES;
 static_assert(WG == BO_CHUNK, "one staged record per lane");
 
 struct Chunk { int first, n, i, j; };          // 256-candidate chunk: first candidate, candidates, the pair
 static_assert(sizeof(Chunk) == 16, "the chunk table is [n_chunks,4] int32");
 
-__device__ __forceinline__ int block_sum(int v, int *s_w)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int t = threadIdx.x;
-    __syncthreads();                           // s_w may still be read from an earlier call
-    if ((t & 63) == 0) s_w[t >> 6] = v;
-    __syncthreads();
-    return s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
 // boxes [B,6] = min xyz, max xyz; *bad = the smallest body index with a non-finite coordinate (INT_MAX: none)
 __global__ __launch_bounds__(WG) void bo_box_kernel(const float *__restrict__ verts, int V, float *__restrict__ boxes, int *__restrict__ bad)
 {
-    __shared__ float s_lo[WG / 64][3], s_hi[WG / 64][3];
-    __shared__ int s_w[WG / 64];
-    const int b = blockIdx.x, t = threadIdx.x;
-    const float *v = verts + (size_t)b * V * 3;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    int nonfinite = 0;
-    for (int k = t; k < V; k += WG) {
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            const float x = v[(size_t)k * 3 + a];
-            nonfinite |= !isfinite(x);
-            lo[a] = fminf(lo[a], x);
-            hi[a] = fmaxf(hi[a], x);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64));
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64));
-        }
-        if ((t & 63) == 0) {
-            s_lo[t >> 6][a] = lo[a];
-            s_hi[t >> 6][a] = hi[a];
-        }
-    }
-    const int any_bad = block_sum(nonfinite, s_w);          // its barriers also publish s_lo / s_hi
-    if (t < 3) {
-        boxes[(size_t)b * 6 + t] = fminf(fminf(s_lo[0][t], s_lo[1][t]), fminf(s_lo[2][t], s_lo[3][t]));
-        boxes[(size_t)b * 6 + 3 + t] = fmaxf(fmaxf(s_hi[0][t], s_hi[1][t]), fmaxf(s_hi[2][t], s_hi[3][t]));
-    }
-    if (t == 0 && any_bad) atomicMin(bad, b);
+    wg_body_box(verts, V, boxes, bad);
 }
 
 // Is (i, j) a pair that is compared, and do its boxes meet?  Loads box j into lo / hi.
@@ -93,7 +52,7 @@ __device__ __forceinline__ bool pair_live(const float *__restrict__ boxes, const
         lo[a] = boxes[(size_t)j * 6 + a];
         hi[a] = boxes[(size_t)j * 6 + 3 + a];
     }
-    return bo_boxes_meet(ilo, ihi, lo, hi);
+    return geom_boxes_meet(ilo, ihi, lo, hi);
 }
 
 // pair_count [B,B]: the vertices of body i inside the closed box of body j (0 for a pair that is not compared); every entry is written
@@ -109,8 +68,8 @@ __global__ __launch_bounds__(WG) void bo_count_kernel(const float *__restrict__ 
     }
     const float *v = verts + (size_t)i * V * 3;
     int n = 0;
-    for (int k = t; k < V; k += WG) n += bo_in_box(v[(size_t)k * 3], v[(size_t)k * 3 + 1], v[(size_t)k * 3 + 2], lo, hi) ? 1 : 0;
-    n = block_sum(n, s_w);
+    for (int k = t; k < V; k += WG) n += geom_in_box(v[(size_t)k * 3], v[(size_t)k * 3 + 1], v[(size_t)k * 3 + 2], lo, hi) ? 1 : 0;
+    n = wg_sum(n, s_w);
     if (t == 0) pair_count[blockIdx.x] = n;
 }
 
@@ -124,7 +83,7 @@ __global__ __launch_bounds__(WG) void bo_emit_kernel(const float *__restrict__ v
     __shared__ int s_wcnt[WG / 64];
     const int pc = pair_count[blockIdx.x];
     if (pc == 0) return;
-    const int i = blockIdx.x / B, j = blockIdx.x % B, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int i = blockIdx.x / B, j = blockIdx.x % B, t = threadIdx.x;
     float lo[3], hi[3];
     if (!pair_live(boxes, group, i, j, lo, hi)) return;
     const long long off = cand_off[blockIdx.x], coff = chunk_off[blockIdx.x];
@@ -134,26 +93,15 @@ __global__ __launch_bounds__(WG) void bo_emit_kernel(const float *__restrict__ v
     int done = 0;                                           // candidates of the vertices before this round
     for (int k0 = 0; k0 < V; k0 += WG) {
         const int k = k0 + t;
-        const bool in = k < V && bo_in_box(v[(size_t)k * 3], v[(size_t)k * 3 + 1], v[(size_t)k * 3 + 2], lo, hi);
-        const unsigned long long m = __ballot(in);
-        if (lane == 0) s_wcnt[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < WG / 64; w++) {
-            const int c = s_wcnt[w];
-            before += w < wave ? c : 0;
-            total += c;
-        }
-        const int idx = done + before + __popcll(m & ((1ull << lane) - 1ull));      // this vertex's place among the pair's candidates
+        const bool in = k < V && geom_in_box(v[(size_t)k * 3], v[(size_t)k * 3 + 1], v[(size_t)k * 3 + 2], lo, hi);
+        const int idx = wg_rank(in, s_wcnt, &done);         // this vertex's place among the pair's candidates
         const long long pos = off + idx;
         if (in && idx < pc && pos < n_cand) {
             cand[pos * 3] = i;
             cand[pos * 3 + 1] = j;
             cand[pos * 3 + 2] = k;
         }
-        done += total;
-        __syncthreads();
+        __syncthreads();                                    // s_wcnt is read by every wave before the next round writes it
     }
 }
 
@@ -182,7 +130,7 @@ __global__ __launch_bounds__(WG) void bo_wind_kernel(const float *__restrict__ v
             const float *a = vj + (size_t)f[0] * 3, *b = vj + (size_t)f[1] * 3, *c = vj + (size_t)f[2] * 3;
             const float A[3] = {a[0], a[1], a[2]}, Bv[3] = {b[0], b[1], b[2]}, C[3] = {c[0], c[1], c[2]};
             float n[3];
-            bo_normal(A, Bv, C, n);
+            geom_normal(A, Bv, C, n);
             stage[3 * t] = make_float4(A[0], A[1], A[2], Bv[0]);
             stage[3 * t + 1] = make_float4(Bv[1], Bv[2], C[0], C[1]);
             stage[3 * t + 2] = make_float4(C[2], n[0], n[1], n[2]);
@@ -192,7 +140,7 @@ __global__ __launch_bounds__(WG) void bo_wind_kernel(const float *__restrict__ v
             float s = 0.0f;
             for (int k = 0; k < nst; k++) {
                 const float4 r0 = stage[3 * k], r1 = stage[3 * k + 1], r2 = stage[3 * k + 2];
-                s += bo_half_omega(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, px, py, pz);
+                s += geom_half_omega(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, px, py, pz);
             }
             acc += (double)s;
         }
@@ -219,8 +167,6 @@ __global__ __launch_bounds__(WG) void bo_decide_kernel(const int *__restrict__ c
     }
 }
 
-constexpr int MAX_B = 46340;                   // B * B < 2^31
-
 }  // namespace psi_bo
 
 extern "C" int psi_body_overlap_create(psi_body_overlap **out, const int32_t *h_faces, int V, int F)
@@ -228,19 +174,11 @@ extern "C" int psi_body_overlap_create(psi_body_overlap **out, const int32_t *h_
     PSI_REQUIRE(out && h_faces, "null pointer");
     PSI_REQUIRE(V >= 1 && F >= 1, "V >= 1 and F >= 1");
     PSI_REQUIRE((long long)F * 3 < (1ll << 31), "F * 3 < 2^31");
-    for (long long k = 0; k < (long long)F * 3; k++)
-        if (h_faces[k] < 0 || h_faces[k] >= V) {
-            psi_set_error("invalid argument: face %lld refers to vertex %d outside [0, %d)", k / 3, (int)h_faces[k], V);
-            return PSI_EINVAL;
-        }
+    int rc = psi_check_faces(h_faces, V, F);
+    if (rc) return rc;
     int32_t *d = nullptr;
-    PSI_CHECK_HIP(hipMalloc((void **)&d, (size_t)F * 3 * sizeof(int32_t)));
-    hipError_t e = hipMemcpy(d, h_faces, (size_t)F * 3 * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        psi_set_error("psi_body_overlap_create: upload failed: %s", hipGetErrorString(e));
-        (void)hipFree(d);
-        return (int)e;
-    }
+    rc = psi_upload(&d, h_faces, (size_t)F * 3, "psi_body_overlap_create");
+    if (rc) return rc;
     *out = new psi_body_overlap{d, V, F};
     return 0;
 }
@@ -269,9 +207,9 @@ extern "C" size_t psi_body_overlap_workspace_bytes(long long n_cand, int F)
 extern "C" int psi_body_overlap_boxes(const psi_body_overlap *h, const float *d_verts, int B, float *d_boxes, int32_t *d_bad, void *stream)
 {
     PSI_REQUIRE(h && d_verts && d_boxes && d_bad, "null pointer");
-    PSI_REQUIRE(B >= 1 && B <= psi_bo::MAX_B, "1 <= B <= 46340");
+    PSI_REQUIRE(B >= 1 && B <= GEOM_MAX_B, "1 <= B <= 46340");
     hipStream_t st = (hipStream_t)stream;
-    PSI_CHECK_HIP(hipMemsetAsync(d_bad, 0x7f, sizeof(int32_t), st));      // 0x7f7f7f7f: above every body index
+    PSI_CHECK_HIP(psi_reset_bad_flag(d_bad, st));
     hipLaunchKernelGGL(psi_bo::bo_box_kernel, dim3(B), dim3(psi_bo::WG), 0, st, d_verts, h->V, d_boxes, d_bad);
     PSI_CHECK_LAUNCH("bo_box_kernel");
     return 0;
@@ -281,7 +219,7 @@ extern "C" int psi_body_overlap_count(const psi_body_overlap *h, const float *d_
                                       int32_t *d_pair_count, void *stream)
 {
     PSI_REQUIRE(h && d_verts && d_boxes && d_pair_count, "null pointer");
-    PSI_REQUIRE(B >= 1 && B <= psi_bo::MAX_B, "1 <= B <= 46340");
+    PSI_REQUIRE(B >= 1 && B <= GEOM_MAX_B, "1 <= B <= 46340");
     hipLaunchKernelGGL(psi_bo::bo_count_kernel, dim3(B * B), dim3(psi_bo::WG), 0, (hipStream_t)stream, d_verts, d_boxes, d_group, B, h->V,
                        d_pair_count);
     PSI_CHECK_LAUNCH("bo_count_kernel");
@@ -293,7 +231,7 @@ extern "C" int psi_body_overlap_emit(const psi_body_overlap *h, const float *d_v
                                      long long n_chunks, int32_t *d_cand, int32_t *d_chunks, void *stream)
 {
     PSI_REQUIRE(h && d_verts && d_boxes && d_pair_count && d_cand_off && d_chunk_off && d_cand && d_chunks, "null pointer");
-    PSI_REQUIRE(B >= 1 && B <= psi_bo::MAX_B, "1 <= B <= 46340");
+    PSI_REQUIRE(B >= 1 && B <= GEOM_MAX_B, "1 <= B <= 46340");
     PSI_REQUIRE(n_cand >= 1 && n_cand < (1ll << 31), "1 <= n_cand < 2^31");
     PSI_REQUIRE(n_chunks >= 1 && n_chunks <= n_cand, "1 <= n_chunks <= n_cand");
     hipLaunchKernelGGL(psi_bo::bo_emit_kernel, dim3(B * B), dim3(psi_bo::WG), 0, (hipStream_t)stream, d_verts, d_boxes, d_group, B, h->V,
@@ -307,7 +245,7 @@ extern "C" int psi_body_overlap_wind(const psi_body_overlap *h, const float *d_v
                                      const int32_t *d_chunks, long long n_chunks, void *d_workspace, size_t workspace_bytes, void *stream)
 {
     PSI_REQUIRE(h && d_verts && d_cand && d_chunks && d_workspace, "null pointer");
-    PSI_REQUIRE(B >= 1 && B <= psi_bo::MAX_B, "1 <= B <= 46340");
+    PSI_REQUIRE(B >= 1 && B <= GEOM_MAX_B, "1 <= B <= 46340");
     PSI_REQUIRE(n_cand >= 1 && n_cand < (1ll << 31), "1 <= n_cand < 2^31");
     PSI_REQUIRE(n_chunks >= 1 && n_chunks <= n_cand, "1 <= n_chunks <= n_cand");
     PSI_REQUIRE(workspace_bytes >= psi_body_overlap_workspace_bytes(n_cand, h->F), "workspace too small");
@@ -321,7 +259,7 @@ extern "C" int psi_body_overlap_decide(const psi_body_overlap *h, int B, const i
                                        size_t workspace_bytes, float *d_w, int32_t *d_counts, uint32_t *d_mask, void *stream)
 {
     PSI_REQUIRE(h && d_cand && d_workspace && d_w && d_counts && d_mask, "null pointer");
-    PSI_REQUIRE(B >= 1 && B <= psi_bo::MAX_B, "1 <= B <= 46340");
+    PSI_REQUIRE(B >= 1 && B <= GEOM_MAX_B, "1 <= B <= 46340");
     PSI_REQUIRE(n_cand >= 1 && n_cand < (1ll << 31), "1 <= n_cand < 2^31");
     PSI_REQUIRE(workspace_bytes >= psi_body_overlap_workspace_bytes(n_cand, h->F), "workspace too small");
     hipLaunchKernelGGL(psi_bo::bo_decide_kernel, dim3(psi_cdiv(n_cand, psi_bo::WG)), dim3(psi_bo::WG), 0, (hipStream_t)stream, d_cand, n_cand,

@@ -4,6 +4,7 @@
 //   node      the positions of csrc/mesh_sdf.hip (psi_mesh_node_pos: the same bits)
 //   pair      with a = A - p, b = B - p, c = C - p and n = (B - A) x (C - A) (fp64 on the host, stored as fp32; a . n = a . (b x c)):
 //             w = atan2(a . n, |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|) = half the solid angle; atan2(0, 0) counts as 0
+//             (geom_half_omega in csrc/geom_shared.h)
 //   dipole    a far cluster (area-vector sum N, area-weighted centroid c) adds N . (c - p) / (2 |c - p|^3) in the same unit
 //   f         -(1 / 2 pi) * the sum: 1 in the free space of a closed room whose triangles face free space, 0 in furniture and outside
 //   sum       fp32 within a staged chunk of 256 records, the chunk sums added in fp64, in a fixed order: kept order in the exact arm
@@ -14,6 +15,7 @@
 // One kernel per call: one 256-lane workgroup per brick, two nodes per lane.  The clusters are visited 256 at a time, one per lane; a scan
 // of their record counts (1 for a far cluster, its triangles for a near one) makes the batch one list of records, staged through LDS 256 at
 // a time; every lane reads every staged record (identical addresses broadcast).  Every loop is bounded by the cluster or triangle count.
+#include "geom_shared.h"
 #include "mesh_sdf_shared.h"
 #include <string.h>
 #include <algorithm>
@@ -43,27 +45,12 @@ struct Nodes {
     int D;
 };
 
-MS_FN float dot3(float ax, float ay, float az, float bx, float by, float bz) { return ax * bx + ay * by + az * bz; }
-
-// half the solid angle of the triangle (A, B, C) seen from p, signed
-MS_FN float half_omega(float Ax, float Ay, float Az, float Bx, float By, float Bz, float Cx, float Cy, float Cz, float nx, float ny, float nz,
-                       float px, float py, float pz)
-{
-    const float ax = Ax - px, ay = Ay - py, az = Az - pz;
-    const float bx = Bx - px, by = By - py, bz = Bz - pz;
-    const float cx = Cx - px, cy = Cy - py, cz = Cz - pz;
-    const float la = sqrtf(dot3(ax, ay, az, ax, ay, az)), lb = sqrtf(dot3(bx, by, bz, bx, by, bz)), lc = sqrtf(dot3(cx, cy, cz, cx, cy, cz));
-    const float det = dot3(ax, ay, az, nx, ny, nz);
-    const float den = la * lb * lc + dot3(ax, ay, az, bx, by, bz) * lc + dot3(bx, by, bz, cx, cy, cz) * la + dot3(cx, cy, cz, ax, ay, az) * lb;
-    return (det == 0.0f && den == 0.0f) ? 0.0f : atan2f(det, den);
-}
-
 // the dipole of a far cluster in the same unit: N . d / (2 |d|^3), d = c - p (never 0: the cluster is farther than beta * r > 0)
 MS_FN float half_dipole(float cx, float cy, float cz, float Nx, float Ny, float Nz, float px, float py, float pz)
 {
     const float dx = cx - px, dy = cy - py, dz = cz - pz;
-    const float d2 = dot3(dx, dy, dz, dx, dy, dz);
-    return 0.5f * dot3(Nx, Ny, Nz, dx, dy, dz) / (d2 * sqrtf(d2));
+    const float d2 = geom_dot3(dx, dy, dz, dx, dy, dz);
+    return 0.5f * geom_dot3(Nx, Ny, Nz, dx, dy, dz) / (d2 * sqrtf(d2));
 }
 
 // Is the cluster far for the brick whose nodes span [lo, hi]?  Squares are compared; every operation is rounded on its own.
@@ -122,8 +109,8 @@ __global__ __launch_bounds__(WG) void mwind_brick_kernel(const WRec *__restrict_
                 s0 += half_dipole(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, px0, py, pz);
                 s1 += half_dipole(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, px1, py, pz);
             } else {
-                s0 += half_omega(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, px0, py, pz);
-                s1 += half_omega(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, px1, py, pz);
+                s0 += geom_half_omega(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, px0, py, pz);
+                s1 += geom_half_omega(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w, px1, py, pz);
             }
         }
         acc0 += (double)s0;
@@ -351,15 +338,7 @@ void destroy_cache(void *p)
 template <class T>
 int upload(const std::vector<T> &h, T **d)
 {
-    PSI_CHECK_HIP(hipMalloc((void **)d, h.size() * sizeof(T)));
-    hipError_t e = hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        psi_set_error("psi_mesh_winding: upload failed: %s", hipGetErrorString(e));
-        (void)hipFree(*d);
-        *d = nullptr;
-        return (int)e;
-    }
-    return 0;
+    return psi_upload(d, h.data(), h.size(), "psi_mesh_winding");
 }
 
 int launch(psi_mesh_sdf *m, const float gmin[3], const float gmax[3], int D, float beta, int cluster, float *d_f, unsigned long long *d_counts,

@@ -49,5 +49,37 @@ void psi_set_error(const char *fmt, ...);
 
 static inline int psi_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// n values of src in fresh device memory at *out (synchronous).  When the copy fails nothing stays allocated, *out is null and the message
+// names `who`, the caller's entry point.
+template <typename T>
+static inline int psi_upload(T **out, const T *src, size_t n, const char *who)
+{
+    T *d = nullptr;
+    *out = nullptr;
+    PSI_CHECK_HIP(hipMalloc((void **)&d, n * sizeof(T)));
+    hipError_t e = hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        psi_set_error("%s: upload failed: %s", who, hipGetErrorString(e));
+        (void)hipFree(d);
+        return (int)e;
+    }
+    *out = d;
+    return 0;
+}
+
+// PSI_EINVAL unless every index of h_faces [F,3] lies in [0, V)
+static inline int psi_check_faces(const int32_t *h_faces, int V, int F)
+{
+    for (long long k = 0; k < (long long)F * 3; k++)
+        if (h_faces[k] < 0 || h_faces[k] >= V) {
+            psi_set_error("invalid argument: face %lld refers to vertex %d outside [0, %d)", k / 3, (int)h_faces[k], V);
+            return PSI_EINVAL;
+        }
+    return 0;
+}
+
+// The non-finite flag of a body-box kernel (wg_body_box in wg_device.h) before its launch: 0x7f7f7f7f, above every body index
+static inline hipError_t psi_reset_bad_flag(int32_t *d_bad, hipStream_t st) { return hipMemsetAsync(d_bad, 0x7f, sizeof(int32_t), st); }
+
 // Per-device scratch that grows on demand (used when the caller passes workspace == NULL).
 void *psi_scratch(size_t bytes, hipStream_t stream);

@@ -1,5 +1,6 @@
 // Surface crossings: which pairs of triangles of the posed body surfaces of a batch properly intersect, for gfx950 (wave64).  The contract is
-// DESIGN.md section 10e; the per-pair statements are csrc/surface_crossings_shared.h.  This file is compiled with -ffp-contract=off.
+// DESIGN.md section 10e; the per-pair statements are csrc/surface_crossings_shared.h, the closed-box test csrc/geom_shared.h, the workgroup
+// sum, box and ordered rank csrc/wg_device.h.  This file is compiled with -ffp-contract=off.
 //
 //   candidate  an unordered pair of faces ((i, s), (j, t)), (i, s) < (j, t): bodies i < j of one group (between), or two faces s < t of one
 //              body that share no vertex index and whose parts are not skipped (self); and the closed face boxes meet
@@ -14,6 +15,7 @@
 // of its pairs in fp64, sequentially in pair order).  No floating-point atomics.
 #include "surface_crossings_shared.h"
 #include "psi_common.h"
+#include "wg_device.h"
 #include <limits.h>
 #include <algorithm>
 #include <numeric>
@@ -29,45 +31,11 @@ struct psi_surface_crossings {
 
 namespace psi_sc {
 
-constexpr int WG = 256;
+constexpr int WG = WG_LANES;
 static_assert(WG == SC_CHUNK, "one staged record per lane");
 
 struct Tile { int i, j, ca, cb; };
 static_assert(sizeof(Tile) == 16, "the tile table is [n_tiles,4] int32");
-
-__device__ __forceinline__ int block_sum(int v, int *s_w)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int t = threadIdx.x;
-    __syncthreads();                           // s_w may still be read from an earlier call
-    if ((t & 63) == 0) s_w[t >> 6] = v;
-    __syncthreads();
-    return s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-// min / max of lo / hi over the workgroup; lanes 0..2 write the six values to out
-__device__ __forceinline__ void block_box(float lo[3], float hi[3], float (*s_lo)[3], float (*s_hi)[3], float *__restrict__ out)
-{
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64));
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64));
-        }
-        if ((t & 63) == 0) {
-            s_lo[t >> 6][a] = lo[a];
-            s_hi[t >> 6][a] = hi[a];
-        }
-    }
-    __syncthreads();
-    if (t < 3) {
-        out[t] = fminf(fminf(s_lo[0][t], s_lo[1][t]), fminf(s_lo[2][t], s_lo[3][t]));
-        out[3 + t] = fmaxf(fmaxf(s_hi[0][t], s_hi[1][t]), fmaxf(s_hi[2][t], s_hi[3][t]));
-    }
-}
 
 __device__ __forceinline__ void load_triangle(const float *__restrict__ v, const int32_t *__restrict__ f, int id[3], float p[3][3])
 {
@@ -92,31 +60,14 @@ __global__ __launch_bounds__(WG) void sc_chunk_box_kernel(const float *__restric
         load_triangle(verts + (size_t)b * V * 3, faces + (size_t)pos * 3, id, p);
         sc_face_box(p, lo, hi);
     }
-    block_box(lo, hi, s_lo, s_hi, chunk_boxes + ((size_t)b * gridDim.x + c) * 6);
+    wg_box(lo, hi, s_lo, s_hi, chunk_boxes + ((size_t)b * gridDim.x + c) * 6);
 }
 
 // body_boxes [B,6] over the V vertices of a body (a superset of its chunk boxes); *bad = the smallest body index with a non-finite
 // coordinate.  One workgroup per body.
 __global__ __launch_bounds__(WG) void sc_body_box_kernel(const float *__restrict__ verts, int V, float *__restrict__ body_boxes, int *__restrict__ bad)
 {
-    __shared__ float s_lo[WG / 64][3], s_hi[WG / 64][3];
-    __shared__ int s_w[WG / 64];
-    const int b = blockIdx.x, t = threadIdx.x;
-    const float *v = verts + (size_t)b * V * 3;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    int nonfinite = 0;
-    for (int k = t; k < V; k += WG) {
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            const float x = v[(size_t)k * 3 + a];
-            nonfinite |= !isfinite(x);
-            lo[a] = fminf(lo[a], x);
-            hi[a] = fmaxf(hi[a], x);
-        }
-    }
-    block_box(lo, hi, s_lo, s_hi, body_boxes + (size_t)b * 6);
-    const int any_bad = block_sum(nonfinite, s_w);
-    if (t == 0 && any_bad) atomicMin(bad, b);
+    wg_body_box(verts, V, body_boxes, bad);
 }
 
 // Is (i, j) a job: admitted by the flags and the groups, and (unless brute) with meeting body boxes?
@@ -126,7 +77,7 @@ __device__ __forceinline__ bool job_live(const float *__restrict__ body_boxes, c
     if (i == j ? !(flags & SC_SELF) : !(flags & SC_BETWEEN)) return false;
     if (i != j && group && group[i] != group[j]) return false;
     if (flags & SC_BRUTE) return true;
-    return sc_boxes_meet(body_boxes + (size_t)i * 6, body_boxes + (size_t)i * 6 + 3, body_boxes + (size_t)j * 6, body_boxes + (size_t)j * 6 + 3);
+    return geom_boxes_meet(body_boxes + (size_t)i * 6, body_boxes + (size_t)i * 6 + 3, body_boxes + (size_t)j * 6, body_boxes + (size_t)j * 6 + 3);
 }
 
 __device__ __forceinline__ bool tile_live(const float *__restrict__ chunk_boxes, int nC, int flags, int i, int j, int ca, int cb)
@@ -134,7 +85,7 @@ __device__ __forceinline__ bool tile_live(const float *__restrict__ chunk_boxes,
     if (i == j && ca > cb) return false;
     if (flags & SC_BRUTE) return true;
     const float *a = chunk_boxes + ((size_t)i * nC + ca) * 6, *b = chunk_boxes + ((size_t)j * nC + cb) * 6;
-    return sc_boxes_meet(a, a + 3, b, b + 3);
+    return geom_boxes_meet(a, a + 3, b, b + 3);
 }
 
 // job_tiles [B,B]: the tiles of job (i, j); every entry is written.  With tiles != null (the emit pass) the tiles are written from
@@ -144,7 +95,7 @@ __global__ __launch_bounds__(WG) void sc_tile_kernel(const float *__restrict__ c
                                                      const long long *__restrict__ job_off, long long n_tiles, Tile *__restrict__ tiles)
 {
     __shared__ int s_w[WG / 64];
-    const int i = blockIdx.x / B, j = blockIdx.x % B, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int i = blockIdx.x / B, j = blockIdx.x % B, t = threadIdx.x;
     if (!job_live(body_boxes, group, flags, i, j)) {        // the same in every lane
         if (!tiles && t == 0) job_tiles[blockIdx.x] = 0;
         return;
@@ -153,7 +104,7 @@ __global__ __launch_bounds__(WG) void sc_tile_kernel(const float *__restrict__ c
     if (!tiles) {
         int n = 0;
         for (int k = t; k < total; k += WG) n += tile_live(chunk_boxes, nC, flags, i, j, k / nC, k % nC) ? 1 : 0;
-        n = block_sum(n, s_w);
+        n = wg_sum(n, s_w);
         if (t == 0) job_tiles[blockIdx.x] = n;
         return;
     }
@@ -164,21 +115,10 @@ __global__ __launch_bounds__(WG) void sc_tile_kernel(const float *__restrict__ c
     for (int k0 = 0; k0 < total; k0 += WG) {
         const int k = k0 + t;
         const bool in = k < total && tile_live(chunk_boxes, nC, flags, i, j, k / nC, k % nC);
-        const unsigned long long m = __ballot(in);
-        if (lane == 0) s_w[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, sum = 0;
-#pragma unroll
-        for (int w = 0; w < WG / 64; w++) {
-            const int c = s_w[w];
-            before += w < wave ? c : 0;
-            sum += c;
-        }
-        const int idx = done + before + __popcll(m & ((1ull << lane) - 1ull));
+        const int idx = wg_rank(in, s_w, &done);
         const long long pos = off + idx;
         if (in && idx < want && pos < n_tiles) tiles[pos] = Tile{i, j, k / nC, k % nC};
-        done += sum;
-        __syncthreads();
+        __syncthreads();                                    // s_w is read by every wave before the next round writes it
     }
 }
 
@@ -232,7 +172,7 @@ __global__ __launch_bounds__(WG) void sc_test_kernel(const float *__restrict__ v
         for (int k = k0; k < nst; k++) {
             const float4 r0 = stage[5 * k], r1 = stage[5 * k + 1];
             const float blo[3] = {r0.x, r0.y, r0.z}, bhi[3] = {r0.w, r1.x, r1.y};
-            if (!sc_boxes_meet(alo, ahi, blo, bhi)) continue;
+            if (!geom_boxes_meet(alo, ahi, blo, bhi)) continue;
             const float4 r2 = stage[5 * k + 2];
             if (self) {
                 const int bid[3] = {__float_as_int(r1.z), __float_as_int(r1.w), __float_as_int(r2.x)};
@@ -259,7 +199,7 @@ __global__ __launch_bounds__(WG) void sc_test_kernel(const float *__restrict__ v
         }
     }
     if (!EMIT) {
-        hits = block_sum(hits, s_w);
+        hits = wg_sum(hits, s_w);
         if (t == 0) tile_hits[blockIdx.x] = hits;
     }
 }
@@ -318,32 +258,14 @@ __global__ __launch_bounds__(WG) void sc_contour_kernel(const int *__restrict__ 
     }
 }
 
-template <typename T>
-static int upload(T **out, const T *src, size_t n)
-{
-    T *d = nullptr;
-    PSI_CHECK_HIP(hipMalloc((void **)&d, n * sizeof(T)));
-    hipError_t e = hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        psi_set_error("psi_surface_crossings_create: upload failed: %s", hipGetErrorString(e));
-        (void)hipFree(d);
-        return (int)e;
-    }
-    *out = d;
-    return 0;
-}
-
 }  // namespace psi_sc
 
 extern "C" int psi_surface_crossings_face_order(const int32_t *h_faces, int V, int F, const float *h_order_verts, int32_t *h_order)
 {
     PSI_REQUIRE(h_faces && h_order, "null pointer");
     PSI_REQUIRE(V >= 1 && F >= 1 && F < SC_MAX_F, "V >= 1 and 1 <= F < 2^21");
-    for (long long k = 0; k < (long long)F * 3; k++)
-        if (h_faces[k] < 0 || h_faces[k] >= V) {
-            psi_set_error("invalid argument: face %lld refers to vertex %d outside [0, %d)", k / 3, (int)h_faces[k], V);
-            return PSI_EINVAL;
-        }
+    const int rc = psi_check_faces(h_faces, V, F);
+    if (rc) return rc;
     std::iota(h_order, h_order + F, 0);
     if (!h_order_verts) return 0;
     // centroids in fp64, quantised to 10 bits per axis of their bounding box; ties keep face order
@@ -400,10 +322,11 @@ extern "C" int psi_surface_crossings_create(psi_surface_crossings **out, const i
                 PSI_REQUIRE((h_part_skip[(size_t)a * P + b] != 0) == (h_part_skip[(size_t)b * P + a] != 0), "part_skip is symmetric");
     }
     psi_surface_crossings h{nullptr, nullptr, nullptr, nullptr, V, F, P};
-    int e = psi_sc::upload(&h.d_faces, faces.data(), faces.size());
-    if (!e) e = psi_sc::upload(&h.d_orig, order.data(), order.size());
-    if (!e && h_face_part) e = psi_sc::upload(&h.d_part, part.data(), part.size());
-    if (!e && h_face_part) e = psi_sc::upload(&h.d_skip, h_part_skip, (size_t)P * P);
+    const char *who = "psi_surface_crossings_create";
+    int e = psi_upload(&h.d_faces, faces.data(), faces.size(), who);
+    if (!e) e = psi_upload(&h.d_orig, order.data(), order.size(), who);
+    if (!e && h_face_part) e = psi_upload(&h.d_part, part.data(), part.size(), who);
+    if (!e && h_face_part) e = psi_upload(&h.d_skip, h_part_skip, (size_t)P * P, who);
     if (e) {
         (void)hipFree(h.d_faces), (void)hipFree(h.d_orig), (void)hipFree(h.d_part), (void)hipFree(h.d_skip);
         return e;
@@ -430,7 +353,7 @@ extern "C" int psi_surface_crossings_info(const psi_surface_crossings *h, int32_
 }
 
 #define SC_REQUIRE_B(h, B)                                                                                          \
-    PSI_REQUIRE(B >= 1 && B <= SC_MAX_B, "1 <= B <= 46340");                                                        \
+    PSI_REQUIRE(B >= 1 && B <= GEOM_MAX_B, "1 <= B <= 46340");                                                      \
     PSI_REQUIRE((double)B * h->F * (double)B * h->F < 9.2e18, "(B * F)^2 < 2^63: the pair key is one int64")
 
 extern "C" int psi_surface_crossings_boxes(const psi_surface_crossings *h, const float *d_verts, int B, float *d_chunk_boxes,
@@ -440,7 +363,7 @@ extern "C" int psi_surface_crossings_boxes(const psi_surface_crossings *h, const
     SC_REQUIRE_B(h, B);
     hipStream_t st = (hipStream_t)stream;
     const int nC = (h->F + SC_CHUNK - 1) / SC_CHUNK;
-    PSI_CHECK_HIP(hipMemsetAsync(d_bad, 0x7f, sizeof(int32_t), st));      // 0x7f7f7f7f: above every body index
+    PSI_CHECK_HIP(psi_reset_bad_flag(d_bad, st));
     hipLaunchKernelGGL(psi_sc::sc_chunk_box_kernel, dim3(nC, B), dim3(psi_sc::WG), 0, st, d_verts, h->d_faces, h->V, h->F, d_chunk_boxes);
     PSI_CHECK_LAUNCH("sc_chunk_box_kernel");
     hipLaunchKernelGGL(psi_sc::sc_body_box_kernel, dim3(B), dim3(psi_sc::WG), 0, st, d_verts, h->V, d_body_boxes, d_bad);

@@ -11,15 +11,14 @@
 // of a pair is therefore a function of the two triangles alone.
 // Event: edge i of P pierces Q iff sP[i] and sP[i+1] are strictly of opposite sign (two comparisons, no product) and D[i][0], D[i][1],
 // D[i][2] are all > 0 or all < 0; the edges of Q against P alike with sQ and the columns of D.  A zero anywhere is no event.
+// The closed-box overlap test (geom_boxes_meet) and the bound on the bodies of a batch (GEOM_MAX_B) are csrc/geom_shared.h.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <math.h>
+#include "geom_shared.h"
 #include <stdint.h>
 
 #define SC_FN __host__ __device__ __forceinline__
 
 constexpr int SC_CHUNK = 256;           // faces per chunk: one workgroup's lanes, one staged record per lane
-constexpr int SC_MAX_B = 46340;         // B * B < 2^31
 constexpr int SC_MAX_F = 1 << 21;       // F < 2^21
 constexpr int SC_SELF = 1, SC_BETWEEN = 2, SC_BRUTE = 4;
 
@@ -53,12 +52,6 @@ SC_FN void sc_face_box(const float p[3][3], float lo[3], float hi[3])
         lo[a] = fminf(fminf(p[0][a], p[1][a]), p[2][a]);
         hi[a] = fmaxf(fmaxf(p[0][a], p[1][a]), p[2][a]);
     }
-}
-
-// the closed boxes [alo, ahi] and [blo, bhi] share a point
-SC_FN bool sc_boxes_meet(const float alo[3], const float ahi[3], const float blo[3], const float bhi[3])
-{
-    return alo[0] <= bhi[0] && blo[0] <= ahi[0] && alo[1] <= bhi[1] && blo[1] <= ahi[1] && alo[2] <= bhi[2] && blo[2] <= ahi[2];
 }
 
 // two faces of one body share a vertex index

@@ -210,27 +210,29 @@ class OverlapResult(NamedTuple):
     per_body: torch.Tensor     # [B] int64: inside.sum(1)
 
 
-class BodyOverlap:
-    """Body against body: which vertices of one body of a batch lie inside another (``ops.body_overlap``; DESIGN.md section 10d).  What
-    ``BodyInterpenetration`` of the reference tree asks an external CUDA package for, as a count per ordered pair.  ``faces`` [F,3]: the
-    one topology of every body, wound outwards."""
+def _as_numpy(x, dtype):
+    return None if x is None else np.ascontiguousarray((x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(dtype))
 
-    def __init__(self, faces, device='cuda'):
+
+class _FacesHandleOwner:
+    """Owns the one topology ``faces`` [F,3] of the bodies of a batch and the library handle made of it for the vertex count last seen.
+    A subclass says how its handle is made (``_create(V)``) and freed (``_destroy(handle)``)."""
+
+    def __init__(self, faces, device):
         self.device = torch.device(device)
-        f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
-        self.faces = np.ascontiguousarray(f.astype(np.int32))
+        self.faces = _as_numpy(faces, np.int32)
         self._handle, self._V = None, None
 
     def _handle_for(self, V):
         if self._handle is None or self._V != V:
             self.close()
             with torch.cuda.device(self.device):
-                self._handle, self._V = ops.body_overlap_create(self.faces, V), V
+                self._handle, self._V = self._create(V), V
         return self._handle
 
     def close(self):
         if getattr(self, '_handle', None):
-            ops.body_overlap_destroy(self._handle)
+            self._destroy(self._handle)
             self._handle = None
 
     def __del__(self):
@@ -239,13 +241,29 @@ class BodyOverlap:
         except Exception:
             pass
 
+    @staticmethod
+    def _group(group, verts):
+        return None if group is None else torch.as_tensor(group, device=verts.device).to(torch.int32).contiguous()
+
+
+class BodyOverlap(_FacesHandleOwner):
+    """Body against body: which vertices of one body of a batch lie inside another (``ops.body_overlap``; DESIGN.md section 10d).  What
+    ``BodyInterpenetration`` of the reference tree asks an external CUDA package for, as a count per ordered pair.  ``faces`` [F,3]: the
+    one topology of every body, wound outwards."""
+
+    def __init__(self, faces, device='cuda'):
+        super().__init__(faces, device)
+
+    def _create(self, V):
+        return ops.body_overlap_create(self.faces, V)
+
+    _destroy = staticmethod(ops.body_overlap_destroy)
+
     @torch.no_grad()
     def counts(self, verts, group=None):
         """verts [B,V,3] fp32 on the device, world frame (``op.body_verts`` / ``BodyDecoder.verts`` / ``model(..., cam_ext=)``); ``group``
         [B] or None: only bodies of equal group are compared (bodies of different scenes in one batch)."""
-        if group is not None:
-            group = torch.as_tensor(group, device=verts.device).to(torch.int32).contiguous()
-        counts, inside = ops.body_overlap(verts.contiguous(), self._handle_for(int(verts.shape[1])), group=group)
+        counts, inside = ops.body_overlap(verts.contiguous(), self._handle_for(int(verts.shape[1])), group=self._group(group, verts))
         return OverlapResult(counts, inside, inside.sum(1))
 
     @torch.no_grad()
@@ -258,25 +276,31 @@ class BodyOverlap:
         return self.counts(verts, group)
 
 
-def select_disjoint(order, counts, max_inside=0):
-    """A greedy set of mutually compatible bodies, on the host: walk the bodies in ``order`` (e.g. best plausibility first) and keep body i
-    iff counts[i,k] + counts[k,i] <= max_inside for every body k already kept.  ``counts`` [B,B]: ``OverlapResult.counts`` (a tensor or an
-    array).  Returns the kept indices in ``order``'s order."""
+def _greedy_walk(name, order, counts, admit, meets):
+    """Walk the bodies in ``order`` and keep body i iff ``admit(c, i)`` and ``meets(c, i, k)`` for every body k already kept; ``c`` is
+    ``counts`` [B,B] (a tensor or an array) as int64.  Returns the kept indices in ``order``'s order."""
     c = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
     if c.ndim != 2 or c.shape[0] != c.shape[1]:
-        raise ValueError('select_disjoint: counts is [B,B], got %s' % (c.shape,))
+        raise ValueError('%s: counts is [B,B], got %s' % (name, c.shape,))
     c = c.astype(np.int64)
     kept = []
     for i in order:
         i = int(i)
         if not 0 <= i < c.shape[0]:
-            raise ValueError('select_disjoint: body %d outside [0, %d)' % (i, c.shape[0]))
-        if i not in kept and all(c[i, k] + c[k, i] <= max_inside for k in kept):
+            raise ValueError('%s: body %d outside [0, %d)' % (name, i, c.shape[0]))
+        if admit(c, i) and i not in kept and all(meets(c, i, k) for k in kept):
             kept.append(i)
     return kept
 
 
-class SurfaceCrossings:
+def select_disjoint(order, counts, max_inside=0):
+    """A greedy set of mutually compatible bodies, on the host: walk the bodies in ``order`` (e.g. best plausibility first) and keep body i
+    iff counts[i,k] + counts[k,i] <= max_inside for every body k already kept.  ``counts`` [B,B]: ``OverlapResult.counts`` (a tensor or an
+    array).  Returns the kept indices in ``order``'s order."""
+    return _greedy_walk('select_disjoint', order, counts, lambda c, i: True, lambda c, i, k: c[i, k] + c[k, i] <= max_inside)
+
+
+class SurfaceCrossings(_FacesHandleOwner):
     """Which pairs of triangles of the body surfaces of a batch properly intersect, between bodies and within one body
     (``ops.surface_crossings``): the search and the body-part filter of the reference tree's
     ``BodyInterpenetration`` (human_body_prior/body_model/body_model.py:460-514), without its distance-field loss.  ``faces`` [F,3]: the
@@ -284,40 +308,20 @@ class SurfaceCrossings:
     ``face_part`` / ``part_skip``: ``face_parts`` and ``part_skip_matrix`` below."""
 
     def __init__(self, faces, device='cuda', order_verts=None, face_part=None, part_skip=None):
-        self.device = torch.device(device)
-        f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
-        self.faces = np.ascontiguousarray(f.astype(np.int32))
-        as_np = lambda x, dt: None if x is None else np.ascontiguousarray((x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).astype(dt))
-        self._order_verts, self._face_part, self._part_skip = as_np(order_verts, np.float32), as_np(face_part, np.int32), as_np(part_skip, np.uint8)
-        self._handle, self._V = None, None
+        super().__init__(faces, device)
+        self._order_verts, self._face_part, self._part_skip = _as_numpy(order_verts, np.float32), _as_numpy(face_part, np.int32), _as_numpy(part_skip, np.uint8)
 
-    def _handle_for(self, V):
-        if self._handle is None or self._V != V:
-            self.close()
-            with torch.cuda.device(self.device):
-                self._handle = ops.surface_crossings_create(self.faces, V, self._order_verts, self._face_part, self._part_skip)
-                self._V = V
-        return self._handle
+    def _create(self, V):
+        return ops.surface_crossings_create(self.faces, V, self._order_verts, self._face_part, self._part_skip)
 
-    def close(self):
-        if getattr(self, '_handle', None):
-            ops.surface_crossings_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = staticmethod(ops.surface_crossings_destroy)
 
     @torch.no_grad()
     def crossings(self, verts, group=None, self_pairs=True, between=True, mode='pruned'):
         """verts [B,V,3] fp32 on the device, world frame; ``group`` [B] or None as in ``BodyOverlap.counts``.  Returns
         ``ops.CrossingsResult``."""
-        if group is not None:
-            group = torch.as_tensor(group, device=verts.device).to(torch.int32).contiguous()
-        return ops.surface_crossings(verts.contiguous(), self._handle_for(int(verts.shape[1])), group=group, self_pairs=self_pairs,
-                                     between=between, mode=mode)
+        return ops.surface_crossings(verts.contiguous(), self._handle_for(int(verts.shape[1])), group=self._group(group, verts),
+                                     self_pairs=self_pairs, between=between, mode=mode)
 
     @torch.no_grad()
     def crossings_of_records(self, xh72, cam_ext, evaluator_or_decoder, chunk=512, group=None, self_pairs=True, between=True):
@@ -365,20 +369,8 @@ def select_uncrossed(order, counts, max_pairs=0, max_self=None):
     """``select_disjoint``'s walk over the crossing counts (``CrossingsResult.counts``, symmetric, self crossings on the diagonal): keep
     body i iff counts[i,k] <= max_pairs for every body k already kept, and, with ``max_self`` given, iff counts[i,i] <= max_self.  Returns
     the kept indices in ``order``'s order."""
-    c = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
-    if c.ndim != 2 or c.shape[0] != c.shape[1]:
-        raise ValueError('select_uncrossed: counts is [B,B], got %s' % (c.shape,))
-    c = c.astype(np.int64)
-    kept = []
-    for i in order:
-        i = int(i)
-        if not 0 <= i < c.shape[0]:
-            raise ValueError('select_uncrossed: body %d outside [0, %d)' % (i, c.shape[0]))
-        if max_self is not None and c[i, i] > max_self:
-            continue
-        if i not in kept and all(c[i, k] <= max_pairs for k in kept):
-            kept.append(i)
-    return kept
+    return _greedy_walk('select_uncrossed', order, counts, lambda c, i: max_self is None or c[i, i] <= max_self,
+                        lambda c, i, k: c[i, k] <= max_pairs)
 
 
 class KMeansRestarts:

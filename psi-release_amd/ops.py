@@ -8,6 +8,7 @@ Inputs must live on the GPU; there is no CPU path (hip.ptr raises).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import NamedTuple
 
 import torch
@@ -1363,6 +1364,54 @@ def mesh_orient_votes(points, tri, verts, faces, free, grid_min, grid_max, delta
 
 
 # ------------------------------------------------------------------------------------------
+# What the ops over a batch of bodies share (body_overlap, surface_crossings)
+# ------------------------------------------------------------------------------------------
+def _host_array(x, dtype, what):
+    import numpy as np
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    if a.dtype != dtype:
+        raise ValueError('expected %s of dtype %s, got %s' % (what, np.dtype(dtype).name, a.dtype))
+    return np.ascontiguousarray(a)
+
+
+def _batch_args(verts, group, name, then=None, max_B=None):
+    """The checks of ``verts`` [B,V,3] fp32 and ``group`` [B] int32 or None, in the order that decides which exception a doubly-wrong call
+    raises: verts, the caller's own argument checks (``then``), group, B <= ``max_B``, the device pointers (``PsiHipError`` for a CPU or
+    non-contiguous tensor), B >= 1.  Returns B, V, dev, pv, pg."""
+    if not torch.is_tensor(verts) or verts.dtype != torch.float32 or verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
+        raise ValueError('expected verts [B,V,3] float32')
+    if then is not None:
+        then()
+    B, V = int(verts.shape[0]), int(verts.shape[1])
+    dev = verts.device
+    if group is not None and (not torch.is_tensor(group) or group.dtype != torch.int32 or tuple(group.shape) != (B,) or group.device != dev):
+        raise ValueError('expected group [%d] int32 on the device of verts' % B)
+    if max_B is not None and B > max_B:
+        raise ValueError('%s: B = %d is more than %d' % (name, B, max_B))
+    pv, pg = hip.ptr(verts), hip.ptr(group)
+    if B < 1:
+        raise hip.PsiHipError('psi_%s: B >= 1' % name)
+    return B, V, dev, pv, pg
+
+
+@contextlib.contextmanager
+def _handle_or_made(given, own, create, destroy):
+    """``given`` itself when it is a handle; when ``own``, the handle ``create(given)`` makes of it, freed when the block ends."""
+    handle = create(given) if own else given
+    try:
+        yield handle
+    finally:
+        if own:
+            destroy(handle)
+
+
+def _unpack_bits(mask, n):
+    """mask [B, ceil(n / 32)] int32, bit k of a row in word k >> 5 at position k & 31 -> [B,n] bool"""
+    bit = torch.arange(n, device=mask.device)
+    return ((mask[:, bit >> 5] >> (bit & 31).to(torch.int32)) & 1).bool()
+
+
+# ------------------------------------------------------------------------------------------
 # Body against body: interpenetration counts of a batch (psi_body_overlap_*)
 # ------------------------------------------------------------------------------------------
 BODY_OVERLAP_CHUNK = 256
@@ -1375,10 +1424,9 @@ def body_overlap_create(faces, V):
     for what the library refuses: F < 1, a face index outside [0, V)."""
     import ctypes
     import numpy as np
-    f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
-    if f.dtype != np.int32 or f.ndim != 2 or f.shape[1] != 3:
+    f = _host_array(faces, np.int32, 'faces [F,3]')
+    if f.ndim != 2 or f.shape[1] != 3:
         raise ValueError('expected faces [F,3] int32')
-    f = np.ascontiguousarray(f)
     h = ctypes.c_void_p()
     hip.check(hip.lib().psi_body_overlap_create(ctypes.byref(h), f.ctypes.data_as(ctypes.c_void_p), int(V), int(f.shape[0])),
               'psi_body_overlap_create')
@@ -1403,20 +1451,11 @@ def body_overlap(verts, faces_handle_or_tensor, group=None, return_candidates=Fa
     wrong dtypes, shapes or devices, for a non-finite vertex (it names the first such body) and for more than 2^31 - 1 candidates;
     ``PsiHipError`` for what the library refuses, CPU tensors included."""
     import ctypes
-    if not torch.is_tensor(verts) or verts.dtype != torch.float32 or verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
-        raise ValueError('expected verts [B,V,3] float32')
-    B, V = int(verts.shape[0]), int(verts.shape[1])
-    dev = verts.device
-    if group is not None and (not torch.is_tensor(group) or group.dtype != torch.int32 or tuple(group.shape) != (B,) or group.device != dev):
-        raise ValueError('expected group [%d] int32 on the device of verts' % B)
-    pv, pg = hip.ptr(verts), hip.ptr(group)
-    if B < 1:
-        raise hip.PsiHipError('psi_body_overlap: B >= 1')
+    B, V, dev, pv, pg = _batch_args(verts, group, 'body_overlap')
     L = hip.lib()
-    own = torch.is_tensor(faces_handle_or_tensor)
     with torch.cuda.device(dev):
-        handle = body_overlap_create(faces_handle_or_tensor, V) if own else faces_handle_or_tensor
-        try:
+        with _handle_or_made(faces_handle_or_tensor, torch.is_tensor(faces_handle_or_tensor), lambda f: body_overlap_create(f, V),
+                             body_overlap_destroy) as handle:
             info = (ctypes.c_int32 * 2)()
             hip.check(L.psi_body_overlap_info(handle, info), 'psi_body_overlap_info')
             if info[0] != V:
@@ -1452,11 +1491,7 @@ def body_overlap(verts, faces_handle_or_tensor, group=None, return_candidates=Fa
                           'psi_body_overlap_wind')
                 hip.check(L.psi_body_overlap_decide(handle, B, hip.ptr(cand), n_cand, hip.ptr(ws), ws_bytes, hip.ptr(w), hip.ptr(counts),
                                                     hip.ptr(mask), st), 'psi_body_overlap_decide')
-        finally:
-            if own:
-                body_overlap_destroy(handle)
-        bit = torch.arange(V, device=dev)
-        inside = ((mask[:, bit >> 5] >> (bit & 31).to(torch.int32)) & 1).bool()
+        inside = _unpack_bits(mask, V)
     if return_candidates:
         return counts, inside, cand, w
     return counts, inside
@@ -1467,7 +1502,7 @@ def body_overlap(verts, faces_handle_or_tensor, group=None, return_candidates=Fa
 # ------------------------------------------------------------------------------------------
 SURFACE_CROSSINGS_CHUNK = 256
 SURFACE_CROSSINGS_MAX = 2 ** 31 - 1             # tiles, and pairs
-SURFACE_CROSSINGS_MAX_B = 46340
+SURFACE_CROSSINGS_MAX_B = 46340                  # GEOM_MAX_B of csrc/geom_shared.h: B * B < 2^31
 SURFACE_CROSSINGS_MAX_F = 2 ** 21
 
 
@@ -1479,14 +1514,6 @@ class CrossingsResult(NamedTuple):
     contour: torch.Tensor      # [B,B] fp64, symmetric: the lengths of the pairs of (i, j) added in pair order
     face_hit: torch.Tensor     # [B,F] bool: the face is in at least one crossing pair
     irregular: torch.Tensor    # [] int32: pairs with events != 2
-
-
-def _host_array(x, dtype, what):
-    import numpy as np
-    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-    if a.dtype != dtype:
-        raise ValueError('expected %s of dtype %s, got %s' % (what, np.dtype(dtype).name, a.dtype))
-    return np.ascontiguousarray(a)
 
 
 def surface_crossings_create(faces, V, order_verts=None, face_part=None, part_skip=None):
@@ -1549,26 +1576,16 @@ def surface_crossings(verts, handle_or_faces, group=None, self_pairs=True, betwe
     shapes or devices, a non-finite vertex (it names the first such body), B > 46340, (B F)^2 >= 2^63 and more than 2^31 - 1 tiles or
     pairs; ``PsiHipError`` for what the library refuses, CPU tensors included."""
     import ctypes
-    if not torch.is_tensor(verts) or verts.dtype != torch.float32 or verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
-        raise ValueError('expected verts [B,V,3] float32')
-    if mode not in ('pruned', 'brute'):
-        raise ValueError("mode is 'pruned' or 'brute', got %r" % (mode,))
-    B, V = int(verts.shape[0]), int(verts.shape[1])
-    dev = verts.device
-    if group is not None and (not torch.is_tensor(group) or group.dtype != torch.int32 or tuple(group.shape) != (B,) or group.device != dev):
-        raise ValueError('expected group [%d] int32 on the device of verts' % B)
-    if B > SURFACE_CROSSINGS_MAX_B:
-        raise ValueError('surface_crossings: B = %d is more than %d' % (B, SURFACE_CROSSINGS_MAX_B))
-    pv, pg = hip.ptr(verts), hip.ptr(group)
-    if B < 1:
-        raise hip.PsiHipError('psi_surface_crossings: B >= 1')
+    def check_mode():
+        if mode not in ('pruned', 'brute'):
+            raise ValueError("mode is 'pruned' or 'brute', got %r" % (mode,))
+    B, V, dev, pv, pg = _batch_args(verts, group, 'surface_crossings', then=check_mode, max_B=SURFACE_CROSSINGS_MAX_B)
     L = hip.lib()
-    own = not isinstance(handle_or_faces, ctypes.c_void_p)
     flags = (1 if self_pairs else 0) | (2 if between else 0) | (4 if mode == 'brute' else 0)
     i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        handle = surface_crossings_create(handle_or_faces, V) if own else handle_or_faces
-        try:
+        with _handle_or_made(handle_or_faces, not isinstance(handle_or_faces, ctypes.c_void_p), lambda f: surface_crossings_create(f, V),
+                             surface_crossings_destroy) as handle:
             info = (ctypes.c_int32 * 4)()
             hip.check(L.psi_surface_crossings_info(handle, info), 'psi_surface_crossings_info')
             if info[0] != V:
@@ -1626,11 +1643,7 @@ def surface_crossings(verts, handle_or_faces, group=None, self_pairs=True, betwe
                 hip.check(L.psi_surface_crossings_finish(handle, B, hip.ptr(keys_sorted), hip.ptr(order), hip.ptr(ev_raw), hip.ptr(len_raw), n_pairs,
                                                          hip.ptr(row_start), hip.ptr(pairs), hip.ptr(events), hip.ptr(length), hip.ptr(counts),
                                                          hip.ptr(contour), hip.ptr(mask), hip.ptr(irregular), st), 'psi_surface_crossings_finish')
-        finally:
-            if own:
-                surface_crossings_destroy(handle)
-        bit = torch.arange(F, device=dev)
-        face_hit = ((mask[:, bit >> 5] >> (bit & 31).to(torch.int32)) & 1).bool()
+        face_hit = _unpack_bits(mask, F)
     res = CrossingsResult(pairs, events, length, counts, contour, face_hit, irregular[0])
     if not return_stats:
         return res

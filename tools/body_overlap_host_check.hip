@@ -1,6 +1,7 @@
-// Host rehearsal of csrc/body_overlap.hip: the per-triple statements of csrc/body_overlap_shared.h (bo_in_box, bo_boxes_meet, bo_normal,
-// bo_half_omega, bo_w_of_sum, bo_inside) run serially on the CPU in the kernels' order: pairs ascending, vertices ascending, fp32 within a
-// chunk of 256 faces, the chunk sums in fp64 within a slice of 2048 faces, the slice sums in fp64 in slice order.  No GPU needed:
+// Host rehearsal of csrc/body_overlap.hip: the per-triple statements of csrc/geom_shared.h (geom_in_box, geom_boxes_meet, geom_normal,
+// geom_half_omega) and csrc/body_overlap_shared.h (bo_w_of_sum, bo_inside) run serially on the CPU in the kernels' order: pairs
+// ascending, vertices ascending, fp32 within a chunk of 256 faces, the chunk sums in fp64 within a slice of 2048 faces, the slice sums in
+// fp64 in slice order.  No GPU needed:
 //
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 tools/body_overlap_host_check.hip -o body_overlap_host_check
 //   body_overlap_host_check BATCH.bin OUT.bin          (add -Xarch_host -fsanitize=address,undefined for a checked run)
@@ -53,11 +54,11 @@ int main(int argc, char **argv)
     for (int i = 0; i < B; i++)
         for (int j = 0; j < B; j++) {
             if (i == j || group[i] != group[j]) continue;
-            if (!bo_boxes_meet(&lo[(size_t)i * 3], &hi[(size_t)i * 3], &lo[(size_t)j * 3], &hi[(size_t)j * 3])) continue;
+            if (!geom_boxes_meet(&lo[(size_t)i * 3], &hi[(size_t)i * 3], &lo[(size_t)j * 3], &hi[(size_t)j * 3])) continue;
             const float *vj = &verts[(size_t)j * V * 3];
             for (int v = 0; v < V; v++) {
                 const float *p = &verts[((size_t)i * V + v) * 3];
-                if (!bo_in_box(p[0], p[1], p[2], &lo[(size_t)j * 3], &hi[(size_t)j * 3])) continue;
+                if (!geom_in_box(p[0], p[1], p[2], &lo[(size_t)j * 3], &hi[(size_t)j * 3])) continue;
                 double total = 0.0;
                 for (int s = 0; s < n_slices; s++) {
                     const int f_end = std::min(F, (s + 1) * BO_SLICE);
@@ -68,8 +69,8 @@ int main(int argc, char **argv)
                             const float *A = vj + (size_t)faces[(size_t)t * 3] * 3, *Bv = vj + (size_t)faces[(size_t)t * 3 + 1] * 3,
                                         *C = vj + (size_t)faces[(size_t)t * 3 + 2] * 3;
                             float n[3];
-                            bo_normal(A, Bv, C, n);
-                            sum += bo_half_omega(A[0], A[1], A[2], Bv[0], Bv[1], Bv[2], C[0], C[1], C[2], n[0], n[1], n[2], p[0], p[1], p[2]);
+                            geom_normal(A, Bv, C, n);
+                            sum += geom_half_omega(A[0], A[1], A[2], Bv[0], Bv[1], Bv[2], C[0], C[1], C[2], n[0], n[1], n[2], p[0], p[1], p[2]);
                         }
                         acc += (double)sum;
                     }

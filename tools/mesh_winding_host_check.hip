@@ -1,6 +1,6 @@
-// Host rehearsal of csrc/mesh_winding.hip: the per-pair, per-dipole and per-cluster statements of mwind_brick_kernel (half_omega,
-// half_dipole, mwind_far, brick_box, the host-side clustering) run serially on the CPU, brick by brick, in the kernel's order of summation
-// (fp32 within a chunk of 256 records, fp64 across chunks).  No GPU needed:
+// Host rehearsal of csrc/mesh_winding.hip: the per-pair, per-dipole and per-cluster statements of mwind_brick_kernel (geom_half_omega
+// of csrc/geom_shared.h, half_dipole, mwind_far, brick_box, the host-side clustering) run serially on the CPU, brick by brick, in the
+// kernel's order of summation (fp32 within a chunk of 256 records, fp64 across chunks).  No GPU needed:
 //
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 tools/mesh_winding_host_check.hip -o mesh_winding_host_check
 //   mesh_winding_host_check MESH.bin D gminx gminy gminz gmaxx gmaxy gmaxz BETA CLUSTER OUT.f32   (add -fsanitize=address,undefined for a checked run)
@@ -104,8 +104,8 @@ int main(int argc, char **argv)
                 while (i < end) {
                     const W::WRec &r = list[i].r;
                     s += list[i].dipole ? W::half_dipole(r.a[0], r.a[1], r.a[2], r.b[0], r.b[1], r.b[2], px, py, pz)
-                                        : W::half_omega(r.a[0], r.a[1], r.a[2], r.b[0], r.b[1], r.b[2], r.c[0], r.c[1], r.c[2], r.n[0], r.n[1], r.n[2],
-                                                        px, py, pz);
+                                        : geom_half_omega(r.a[0], r.a[1], r.a[2], r.b[0], r.b[1], r.b[2], r.c[0], r.c[1], r.c[2], r.n[0], r.n[1], r.n[2],
+                                                          px, py, pz);
                     i++;
                 }
                 acc += (double)s;

@@ -1,6 +1,6 @@
-// Host rehearsal of csrc/surface_crossings.hip: the statements of csrc/surface_crossings_shared.h (sc_face_box, sc_boxes_meet,
-// sc_share_vertex, sc_pair with its division and square root) run serially on the CPU over every candidate in ascending (i, s, j, t)
-// order.  No GPU needed:
+// Host rehearsal of csrc/surface_crossings.hip: the statements of csrc/surface_crossings_shared.h (sc_face_box, sc_share_vertex, sc_pair
+// with its division and square root) and the closed-box test of csrc/geom_shared.h (geom_boxes_meet) run serially on the CPU over every
+// candidate in ascending (i, s, j, t) order.  No GPU needed:
 //
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 -ffp-contract=off tools/surface_crossings_host_check.hip -o surface_crossings_host_check
 //   surface_crossings_host_check BATCH.bin OUT.bin     (add -Xarch_host -fsanitize=address,undefined for a checked run)
@@ -58,7 +58,7 @@ int main(int argc, char **argv)
                 if (i == j ? !(flags & SC_SELF) : (!(flags & SC_BETWEEN) || group[i] != group[j])) continue;
                 for (int t = (i == j ? s + 1 : 0); t < F; t++) {
                     const size_t b = (size_t)j * F + t;
-                    if (!sc_boxes_meet(&lo[a * 3], &hi[a * 3], &lo[b * 3], &hi[b * 3])) continue;
+                    if (!geom_boxes_meet(&lo[a * 3], &hi[a * 3], &lo[b * 3], &hi[b * 3])) continue;
                     if (i == j) {
                         if (sc_share_vertex(&faces[(size_t)s * 3], &faces[(size_t)t * 3])) continue;
                         if (P && skip[(size_t)part[s] * P + part[t]]) continue;
