@@ -761,6 +761,54 @@ int psi_body_overlap_wind(const psi_body_overlap *h, const float *d_verts, int B
 int psi_body_overlap_decide(const psi_body_overlap *h, int B, const int32_t *d_cand, long long n_cand, const void *d_workspace,
                             size_t workspace_bytes, float *d_w, int32_t *d_counts, uint32_t *d_mask, void *stream);
 
+/* ---- body against body: penetration depth, its aggregates and the gradient rows of the penetration loss ----
+ * Contract (csrc/body_depth_shared.h and csrc/closest_point_shared.h hold the statements; no contraction, IEEE division and square root:
+ * an fp32 NumPy restatement gives the same bits).  h: a psi_body_overlap handle (its faces); d_verts [B,V,3] fp32; d_trip [n,3] int32 =
+ * (i, j, v), strictly ascending, i != j, every index in range: vertex v of body i against body j.  Any triple is allowed; the inside triples
+ * of a batch are the candidates of psi_body_overlap_* with w > 0.5, in their order.
+ *   record     of face t of body j: a = X[f0], ab = X[f1] - a, ac = X[f2] - a, each rounded once, from the current vertices
+ *   test       ap = p - a; the seven-region closest point of psi_mesh_sdf (same routine, same order of tests) gives r = p - c and the
+ *              region (0 face, 1 edge ab, 2 edge bc, 3 edge ca, 4 5 6 vertex a b c); d2 = (r.x*r.x + r.y*r.y) + r.z*r.z
+ *   winner     the face with the smallest key = bits(d2) << 32 | t, compared as unsigned: equal d2 goes to the lower face, a non-finite d2
+ *              (a collinear face can give one) loses to every finite one; the visiting order is free
+ *   row        face, region, depth = sqrt(d2), r [3], bary [3] = the barycentric coordinates of c, from the quotients v, w the routine
+ *              forms: region 4 (1,0,0), 5 (0,1,0), 6 (0,0,1), 1 (1-v,v,0), 3 (1-w,0,w), 2 (0,1-w,w), 0 ((1-v)-w,v,w)
+ *   aggregates over the inside triples, in triple order: max_depth [B,B] fp32 (integer maximum of the bits), sum_depth and sum_sq [B,B]
+ *              fp64 (sum += (double)depth; sum_sq += (double)depth * (double)depth, one triple after the other), depth_of [B,V] fp32 (the
+ *              largest depth of a vertex over all j), loss [2,B] fp32: loss[0,i] = (float) sum_j sum_depth[i,j], loss[1,i] the same of
+ *              sum_sq, the pair sums added in fp64 in j order
+ *   gradient   of sum_i g[i] loss[p,i], exact where the winner is unique: s = (depth > 0 ? 1 / depth : 0) for penalty 0 (depth), s = 2
+ *              for penalty 1 (squared); u = (g[i] * s) * r; triple k gives rows 4k .. 4k+3: (i V + v, +u) and (j V + f_m, -(bary[m] * u)),
+ *              m = 0, 1, 2.  The caller sorts the targets stably; psi_segment_sum3 adds every run in sorted order in fp32
+ * No floating-point atomics: every output is bit-identical from run to run, and the row of a triple does not depend on the rest of the
+ * batch.  The passes (each one kernel on `stream`, no host synchronisation, none launches an empty grid: with n = 0 the caller stops):
+ *   nearest    the hot pass, grid = (256-triple chunk of ONE pair, 2048-face slice).  d_chunks [n_chunks,4] int32 = (first triple,
+ *              triples, i, j) as psi_body_overlap_emit writes it, rebuilt by the caller for its list.  Writes one uint64 key per (slice,
+ *              triple) into d_workspace (psi_body_depth_workspace_bytes(n, F) = ceil(F / 2048) * n * 8 bytes; 0 for n outside [1, 2^29))
+ *   finish     the smallest key over the slices, the winner's statement once more (the same inputs, the same bits); writes d_face,
+ *              d_region [n] int32, d_depth [n], d_r and d_bary [n,3] fp32
+ *   pairs      one workgroup per body; d_row_start [B+1] int64 = the first triple of every body i.  Writes d_loss [2,B] and the non-zero
+ *              entries of d_max_depth, d_sum_depth, d_sum_sq [B,B] and d_depth_of [B,V], all four ZEROED BY THE CALLER
+ *   grad_rows  d_g [B] fp32; writes d_targets [4n] int64 and d_rows [4n,3] fp32
+ *   psi_segment_sum3  general: d_targets_sorted [m] int64 ascending, d_order [m] int64 (row d_order[k] belongs to sorted position k) or NULL
+ *              (the rows are in sorted order), d_rows [m,3] fp32.  The lane that starts a run of equal targets adds the run in order,
+ *              ((0 + x0) + x1) + ..., and stores d_out[target] once; d_out [n_out,3] is ZEROED BY THE CALLER, targets outside [0, n_out)
+ *              are ignored
+ * PSI_EINVAL: a null pointer (d_order excepted), B < 1 or B > 46340, n outside [1, 2^29), n_chunks outside [1, n], a workspace smaller than
+ * the query's value, a penalty other than 0 or 1, m outside [1, 2^31), n_out < 1. */
+size_t psi_body_depth_workspace_bytes(long long n, int F);
+int psi_body_depth_nearest(const psi_body_overlap *h, const float *d_verts, int B, const int32_t *d_trip, long long n, const int32_t *d_chunks,
+                           long long n_chunks, void *d_workspace, size_t workspace_bytes, void *stream);
+int psi_body_depth_finish(const psi_body_overlap *h, const float *d_verts, int B, const int32_t *d_trip, long long n, const void *d_workspace,
+                          size_t workspace_bytes, int32_t *d_face, int32_t *d_region, float *d_depth, float *d_r, float *d_bary, void *stream);
+int psi_body_depth_pairs(const psi_body_overlap *h, int B, const int32_t *d_trip, long long n, const float *d_depth, const int64_t *d_row_start,
+                         float *d_max_depth, double *d_sum_depth, double *d_sum_sq, float *d_depth_of, float *d_loss, void *stream);
+int psi_body_depth_grad_rows(const psi_body_overlap *h, int B, const int32_t *d_trip, long long n, const int32_t *d_face, const float *d_depth,
+                             const float *d_r, const float *d_bary, const float *d_g, int penalty, int64_t *d_targets, float *d_rows,
+                             void *stream);
+int psi_segment_sum3(const int64_t *d_targets_sorted, const int64_t *d_order, const float *d_rows, long long m, float *d_out, long long n_out,
+                     void *stream);
+
 /* ---- Surface crossings: which pairs of triangles of the posed body surfaces of a batch properly intersect (csrc/surface_crossings.hip) ----
  * Contract (csrc/surface_crossings_shared.h holds the statements).  d_verts [B,V,3] fp32, world frame; the faces
  * [F,3] int32 of the handle are shared by all bodies; d_group [B] int32 or NULL; flags = 1 (self pairs) | 2 (between bodies) | 4 (brute:

@@ -20,11 +20,6 @@
 #include <limits.h>
 #include <vector>
 
-struct psi_body_overlap {
-    int32_t *d_faces;
-    int V, F;
-};
-
 namespace psi_bo {
 
 constexpr int WG = WG_LANES;

@@ -4,6 +4,13 @@
 // tests (geom_in_box, geom_boxes_meet), the fp32 normal (geom_normal) and the solid angle (geom_half_omega) are csrc/geom_shared.h.
 #pragma once
 #include "geom_shared.h"
+#include <stdint.h>
+
+// The handle of psi_body_overlap_create, which csrc/body_depth.hip takes as well: the one topology of every body, on the device
+struct psi_body_overlap {
+    int32_t *d_faces;
+    int V, F;
+};
 
 constexpr int BO_CHUNK = 256;       // consecutive faces summed in fp32: a constant of the contract, not a launch parameter
 constexpr int BO_SLICE = 2048;      // consecutive faces whose chunk sums are added in fp64, in order, before the slices are

@@ -6,6 +6,8 @@ Same SMPL-X + SDF path as fitting (HIP operators), Habitat camera flip (:160-165
 time through the operators; ``scores_many`` / ``eval_folder_batched`` / ``evaluate_scenes`` score whole folders with one fused
 skin + sign-count launch per chunk of bodies (psi_lbs_sdf_counts) and one device -> host copy.
 
+Body against body: ``BodyOverlap.depths`` and ``.penetration_loss`` say how deep the vertices stand and push the bodies apart (psi_body_depth_*,
+DESIGN.md section 10f), ``select_shallow`` keeps a set of bodies no deeper in each other than a tolerance.
 Body against body: ``BodyOverlap`` counts, per ordered pair of a batch, the vertices of one body inside the other (psi_body_overlap_*,
 DESIGN.md section 10d), and ``select_disjoint`` picks a greedy set of bodies that do not stand in each other; the reference has no
 counterpart on the path (its BodyInterpenetration needs an external CUDA package).  ``SurfaceCrossings`` lists the pairs of triangles of
@@ -275,6 +277,26 @@ class BodyOverlap(_FacesHandleOwner):
         verts = _verts_of_records(xh72, cam_ext, evaluator_or_decoder, chunk, self.device, 'counts_of_records')
         return self.counts(verts, group)
 
+    @torch.no_grad()
+    def depths(self, verts, group=None):
+        """How deep the vertices of ``counts`` stand in the other body (``ops.body_penetration``): the inside
+        triples with the nearest face, region, depth, r and barycentric coordinates of each, max_depth [B,B] fp32, sum_depth and sum_sq
+        [B,B] fp64, depth_of [B,V] fp32, together with ``counts`` and ``inside``.  Returns ``ops.PenetrationResult``."""
+        return ops.body_penetration(verts.contiguous(), self._handle_for(int(verts.shape[1])), group=self._group(group, verts))
+
+    @torch.no_grad()
+    def depths_of_records(self, xh72, cam_ext, evaluator_or_decoder, chunk=512, group=None):
+        """``depths`` of the bodies ``xh72`` [N,72], skinned exactly as ``counts_of_records`` skins them, in ONE call over all N."""
+        verts = _verts_of_records(xh72, cam_ext, evaluator_or_decoder, chunk, self.device, 'depths_of_records')
+        return self.depths(verts, group)
+
+    def penetration_loss(self, verts, group=None, penalty='depth'):
+        """loss [B] fp32, differentiable with respect to ``verts`` (``ops.body_penetration_loss``): the sum of the depths of the vertices
+        of body i inside other bodies (``penalty='depth'``) or of their squares (``'squared'``).  ``verts`` must be contiguous."""
+        if penalty not in ops.BODY_DEPTH_PENALTIES:
+            raise ValueError('penalty is one of %s, got %r' % (sorted(ops.BODY_DEPTH_PENALTIES), penalty))
+        return ops.body_penetration_loss(verts, self._handle_for(int(verts.shape[1])), group=self._group(group, verts), penalty=penalty)
+
 
 def _greedy_walk(name, order, counts, admit, meets):
     """Walk the bodies in ``order`` and keep body i iff ``admit(c, i)`` and ``meets(c, i, k)`` for every body k already kept; ``c`` is
@@ -298,6 +320,18 @@ def select_disjoint(order, counts, max_inside=0):
     iff counts[i,k] + counts[k,i] <= max_inside for every body k already kept.  ``counts`` [B,B]: ``OverlapResult.counts`` (a tensor or an
     array).  Returns the kept indices in ``order``'s order."""
     return _greedy_walk('select_disjoint', order, counts, lambda c, i: True, lambda c, i, k: c[i, k] + c[k, i] <= max_inside)
+
+
+def select_shallow(order, max_depth, tol):
+    """``select_disjoint``'s walk over the penetration depths (``PenetrationResult.max_depth`` [B,B] fp32): keep body i iff
+    max(max_depth[i,k], max_depth[k,i]) <= tol for every body k already kept.  Returns the kept indices in ``order``'s order."""
+    m = max_depth.detach().cpu().numpy() if torch.is_tensor(max_depth) else np.asarray(max_depth)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError('select_shallow: max_depth is [B,B], got %s' % (m.shape,))
+    if not tol >= 0:
+        raise ValueError('select_shallow: tol must not be negative')
+    deeper = (~(m.astype(np.float64) <= float(tol))).astype(np.int64)        # 1 where the pair is deeper than tol (or not a number)
+    return _greedy_walk('select_shallow', order, deeper, lambda c, i: True, lambda c, i, k: c[i, k] == 0 and c[k, i] == 0)
 
 
 class SurfaceCrossings(_FacesHandleOwner):

@@ -155,6 +155,12 @@ SIGNATURES = {
     'psi_body_overlap_emit': (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 4 + [ctypes.c_longlong] * 2 + [c_void_p] * 3),
     'psi_body_overlap_wind': (c_int, [c_void_p] * 2 + [c_int, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_size_t, c_void_p]),
     'psi_body_overlap_decide': (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_void_p, c_size_t] + [c_void_p] * 4),
+    'psi_body_depth_workspace_bytes': (c_size_t, [ctypes.c_longlong, c_int]),
+    'psi_body_depth_nearest': (c_int, [c_void_p] * 2 + [c_int, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_size_t, c_void_p]),
+    'psi_body_depth_finish': (c_int, [c_void_p] * 2 + [c_int, c_void_p, ctypes.c_longlong, c_void_p, c_size_t] + [c_void_p] * 6),
+    'psi_body_depth_pairs': (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong] + [c_void_p] * 8),
+    'psi_body_depth_grad_rows': (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong] + [c_void_p] * 5 + [c_int] + [c_void_p] * 3),
+    'psi_segment_sum3': (c_int, [c_void_p] * 3 + [ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p]),
     'psi_surface_crossings_face_order': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'psi_surface_crossings_create': (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 3 + [c_int]),
     'psi_surface_crossings_destroy': (None, [c_void_p]),

@@ -1498,6 +1498,244 @@ def body_overlap(verts, faces_handle_or_tensor, group=None, return_candidates=Fa
 
 
 # ------------------------------------------------------------------------------------------
+# Body against body: penetration depth, its aggregates, the loss and its gradient (psi_body_depth_*, psi_segment_sum3)
+# ------------------------------------------------------------------------------------------
+BODY_DEPTH_MAX_TRIPLES = 2 ** 29 - 1
+BODY_DEPTH_PENALTIES = {'depth': 0, 'squared': 1}
+
+
+class DepthRows(NamedTuple):
+    face: torch.Tensor         # [n] int32: the nearest face of body j
+    region: torch.Tensor       # [n] int32: 0 face, 1 edge ab, 2 edge bc, 3 edge ca, 4 5 6 vertex a b c
+    depth: torch.Tensor        # [n] fp32: the distance of the vertex to that face
+    r: torch.Tensor            # [n,3] fp32: the vertex minus its closest point c
+    bary: torch.Tensor         # [n,3] fp32: the barycentric coordinates of c in the face
+
+
+class PenetrationResult(NamedTuple):
+    triples: torch.Tensor      # [n,3] int32 (i, j, v): the inside triples, ascending
+    rows: DepthRows
+    max_depth: torch.Tensor    # [B,B] fp32: the deepest vertex of i inside j
+    sum_depth: torch.Tensor    # [B,B] fp64: the depths of the vertices of i inside j, added in triple order
+    sum_sq: torch.Tensor       # [B,B] fp64: their squares
+    depth_of: torch.Tensor     # [B,V] fp32: the largest depth of the vertex over all j, 0 where it is inside no body
+    loss: torch.Tensor         # [2,B] fp32: row 0 = (float) sum_j sum_depth[i,j], row 1 the same of sum_sq
+    counts: torch.Tensor       # [B,B] int32 and
+    inside: torch.Tensor       # [B,V] bool: as body_overlap returns them
+
+
+def _overlap_handle(handle_or_faces, V):
+    return _handle_or_made(handle_or_faces, torch.is_tensor(handle_or_faces), lambda f: body_overlap_create(f, V), body_overlap_destroy)
+
+
+def _overlap_handle_F(handle, V):
+    import ctypes
+    info = (ctypes.c_int32 * 2)()
+    hip.check(hip.lib().psi_body_overlap_info(handle, info), 'psi_body_overlap_info')
+    if info[0] != V:
+        raise ValueError('the handle was made for %d vertices per body, verts has %d' % (info[0], V))
+    return int(info[1])
+
+
+def _depth_chunk_table(pair_count, B, n_chunks):
+    """The chunk table of psi_body_overlap_emit, [n_chunks,4] int32 = (first triple, triples, i, j), for an ascending triple list with
+    ``pair_count`` [B*B] int64 triples per ordered pair: plumbing, no host synchronisation."""
+    pair_chunks = (pair_count + (BODY_OVERLAP_CHUNK - 1)) // BODY_OVERLAP_CHUNK
+    chunk_inc, trip_inc = torch.cumsum(pair_chunks, 0), torch.cumsum(pair_count, 0)
+    c = torch.arange(n_chunks, dtype=torch.int64, device=pair_count.device)
+    p = torch.searchsorted(chunk_inc, c, right=True).clamp_(max=B * B - 1)
+    k = c - (chunk_inc - pair_chunks)[p]
+    first = (trip_inc - pair_count)[p] + k * BODY_OVERLAP_CHUNK
+    cnt = (pair_count[p] - k * BODY_OVERLAP_CHUNK).clamp_(min=0, max=BODY_OVERLAP_CHUNK)
+    return torch.stack([first, cnt, p // B, p % B], 1).to(torch.int32).contiguous()
+
+
+def _depth_rows(handle, F, verts, trip, pair_count, n_chunks):
+    """nearest and finish for the ascending triples ``trip`` [n,3], n >= 1."""
+    L, st, dev = hip.lib(), hip.stream(), verts.device
+    B, n = int(verts.shape[0]), int(trip.shape[0])
+    chunks = _depth_chunk_table(pair_count, B, n_chunks)
+    ws_bytes = int(L.psi_body_depth_workspace_bytes(n, F))
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    rows = DepthRows(torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                     torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, 3, dtype=torch.float32, device=dev),
+                     torch.empty(n, 3, dtype=torch.float32, device=dev))
+    hip.check(L.psi_body_depth_nearest(handle, hip.ptr(verts), B, hip.ptr(trip), n, hip.ptr(chunks), n_chunks, hip.ptr(ws), ws_bytes, st),
+              'psi_body_depth_nearest')
+    hip.check(L.psi_body_depth_finish(handle, hip.ptr(verts), B, hip.ptr(trip), n, hip.ptr(ws), ws_bytes, hip.ptr(rows.face),
+                                      hip.ptr(rows.region), hip.ptr(rows.depth), hip.ptr(rows.r), hip.ptr(rows.bary), st), 'psi_body_depth_finish')
+    return rows
+
+
+def _empty_depth_rows(dev):
+    return DepthRows(torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                     torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, 3, dtype=torch.float32, device=dev),
+                     torch.empty(0, 3, dtype=torch.float32, device=dev))
+
+
+def body_depth(verts, handle_or_faces, triples):
+    """How far vertex v of body i is from the surface of body j, for every row (i, j, v) of ``triples`` (include/psi_hip.h:
+    psi_body_depth_*): the nearest of the F current triangles of j by the seven-region closest point, bit-equal to
+    the fp32 NumPy restatement.  verts [B,V,3] fp32 on the GPU; ``handle_or_faces``: a handle of ``body_overlap_create`` or faces [F,3]
+    int32; ``triples`` [n,3] int32 on the device of verts, strictly ascending, i != j, every index in range — any such triple, not only
+    one whose vertex is inside.  Returns ``DepthRows``, on the device.
+
+    Two kernels on the current stream; the chunk table is plumbing.  ONE read-back: the verdict on the triples together with the number
+    of 256-triple chunks.  n = 0 launches nothing.  ``ValueError`` for wrong dtypes, shapes or devices and for triples that are not strictly
+    ascending, have i == j or an index out of range; ``PsiHipError`` for what the library refuses, CPU tensors included."""
+    def check_triples():
+        if not torch.is_tensor(triples) or triples.dtype != torch.int32 or triples.dim() != 2 or triples.shape[1] != 3:
+            raise ValueError('expected triples [n,3] int32')
+        if triples.device != verts.device:
+            raise ValueError('expected triples on the device of verts')
+        if triples.shape[0] > BODY_DEPTH_MAX_TRIPLES:
+            raise ValueError('%d triples: more than 2^29 - 1' % triples.shape[0])
+
+    B, V, dev, pv, _ = _batch_args(verts, None, 'body_depth', then=check_triples)
+    n = int(triples.shape[0])
+    with torch.cuda.device(dev), torch.no_grad():
+        with _overlap_handle(handle_or_faces, V) as handle:
+            F = _overlap_handle_F(handle, V)
+            if n == 0:
+                return _empty_depth_rows(dev)
+            trip = triples.contiguous()
+            t = trip.to(torch.int64)
+            i, j, v = t[:, 0], t[:, 1], t[:, 2]
+            key = (i * B + j) * V + v
+            bad = ((i < 0) | (i >= B) | (j < 0) | (j >= B) | (v < 0) | (v >= V) | (i == j)).any() | (key[1:] <= key[:-1]).any()
+            pair_count = torch.zeros(B * B, dtype=torch.int64, device=dev).scatter_add_(0, (i * B + j).clamp(0, B * B - 1), torch.ones_like(i))
+            n_chunks = ((pair_count + (BODY_OVERLAP_CHUNK - 1)) // BODY_OVERLAP_CHUNK).sum()
+            is_bad, n_chunks = torch.stack([bad.to(torch.int64), n_chunks]).cpu().tolist()
+            if is_bad:
+                raise ValueError('triples must be strictly ascending (i, j, v) rows with i != j, i and j in [0, %d) and v in [0, %d)' % (B, V))
+            return _depth_rows(handle, F, verts, trip, pair_count, n_chunks)
+
+
+def body_penetration(verts, handle_or_faces, group=None):
+    """``body_overlap`` and, for its inside triples (the candidates with w > 0.5, in their order), ``body_depth`` and the aggregates of
+    DESIGN.md section 10f.  Arguments as ``body_overlap``.  Returns ``PenetrationResult``, on the device.
+
+    Host read-backs: ``body_overlap``'s one, and ONE more (the number of inside triples and of their 256-triple chunks); the inside
+    triples are gathered with a stable sort of the decisions, whose size is then known, not with a boolean index.  A batch with no candidate
+    stops after ``body_overlap``; one with no inside vertex gives zeros and launches nothing more."""
+    B, V, dev, pv, pg = _batch_args(verts, group, 'body_penetration')
+    L = hip.lib()
+    with torch.cuda.device(dev), torch.no_grad():
+        with _overlap_handle(handle_or_faces, V) as handle:
+            F = _overlap_handle_F(handle, V)
+            counts, inside, cand, w = body_overlap(verts, handle, group=group, return_candidates=True)
+            max_depth = torch.zeros(B, B, dtype=torch.float32, device=dev)
+            sum_depth, sum_sq = torch.zeros(B, B, dtype=torch.float64, device=dev), torch.zeros(B, B, dtype=torch.float64, device=dev)
+            depth_of = torch.zeros(B, V, dtype=torch.float32, device=dev)
+            loss = torch.zeros(2, B, dtype=torch.float32, device=dev)
+            n_in = n_chunks = 0
+            if cand.shape[0] > 0:
+                pair_count = counts.reshape(-1).to(torch.int64)
+                n_in, n_chunks = torch.stack([pair_count.sum(), ((pair_count + (BODY_OVERLAP_CHUNK - 1)) // BODY_OVERLAP_CHUNK).sum()]).cpu().tolist()
+            if n_in == 0:
+                return PenetrationResult(cand[:0], _empty_depth_rows(dev), max_depth, sum_depth, sum_sq, depth_of, loss, counts, inside)
+            if n_in > BODY_DEPTH_MAX_TRIPLES:
+                raise ValueError('the batch has %d inside triples: more than 2^29 - 1' % n_in)
+            keep = torch.sort((~(w > 0.5)).to(torch.uint8), stable=True).indices[:n_in]       # the triples with w > 0.5, in their order
+            trip = cand[keep].contiguous()
+            rows = _depth_rows(handle, F, verts, trip, pair_count, n_chunks)
+            row_start = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+            row_start[1:] = torch.cumsum(pair_count.view(B, B).sum(1), 0)
+            hip.check(L.psi_body_depth_pairs(handle, B, hip.ptr(trip), n_in, hip.ptr(rows.depth), hip.ptr(row_start), hip.ptr(max_depth),
+                                             hip.ptr(sum_depth), hip.ptr(sum_sq), hip.ptr(depth_of), hip.ptr(loss), hip.stream()),
+                      'psi_body_depth_pairs')
+            return PenetrationResult(trip, rows, max_depth, sum_depth, sum_sq, depth_of, loss, counts, inside)
+
+
+def segment_sum3(targets_sorted, rows, n_out, order=None):
+    """out [n_out,3] fp32 with out[t] = ((0 + x0) + x1) + ... over the run of rows whose target is t, in the order of the list
+    (psi_segment_sum3): ``targets_sorted`` [m] int64 ascending, ``rows`` [m,3] fp32, ``order`` [m] int64 or None: sorted position k takes
+    row order[k].  Rows of untouched targets are 0; a target outside [0, n_out) is ignored.  No floating-point atomics."""
+    if (not torch.is_tensor(targets_sorted) or targets_sorted.dtype != torch.int64 or targets_sorted.dim() != 1 or not torch.is_tensor(rows)
+            or rows.dtype != torch.float32 or tuple(rows.shape) != (targets_sorted.shape[0], 3) or rows.device != targets_sorted.device):
+        raise ValueError('expected targets_sorted [m] int64 and rows [m,3] float32 on one device')
+    if order is not None and (not torch.is_tensor(order) or order.dtype != torch.int64 or order.shape != targets_sorted.shape
+                              or order.device != rows.device):
+        raise ValueError('expected order [m] int64 on the device of rows')
+    if int(n_out) < 1:
+        raise ValueError('n_out >= 1')
+    pt, pr, po = hip.ptr(targets_sorted), hip.ptr(rows), hip.ptr(order)
+    m = int(targets_sorted.shape[0])
+    with torch.cuda.device(rows.device):
+        out = torch.zeros(int(n_out), 3, dtype=torch.float32, device=rows.device)
+        if m > 0:
+            hip.check(hip.lib().psi_segment_sum3(pt, po, pr, m, hip.ptr(out), int(n_out), hip.stream()), 'psi_segment_sum3')
+    return out
+
+
+def body_penetration_grad(verts_shape, handle, triples, rows, g, penalty='depth'):
+    """G [B,V,3] fp32: the gradient of sum_i g[i] loss[i] with respect to the vertices, for the inside ``triples`` and their ``rows``
+    (``PenetrationResult``): grad_rows, a stable ``torch.sort`` of the targets, the segment sum.  No read-back."""
+    if penalty not in BODY_DEPTH_PENALTIES:
+        raise ValueError('penalty is one of %s, got %r' % (sorted(BODY_DEPTH_PENALTIES), penalty))
+    B, V = int(verts_shape[0]), int(verts_shape[1])
+    if not torch.is_tensor(g) or g.dtype != torch.float32 or tuple(g.shape) != (B,):
+        raise ValueError('expected g [%d] float32' % B)
+    dev, n = g.device, int(triples.shape[0])
+    with torch.cuda.device(dev), torch.no_grad():
+        if n == 0:
+            return torch.zeros(B, V, 3, dtype=torch.float32, device=dev)
+        g = g.contiguous()
+        targets = torch.empty(4 * n, dtype=torch.int64, device=dev)
+        grows = torch.empty(4 * n, 3, dtype=torch.float32, device=dev)
+        hip.check(hip.lib().psi_body_depth_grad_rows(handle, B, hip.ptr(triples), n, hip.ptr(rows.face), hip.ptr(rows.depth), hip.ptr(rows.r),
+                                                     hip.ptr(rows.bary), hip.ptr(g), BODY_DEPTH_PENALTIES[penalty], hip.ptr(targets),
+                                                     hip.ptr(grows), hip.stream()), 'psi_body_depth_grad_rows')
+        srt = torch.sort(targets, stable=True)
+        return segment_sum3(srt.values, grows, B * V, order=srt.indices).view(B, V, 3)
+
+
+class _OwnedOverlapHandle:
+    """A handle made for one call of ``body_penetration_loss`` from a faces tensor: it lives as long as the graph that needs it."""
+
+    def __init__(self, faces, V):
+        self.handle = body_overlap_create(faces, V)
+
+    def __del__(self):
+        try:
+            body_overlap_destroy(self.handle)
+        except Exception:
+            pass
+
+
+class _BodyPenetrationLoss(Function):
+    @staticmethod
+    def forward(ctx, verts, handle, owner, group, penalty):
+        res = body_penetration(verts, handle, group=group)
+        ctx.handle, ctx.owner, ctx.penalty, ctx.shape = handle, owner, penalty, tuple(verts.shape)
+        ctx.save_for_backward(res.triples, *res.rows)
+        return res.loss[BODY_DEPTH_PENALTIES[penalty]].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        trip, *rows = ctx.saved_tensors
+        G = body_penetration_grad(ctx.shape, ctx.handle, trip, DepthRows(*rows), g.to(torch.float32).contiguous(), ctx.penalty)
+        return G, None, None, None, None
+
+
+def body_penetration_loss(verts, handle_or_faces, group=None, penalty='depth'):
+    """loss [B] fp32: how deep body i stands in the other bodies of the batch, (float) sum_j sum_depth[i,j] for ``penalty='depth'`` (the
+    L1 form of the scene collision term; the default) or (float) sum_j sum_sq[i,j] for ``'squared'``.
+    Differentiable with respect to ``verts``: the gradient reaches the inside vertex and, with the barycentric weights of its closest
+    point, the three corners of the nearest face of the other body; it is exact by the envelope theorem wherever the winner is unique.
+    The backward pass runs grad_rows, a stable ``torch.sort`` and the segment sum: no floating-point atomics, bit-identical from run to
+    run, no read-back.  The forward pass is ``body_penetration`` (two read-backs, ``body_overlap``'s included).  No inside vertex: zeros, a
+    zero gradient and no launch.  ``ValueError`` for an unknown penalty and for what ``body_overlap`` refuses."""
+    if penalty not in BODY_DEPTH_PENALTIES:
+        raise ValueError('penalty is one of %s, got %r' % (sorted(BODY_DEPTH_PENALTIES), penalty))
+    if not torch.is_tensor(verts) or verts.dtype != torch.float32 or verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
+        raise ValueError('expected verts [B,V,3] float32')
+    hip.ptr(verts)                              # a CPU or non-contiguous tensor is refused before a handle is made
+    owner = _OwnedOverlapHandle(handle_or_faces, int(verts.shape[1])) if torch.is_tensor(handle_or_faces) else None
+    return _BodyPenetrationLoss.apply(verts, owner.handle if owner else handle_or_faces, owner, group, penalty)
+
+
+# ------------------------------------------------------------------------------------------
 # Surface crossings: triangle pairs of the bodies of a batch that intersect (psi_surface_crossings_*)
 # ------------------------------------------------------------------------------------------
 SURFACE_CROSSINGS_CHUNK = 256

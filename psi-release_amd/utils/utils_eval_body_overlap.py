@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """python utils_eval_body_overlap.py GEN_FOLDER [--human_model_path ... --vposer_ckpt_path ... | --synthetic DIR] [--no_flip]
-                                                 [--max_inside 0] [--out JSON] [--crossings [--self] [--parts]]
+                                                 [--max_inside 0] [--out JSON] [--crossings [--self] [--parts]] [--depth [--tol M]]
 
 Which bodies of GEN_FOLDER/body_gen_*.pkl stand in each other: every body is placed as utils_show_test_results.py places it (cam_ext .
 T_mat for Habitat trees, cam_ext with --no_flip for PROX-E), and every vertex of every body is tested against every other body
@@ -14,7 +14,12 @@ of every pair of bodies with the length of their contour, the number of irregula
 vertex of either is inside the other.  --self also tests every body against itself and ranks the bodies by self crossings; --parts
 then ignores pairs of faces of the same body part, of a part and its kinematic parent and of the pairs of parts
 human_body_prior/body_model/body_model.py:488 lists, the parts taken from the model's own skinning weights and kinematic tree.  Without
---crossings every printed line and every JSON field is what it was."""
+--crossings every printed line and every JSON field is what it was.
+
+--depth adds how far in the vertices are (evaluation.BodyOverlap.depths: the distance of every inside vertex to the nearest triangle of
+the body it is in): the largest and the mean depth of every overlapping ordered pair, the bodies ranked by their deepest vertex, and the
+greedy set of bodies that stand no deeper than --tol metres in each other (evaluation.select_shallow, in file order).  Without --depth
+every printed line and every JSON field is what it was."""
 import argparse
 import json
 
@@ -37,7 +42,13 @@ def parse_args(argv=None):
     ap.add_argument('--crossings', action='store_true', help='also list the pairs of triangles of the surfaces that intersect')
     ap.add_argument('--self', dest='self_pairs', action='store_true', help='with --crossings: also every body against itself')
     ap.add_argument('--parts', action='store_true', help='with --crossings --self: ignore pairs of faces of adjacent body parts')
+    ap.add_argument('--depth', action='store_true', help='also report how deep the inside vertices are')
+    ap.add_argument('--tol', type=float, default=0.0, metavar='M', help='with --depth: the depth two kept bodies may reach in each other, in metres')
     a = ap.parse_args(argv)
+    if a.tol != 0.0 and not a.depth:
+        ap.error('--tol needs --depth')
+    if not a.tol >= 0.0:
+        ap.error('--tol must not be negative')
     if a.self_pairs and not a.crossings:
         ap.error('--self needs --crossings')
     if a.parts and not a.self_pairs:
@@ -92,6 +103,18 @@ def crossings_report(res, overlap_counts):
             'unseen_by_vertex_test': sum(1 for i, j, _, _ in pairs if ov[i, j] == 0 and ov[j, i] == 0)}
 
 
+def depth_report(max_depth, sum_depth, counts, depth_of, tol):
+    """The JSON fields of --depth: max_depth, sum_depth and counts [B,B], depth_of [B,V], as host arrays."""
+    from psi_release_amd.evaluation import select_shallow
+    max_depth, sum_depth, counts = np.asarray(max_depth, np.float32), np.asarray(sum_depth, np.float64), np.asarray(counts, np.int64)
+    B = len(counts)
+    deepest = np.asarray(depth_of, np.float32).max(1)
+    pairs = [[i, j, float(max_depth[i, j]), float(sum_depth[i, j] / counts[i, j])] for i in range(B) for j in range(B) if counts[i, j]]
+    return {'depth_pairs': pairs, 'max_depth': max_depth.astype(np.float64).tolist(), 'deepest': deepest.astype(np.float64).tolist(),
+            'deepest_ranked': sorted(range(B), key=lambda i: (-float(deepest[i]), i)), 'tol': float(tol),
+            'shallow': select_shallow(range(B), max_depth, tol)}
+
+
 def main(argv=None):
     a = parse_args(argv)
     from psi_release_amd import synth
@@ -106,8 +129,12 @@ def main(argv=None):
         raise SystemExit('no body_gen_*.pkl in %s' % a.gen_folder)
     decoder = BodyDecoder(smplx_src, vposer_src, device)
     overlap = BodyOverlap(decoder.faces, device)
-    res = overlap.counts_of_records(xh, camera_pose(cam, a.no_flip), decoder, chunk=a.chunk)
-    rep = report_of(res.counts.cpu().numpy(), res.per_body.cpu().numpy(), a.max_inside)
+    if a.depth:
+        pen = overlap.depths_of_records(xh, camera_pose(cam, a.no_flip), decoder, chunk=a.chunk)
+        rep = report_of(pen.counts.cpu().numpy(), pen.inside.sum(1).cpu().numpy(), a.max_inside)
+    else:
+        res = overlap.counts_of_records(xh, camera_pose(cam, a.no_flip), decoder, chunk=a.chunk)
+        rep = report_of(res.counts.cpu().numpy(), res.per_body.cpu().numpy(), a.max_inside)
     print('[INFO] %d bodies, %d overlapping pairs' % (rep['bodies'], rep['overlapping_pairs']))
     for i in rep['ranked']:
         print('body %6d: %6d vertices inside other bodies' % (i, rep['per_body'][i]))
@@ -127,6 +154,14 @@ def main(argv=None):
             for i in crep['self_ranked']:
                 print('body %6d: %6d self crossings' % (i, crep['self_crossings'][i]))
         print('[INFO] %d pairs of bodies cross although no vertex of either is inside the other' % crep['unseen_by_vertex_test'])
+    if a.depth:
+        drep = depth_report(pen.max_depth.cpu().numpy(), pen.sum_depth.cpu().numpy(), rep['counts'], pen.depth_of.cpu().numpy(), a.tol)
+        rep.update(drep)
+        for i, j, mx, mean in drep['depth_pairs']:
+            print('body %6d in %6d: deepest %.4f m, mean %.4f m' % (i, j, mx, mean))
+        for i in drep['deepest_ranked']:
+            print('body %6d: deepest vertex %.4f m' % (i, drep['deepest'][i]))
+        print('--shallow=' + ','.join(str(i) for i in drep['shallow']))
     if a.out:
         with open(a.out, 'w') as f:
             json.dump(rep, f, indent=1)
