@@ -862,6 +862,34 @@ int psi_surface_crossings_finish(const psi_surface_crossings *h, int B, const in
                                  int32_t *d_pairs, int32_t *d_events, float *d_length, int32_t *d_counts, double *d_contour,
                                  uint32_t *d_face_mask, int32_t *d_irregular, void *stream);
 
+/* ---- Surface crossings: the conic distance field of a list of triangle pairs, its loss and the rows of its gradient (csrc/crossing_field.hip) ----
+ * Contract (csrc/crossing_field_shared.h holds the statements and their association).  d_verts [B,V,3] fp32; h a
+ * psi_surface_crossings handle; d_pairs [n,4] int32 (i, s, j, t) in the caller's face indices, strictly ascending, i <= j, 16-byte aligned;
+ * 0 < sigma <= 0.5.  The field is the conic distance field of Tzionas et al. 2016, zero outside the cone; no compatibility with any other
+ * implementation is claimed.
+ *   record      of the receiver (a,b,c): N = (b-a) x (c-a), n = N / sqrt(N.N), the circumcentre o and the circumradius r
+ *   evaluation  of p: h = n.(p-o), rho = |(p-o) - h n|; gate 1: h < sigma; Phi = rho / (r (1 - h/sigma)); gate 2: Phi < 1; Psi = (1 - Phi) Y(h),
+ *               Y = (1 - h) - sigma for h <= -sigma, else (c0 - c1 h) - (c2 h) h.  Both gates are positive comparisons: a NaN or an infinity
+ *               anywhere (a collinear receiver) gives Psi = 0 and zero gradient rows
+ *   role        0: the corners of (i,s) in the record of (j,t); 1: the other way round.  energy = (Psi0^2 + Psi1^2) + Psi2^2
+ *   eval        writes d_psi [n,2,3] and d_energy [n,2]
+ *   pairs       d_cells_sorted [2n] int64 ascending and d_order [2n] int64: the caller's STABLE sort of the entries e = 2 k + role by their
+ *               cell (role 0: i B + j; role 1: j B + i); d_row_start [B+1] int64 = the first sorted position of every row of cells.  Writes
+ *               into d_pair_energy [B,B] fp64 (ZEROED BY THE CALLER; not symmetric) the entries of a cell added one after the other in pair
+ *               order, a self pair as (double) e0 + (double) e1 at its role-0 entry, and d_loss [B] = (float) sum_j E[i,j] in j order
+ *   grad_rows   the forward once more, then per (pair, role) six rows d_rows [12 n,3] and targets d_targets [12 n] int64 = body V + vertex:
+ *               the intruder's corners, then the receiver's; role 0 scaled by d_g[i], role 1 by d_g[j]; -1 targets for a pair out of range.
+ *               The caller sorts the targets stably and reduces with psi_segment_sum3
+ * No floating-point atomics; every index read from a caller's table is range-checked; no pass launches an empty grid (n = 0: the caller
+ * stops).  PSI_EINVAL: a null pointer, B < 1 or B > 46340, n outside [1, 2^27), sigma outside (0, 0.5], a misaligned d_pairs. */
+int psi_crossing_field_eval(const psi_surface_crossings *h, const float *d_verts, int B, const int32_t *d_pairs, long long n, float sigma,
+                            float *d_psi, float *d_energy, void *stream);
+int psi_crossing_field_pairs(const psi_surface_crossings *h, int B, const int32_t *d_pairs, long long n, const float *d_energy,
+                             const int64_t *d_cells_sorted, const int64_t *d_order, const int64_t *d_row_start, double *d_pair_energy,
+                             float *d_loss, void *stream);
+int psi_crossing_field_grad_rows(const psi_surface_crossings *h, const float *d_verts, int B, const int32_t *d_pairs, long long n,
+                                 float sigma, const float *d_g, int64_t *d_targets, float *d_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

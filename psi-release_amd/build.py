@@ -42,6 +42,8 @@ PER_FILE = {'chamfer.hip': ['-ffp-contract=off', '-fno-slp-vectorize'], 'nnindex
             'surface_crossings.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
             # the closest point, the division and the square root of a depth, rounding for rounding
             'body_depth.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
+            # the record, the evaluation and their reverse mode, rounding for rounding
+            'crossing_field.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
             'body_overlap.hip': []}               # default contraction: the contract on w is a tolerance, and
                                                         # everything that decides membership (box, threshold) is a comparison
 

@@ -14,20 +14,13 @@
 // sort of the keys: pairs, counts, face mask and irregular count by integer atomics) and contour (one workgroup per job adds the lengths
 // of its pairs in fp64, sequentially in pair order).  No floating-point atomics.
 #include "surface_crossings_shared.h"
+#include "surface_crossings_handle.h"
 #include "psi_common.h"
 #include "wg_device.h"
 #include <limits.h>
 #include <algorithm>
 #include <numeric>
 #include <vector>
-
-struct psi_surface_crossings {
-    int32_t *d_faces;          // [F,3] in chunk order
-    int32_t *d_orig;           // [F] the caller's index of the face at a position
-    int32_t *d_part;           // [F] in chunk order, or null
-    uint8_t *d_skip;           // [P,P], or null
-    int V, F, P;
-};
 
 namespace psi_sc {
 
@@ -321,14 +314,15 @@ extern "C" int psi_surface_crossings_create(psi_surface_crossings **out, const i
             for (int b = 0; b < P; b++)
                 PSI_REQUIRE((h_part_skip[(size_t)a * P + b] != 0) == (h_part_skip[(size_t)b * P + a] != 0), "part_skip is symmetric");
     }
-    psi_surface_crossings h{nullptr, nullptr, nullptr, nullptr, V, F, P};
+    psi_surface_crossings h{nullptr, nullptr, nullptr, nullptr, V, F, P, nullptr};
     const char *who = "psi_surface_crossings_create";
     int e = psi_upload(&h.d_faces, faces.data(), faces.size(), who);
     if (!e) e = psi_upload(&h.d_orig, order.data(), order.size(), who);
     if (!e && h_face_part) e = psi_upload(&h.d_part, part.data(), part.size(), who);
     if (!e && h_face_part) e = psi_upload(&h.d_skip, h_part_skip, (size_t)P * P, who);
+    if (!e) e = psi_upload(&h.d_caller, h_faces, (size_t)F * 3, who);
     if (e) {
-        (void)hipFree(h.d_faces), (void)hipFree(h.d_orig), (void)hipFree(h.d_part), (void)hipFree(h.d_skip);
+        (void)hipFree(h.d_faces), (void)hipFree(h.d_orig), (void)hipFree(h.d_part), (void)hipFree(h.d_skip), (void)hipFree(h.d_caller);
         return e;
     }
     *out = new psi_surface_crossings(h);
@@ -338,7 +332,7 @@ extern "C" int psi_surface_crossings_create(psi_surface_crossings **out, const i
 extern "C" void psi_surface_crossings_destroy(psi_surface_crossings *h)
 {
     if (!h) return;
-    (void)hipFree(h->d_faces), (void)hipFree(h->d_orig), (void)hipFree(h->d_part), (void)hipFree(h->d_skip);
+    (void)hipFree(h->d_faces), (void)hipFree(h->d_orig), (void)hipFree(h->d_part), (void)hipFree(h->d_skip), (void)hipFree(h->d_caller);
     delete h;
 }
 

@@ -337,7 +337,8 @@ def select_shallow(order, max_depth, tol):
 class SurfaceCrossings(_FacesHandleOwner):
     """Which pairs of triangles of the body surfaces of a batch properly intersect, between bodies and within one body
     (``ops.surface_crossings``): the search and the body-part filter of the reference tree's
-    ``BodyInterpenetration`` (human_body_prior/body_model/body_model.py:460-514), without its distance-field loss.  ``faces`` [F,3]: the
+    ``BodyInterpenetration`` (human_body_prior/body_model/body_model.py:460-514); ``field`` and ``penetration_loss`` add a conic
+    distance-field loss over the pairs found (section 10g; not the external package's, whose source is not available).  ``faces`` [F,3]: the
     one topology of every body; ``order_verts`` [V,3]: a representative pose (``v_template``) the faces are sorted along once;
     ``face_part`` / ``part_skip``: ``face_parts`` and ``part_skip_matrix`` below."""
 
@@ -363,6 +364,28 @@ class SurfaceCrossings(_FacesHandleOwner):
         ``BodyOverlap.counts_of_records`` skins them, then ONE crossings call over all N."""
         verts = _verts_of_records(xh72, cam_ext, evaluator_or_decoder, chunk, self.device, 'crossings_of_records')
         return self.crossings(verts, group, self_pairs, between)
+
+    @torch.no_grad()
+    def field(self, verts, group=None, self_pairs=True, between=True, sigma=ops.CROSSING_FIELD_SIGMA):
+        """``crossings`` and, for its pairs, the conic distance field (``ops.crossing_penetration``): the rows
+        ``energy`` [n,2] and ``psi`` [n,2,3], ``pair_energy`` [B,B] fp64 (what body i pays for standing in body j; the diagonal is self
+        energy) and ``loss`` [B].  ``sigma`` in (0, 0.5]: the default is the reference's 1e-3, SMPLify-X uses 0.5.  Returns
+        ``ops.CrossingFieldResult``."""
+        return ops.crossing_penetration(verts.contiguous(), self._handle_for(int(verts.shape[1])), group=self._group(group, verts),
+                                        self_pairs=self_pairs, between=between, sigma=sigma)
+
+    def penetration_loss(self, verts, group=None, self_pairs=True, between=True, sigma=ops.CROSSING_FIELD_SIGMA):
+        """loss [B] fp32 of ``field``, differentiable with respect to ``verts`` (``ops.crossing_penetration_loss``): the only term that acts
+        on a body that passes through itself and on surfaces that cross with no vertex inside.  ``verts`` must be contiguous."""
+        return ops.crossing_penetration_loss(verts, self._handle_for(int(verts.shape[1])), group=self._group(group, verts),
+                                             self_pairs=self_pairs, between=between, sigma=sigma)
+
+    @torch.no_grad()
+    def field_of_records(self, xh72, cam_ext, evaluator_or_decoder, chunk=512, group=None, self_pairs=True, between=True,
+                         sigma=ops.CROSSING_FIELD_SIGMA):
+        """``field`` of the bodies ``xh72`` [N,72], skinned exactly as ``crossings_of_records`` skins them, in ONE call over all N."""
+        verts = _verts_of_records(xh72, cam_ext, evaluator_or_decoder, chunk, self.device, 'field_of_records')
+        return self.field(verts, group, self_pairs, between, sigma)
 
 
 # the pairs of joints human_body_prior/body_model/body_model.py:488 lists for SMPL-X as additionally ignored in self contact

@@ -170,6 +170,9 @@ SIGNATURES = {
     'psi_surface_crossings_test': (c_int, [c_void_p] * 2 + [c_int, c_void_p, ctypes.c_longlong] + [c_void_p] * 2 + [ctypes.c_longlong]
                                    + [c_void_p] * 4),
     'psi_surface_crossings_finish': (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [ctypes.c_longlong] + [c_void_p] * 9),
+    'psi_crossing_field_eval': (c_int, [c_void_p] * 2 + [c_int, c_void_p, ctypes.c_longlong, c_float] + [c_void_p] * 3),
+    'psi_crossing_field_pairs': (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong] + [c_void_p] * 7),
+    'psi_crossing_field_grad_rows': (c_int, [c_void_p] * 2 + [c_int, c_void_p, ctypes.c_longlong, c_float] + [c_void_p] * 4),
 }
 
 

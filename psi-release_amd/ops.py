@@ -1892,3 +1892,212 @@ def surface_crossings(verts, handle_or_faces, group=None, self_pairs=True, betwe
         diagonal = (t[:, 0] == t[:, 1]) & (t[:, 2] == t[:, 3])
         box_tests = int(torch.where(diagonal, na * (na - 1) // 2, na * nb).sum().item())
     return res, {'tiles': int(n_tiles), 'pairs': int(n_pairs), 'box_tests': box_tests}
+
+
+# ------------------------------------------------------------------------------------------
+# Surface crossings: the conic distance field of triangle pairs, its loss and gradient (psi_crossing_field_*)
+# ------------------------------------------------------------------------------------------
+CROSSING_FIELD_MAX_PAIRS = 2 ** 27 - 1
+CROSSING_FIELD_SIGMA = 1e-3                      # the reference's constructor default (body_model.py:461); SMPLify-X uses 0.5
+
+
+class FieldRows(NamedTuple):
+    energy: torch.Tensor       # [n,2] fp32: column 0 = face s of body i in the field of face t of body j (i intrudes), column 1 the reverse
+    psi: torch.Tensor          # [n,2,3] fp32: the six values Psi, per role in corner order
+
+
+class CrossingFieldResult(NamedTuple):
+    crossings: CrossingsResult
+    rows: FieldRows            # of crossings.pairs
+    pair_energy: torch.Tensor  # [B,B] fp64, NOT symmetric: E[i,j] = what body i pays for being inside body j; the diagonal is self energy
+    loss: torch.Tensor         # [B] fp32: (float) sum_j E[i,j] in j order
+
+
+def _check_sigma(sigma):
+    import math
+    import numbers
+    if isinstance(sigma, bool) or not isinstance(sigma, numbers.Real) or not math.isfinite(sigma) or not 0.0 < sigma <= 0.5:
+        raise ValueError('sigma is a finite number in (0, 0.5], got %r' % (sigma,))
+    return float(sigma)
+
+
+def _crossings_handle(handle_or_faces, V):
+    import ctypes
+    return _handle_or_made(handle_or_faces, not isinstance(handle_or_faces, ctypes.c_void_p), lambda f: surface_crossings_create(f, V),
+                           surface_crossings_destroy)
+
+
+def _crossings_handle_F(handle, V):
+    import ctypes
+    info = (ctypes.c_int32 * 4)()
+    hip.check(hip.lib().psi_surface_crossings_info(handle, info), 'psi_surface_crossings_info')
+    if info[0] != V:
+        raise ValueError('the handle was made for %d vertices per body, verts has %d' % (info[0], V))
+    return int(info[1])
+
+
+def _field_rows(handle, verts, pairs, sigma):
+    """eval for the pairs [n,4], n >= 1"""
+    B, n, dev = int(verts.shape[0]), int(pairs.shape[0]), verts.device
+    rows = FieldRows(torch.empty(n, 2, dtype=torch.float32, device=dev), torch.empty(n, 2, 3, dtype=torch.float32, device=dev))
+    hip.check(hip.lib().psi_crossing_field_eval(handle, hip.ptr(verts), B, hip.ptr(pairs), n, sigma, hip.ptr(rows.psi), hip.ptr(rows.energy),
+                                                hip.stream()), 'psi_crossing_field_eval')
+    return rows
+
+
+def _empty_field_rows(dev):
+    return FieldRows(torch.empty(0, 2, dtype=torch.float32, device=dev), torch.empty(0, 2, 3, dtype=torch.float32, device=dev))
+
+
+def _check_pairs_arg(pairs, verts):
+    if not torch.is_tensor(pairs) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 4:
+        raise ValueError('expected pairs [n,4] int32')
+    if pairs.device != verts.device:
+        raise ValueError('expected pairs on the device of verts')
+    if pairs.shape[0] > CROSSING_FIELD_MAX_PAIRS:
+        raise ValueError('%d pairs: more than 2^27 - 1' % pairs.shape[0])
+
+
+def crossing_field(verts, handle_or_faces, pairs, sigma=CROSSING_FIELD_SIGMA):
+    """The conic distance field (Tzionas et al. 2016; zero outside the cone) of every row (i, s, j, t) of ``pairs``: the three corners of face
+    s of body i evaluated in the cone of face t of body j, and the other way round (include/psi_hip.h: psi_crossing_field_*; DESIGN.md
+    section 10g), bit-equal to the fp32 NumPy restatement.  verts [B,V,3] fp32 on the GPU; ``handle_or_faces``: a handle of
+    ``surface_crossings_create`` or faces [F,3] int32; ``pairs`` [n,4] int32 on the device of verts, in the handle's caller face indices,
+    strictly ascending, i <= j, every index in range: any such pair, not only a crossing one; ``sigma`` in (0, 0.5] (the default 1e-3 is
+    the reference's; SMPLify-X uses 0.5).  Returns ``FieldRows`` on the device.
+
+    One kernel on the current stream and ONE read-back, the verdict on the pairs.  n = 0 launches nothing.  ``ValueError`` for wrong dtypes,
+    shapes or devices, a sigma outside (0, 0.5] and a bad pair list; ``PsiHipError`` for what the library refuses, CPU tensors included."""
+    def check():
+        _check_sigma(sigma)
+        _check_pairs_arg(pairs, verts)
+
+    B, V, dev, pv, _ = _batch_args(verts, None, 'crossing_field', then=check, max_B=SURFACE_CROSSINGS_MAX_B)
+    n = int(pairs.shape[0])
+    with torch.cuda.device(dev), torch.no_grad():
+        with _crossings_handle(handle_or_faces, V) as handle:
+            F = _crossings_handle_F(handle, V)
+            if n == 0:
+                return _empty_field_rows(dev)
+            prs = pairs.contiguous()
+            p = prs.to(torch.int64)
+            i, s, j, t = p[:, 0], p[:, 1], p[:, 2], p[:, 3]
+            bad = ((i < 0) | (i >= B) | (j < i) | (j >= B) | (s < 0) | (s >= F) | (t < 0) | (t >= F)).any()
+            if (B * F) ** 2 < 2 ** 63:
+                key = ((i * F + s) * B + j) * F + t
+                bad = bad | (key[1:] <= key[:-1]).any()
+            else:                               # the key does not fit one int64: compare the rows lexicographically
+                d = p[1:] - p[:-1]
+                first = (d != 0).to(torch.int8).argmax(1)
+                bad = bad | ((d == 0).all(1) | (d.gather(1, first[:, None])[:, 0] < 0)).any()
+            if bool(bad.item()):                                                                            # the read-back
+                raise ValueError('pairs must be strictly ascending (i, s, j, t) rows with i <= j, i and j in [0, %d) and s and t in [0, %d)'
+                                 % (B, F))
+            return _field_rows(handle, verts, prs, float(sigma))
+
+
+def _field_aggregates(handle, B, pairs, energy):
+    """pair_energy [B,B] fp64 and loss [B] fp32 of the pairs [n,4], n >= 1: the stable sort of the 2n entries by cell is plumbing."""
+    dev, n = pairs.device, int(pairs.shape[0])
+    p = pairs.to(torch.int64)
+    cells = torch.stack([p[:, 0] * B + p[:, 2], p[:, 2] * B + p[:, 0]], 1).reshape(-1)
+    srt = torch.sort(cells, stable=True)
+    row_start = torch.searchsorted(srt.values, torch.arange(B + 1, dtype=torch.int64, device=dev) * B).contiguous()
+    pair_energy = torch.zeros(B, B, dtype=torch.float64, device=dev)
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    hip.check(hip.lib().psi_crossing_field_pairs(handle, B, hip.ptr(pairs), n, hip.ptr(energy), hip.ptr(srt.values), hip.ptr(srt.indices),
+                                                 hip.ptr(row_start), hip.ptr(pair_energy), hip.ptr(loss), hip.stream()),
+              'psi_crossing_field_pairs')
+    return pair_energy, loss
+
+
+def crossing_penetration(verts, handle_or_faces, group=None, self_pairs=True, between=True, sigma=CROSSING_FIELD_SIGMA, mode='pruned'):
+    """``surface_crossings`` and, for its pairs, the conic distance field and the aggregates of DESIGN.md section 10g.  Arguments as
+    ``surface_crossings``, and ``sigma`` as ``crossing_field``.  Returns ``CrossingFieldResult`` on the device: ``pair_energy[i,j]`` is what
+    body i pays for standing in body j (not symmetric; the diagonal is the energy of a body that passes through itself), ``loss[i]`` its
+    row sum.  The only term of the family that sees a body passing through itself and surfaces that cross with no vertex inside.
+
+    No read-back beyond ``surface_crossings``' two.  No crossing pair: zeros, and nothing more is launched."""
+    _check_sigma(sigma)
+    B, V, dev, pv, pg = _batch_args(verts, group, 'crossing_penetration', max_B=SURFACE_CROSSINGS_MAX_B)
+    with torch.cuda.device(dev), torch.no_grad():
+        with _crossings_handle(handle_or_faces, V) as handle:
+            res = surface_crossings(verts, handle, group=group, self_pairs=self_pairs, between=between, mode=mode)
+            n = int(res.pairs.shape[0])
+            if n == 0:
+                return CrossingFieldResult(res, _empty_field_rows(dev), torch.zeros(B, B, dtype=torch.float64, device=dev),
+                                           torch.zeros(B, dtype=torch.float32, device=dev))
+            if n > CROSSING_FIELD_MAX_PAIRS:
+                raise ValueError('the batch has %d crossing pairs: more than 2^27 - 1' % n)
+            rows = _field_rows(handle, verts, res.pairs, float(sigma))
+            pair_energy, loss = _field_aggregates(handle, B, res.pairs, rows.energy)
+            return CrossingFieldResult(res, rows, pair_energy, loss)
+
+
+def crossing_field_grad(verts, handle, pairs, g, sigma=CROSSING_FIELD_SIGMA):
+    """G [B,V,3] fp32: the exact gradient of sum_i g[i] loss[i] with respect to the vertices for the constant list ``pairs`` (role 0 of a
+    pair scaled by g[i], role 1 by g[j]): grad_rows, a stable ``torch.sort`` of the targets, the segment sum.  No read-back, no
+    floating-point atomics."""
+    _check_sigma(sigma)
+    B, V = int(verts.shape[0]), int(verts.shape[1])
+    if not torch.is_tensor(g) or g.dtype != torch.float32 or tuple(g.shape) != (B,) or g.device != verts.device:
+        raise ValueError('expected g [%d] float32 on the device of verts' % B)
+    _check_pairs_arg(pairs, verts)
+    dev, n = verts.device, int(pairs.shape[0])
+    with torch.cuda.device(dev), torch.no_grad():
+        if n == 0:
+            return torch.zeros(B, V, 3, dtype=torch.float32, device=dev)
+        g, pairs = g.contiguous(), pairs.contiguous()
+        targets = torch.empty(12 * n, dtype=torch.int64, device=dev)
+        grows = torch.empty(12 * n, 3, dtype=torch.float32, device=dev)
+        hip.check(hip.lib().psi_crossing_field_grad_rows(handle, hip.ptr(verts), B, hip.ptr(pairs), n, float(sigma), hip.ptr(g), hip.ptr(targets),
+                                                         hip.ptr(grows), hip.stream()), 'psi_crossing_field_grad_rows')
+        srt = torch.sort(targets, stable=True)
+        return segment_sum3(srt.values, grows, B * V, order=srt.indices).view(B, V, 3)
+
+
+class _OwnedCrossingsHandle:
+    """A handle made for one call of ``crossing_penetration_loss`` from a faces tensor: it lives as long as the graph that needs it."""
+
+    def __init__(self, faces, V):
+        self.handle = surface_crossings_create(faces, V)
+
+    def __del__(self):
+        try:
+            surface_crossings_destroy(self.handle)
+        except Exception:
+            pass
+
+
+class _CrossingPenetrationLoss(Function):
+    @staticmethod
+    def forward(ctx, verts, handle, owner, group, self_pairs, between, sigma, mode):
+        res = crossing_penetration(verts, handle, group=group, self_pairs=self_pairs, between=between, sigma=sigma, mode=mode)
+        ctx.handle, ctx.owner, ctx.sigma = handle, owner, sigma
+        ctx.save_for_backward(verts.detach(), res.crossings.pairs)
+        return res.loss.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        verts, pairs = ctx.saved_tensors
+        G = crossing_field_grad(verts, ctx.handle, pairs, g.to(torch.float32).contiguous(), ctx.sigma)
+        return G, None, None, None, None, None, None, None
+
+
+def crossing_penetration_loss(verts, handle_or_faces, group=None, self_pairs=True, between=True, sigma=CROSSING_FIELD_SIGMA, mode='pruned'):
+    """loss [B] fp32 of ``crossing_penetration``: what body i pays for passing through the other bodies of the batch and through itself
+    (DESIGN.md section 10g).  Differentiable with respect to ``verts``: the gradient is exact for the pair list of the forward pass, which
+    is a constant (the loss jumps when a pair appears); it reaches the three corners of the intruding face and, through the normal, the
+    circumcentre and the circumradius, the three corners of the receiving face.  The backward pass runs grad_rows (which recomputes the
+    forward), a stable ``torch.sort`` and the segment sum: no floating-point atomics, bit-identical from run to run, no read-back.  No
+    crossing pair: zeros, a zero gradient and no launch.  ``ValueError`` as ``crossing_penetration``."""
+    _check_sigma(sigma)
+    if mode not in ('pruned', 'brute'):
+        raise ValueError("mode is 'pruned' or 'brute', got %r" % (mode,))
+    if not torch.is_tensor(verts) or verts.dtype != torch.float32 or verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
+        raise ValueError('expected verts [B,V,3] float32')
+    import ctypes
+    hip.ptr(verts)                              # a CPU or non-contiguous tensor is refused before a handle is made
+    owner = None if isinstance(handle_or_faces, ctypes.c_void_p) else _OwnedCrossingsHandle(handle_or_faces, int(verts.shape[1]))
+    return _CrossingPenetrationLoss.apply(verts, owner.handle if owner else handle_or_faces, owner, group, bool(self_pairs), bool(between),
+                                          float(sigma), mode)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """python utils_eval_body_overlap.py GEN_FOLDER [--human_model_path ... --vposer_ckpt_path ... | --synthetic DIR] [--no_flip]
-                                                 [--max_inside 0] [--out JSON] [--crossings [--self] [--parts]] [--depth [--tol M]]
+                                                 [--max_inside 0] [--out JSON] [--crossings [--self] [--parts] [--field [--sigma S]]]
+                                                 [--depth [--tol M]]
 
 Which bodies of GEN_FOLDER/body_gen_*.pkl stand in each other: every body is placed as utils_show_test_results.py places it (cam_ext .
 T_mat for Habitat trees, cam_ext with --no_flip for PROX-E), and every vertex of every body is tested against every other body
@@ -15,6 +16,11 @@ vertex of either is inside the other.  --self also tests every body against itse
 then ignores pairs of faces of the same body part, of a part and its kinematic parent and of the pairs of parts
 human_body_prior/body_model/body_model.py:488 lists, the parts taken from the model's own skinning weights and kinematic tree.  Without
 --crossings every printed line and every JSON field is what it was.
+
+--crossings --field adds the conic distance field over the crossing pairs (evaluation.SurfaceCrossings.field): the
+energy of every pair of bodies that cross, both ways, the bodies ranked by their loss and, with --self, the energy of every body against
+itself.  --sigma is the height of the cones (default 1e-3, the reference's; SMPLify-X uses 0.5).  Without --field every printed line and
+every JSON field is what it was.
 
 --depth adds how far in the vertices are (evaluation.BodyOverlap.depths: the distance of every inside vertex to the nearest triangle of
 the body it is in): the largest and the mean depth of every overlapping ordered pair, the bodies ranked by their deepest vertex, and the
@@ -42,6 +48,8 @@ def parse_args(argv=None):
     ap.add_argument('--crossings', action='store_true', help='also list the pairs of triangles of the surfaces that intersect')
     ap.add_argument('--self', dest='self_pairs', action='store_true', help='with --crossings: also every body against itself')
     ap.add_argument('--parts', action='store_true', help='with --crossings --self: ignore pairs of faces of adjacent body parts')
+    ap.add_argument('--field', action='store_true', help='with --crossings: the conic distance-field energy of the crossing pairs')
+    ap.add_argument('--sigma', type=float, default=None, metavar='S', help='with --field: the height of the cones, in (0, 0.5]; default 1e-3')
     ap.add_argument('--depth', action='store_true', help='also report how deep the inside vertices are')
     ap.add_argument('--tol', type=float, default=0.0, metavar='M', help='with --depth: the depth two kept bodies may reach in each other, in metres')
     a = ap.parse_args(argv)
@@ -53,6 +61,14 @@ def parse_args(argv=None):
         ap.error('--self needs --crossings')
     if a.parts and not a.self_pairs:
         ap.error('--parts needs --crossings --self')
+    if a.field and not a.crossings:
+        ap.error('--field needs --crossings')
+    if a.sigma is not None and not a.field:
+        ap.error('--sigma needs --crossings --field')
+    if a.sigma is None:
+        a.sigma = 1e-3
+    if not 0.0 < a.sigma <= 0.5:
+        ap.error('--sigma must lie in (0, 0.5]')
     if a.max_inside < 0:
         ap.error('--max_inside must not be negative')
     if a.chunk < 1:
@@ -103,6 +119,17 @@ def crossings_report(res, overlap_counts):
             'unseen_by_vertex_test': sum(1 for i, j, _, _ in pairs if ov[i, j] == 0 and ov[j, i] == 0)}
 
 
+def field_report(pair_energy, loss, crossing_counts, with_self):
+    """The JSON fields of --field: pair_energy [B,B] fp64 (not symmetric), loss [B] and the crossing counts [B,B], as host arrays."""
+    E, loss, counts = np.asarray(pair_energy, np.float64), np.asarray(loss, np.float32), np.asarray(crossing_counts, np.int64)
+    B = len(loss)
+    rep = {'field_pairs': [[i, j, float(E[i, j]), float(E[j, i])] for i in range(B) for j in range(i + 1, B) if counts[i, j]],
+           'field_loss': loss.astype(np.float64).tolist(), 'field_ranked': sorted(range(B), key=lambda i: (-float(loss[i]), i))}
+    if with_self:
+        rep['self_energy'] = np.diag(E).tolist()
+    return rep
+
+
 def depth_report(max_depth, sum_depth, counts, depth_of, tol):
     """The JSON fields of --depth: max_depth, sum_depth and counts [B,B], depth_of [B,V], as host arrays."""
     from psi_release_amd.evaluation import select_shallow
@@ -143,7 +170,11 @@ def main(argv=None):
         from psi_release_amd.evaluation import SurfaceCrossings
         part, skip, rest = model_parts(smplx_src, decoder.faces.cpu().numpy()) if a.parts else (None, None, None)
         sc = SurfaceCrossings(decoder.faces, device, order_verts=rest, face_part=part, part_skip=skip)
-        cres = sc.crossings_of_records(xh, camera_pose(cam, a.no_flip), decoder, chunk=a.chunk, self_pairs=a.self_pairs)
+        if a.field:
+            fres = sc.field_of_records(xh, camera_pose(cam, a.no_flip), decoder, chunk=a.chunk, self_pairs=a.self_pairs, sigma=a.sigma)
+            cres = fres.crossings
+        else:
+            cres = sc.crossings_of_records(xh, camera_pose(cam, a.no_flip), decoder, chunk=a.chunk, self_pairs=a.self_pairs)
         crep = crossings_report(cres, rep['counts'])
         rep.update(crep)
         print('[INFO] %d pairs of bodies cross, %d pairs of triangles (%d irregular)' % (len(crep['crossing_pairs']), crep['triangle_pairs'],
@@ -154,6 +185,17 @@ def main(argv=None):
             for i in crep['self_ranked']:
                 print('body %6d: %6d self crossings' % (i, crep['self_crossings'][i]))
         print('[INFO] %d pairs of bodies cross although no vertex of either is inside the other' % crep['unseen_by_vertex_test'])
+        if a.field:
+            frep = field_report(fres.pair_energy.cpu().numpy(), fres.loss.cpu().numpy(), crep['crossing_counts'], a.self_pairs)
+            rep.update(frep)
+            rep['sigma'] = float(a.sigma)
+            for i, j, e_ij, e_ji in frep['field_pairs']:
+                print('bodies %6d %6d: field energy %.6g of the first in the second, %.6g of the second in the first' % (i, j, e_ij, e_ji))
+            for i in frep['field_ranked']:
+                print('body %6d: field loss %.6g' % (i, frep['field_loss'][i]))
+            if a.self_pairs:
+                for i in range(rep['bodies']):
+                    print('body %6d: self energy %.6g' % (i, frep['self_energy'][i]))
     if a.depth:
         drep = depth_report(pen.max_depth.cpu().numpy(), pen.sum_depth.cpu().numpy(), rep['counts'], pen.depth_of.cpu().numpy(), a.tol)
         rep.update(drep)
