@@ -890,6 +890,32 @@ int psi_crossing_field_pairs(const psi_surface_crossings *h, int B, const int32_
 int psi_crossing_field_grad_rows(const psi_surface_crossings *h, const float *d_verts, int B, const int32_t *d_pairs, long long n,
                                  float sigma, const float *d_g, int64_t *d_targets, float *d_rows, void *stream);
 
+/* ---- Body against body: move overlapping bodies apart rigidly (csrc/body_separate.hip) ----
+ * Contract (csrc/body_separate_shared.h holds the statements and their association).  Every body of a batch has a
+ * rigid state, all fp32: d_quat [B,4] (w, x, y, z), d_transl [B,3], d_pivot [B,3], and the Adam moments d_m, d_s [B,6].
+ *   pose     d_verts [B,V,3] = R(quat) (d_base - pivot) + (pivot + transl), x_k = ((R_k0 d0 + R_k1 d1) + R_k2 d2) + p_k; a body whose state is
+ *            exactly quat = (1,0,0,0), transl = 0 gets the bits of d_base
+ *   wrench   d_G [B,V,3] = dL/dverts, d_p [B,3] = pivot + transl.  Per vertex a = x - p, c = a x G in fp32; (G, c) widened to fp64 and added
+ *            over every chunk of 256 consecutive vertices by the tree s[l] += s[l + stride], stride = 128 .. 1 (lanes past V hold +0):
+ *            d_chunks [B, ceil(V / 256), 6] fp64.  With d_g6 != NULL a second launch adds the chunks of a body in chunk order in fp64 and
+ *            rounds once: d_g6 [B,6] fp32 = (force, torque about p)
+ *   step     step k of Adam on g6 (zero for a body with d_fixed[b] != 0; d_fixed [B] int32 or NULL), in place: m = b1 m + (1 - b1) g,
+ *            s = b2 s + ((1 - b2) g) g, u = (m / c1) / (sqrt(s / c2) + eps), transl -= lr_t u[0:3], delta = -(lr_r u[3:6]),
+ *            quat <- normalise((1, delta / 2) (x) quat) unless delta is exactly zero.  c1 = (float)(1 - b1^k) and c2 = (float)(1 - b2^k)
+ *            come from the caller, computed in fp64.  With d_chunks != NULL (nchunk = ceil(V / 256)) the launch first adds the chunks as
+ *            wrench's second stage does and stores d_g6; with d_chunks == NULL, nchunk == 0 it reads d_g6
+ * Each pass is one kernel on `stream` (wrench with d_g6: two), no host synchronisation, no floating-point atomics: the sums do not depend
+ * on the grid and every output is bit-identical from run to run and to the fp32 NumPy restatement.  None launches an empty grid.
+ * PSI_EINVAL: a null pointer, B < 1 or B > 46340, V < 1 or V > 2^24, a beta outside [0, 1), a bias correction outside (0, 1], a negative or
+ * non-finite eps, a non-positive or non-finite learning rate, nchunk that does not go with d_chunks. */
+int psi_body_separate_pose(const float *d_base, const float *d_quat, const float *d_transl, const float *d_pivot, int B, int V, float *d_verts,
+                           void *stream);
+int psi_body_separate_wrench(const float *d_verts, const float *d_G, const float *d_p, int B, int V, double *d_chunks, float *d_g6,
+                             void *stream);
+int psi_body_separate_step(const double *d_chunks, int nchunk, float *d_g6, float *d_quat, float *d_transl, float *d_m, float *d_s,
+                           const int32_t *d_fixed, int B, float b1, float b2, float c1, float c2, float eps, float lr_t, float lr_r,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -388,6 +388,43 @@ class SurfaceCrossings(_FacesHandleOwner):
         return self.field(verts, group, self_pairs, between, sigma)
 
 
+class BodySeparator:
+    """Repairs a batch of overlapping bodies: every body is moved rigidly, by a rotation about its pivot and a translation, until no vertex
+    of one lies inside another and no surfaces cross (``ops.rigid_separate``).  Shape and pose are kept.  Owns the
+    two handles the searches need (``BodyOverlap`` and ``SurfaceCrossings`` of the same ``faces``; the other arguments as
+    ``SurfaceCrossings``).  The room is not looked at: a body may be pushed into furniture, and ``shift`` / ``angle`` of the result say
+    how far every body went."""
+
+    def __init__(self, faces, device='cuda', order_verts=None, face_part=None, part_skip=None):
+        self.device = torch.device(device)
+        self.overlap = BodyOverlap(faces, device)
+        self.crossings = SurfaceCrossings(faces, device, order_verts=order_verts, face_part=face_part, part_skip=part_skip)
+
+    def close(self):
+        self.overlap.close()
+        self.crossings.close()
+
+    @torch.no_grad()
+    def separate(self, verts, group=None, **kw):
+        """verts [B,V,3] fp32 on the device, world frame; ``group`` as in ``BodyOverlap.counts``; the keywords of ``ops.rigid_separate``
+        (fixed, pivot, max_iter, lr_t, lr_r, betas, eps, w_pen, w_cross, penalty, sigma, mode).  Returns ``ops.SeparationResult``."""
+        V = int(verts.shape[1])
+        return ops.rigid_separate(verts.contiguous(), self.overlap._handle_for(V), self.crossings._handle_for(V),
+                                  group=_FacesHandleOwner._group(group, verts), **kw)
+
+    @torch.no_grad()
+    def separate_records(self, xh72, cam_ext, evaluator_or_decoder, chunk=512, group=None, **kw):
+        """The bodies ``xh72`` [N,72] with cameras ``cam_ext`` [N,4,4] or [1,4,4], skinned exactly as ``BodyOverlap.counts_of_records``
+        skins them, separated as ONE batch.  Returns (``ops.SeparationResult``, cam_ext' [N,4,4] fp64 host array) with cam_ext'[b] =
+        transform[b] cam_ext[b]: a record is repaired by replacing its camera pose and nothing else (an evaluator's Habitat flip
+        multiplies from the right and is not affected)."""
+        verts = _verts_of_records(xh72, cam_ext, evaluator_or_decoder, chunk, self.device, 'separate_records')
+        res = self.separate(verts, group, **kw)
+        cam = (cam_ext.detach().cpu().numpy() if torch.is_tensor(cam_ext) else np.asarray(cam_ext)).astype(np.float64).reshape(-1, 4, 4)
+        cam = np.broadcast_to(cam, (verts.shape[0], 4, 4))
+        return res, np.matmul(res.transform.cpu().numpy(), cam)
+
+
 # the pairs of joints human_body_prior/body_model/body_model.py:488 lists for SMPL-X as additionally ignored in self contact
 SMPLX_SELF_CONTACT_PAIRS = ((9, 16), (9, 17), (6, 16), (6, 17), (1, 2), (12, 22))
 

@@ -173,6 +173,9 @@ SIGNATURES = {
     'psi_crossing_field_eval': (c_int, [c_void_p] * 2 + [c_int, c_void_p, ctypes.c_longlong, c_float] + [c_void_p] * 3),
     'psi_crossing_field_pairs': (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong] + [c_void_p] * 7),
     'psi_crossing_field_grad_rows': (c_int, [c_void_p] * 2 + [c_int, c_void_p, ctypes.c_longlong, c_float] + [c_void_p] * 4),
+    'psi_body_separate_pose': (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p] * 2),
+    'psi_body_separate_wrench': (c_int, [c_void_p] * 3 + [c_int] * 2 + [c_void_p] * 3),
+    'psi_body_separate_step': (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_int] + [c_float] * 7 + [c_void_p]),
 }
 
 

@@ -2101,3 +2101,285 @@ def crossing_penetration_loss(verts, handle_or_faces, group=None, self_pairs=Tru
     owner = None if isinstance(handle_or_faces, ctypes.c_void_p) else _OwnedCrossingsHandle(handle_or_faces, int(verts.shape[1]))
     return _CrossingPenetrationLoss.apply(verts, owner.handle if owner else handle_or_faces, owner, group, bool(self_pairs), bool(between),
                                           float(sigma), mode)
+
+
+# ------------------------------------------------------------------------------------------
+# Body against body: move overlapping bodies apart rigidly (psi_body_separate_*)
+# ------------------------------------------------------------------------------------------
+RIGID_CHUNK = 256
+
+
+class RigidState(NamedTuple):
+    quat: torch.Tensor         # [B,4] fp32 (w, x, y, z)
+    transl: torch.Tensor       # [B,3] fp32
+    pivot: torch.Tensor        # [B,3] fp32, constant: the body turns about pivot + transl
+    m: torch.Tensor            # [B,6] fp32 and
+    s: torch.Tensor            # [B,6] fp32: the Adam moments of (force, torque)
+
+
+class SeparationResult(NamedTuple):
+    verts: torch.Tensor        # [B,V,3] fp32: the bodies under their final state
+    quat: torch.Tensor         # [B,4] fp32
+    transl: torch.Tensor       # [B,3] fp32
+    pivot: torch.Tensor        # [B,3] fp32
+    transform: torch.Tensor    # [B,4,4] fp64: x' = M x for the vertices given
+    iterations: int            # steps taken
+    separated: bool            # the last pass found nothing inside and nothing crossing
+    history: dict              # per pass: 'triples', 'pairs' (lists of int; -1: not searched), 'loss_pen', 'loss_cross' ([passes,B] fp32)
+    shift: torch.Tensor        # [B] fp64: |transl|
+    angle: torch.Tensor        # [B] fp64: the rotation angle, radians
+
+
+def rigid_state(pivot):
+    """The identity state about ``pivot`` [B,3] fp32: quat (1,0,0,0), transl 0, zero moments."""
+    if not torch.is_tensor(pivot) or pivot.dtype != torch.float32 or pivot.dim() != 2 or pivot.shape[1] != 3 or pivot.shape[0] < 1:
+        raise ValueError('expected pivot [B,3] float32')
+    B, dev = int(pivot.shape[0]), pivot.device
+    quat = torch.zeros(B, 4, dtype=torch.float32, device=dev)
+    quat[:, 0] = 1.0
+    return RigidState(quat, torch.zeros(B, 3, dtype=torch.float32, device=dev), pivot.contiguous(),
+                      torch.zeros(B, 6, dtype=torch.float32, device=dev), torch.zeros(B, 6, dtype=torch.float32, device=dev))
+
+
+def _check_rows(t, B, width, name, dev, dtype=torch.float32):
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (B, width) or t.device != dev:
+        raise ValueError('expected %s [%d,%d] %s on the device of the vertices' % (name, B, width, str(dtype).replace('torch.', '')))
+
+
+def _check_verts3(v, name):
+    if not torch.is_tensor(v) or v.dtype != torch.float32 or v.dim() != 3 or v.shape[2] != 3 or v.shape[1] < 1 or v.shape[0] < 1:
+        raise ValueError('expected %s [B,V,3] float32' % name)
+
+
+def rigid_pose(base, quat, transl, pivot):
+    """verts [B,V,3] fp32 = R(quat) (base - pivot) + (pivot + transl) per body (psi_body_separate_pose), bit-equal to
+    the fp32 NumPy restatement.  A body whose state is exactly quat = (1,0,0,0), transl = 0 gets the bits of ``base``.  One kernel on the
+    current stream, no read-back.  ``ValueError`` for wrong dtypes, shapes or devices; ``PsiHipError`` for CPU tensors."""
+    _check_verts3(base, 'base')
+    B, V, dev = int(base.shape[0]), int(base.shape[1]), base.device
+    _check_rows(quat, B, 4, 'quat', dev), _check_rows(transl, B, 3, 'transl', dev), _check_rows(pivot, B, 3, 'pivot', dev)
+    pb, pq, pt, pc = hip.ptr(base), hip.ptr(quat), hip.ptr(transl), hip.ptr(pivot)
+    with torch.cuda.device(dev):
+        verts = torch.empty_like(base)
+        hip.check(hip.lib().psi_body_separate_pose(pb, pq, pt, pc, B, V, hip.ptr(verts), hip.stream()), 'psi_body_separate_pose')
+    return verts
+
+
+def _rigid_chunks(verts, G, p, g6):
+    B, V = int(verts.shape[0]), int(verts.shape[1])
+    chunks = torch.empty(B, (V + RIGID_CHUNK - 1) // RIGID_CHUNK, 6, dtype=torch.float64, device=verts.device)
+    hip.check(hip.lib().psi_body_separate_wrench(hip.ptr(verts), hip.ptr(G), hip.ptr(p), B, V, hip.ptr(chunks), hip.ptr(g6), hip.stream()),
+              'psi_body_separate_wrench')
+    return chunks
+
+
+def rigid_wrench(verts, G, pivot_plus_transl, return_chunks=False):
+    """g6 [B,6] fp32 = (force, torque about p) of the gradient ``G`` [B,V,3] = dL/dverts on the bodies ``verts`` [B,V,3], p =
+    ``pivot_plus_transl`` [B,3] (psi_body_separate_wrench): sum_v G and sum_v (x - p) x G, the terms in fp32, the sums in fp64 in a fixed
+    order (a 256-lane tree per chunk of 256 vertices, then the chunks in order), rounded once.  No floating-point atomics; bit-equal to
+    the restatement and from run to run.  ``return_chunks``: also the chunk sums [B, ceil(V/256), 6] fp64.  Two kernels, no read-back."""
+    _check_verts3(verts, 'verts')
+    B, dev = int(verts.shape[0]), verts.device
+    if not torch.is_tensor(G) or G.dtype != torch.float32 or G.shape != verts.shape or G.device != dev:
+        raise ValueError('expected G float32 of the shape and on the device of verts')
+    _check_rows(pivot_plus_transl, B, 3, 'pivot_plus_transl', dev)
+    hip.ptr(verts), hip.ptr(G), hip.ptr(pivot_plus_transl)
+    with torch.cuda.device(dev):
+        g6 = torch.empty(B, 6, dtype=torch.float32, device=dev)
+        chunks = _rigid_chunks(verts, G, pivot_plus_transl, g6)
+    return (g6, chunks) if return_chunks else g6
+
+
+def _check_step_args(lr_t, lr_r, betas, eps):
+    import math
+    import numbers
+
+    def real(x):
+        return not isinstance(x, bool) and isinstance(x, numbers.Real) and math.isfinite(x)
+
+    for name, lr in (('lr_t', lr_t), ('lr_r', lr_r)):
+        if not real(lr) or not lr > 0:
+            raise ValueError('%s is a finite positive number, got %r' % (name, lr))
+    if not isinstance(betas, (tuple, list)) or len(betas) != 2 or not all(real(b) and 0.0 <= b < 1.0 for b in betas):
+        raise ValueError('betas is a pair of numbers in [0, 1), got %r' % (betas,))
+    if not real(eps) or eps < 0:
+        raise ValueError('eps is a finite number >= 0, got %r' % (eps,))
+
+
+def _fixed_mask(fixed, B, dev):
+    """[B] int32 on ``dev`` (1: the body is held) or None, of a list of body indices or a [B] bool / int32 tensor."""
+    if fixed is None:
+        return None
+    if torch.is_tensor(fixed):
+        if fixed.dtype not in (torch.bool, torch.int32) or tuple(fixed.shape) != (B,) or fixed.device != dev:
+            raise ValueError('expected fixed [%d] bool or int32 on the device of the vertices, or a list of bodies' % B)
+        return fixed.to(torch.int32).contiguous()
+    try:
+        idx = [int(i) for i in fixed]
+    except TypeError:
+        raise ValueError('fixed is a list of bodies or a [B] mask, got %r' % (fixed,))
+    if any(not 0 <= i < B or i != f for i, f in zip(idx, fixed)):
+        raise ValueError('fixed: a body outside [0, %d)' % B)
+    mask = torch.zeros(B, dtype=torch.int32)
+    if idx:
+        mask[idx] = 1
+    return mask.to(dev)
+
+
+def _rigid_step(state, g6, chunks, k, lr_t, lr_r, betas, eps, mask):
+    B = int(state.quat.shape[0])
+    c1, c2 = 1.0 - float(betas[0]) ** k, 1.0 - float(betas[1]) ** k         # fp64; rounded to fp32 once on the way into the library
+    hip.check(hip.lib().psi_body_separate_step(hip.ptr(chunks), 0 if chunks is None else int(chunks.shape[1]), hip.ptr(g6), hip.ptr(state.quat),
+                                               hip.ptr(state.transl), hip.ptr(state.m), hip.ptr(state.s), hip.ptr(mask), B, float(betas[0]),
+                                               float(betas[1]), c1, c2, float(eps), float(lr_t), float(lr_r), hip.stream()),
+              'psi_body_separate_step')
+
+
+def rigid_step(state, g6, k, lr_t=0.01, lr_r=0.01, betas=(0.9, 0.999), eps=1e-8, fixed=None):
+    """Step ``k`` = 1, 2, ... of Adam on the wrench ``g6`` [B,6], in place on ``state`` (a ``RigidState``; psi_body_separate_step): the
+    moments, transl -= lr_t u[0:3], and the quaternion turned by delta = -lr_r u[3:6] through the Cayley map, normalise((1, delta/2) (x)
+    quat); a body whose delta is exactly zero keeps its quaternion's bits, a body in ``fixed`` (a list of bodies or a [B] mask) sees g6 = 0.
+    The bias corrections 1 - beta^k are computed in fp64 on the host.  One kernel, no read-back.  Returns ``state``."""
+    if not isinstance(state, RigidState):
+        raise ValueError('expected a RigidState')
+    _check_rows(state.quat, int(state.quat.shape[0]) if torch.is_tensor(state.quat) and state.quat.dim() == 2 else 0, 4, 'quat',
+                getattr(state.quat, 'device', None))
+    B, dev = int(state.quat.shape[0]), state.quat.device
+    if B < 1:
+        raise ValueError('B >= 1')
+    _check_rows(state.transl, B, 3, 'transl', dev), _check_rows(state.m, B, 6, 'm', dev), _check_rows(state.s, B, 6, 's', dev)
+    _check_rows(g6, B, 6, 'g6', dev)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError('k is an integer >= 1, got %r' % (k,))
+    _check_step_args(lr_t, lr_r, betas, eps)
+    mask = _fixed_mask(fixed, B, dev)
+    for t in (state.quat, state.transl, state.m, state.s, g6):
+        hip.ptr(t)
+    with torch.cuda.device(dev):
+        _rigid_step(state, g6, None, k, lr_t, lr_r, betas, eps, mask)
+    return state
+
+
+def _rigid_transform(quat, transl, pivot):
+    """M [B,4,4] fp64, shift [B] and angle [B] fp64 of a state: the nine entries of R in fp64, t = (pivot + transl) - R pivot."""
+    q, t, c = quat.double(), transl.double(), pivot.double()
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                     2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                     2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], 1).view(-1, 3, 3)
+    M = torch.zeros(q.shape[0], 4, 4, dtype=torch.float64, device=q.device)
+    M[:, :3, :3] = R
+    M[:, :3, 3] = (c + t) - torch.einsum('bkl,bl->bk', R, c)
+    M[:, 3, 3] = 1.0
+    return M, t.norm(dim=1), 2.0 * torch.atan2(q[:, 1:].norm(dim=1), w.abs())
+
+
+class RigidPass(NamedTuple):
+    verts: torch.Tensor        # [B,V,3] fp32: the pose of the state the pass was given
+    triples: int               # inside triples found (-1: w_pen == 0, not searched)
+    pairs: int                 # crossing pairs found (-1: w_cross == 0, not searched)
+    loss_pen: torch.Tensor     # [B] fp32
+    loss_cross: torch.Tensor   # [B] fp32
+    clean: bool                # nothing inside and nothing crossing
+    stepped: bool              # the state was advanced
+    g6: torch.Tensor           # [B,6] fp32 when stepped, else None
+
+
+def rigid_pass(base, state, k, overlap_handle, crossings_handle, group=None, fixed_mask=None, step=True, lr_t=0.01, lr_r=0.01,
+               betas=(0.9, 0.999), eps=1e-8, w_pen=1.0, w_cross=1.0, penalty='depth', sigma=0.5, mode='pruned'):
+    """One pass of ``rigid_separate``'s loop from ``state`` (a ``RigidState``, advanced in place when the pass steps): the pose, the two
+    searches, the stop test and, unless the batch is clean or ``step`` is false, the two gradients, their sum, the wrench and step ``k`` of
+    the optimiser (the chunk sums go straight into the step's launch).  ``fixed_mask``: [B] int32 on the device or None.  The arguments
+    are ``rigid_separate``'s, which has checked them.  Returns ``RigidPass``."""
+    B, dev = int(base.shape[0]), base.device
+    with torch.cuda.device(dev), torch.no_grad():
+        verts = rigid_pose(base, state.quat, state.transl, state.pivot)
+        pen = body_penetration(verts, overlap_handle, group=group) if w_pen != 0 else None
+        cr = crossing_penetration(verts, crossings_handle, group=group, self_pairs=False, between=True, sigma=sigma, mode=mode) if w_cross != 0 else None
+        n_tri = -1 if pen is None else int(pen.triples.shape[0])
+        n_pairs = -1 if cr is None else int(cr.crossings.pairs.shape[0])
+        loss_pen = torch.zeros(B, dtype=torch.float32, device=dev) if pen is None else pen.loss[BODY_DEPTH_PENALTIES[penalty]]
+        loss_cross = torch.zeros(B, dtype=torch.float32, device=dev) if cr is None else cr.loss
+        clean = n_tri <= 0 and n_pairs <= 0
+        if clean or not step:
+            return RigidPass(verts, n_tri, n_pairs, loss_pen, loss_cross, clean, False, None)
+        G = None
+        if pen is not None:
+            G = body_penetration_grad(verts.shape, overlap_handle, pen.triples, pen.rows, torch.full((B,), float(w_pen), dtype=torch.float32, device=dev),
+                                      penalty)
+        if cr is not None:
+            Gc = crossing_field_grad(verts, crossings_handle, cr.crossings.pairs, torch.full((B,), float(w_cross), dtype=torch.float32, device=dev),
+                                     sigma)
+            G = Gc if G is None else G + Gc
+        g6 = torch.empty(B, 6, dtype=torch.float32, device=dev)
+        chunks = _rigid_chunks(verts, G, state.pivot + state.transl, None)
+        _rigid_step(state, g6, chunks, k, lr_t, lr_r, betas, eps, fixed_mask)
+        return RigidPass(verts, n_tri, n_pairs, loss_pen, loss_cross, False, True, g6)
+
+
+def rigid_separate(base, overlap_handle_or_faces, crossings_handle_or_faces, group=None, fixed=None, pivot=None, max_iter=100, lr_t=0.01,
+                   lr_r=0.01, betas=(0.9, 0.999), eps=1e-8, w_pen=1.0, w_cross=1.0, penalty='depth', sigma=0.5, mode='pruned'):
+    """Moves the bodies ``base`` [B,V,3] fp32 rigidly, each by a rotation about its pivot and a translation, until no vertex of one lies
+    inside another and no surfaces cross.  Shape and pose of every body are kept.  ``overlap_handle_or_faces``: a
+    handle of ``body_overlap_create`` or faces [F,3] int32 (a tensor); ``crossings_handle_or_faces``: a handle of
+    ``surface_crossings_create`` or faces; ``group`` [B] int32 on the device or None: only bodies of equal group meet; ``fixed``: bodies
+    that must not move (a list, or a [B] mask on the device) — two fixed bodies that overlap each other never separate; ``pivot`` [B,3] fp32
+    on the device or None: the mean of the body's vertices, in fp64, rounded once.
+
+    One pass: ``rigid_pose``; ``body_penetration`` and ``crossing_penetration(self_pairs=False, between=True)``; stop when there is no
+    inside triple and no crossing pair (these counts are on the host already: no read-back of the loop's own); otherwise
+    ``body_penetration_grad`` with g = w_pen and ``crossing_field_grad`` with g = w_cross from the rows and lists just found (nothing is
+    searched twice, no autograd graph), one fp32 add, ``rigid_wrench`` and ``rigid_step``.  A weight of zero leaves that term's search out
+    (its history entry is -1) and the stop test looks at the other term alone.  At most ``max_iter`` steps.  Self crossings are not looked
+    at: a rigid motion cannot change them.  Returns ``SeparationResult``; ``verts`` is always the pose of the state returned.
+
+    ``ValueError`` for wrong shapes, dtypes or devices, max_iter < 1, a non-positive or non-finite learning rate, sigma outside (0, 0.5], a
+    negative weight, both weights zero, an unknown penalty or mode; ``PsiHipError`` for what the library refuses, CPU tensors included."""
+    import math
+    import numbers
+    import numpy as np
+
+    def check():
+        if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
+            raise ValueError('max_iter is an integer >= 1, got %r' % (max_iter,))
+        _check_step_args(lr_t, lr_r, betas, eps)
+        _check_sigma(sigma)
+        for name, w in (('w_pen', w_pen), ('w_cross', w_cross)):
+            if isinstance(w, bool) or not isinstance(w, numbers.Real) or not math.isfinite(w) or w < 0:
+                raise ValueError('%s is a finite number >= 0, got %r' % (name, w))
+        if w_pen == 0 and w_cross == 0:
+            raise ValueError('w_pen and w_cross are both zero: nothing to separate by')
+        if penalty not in BODY_DEPTH_PENALTIES:
+            raise ValueError('penalty is one of %s, got %r' % (sorted(BODY_DEPTH_PENALTIES), penalty))
+        if mode not in ('pruned', 'brute'):
+            raise ValueError("mode is 'pruned' or 'brute', got %r" % (mode,))
+        if base.shape[0] >= 1:
+            if pivot is not None:
+                _check_rows(pivot, int(base.shape[0]), 3, 'pivot', base.device)
+            if fixed is not None:
+                _fixed_mask(fixed, int(base.shape[0]), base.device if torch.is_tensor(fixed) else 'cpu')
+
+    if torch.is_tensor(base) and base.dim() == 3 and base.shape[0] < 1:
+        raise ValueError('expected base [B,V,3] float32 with B >= 1')
+    B, V, dev, pb, pg = _batch_args(base, group, 'rigid_separate', then=check, max_B=SURFACE_CROSSINGS_MAX_B)
+    with torch.cuda.device(dev), torch.no_grad():
+        mask = _fixed_mask(fixed, B, dev)
+        if pivot is None:
+            pivot = torch.from_numpy(base.detach().cpu().numpy().astype(np.float64).mean(1).astype(np.float32)).to(dev)
+        state = rigid_state(pivot.clone())
+        hist = {'triples': [], 'pairs': [], 'loss_pen': [], 'loss_cross': []}
+        k, separated = 0, False
+        with _overlap_handle(overlap_handle_or_faces, V) as oh, _crossings_handle(crossings_handle_or_faces, V) as ch:
+            while True:
+                one = rigid_pass(base, state, k + 1, oh, ch, group=group, fixed_mask=mask, step=k < max_iter, lr_t=lr_t, lr_r=lr_r, betas=betas,
+                                 eps=eps, w_pen=w_pen, w_cross=w_cross, penalty=penalty, sigma=sigma, mode=mode)
+                verts = one.verts
+                hist['triples'].append(one.triples), hist['pairs'].append(one.pairs)
+                hist['loss_pen'].append(one.loss_pen), hist['loss_cross'].append(one.loss_cross)
+                separated = one.clean
+                if not one.stepped:
+                    break
+                k += 1
+        hist['loss_pen'], hist['loss_cross'] = torch.stack(hist['loss_pen']), torch.stack(hist['loss_cross'])
+        M, shift, angle = _rigid_transform(state.quat, state.transl, state.pivot)
+        return SeparationResult(verts, state.quat, state.transl, state.pivot, M, k, separated, hist, shift, angle)

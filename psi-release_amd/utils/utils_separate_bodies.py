@@ -1,0 +1,144 @@
+#!/usr/bin/env python
+"""python utils_separate_bodies.py GEN_FOLDER OUT_FOLDER [--human_model_path ... --vposer_ckpt_path ... | --synthetic DIR] [--no_flip]
+                                                          [--fixed I,J,...] [--max_iter N] [--lr_t M] [--lr_r RAD] [--sigma S]
+                                                          [--no_crossings] [--parts] [--out JSON]
+
+Moves the bodies of GEN_FOLDER/body_gen_*.pkl apart: every body is placed as utils_eval_body_overlap.py places it, all bodies are separated
+as ONE batch (evaluation.BodySeparator, DESIGN.md section 10h: a rotation about the body's centre and a translation per body, until no
+vertex of one is inside another and no surfaces cross), and OUT_FOLDER/body_gen_%06d.pkl is written per body in row order: the record as
+it was, with its own cam_ext replaced by (rigid motion) . cam_ext and nothing else changed.  Prints the overlapping pairs and the crossing
+pairs before and after, the iterations, and the largest shift and angle.
+
+--fixed holds the listed rows where they are (two fixed bodies that overlap each other never separate); --no_crossings separates by the
+vertex test alone (w_cross = 0: surfaces may still cross afterwards); --parts hands the body parts to the crossings handle (they matter to
+self crossings only, which a rigid motion cannot change); --lr_t and --lr_r are the step lengths in metres and radians.  The room is not
+looked at: a body may be pushed into furniture."""
+import argparse
+import json
+import math
+import os
+import pickle
+
+import _eval_common as C  # noqa: F401  (path setup)
+import numpy as np
+import torch
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('gen_folder')
+    ap.add_argument('out_folder')
+    ap.add_argument('--human_model_path', default='/is/ps2/yzhang/body_models/VPoser')
+    ap.add_argument('--vposer_ckpt_path', default='/is/ps2/yzhang/body_models/VPoser/vposer_v1_0')
+    ap.add_argument('--synthetic', default=None, metavar='DIR', help='stand-in body model and VPoser')
+    ap.add_argument('--no_flip', action='store_true', help='PROX-E trees: no Habitat camera flip')
+    ap.add_argument('--fixed', default='', metavar='I,J,...', help='rows that must not move')
+    ap.add_argument('--max_iter', type=int, default=100)
+    ap.add_argument('--lr_t', type=float, default=0.01, metavar='M', help='translation step, metres')
+    ap.add_argument('--lr_r', type=float, default=0.01, metavar='RAD', help='rotation step, radians')
+    ap.add_argument('--sigma', type=float, default=0.5, metavar='S', help='the height of the cones of the crossing term, in (0, 0.5]')
+    ap.add_argument('--no_crossings', action='store_true', help='separate by the vertex test alone')
+    ap.add_argument('--parts', action='store_true', help='give the crossings handle the body parts of the model')
+    ap.add_argument('--max_files', type=int, default=8000)
+    ap.add_argument('--chunk', type=int, default=512, help='bodies per skinning call')
+    ap.add_argument('--out', default=None, metavar='JSON')
+    a = ap.parse_args(argv)
+    try:
+        a.fixed = [int(x) for x in a.fixed.split(',') if x.strip() != '']
+    except ValueError:
+        ap.error('--fixed is a comma-separated list of rows')
+    if any(i < 0 for i in a.fixed):
+        ap.error('--fixed: rows are not negative')
+    if a.max_iter < 1:
+        ap.error('--max_iter must be at least 1')
+    for name in ('lr_t', 'lr_r'):
+        if not (math.isfinite(getattr(a, name)) and getattr(a, name) > 0):
+            ap.error('--%s must be positive and finite' % name)
+    if not 0.0 < a.sigma <= 0.5:
+        ap.error('--sigma must lie in (0, 0.5]')
+    if a.chunk < 1:
+        ap.error('--chunk must be at least 1')
+    return a
+
+
+def read_records(folder, max_files):
+    """The records of the folder one body each, in the row order of PlausibilityEvaluator._read_folder: a pkl of n bodies gives n records,
+    every per-body array cut to its row; cam_ext is the file's first camera, as the reader takes it."""
+    from psi_release_amd.geometry import BodyParamParser
+    out = []
+    for ii in range(max_files):
+        fn = os.path.join(folder, 'body_gen_{:06d}.pkl'.format(ii))
+        if not os.path.exists(fn):
+            continue
+        with open(fn, 'rb') as f:
+            rec = pickle.load(f)
+        n = np.asarray(BodyParamParser._vector(rec)).reshape(-1, 72).shape[0]
+        for b in range(n):
+            one = {}
+            for k, v in rec.items():
+                arr = np.asarray(v) if isinstance(v, (np.ndarray, list, tuple)) else None
+                one[k] = arr[b:b + 1].copy() if arr is not None and arr.ndim >= 1 and arr.shape[0] == n and k != 'cam_ext' else v
+            one['cam_ext'] = np.asarray(rec['cam_ext'], np.float32).reshape(-1, 4, 4)[:1].copy()
+            out.append(one)
+    return out
+
+
+def pairs_of(counts):
+    c = np.asarray(counts, np.int64)
+    return [[i, j, int(c[i, j]), int(c[j, i])] for i in range(len(c)) for j in range(i + 1, len(c)) if c[i, j] or c[j, i]]
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from psi_release_amd import synth
+    from psi_release_amd.evaluation import BodySeparator, PlausibilityEvaluator
+    from utils_show_test_results import BodyDecoder, camera_pose
+    device = torch.device('cuda', torch.cuda.current_device())
+    smplx_src, vposer_src = a.human_model_path, a.vposer_ckpt_path
+    if a.synthetic:
+        smplx_src, vposer_src = synth.make_smplx(7), synth.make_vposer_state(3)
+    xh, cam = PlausibilityEvaluator._read_folder(a.gen_folder, a.max_files)
+    if not len(xh):
+        raise SystemExit('no body_gen_*.pkl in %s' % a.gen_folder)
+    if any(i >= len(xh) for i in a.fixed):
+        raise SystemExit('--fixed: the folder has %d bodies' % len(xh))
+    decoder = BodyDecoder(smplx_src, vposer_src, device)
+    part = skip = rest = None
+    if a.parts:
+        from utils_eval_body_overlap import model_parts
+        part, skip, rest = model_parts(smplx_src, decoder.faces.cpu().numpy())
+    sep = BodySeparator(decoder.faces, device, order_verts=rest, face_part=part, part_skip=skip)
+    pose = camera_pose(cam, a.no_flip)
+    res, _ = sep.separate_records(xh, pose, decoder, chunk=a.chunk, fixed=a.fixed or None, max_iter=a.max_iter, lr_t=a.lr_t, lr_r=a.lr_r,
+                                  sigma=a.sigma, w_cross=0.0 if a.no_crossings else 1.0)
+    M = res.transform.cpu().numpy()
+    cam_new = np.matmul(M, np.asarray(cam, np.float64)).astype(np.float32)                  # the flip multiplies from the right: unaffected
+    before_ov = sep.overlap.counts_of_records(xh, pose, decoder, chunk=a.chunk).counts.cpu().numpy()
+    before_cr = sep.crossings.crossings_of_records(xh, pose, decoder, chunk=a.chunk, self_pairs=False).counts.cpu().numpy()
+    after_pose = camera_pose(cam_new, a.no_flip)
+    after_ov = sep.overlap.counts_of_records(xh, after_pose, decoder, chunk=a.chunk).counts.cpu().numpy()
+    after_cr = sep.crossings.crossings_of_records(xh, after_pose, decoder, chunk=a.chunk, self_pairs=False).counts.cpu().numpy()
+    shift, angle = res.shift.cpu().numpy(), res.angle.cpu().numpy()
+    rep = {'bodies': int(len(xh)), 'iterations': int(res.iterations), 'separated': bool(res.separated), 'fixed': list(a.fixed),
+           'overlapping_pairs_before': pairs_of(before_ov), 'overlapping_pairs_after': pairs_of(after_ov),
+           'crossing_pairs_before': pairs_of(np.triu(before_cr, 1)), 'crossing_pairs_after': pairs_of(np.triu(after_cr, 1)),
+           'triples': list(res.history['triples']), 'pairs': list(res.history['pairs']),
+           'shift': shift.tolist(), 'angle': angle.tolist(), 'max_shift': float(shift.max()), 'max_angle': float(angle.max())}
+    os.makedirs(a.out_folder, exist_ok=True)
+    for k, rec in enumerate(read_records(a.gen_folder, a.max_files)):
+        rec['cam_ext'] = cam_new[k:k + 1]
+        with open(os.path.join(a.out_folder, 'body_gen_{:06d}.pkl'.format(k)), 'wb') as f:
+            pickle.dump(rec, f)
+    print('[INFO] %d bodies, %d iterations, %s' % (rep['bodies'], rep['iterations'], 'separated' if rep['separated'] else 'NOT separated'))
+    print('[INFO] overlapping pairs: %d before, %d after' % (len(rep['overlapping_pairs_before']), len(rep['overlapping_pairs_after'])))
+    print('[INFO] crossing pairs of bodies: %d before, %d after' % (len(rep['crossing_pairs_before']), len(rep['crossing_pairs_after'])))
+    print('[INFO] largest shift %.4f m, largest angle %.4f rad' % (rep['max_shift'], rep['max_angle']))
+    sep.close()
+    if a.out:
+        with open(a.out, 'w') as f:
+            json.dump(rep, f, indent=1)
+    return rep
+
+
+if __name__ == '__main__':
+    main()
