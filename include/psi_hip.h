@@ -915,6 +915,21 @@ int psi_body_separate_wrench(const float *d_verts, const float *d_G, const float
 int psi_body_separate_step(const double *d_chunks, int nchunk, float *d_g6, float *d_quat, float *d_transl, float *d_m, float *d_s,
                            const int32_t *d_fixed, int B, float b1, float b2, float c1, float c2, float eps, float lr_t, float lr_r,
                            void *stream);
+/* The scene term of the separation: the bodies d_verts [B,V,3] against signed distance volumes.  The scene table has the form of
+ * psi_sdf_sample_forward with align_corners = 1: d_sdf [S,D,D,D] fp32, element [ix][iy][iz]; d_gmin, d_gmax [S,3] (device); d_scene_id [B]
+ * int32 or NULL (scene 0; a value outside [0,S) is clamped).  Per axis k = (float)((D - 1) / ((double)gmax - gmin)), u = (x - gmin) k,
+ * clamped to [0, D - 1]; the eight corners of the cell are interpolated along z, then y, then x with lerp(a, b, w) = a + w (b - a); the
+ * gradient comes from the same differences, times k, and is an exact zero along an axis whose u is not strictly inside (0, D - 1)
+ * (csrc/body_separate_shared.h has every statement).  A vertex with value < 0 is in the scene: G = (-w_scene) g and -value its loss;
+ * every other vertex contributes exact zeros.  Outputs per chunk of 256 consecutive vertices, by the tree of wrench: d_chunks
+ * [B, ceil(V / 256), 6] fp64 = the sums of (G, (x - p) x G) with d_p [B,3] = pivot + transl, d_count [B, ceil(V / 256)] int32 = the
+ * vertices in the scene, d_loss [B, ceil(V / 256)] fp64 = the sum of -value.  d_sdf_out [B,V] and d_G_out [B,V,3] (fp32) receive the value
+ * and G of every vertex when not NULL.  One kernel on `stream`, no host synchronisation, no floating-point atomics; bit-identical from
+ * run to run and to the fp32 NumPy restatement.  PSI_EINVAL: a null pointer (but d_scene_id, d_sdf_out, d_G_out), B or V outside the
+ * limits above, D < 2, S < 1, a negative or non-finite w_scene. */
+int psi_body_separate_scene(const float *d_verts, const float *d_p, const float *d_sdf, const float *d_gmin, const float *d_gmax,
+                            const int32_t *d_scene_id, int B, int V, int D, int S, float w_scene, double *d_chunks, int32_t *d_count,
+                            double *d_loss, float *d_sdf_out, float *d_G_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -5,9 +5,10 @@
 // Kernels: pose (one lane per vertex; the body is blockIdx.y, so the ten state scalars and the nine entries of R are uniform over the wave:
 // scalar loads, scalar registers), wrench (one workgroup per (body, chunk of 256 consecutive vertices): six fp64 terms per lane, the fixed
 // tree s[l] += s[l + stride], stride = 128 .. 1 — the strides 128 and 64 through LDS, 32 .. 1 by lane shifts within wave 0, which adds the
-// same pairs) and step (eight lanes per body, six of them at work: lane c adds the chunk sums of component c in chunk order in fp64, rounds
-// once, takes the Adam step of its component; lane 0 of the body then moves transl and the quaternion).  The sums use no floating-point
-// atomics and do not depend on the shape of the grid.  No scratch.
+// same pairs), step (eight lanes per body, six of them at work: lane c adds the chunk sums of component c in chunk order in fp64, rounds
+// once, takes the Adam step of its component; lane 0 of the body then moves transl and the quaternion) and scene (the grid and the tree of
+// wrench: one lane per vertex samples the body's scene volume and forms its own G; nothing per vertex is stored).  The sums use no
+// floating-point atomics and do not depend on the shape of the grid.  No scratch.
 #include "body_separate_shared.h"
 #include "psi_common.h"
 #include "wg_device.h"
@@ -38,6 +39,36 @@ __global__ __launch_bounds__(WG) void bs_pose_kernel(const float *__restrict__ b
     verts[at] = x.x, verts[at + 1] = x.y, verts[at + 2] = x.z;
 }
 
+// The tree s[l] += s[l + stride], stride = 128 .. 1, of N values per lane over the 256 lanes of a workgroup: the strides 128 and 64 through
+// LDS, 32 .. 1 by lane shifts within wave 0.  Every lane of the workgroup calls it; it returns false for the lanes past wave 0, and lane 0
+// holds the sums.
+template <int N>
+__device__ __forceinline__ bool bs_tree(double (&a)[N], double (&s)[N][WG], int t)
+{
+    if (t >= 64) {
+#pragma unroll
+        for (int k = 0; k < N; k++) s[k][t] = a[k];
+    }
+    __syncthreads();
+    if (t < 128) {                                              // stride 128
+#pragma unroll
+        for (int k = 0; k < N; k++) a[k] = a[k] + s[k][t + 128];
+    }
+    if (t >= 64 && t < 128) {                                   // its own slot, which stride 128 did not read
+#pragma unroll
+        for (int k = 0; k < N; k++) s[k][t] = a[k];
+    }
+    __syncthreads();
+    if (t >= 64) return false;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        a[k] = a[k] + s[k][t + 64];                             // stride 64
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a[k] = a[k] + __shfl_down(a[k], o, 64);       // strides 32 .. 1: lane l takes lane l + o
+    }
+    return true;
+}
+
 // chunks [B, nchunk, 6] fp64: (F, T) of the vertices 256 k .. 256 k + 255 of body b; lanes past V hold +0
 __global__ __launch_bounds__(WG) void bs_wrench_kernel(const float *__restrict__ verts, const float *__restrict__ G, const float *__restrict__ p,
                                                        int V, double *__restrict__ chunks)
@@ -52,31 +83,51 @@ __global__ __launch_bounds__(WG) void bs_wrench_kernel(const float *__restrict__
         const bs3 c = bs_torque(bs_load(verts + at), bs_load(p + 3 * b), g);
         a[0] = (double)g.x, a[1] = (double)g.y, a[2] = (double)g.z, a[3] = (double)c.x, a[4] = (double)c.y, a[5] = (double)c.z;
     }
-    if (t >= 64) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) s[k][t] = a[k];
-    }
-    __syncthreads();
-    if (t < 128) {                                              // stride 128
-#pragma unroll
-        for (int k = 0; k < 6; k++) a[k] = a[k] + s[k][t + 128];
-    }
-    if (t >= 64 && t < 128) {                                   // its own slot, which stride 128 did not read
-#pragma unroll
-        for (int k = 0; k < 6; k++) s[k][t] = a[k];
-    }
-    __syncthreads();
-    if (t >= 64) return;
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        a[k] = a[k] + s[k][t + 64];                             // stride 64
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a[k] = a[k] + __shfl_down(a[k], o, 64);       // strides 32 .. 1: lane l takes lane l + o
-    }
+    if (!bs_tree<6>(a, s, t)) return;
     if (t == 0) {
         double *out = chunks + ((size_t)b * gridDim.x + blockIdx.x) * 6;
 #pragma unroll
         for (int k = 0; k < 6; k++) out[k] = a[k];
+    }
+}
+
+// The scene term (bs_scene_vertex): one lane per vertex gathers the eight corners of its cell in the body's scene volume; a vertex with
+// value < 0 contributes G = (-w_scene) g, c = a x G and -value, every other lane +0.  Per chunk: the six sums, the fp64 sum of -value and
+// the count (carried through the tree as a double: an integer <= 256 is exact).  The body, hence the scene, its box and p, is uniform over
+// the workgroup.  sdf_out [B,V] and G_out [B,V,3] are written only when given.
+__global__ __launch_bounds__(WG) void bs_scene_kernel(const float *__restrict__ verts, const float *__restrict__ p, const float *__restrict__ sdf,
+                                                      const float *__restrict__ gmin, const float *__restrict__ gmax,
+                                                      const int32_t *__restrict__ scene_id, int V, int D, int S, float w_scene,
+                                                      double *__restrict__ chunks, int32_t *__restrict__ count, double *__restrict__ loss,
+                                                      float *__restrict__ sdf_out, float *__restrict__ G_out)
+{
+    __shared__ double s[8][WG];
+    const int b = blockIdx.y, t = threadIdx.x;
+    const int sc = bs_scene_of(scene_id, b, S);
+    const BsSceneBox box = bs_scene_box(gmin + 3 * sc, gmax + 3 * sc, D);
+    const int v = blockIdx.x * WG + t;
+    double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (v < V) {
+        const size_t at = ((size_t)b * V + v) * 3;
+        const bs3 x = bs_load(verts + at);
+        bs3 g;
+        bool inside;
+        const BsSceneSample sm = bs_scene_vertex(sdf + (size_t)sc * D * D * D, D, box, x, w_scene, g, inside);
+        if (inside) {
+            const bs3 c = bs_torque(x, bs_load(p + 3 * b), g);
+            a[0] = (double)g.x, a[1] = (double)g.y, a[2] = (double)g.z, a[3] = (double)c.x, a[4] = (double)c.y, a[5] = (double)c.z;
+            a[6] = (double)(-sm.value), a[7] = 1.0;
+        }
+        if (sdf_out) sdf_out[(size_t)b * V + v] = sm.value;
+        if (G_out) G_out[at] = g.x, G_out[at + 1] = g.y, G_out[at + 2] = g.z;
+    }
+    if (!bs_tree<8>(a, s, t)) return;
+    if (t == 0) {
+        const size_t ch = (size_t)b * gridDim.x + blockIdx.x;
+#pragma unroll
+        for (int k = 0; k < 6; k++) chunks[ch * 6 + k] = a[k];
+        loss[ch] = a[6];
+        count[ch] = (int32_t)a[7];
     }
 }
 
@@ -159,6 +210,20 @@ extern "C" int psi_body_separate_wrench(const float *d_verts, const float *d_G, 
     PSI_CHECK_LAUNCH("bs_wrench_kernel");
     if (!d_g6) return 0;
     return bs_launch_step(d_chunks, nchunk, d_g6, nullptr, nullptr, nullptr, nullptr, nullptr, B, 0, BsStep{}, (hipStream_t)stream);
+}
+
+extern "C" int psi_body_separate_scene(const float *d_verts, const float *d_p, const float *d_sdf, const float *d_gmin, const float *d_gmax,
+                                       const int32_t *d_scene_id, int B, int V, int D, int S, float w_scene, double *d_chunks,
+                                       int32_t *d_count, double *d_loss, float *d_sdf_out, float *d_G_out, void *stream)
+{
+    PSI_REQUIRE(d_verts && d_p && d_sdf && d_gmin && d_gmax && d_chunks && d_count && d_loss, "null pointer");
+    BS_REQUIRE(B, V);
+    PSI_REQUIRE(D >= 2 && S >= 1, "D >= 2, S >= 1");
+    PSI_REQUIRE(w_scene >= 0.0f && w_scene < INFINITY, "w_scene >= 0, finite");
+    hipLaunchKernelGGL(psi_bs::bs_scene_kernel, dim3(psi_cdiv(V, psi_bs::WG), B), dim3(psi_bs::WG), 0, (hipStream_t)stream, d_verts, d_p, d_sdf,
+                       d_gmin, d_gmax, d_scene_id, V, D, S, w_scene, d_chunks, d_count, d_loss, d_sdf_out, d_G_out);
+    PSI_CHECK_LAUNCH("bs_scene_kernel");
+    return 0;
 }
 
 extern "C" int psi_body_separate_step(const double *d_chunks, int nchunk, float *d_g6, float *d_quat, float *d_transl, float *d_m, float *d_s,

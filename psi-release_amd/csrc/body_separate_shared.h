@@ -9,6 +9,10 @@
 //   wrench   a = x - p, c = a x G (a component is a*b - c*d); (G, c) are widened to fp64 by the caller and added in a fixed order
 //   step     m = b1 m + (1 - b1) g, s = b2 s + ((1 - b2) g) g, u = (m / c1) / (sqrt(s / c2) + eps); transl -= lr_t u[0:3];
 //            delta = -(lr_r u[3:6]); quat <- normalise((1, delta / 2) (x) quat) unless delta is exactly zero
+//   scene    a node-centred volume sdf [D][D][D] over the box gmin .. gmax: k = fp32((D - 1) / (gmax - gmin)) formed in fp64, o = gmin;
+//            u = (x - o) k, clamp to [0, D - 1], cell and fraction, in = 0 < u < D - 1; the eight corners interpolated along z, y, x with
+//            lerp(a, b, w) = a + w (b - a); the grid-unit gradient from the same differences, times k under the mask; a vertex with
+//            value < 0 is in the scene: G = (-w_scene) g, loss -value; every other vertex gives exact zeros
 #pragma once
 #include "geom_shared.h"
 #include <stdint.h>
@@ -89,4 +93,81 @@ GEOM_FN BsQuat bs_quat_step(BsQuat q, bs3 delta)
     BsQuat o;
     o.w = nw / n, o.x = nx / n, o.y = ny / n, o.z = nz / n;
     return o;
+}
+
+// ---- the scene term: a vertex against the signed distance volume of its scene ----
+struct BsSceneBox { float k[3], o[3]; };
+struct BsAxis { int i0, i1; float w; bool in; };
+struct BsSceneSample { float value; bs3 g; };              // g: d value / d x in the world, an exact zero along a clamped axis
+
+// k = (D - 1) / (max - min) in fp64, rounded once; o = min (node-centred volumes: the first node lies on the box)
+GEOM_FN BsSceneBox bs_scene_box(const float *gmin, const float *gmax, int D)
+{
+    BsSceneBox b;
+    for (int a = 0; a < 3; a++) {
+        b.k[a] = (float)((double)(D - 1) / ((double)gmax[a] - (double)gmin[a]));
+        b.o[a] = gmin[a];
+    }
+    return b;
+}
+
+// u = (x - o) k; the median-of-three clamp written as max then min returns 0 for a NaN, so both indices lie in [0, D - 1] for every input
+GEOM_FN BsAxis bs_scene_axis(float x, float o, float k, int D)
+{
+    const float dm1 = (float)(D - 1);
+    const float u = (x - o) * k;
+    BsAxis A;
+    A.in = u > 0.0f && u < dm1;
+    const float uc = fminf(fmaxf(u, 0.0f), dm1);
+    const float fl = floorf(uc);
+    A.i0 = (int)fl;
+    A.w = uc - fl;
+    A.i1 = A.i0 + 1 < D - 1 ? A.i0 + 1 : D - 1;
+    return A;
+}
+
+GEOM_FN float bs_lerp(float a, float b, float w) { return a + w * (b - a); }
+
+// q[dx][dy][dz]: the eight corners of the cell
+GEOM_FN BsSceneSample bs_scene_sample(const float (&q)[2][2][2], BsAxis X, BsAxis Y, BsAxis Z, BsSceneBox box)
+{
+    float dz[2][2], r[2][2];
+    for (int dx = 0; dx < 2; dx++)
+        for (int dy = 0; dy < 2; dy++) {
+            dz[dx][dy] = q[dx][dy][1] - q[dx][dy][0];
+            r[dx][dy] = q[dx][dy][0] + Z.w * dz[dx][dy];
+        }
+    const float r0 = bs_lerp(r[0][0], r[0][1], Y.w), r1 = bs_lerp(r[1][0], r[1][1], Y.w);
+    BsSceneSample s;
+    s.value = bs_lerp(r0, r1, X.w);
+    const float gx = r1 - r0;
+    const float gy = bs_lerp(r[0][1] - r[0][0], r[1][1] - r[1][0], X.w);
+    const float gz = bs_lerp(bs_lerp(dz[0][0], dz[0][1], Y.w), bs_lerp(dz[1][0], dz[1][1], Y.w), X.w);
+    s.g = bs_make(X.in ? gx * box.k[0] : 0.0f, Y.in ? gy * box.k[1] : 0.0f, Z.in ? gz * box.k[2] : 0.0f);
+    return s;
+}
+
+// The vertex x of a body in scene volume `vol` [D][D][D] (element [ix][iy][iz]): its sample; G = (-w_scene) g when value < 0, else +0
+GEOM_FN BsSceneSample bs_scene_vertex(const float *vol, int D, BsSceneBox box, bs3 x, float w_scene, bs3 &G, bool &inside)
+{
+    const BsAxis X = bs_scene_axis(x.x, box.o[0], box.k[0], D), Y = bs_scene_axis(x.y, box.o[1], box.k[1], D);
+    const BsAxis Z = bs_scene_axis(x.z, box.o[2], box.k[2], D);
+    float q[2][2][2];
+    for (int dx = 0; dx < 2; dx++)
+        for (int dy = 0; dy < 2; dy++) {
+            const size_t row = ((size_t)(dx ? X.i1 : X.i0) * D + (size_t)(dy ? Y.i1 : Y.i0)) * D;
+            q[dx][dy][0] = vol[row + Z.i0], q[dx][dy][1] = vol[row + Z.i1];
+        }
+    const BsSceneSample s = bs_scene_sample(q, X, Y, Z, box);
+    inside = s.value < 0.0f;
+    const float nw = -w_scene;
+    G = inside ? bs_make(nw * s.g.x, nw * s.g.y, nw * s.g.z) : bs_make(0.0f, 0.0f, 0.0f);
+    return s;
+}
+
+// scene_id of a body: NULL is scene 0, a value outside [0, S) is clamped
+GEOM_FN int bs_scene_of(const int32_t *scene_id, int b, int S)
+{
+    const int s = scene_id ? scene_id[b] : 0;
+    return s < 0 ? 0 : (s > S - 1 ? S - 1 : s);
 }

@@ -392,8 +392,8 @@ class BodySeparator:
     """Repairs a batch of overlapping bodies: every body is moved rigidly, by a rotation about its pivot and a translation, until no vertex
     of one lies inside another and no surfaces cross (``ops.rigid_separate``).  Shape and pose are kept.  Owns the
     two handles the searches need (``BodyOverlap`` and ``SurfaceCrossings`` of the same ``faces``; the other arguments as
-    ``SurfaceCrossings``).  The room is not looked at: a body may be pushed into furniture, and ``shift`` / ``angle`` of the result say
-    how far every body went."""
+    ``SurfaceCrossings``).  Without a ``scene`` the room is not looked at and a body may be pushed into furniture; with one the bodies
+    are kept out of its signed distance volume as well.  ``shift`` / ``angle`` of the result say how far every body went."""
 
     def __init__(self, faces, device='cuda', order_verts=None, face_part=None, part_skip=None):
         self.device = torch.device(device)
@@ -404,11 +404,40 @@ class BodySeparator:
         self.overlap.close()
         self.crossings.close()
 
+    def scene_table(self, scene, scene_id=None):
+        """The tuple (sdf [S,D,D,D], grid_min [S,3], grid_max [S,3], scene_id [B] int32 or None) on this device that ``ops.rigid_separate``
+        takes, of a ``synth.SceneData``, of a list of them (all of one D; ``scene_id`` [B] then says which body stands in which) or of such
+        a tuple, which is passed on as it is.  One upload."""
+        from . import synth
+        if isinstance(scene, tuple):
+            if scene_id is not None:
+                raise ValueError('a scene tuple carries its own scene_id')
+            return scene
+        many = isinstance(scene, list)
+        scenes = scene if many else [scene]
+        if not scenes or not all(isinstance(s, synth.SceneData) for s in scenes):
+            raise ValueError('scene is a synth.SceneData, a list of them, or a tuple (sdf, grid_min, grid_max, scene_id)')
+        if len({tuple(np.asarray(s.sdf).shape) for s in scenes}) != 1:
+            raise ValueError('the scenes of one call share one D')
+        if scene_id is None and len(scenes) > 1:
+            raise ValueError('several scenes need scene_id [B]')
+        sdf = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(s.sdf, np.float32) for s in scenes]))).to(self.device)
+        lo = torch.from_numpy(np.stack([np.asarray(s.grid_min, np.float32).reshape(3) for s in scenes])).to(self.device)
+        hi = torch.from_numpy(np.stack([np.asarray(s.grid_max, np.float32).reshape(3) for s in scenes])).to(self.device)
+        if scene_id is not None:
+            scene_id = torch.as_tensor(np.asarray(scene_id.detach().cpu().numpy() if torch.is_tensor(scene_id) else scene_id).astype(np.int32)).to(self.device)
+        return sdf, lo, hi, scene_id
+
     @torch.no_grad()
-    def separate(self, verts, group=None, **kw):
+    def separate(self, verts, group=None, scene=None, scene_id=None, w_scene=1.0, **kw):
         """verts [B,V,3] fp32 on the device, world frame; ``group`` as in ``BodyOverlap.counts``; the keywords of ``ops.rigid_separate``
-        (fixed, pivot, max_iter, lr_t, lr_r, betas, eps, w_pen, w_cross, penalty, sigma, mode).  Returns ``ops.SeparationResult``."""
+        (fixed, pivot, max_iter, lr_t, lr_r, betas, eps, w_pen, w_cross, penalty, sigma, mode).  ``scene``: what ``scene_table`` takes,
+        with ``scene_id`` and ``w_scene``; uploaded once per call.  Returns ``ops.SeparationResult``."""
         V = int(verts.shape[1])
+        if scene is not None:
+            kw = dict(kw, scene=self.scene_table(scene, scene_id), w_scene=w_scene)
+        elif scene_id is not None:
+            raise ValueError('scene_id without a scene')
         return ops.rigid_separate(verts.contiguous(), self.overlap._handle_for(V), self.crossings._handle_for(V),
                                   group=_FacesHandleOwner._group(group, verts), **kw)
 
@@ -417,7 +446,7 @@ class BodySeparator:
         """The bodies ``xh72`` [N,72] with cameras ``cam_ext`` [N,4,4] or [1,4,4], skinned exactly as ``BodyOverlap.counts_of_records``
         skins them, separated as ONE batch.  Returns (``ops.SeparationResult``, cam_ext' [N,4,4] fp64 host array) with cam_ext'[b] =
         transform[b] cam_ext[b]: a record is repaired by replacing its camera pose and nothing else (an evaluator's Habitat flip
-        multiplies from the right and is not affected)."""
+        multiplies from the right and is not affected).  ``scene``, ``scene_id`` and ``w_scene`` as in ``separate``."""
         verts = _verts_of_records(xh72, cam_ext, evaluator_or_decoder, chunk, self.device, 'separate_records')
         res = self.separate(verts, group, **kw)
         cam = (cam_ext.detach().cpu().numpy() if torch.is_tensor(cam_ext) else np.asarray(cam_ext)).astype(np.float64).reshape(-1, 4, 4)

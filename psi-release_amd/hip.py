@@ -176,6 +176,7 @@ SIGNATURES = {
     'psi_body_separate_pose': (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p] * 2),
     'psi_body_separate_wrench': (c_int, [c_void_p] * 3 + [c_int] * 2 + [c_void_p] * 3),
     'psi_body_separate_step': (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_int] + [c_float] * 7 + [c_void_p]),
+    'psi_body_separate_scene': (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_float] + [c_void_p] * 6),
 }
 
 

@@ -2124,10 +2124,21 @@ class SeparationResult(NamedTuple):
     pivot: torch.Tensor        # [B,3] fp32
     transform: torch.Tensor    # [B,4,4] fp64: x' = M x for the vertices given
     iterations: int            # steps taken
-    separated: bool            # the last pass found nothing inside and nothing crossing
-    history: dict              # per pass: 'triples', 'pairs' (lists of int; -1: not searched), 'loss_pen', 'loss_cross' ([passes,B] fp32)
+    separated: bool            # the last pass found nothing inside, nothing crossing and, with a scene, no vertex of a free body in it
+    history: dict              # per pass: 'triples', 'pairs' (lists of int; -1: not searched), 'loss_pen', 'loss_cross' ([passes,B] fp32);
+                               # with a scene also 'scene_inside' (a list of [B] int64 on the host) and 'loss_scene' ([passes,B] fp64)
     shift: torch.Tensor        # [B] fp64: |transl|
     angle: torch.Tensor        # [B] fp64: the rotation angle, radians
+
+
+class SceneSeparationResult(SeparationResult):
+    """What ``rigid_separate`` returns with a scene: the ten fields of ``SeparationResult`` in their order, and beside them the attribute
+    ``scene_inside`` [B] int64 on the host, the vertices of every body in its scene at the last pass."""
+
+    def __new__(cls, *fields, scene_inside=None):
+        self = super().__new__(cls, *fields)
+        self.scene_inside = scene_inside
+        return self
 
 
 def rigid_state(pivot):
@@ -2188,6 +2199,99 @@ def rigid_wrench(verts, G, pivot_plus_transl, return_chunks=False):
         g6 = torch.empty(B, 6, dtype=torch.float32, device=dev)
         chunks = _rigid_chunks(verts, G, pivot_plus_transl, g6)
     return (g6, chunks) if return_chunks else g6
+
+
+def _check_w_scene(w_scene, positive=False):
+    import math
+    import numbers
+    if isinstance(w_scene, bool) or not isinstance(w_scene, numbers.Real) or not math.isfinite(w_scene) or w_scene < 0:
+        raise ValueError('w_scene is a finite number >= 0, got %r' % (w_scene,))
+    if positive and w_scene == 0:
+        raise ValueError('w_scene is zero with a scene given: leave the scene out instead')
+
+
+def _check_scene(sdf, grid_min, grid_max, scene_id, B, dev):
+    """The scene table of the separation: sdf [S,D,D,D] fp32 with D >= 2, grid_min, grid_max [S,3] fp32, scene_id [B] int32 or None, all
+    on ``dev``.  ``ValueError`` otherwise.  Returns S, D."""
+    if not torch.is_tensor(sdf) or sdf.dtype != torch.float32 or sdf.dim() != 4 or sdf.shape[0] < 1 or sdf.device != dev:
+        raise ValueError('expected sdf [S,D,D,D] float32 on the device of the vertices')
+    S, D = int(sdf.shape[0]), int(sdf.shape[1])
+    if tuple(sdf.shape[1:]) != (D, D, D):
+        raise ValueError('the volumes are cubic, got %s' % (tuple(sdf.shape[1:]),))
+    if D < 2:
+        raise ValueError('D >= 2, got %d' % D)
+    _check_rows(grid_min, S, 3, 'grid_min', dev), _check_rows(grid_max, S, 3, 'grid_max', dev)
+    if scene_id is not None and (not torch.is_tensor(scene_id) or scene_id.dtype != torch.int32 or tuple(scene_id.shape) != (B,) or scene_id.device != dev):
+        raise ValueError('expected scene_id [%d] int32 on the device of the vertices, or None' % B)
+    return S, D
+
+
+def _scene_launch(verts, p, scene, w_scene, value=None, G=None):
+    """psi_body_separate_scene on checked arguments: chunks [B,nchunk,6] fp64, count [B,nchunk] int32, loss [B,nchunk] fp64."""
+    sdf, gmin, gmax, scene_id = scene
+    B, V, dev = int(verts.shape[0]), int(verts.shape[1]), verts.device
+    nchunk = (V + RIGID_CHUNK - 1) // RIGID_CHUNK
+    chunks = torch.empty(B, nchunk, 6, dtype=torch.float64, device=dev)
+    count = torch.empty(B, nchunk, dtype=torch.int32, device=dev)
+    loss = torch.empty(B, nchunk, dtype=torch.float64, device=dev)
+    hip.check(hip.lib().psi_body_separate_scene(hip.ptr(verts), hip.ptr(p), hip.ptr(sdf), hip.ptr(gmin), hip.ptr(gmax), hip.ptr(scene_id), B, V,
+                                                int(sdf.shape[1]), int(sdf.shape[0]), float(w_scene), hip.ptr(chunks), hip.ptr(count),
+                                                hip.ptr(loss), hip.ptr(value), hip.ptr(G), hip.stream()), 'psi_body_separate_scene')
+    return chunks, count, loss
+
+
+def _chunk_order_sum(rows):
+    """[..., nchunk] -> [...]: the chunk rows added in chunk order from +0 (an fp64 sum whose order is part of the contract)."""
+    acc = torch.zeros(rows.shape[:-1], dtype=rows.dtype, device=rows.device)
+    for c in range(rows.shape[-1]):
+        acc = acc + rows[..., c]
+    return acc
+
+
+def rigid_scene_wrench(verts, pivot_plus_transl, sdf, grid_min, grid_max, scene_id=None, w_scene=1.0, return_fields=False):
+    """The scene term of ``rigid_separate`` on the bodies ``verts`` [B,V,3] fp32 (psi_body_separate_scene).  ``sdf``
+    [S,D,D,D] fp32 holds one node-centred signed distance volume per scene (element [ix][iy][iz]) over the boxes ``grid_min``, ``grid_max``
+    [S,3] fp32; ``scene_id`` [B] int32 picks the volume of a body (None: scene 0; clamped to [0, S)).  A vertex whose trilinear value is
+    < 0 is in the scene: G = -w_scene * gradient (zero along an axis on which the vertex is outside the box), loss -value.  Returns
+    ``chunks`` [B, ceil(V/256), 6] fp64, the sums of (G, (x - p) x G) per chunk of 256 vertices by the tree of ``rigid_wrench`` with p =
+    ``pivot_plus_transl`` [B,3]; ``count`` [B] int64, the vertices in the scene; ``loss`` [B] fp64, the chunk sums of -value added in chunk
+    order.  ``return_fields``: also the value [B,V] and G [B,V,3] of every vertex.  One kernel, no read-back, no floating-point atomics;
+    bit-equal to the fp32 NumPy restatement and from run to run.  ``ValueError`` for wrong shapes, dtypes or devices, a volume that is not
+    cubic, D < 2, a negative or non-finite w_scene; ``PsiHipError`` for CPU tensors."""
+    _check_verts3(verts, 'verts')
+    B, V, dev = int(verts.shape[0]), int(verts.shape[1]), verts.device
+    _check_rows(pivot_plus_transl, B, 3, 'pivot_plus_transl', dev)
+    _check_scene(sdf, grid_min, grid_max, scene_id, B, dev)
+    _check_w_scene(w_scene)
+    for t in (verts, pivot_plus_transl, sdf, grid_min, grid_max, scene_id):
+        hip.ptr(t)
+    with torch.cuda.device(dev), torch.no_grad():
+        value = torch.empty(B, V, dtype=torch.float32, device=dev) if return_fields else None
+        G = torch.empty(B, V, 3, dtype=torch.float32, device=dev) if return_fields else None
+        chunks, count, loss = _scene_launch(verts, pivot_plus_transl, (sdf, grid_min, grid_max, scene_id), w_scene, value, G)
+        count, loss = count.to(torch.int64).sum(1), _chunk_order_sum(loss)
+    return (chunks, count, loss, value, G) if return_fields else (chunks, count, loss)
+
+
+def _check_scene_tuple(scene, B, dev):
+    if not isinstance(scene, (tuple, list)) or len(scene) != 4:
+        raise ValueError('scene is a tuple (sdf, grid_min, grid_max, scene_id) of tensors on the device of the vertices; scene_id may be None')
+    _check_scene(scene[0], scene[1], scene[2], scene[3], B, dev)
+
+
+class _RigidScene:
+    """A checked scene tuple for the loop, with what a pass needs beside it: the pinned host buffer its counts are copied to, the event
+    that marks the copy, and the bodies that may move, on the host (one read-back when it is made, none in a pass)."""
+
+    def __init__(self, scene, B, dev, fixed_mask):
+        _check_scene_tuple(scene, B, dev)
+        self.tensors = tuple(scene)
+        for t in self.tensors:
+            hip.ptr(t)
+        self.free = None if fixed_mask is None else (fixed_mask == 0).cpu()
+        self.host = torch.empty(B, dtype=torch.int64).pin_memory()
+        self.copied = torch.cuda.Event()
+        self.loss_rows = False         # rigid_separate sets it: a pass then hands on its [B,nchunk] loss rows, added once after the loop
 
 
 def _check_step_args(lr_t, lr_r, betas, eps):
@@ -2283,15 +2387,30 @@ class RigidPass(NamedTuple):
     clean: bool                # nothing inside and nothing crossing
     stepped: bool              # the state was advanced
     g6: torch.Tensor           # [B,6] fp32 when stepped, else None
+    scene_inside: torch.Tensor = None      # with a scene: [B] int64 on the host, the vertices of every body in its scene
+    stop: bool = None                      # with a scene: clean, and no body that may move has a vertex in its scene
+    loss_scene: torch.Tensor = None        # with a scene: [B] fp64
+    chunks: torch.Tensor = None            # with a scene, when stepped: [B,nchunk,6] fp64, the bodies' chunk sums plus the scene's
 
 
 def rigid_pass(base, state, k, overlap_handle, crossings_handle, group=None, fixed_mask=None, step=True, lr_t=0.01, lr_r=0.01,
-               betas=(0.9, 0.999), eps=1e-8, w_pen=1.0, w_cross=1.0, penalty='depth', sigma=0.5, mode='pruned'):
+               betas=(0.9, 0.999), eps=1e-8, w_pen=1.0, w_cross=1.0, penalty='depth', sigma=0.5, mode='pruned', scene=None, w_scene=1.0):
     """One pass of ``rigid_separate``'s loop from ``state`` (a ``RigidState``, advanced in place when the pass steps): the pose, the two
     searches, the stop test and, unless the batch is clean or ``step`` is false, the two gradients, their sum, the wrench and step ``k`` of
     the optimiser (the chunk sums go straight into the step's launch).  ``fixed_mask``: [B] int32 on the device or None.  The arguments
-    are ``rigid_separate``'s, which has checked them.  Returns ``RigidPass``."""
+    are ``rigid_separate``'s, which has checked them.  Returns ``RigidPass``.
+
+    ``scene``: None, or the tuple (sdf, grid_min, grid_max, scene_id) of ``rigid_scene_wrench``.  The scene kernel is then launched after
+    the pose and before the searches, and its [B] counts go to a pinned host buffer with a non-blocking copy on the same stream.  Every
+    search reads its own counts back with a blocking copy on that stream, queued after ours, so ours has landed when the first search
+    returns: the pass has no host wait of its own (the event recorded behind the copy is queried, and waited for only if a search ever
+    returned without a read-back).  The pass stops when the bodies are clean and no body outside ``fixed_mask`` has a vertex in its
+    scene; otherwise the bodies' chunk sums (zeros when they are clean) and the scene's are added in fp64 and go into the step."""
     B, dev = int(base.shape[0]), base.device
+    if scene is not None:
+        return _rigid_pass_scene(base, state, k, overlap_handle, crossings_handle, group, fixed_mask, step, lr_t, lr_r, betas, eps, w_pen,
+                                 w_cross, penalty, sigma, mode, scene if isinstance(scene, _RigidScene) else _RigidScene(scene, B, dev, fixed_mask),
+                                 w_scene)
     with torch.cuda.device(dev), torch.no_grad():
         verts = rigid_pose(base, state.quat, state.transl, state.pivot)
         pen = body_penetration(verts, overlap_handle, group=group) if w_pen != 0 else None
@@ -2317,8 +2436,50 @@ def rigid_pass(base, state, k, overlap_handle, crossings_handle, group=None, fix
         return RigidPass(verts, n_tri, n_pairs, loss_pen, loss_cross, False, True, g6)
 
 
+def _rigid_pass_scene(base, state, k, overlap_handle, crossings_handle, group, fixed_mask, step, lr_t, lr_r, betas, eps, w_pen, w_cross, penalty,
+                      sigma, mode, scene, w_scene):
+    B, dev = int(base.shape[0]), base.device
+    with torch.cuda.device(dev), torch.no_grad():
+        verts = rigid_pose(base, state.quat, state.transl, state.pivot)
+        p = state.pivot + state.transl
+        chunks_scene, count, loss = _scene_launch(verts, p, scene.tensors, w_scene)
+        scene.host.copy_(count.to(torch.int64).sum(1), non_blocking=True)
+        scene.copied.record()
+        loss_scene = loss if scene.loss_rows else _chunk_order_sum(loss)
+        pen = body_penetration(verts, overlap_handle, group=group) if w_pen != 0 else None
+        cr = crossing_penetration(verts, crossings_handle, group=group, self_pairs=False, between=True, sigma=sigma, mode=mode) if w_cross != 0 else None
+        if not scene.copied.query():
+            scene.copied.synchronize()
+        inside = scene.host.clone()
+        n_tri = -1 if pen is None else int(pen.triples.shape[0])
+        n_pairs = -1 if cr is None else int(cr.crossings.pairs.shape[0])
+        loss_pen = torch.zeros(B, dtype=torch.float32, device=dev) if pen is None else pen.loss[BODY_DEPTH_PENALTIES[penalty]]
+        loss_cross = torch.zeros(B, dtype=torch.float32, device=dev) if cr is None else cr.loss
+        clean = n_tri <= 0 and n_pairs <= 0
+        stop = clean and int((inside if scene.free is None else inside[scene.free]).sum()) == 0
+        if stop or not step:
+            return RigidPass(verts, n_tri, n_pairs, loss_pen, loss_cross, clean, False, None, inside, stop, loss_scene, None)
+        chunks = chunks_scene
+        if not clean:
+            G = None
+            if pen is not None:
+                G = body_penetration_grad(verts.shape, overlap_handle, pen.triples, pen.rows,
+                                          torch.full((B,), float(w_pen), dtype=torch.float32, device=dev), penalty)
+            if cr is not None:
+                Gc = crossing_field_grad(verts, crossings_handle, cr.crossings.pairs, torch.full((B,), float(w_cross), dtype=torch.float32, device=dev),
+                                         sigma)
+                G = Gc if G is None else G + Gc
+            chunks = _rigid_chunks(verts, G, p, None) + chunks_scene
+        else:
+            chunks = torch.zeros_like(chunks_scene) + chunks_scene         # the bodies' chunk sums are +0: the same fp64 add
+        g6 = torch.empty(B, 6, dtype=torch.float32, device=dev)
+        _rigid_step(state, g6, chunks, k, lr_t, lr_r, betas, eps, fixed_mask)
+        return RigidPass(verts, n_tri, n_pairs, loss_pen, loss_cross, clean, True, g6, inside, stop, loss_scene, chunks)
+
+
 def rigid_separate(base, overlap_handle_or_faces, crossings_handle_or_faces, group=None, fixed=None, pivot=None, max_iter=100, lr_t=0.01,
-                   lr_r=0.01, betas=(0.9, 0.999), eps=1e-8, w_pen=1.0, w_cross=1.0, penalty='depth', sigma=0.5, mode='pruned'):
+                   lr_r=0.01, betas=(0.9, 0.999), eps=1e-8, w_pen=1.0, w_cross=1.0, penalty='depth', sigma=0.5, mode='pruned', scene=None,
+                   w_scene=1.0):
     """Moves the bodies ``base`` [B,V,3] fp32 rigidly, each by a rotation about its pivot and a translation, until no vertex of one lies
     inside another and no surfaces cross.  Shape and pose of every body are kept.  ``overlap_handle_or_faces``: a
     handle of ``body_overlap_create`` or faces [F,3] int32 (a tensor); ``crossings_handle_or_faces``: a handle of
@@ -2333,8 +2494,17 @@ def rigid_separate(base, overlap_handle_or_faces, crossings_handle_or_faces, gro
     (its history entry is -1) and the stop test looks at the other term alone.  At most ``max_iter`` steps.  Self crossings are not looked
     at: a rigid motion cannot change them.  Returns ``SeparationResult``; ``verts`` is always the pose of the state returned.
 
+    ``scene`` = (sdf [S,D,D,D], grid_min [S,3], grid_max [S,3], scene_id [B] int32 or None), fp32 tensors on the device (the table of
+    ``rigid_scene_wrench``), keeps the bodies out of their scenes as well: every pass adds the wrench of the hinge term w_scene * sum of
+    -sdf over the vertices with sdf < 0 to the bodies' (``rigid_pass`` says how, and why without a host wait), and the loop goes on until
+    the bodies are clean AND no body that may move has a vertex in its scene.  The scene term is always the hinge, whatever ``penalty``
+    is: a squared depth has no gradient at the surface and does not finish.  The result then is a ``SceneSeparationResult``, with ``scene_inside`` [B], and the history
+    keys 'scene_inside' and 'loss_scene'; a fixed body's vertices are counted there but do not hold the loop open.  A body wedged between
+    furniture and another body may not finish: ``separated`` says so.  Without a scene every launch and every bit is what it was.
+
     ``ValueError`` for wrong shapes, dtypes or devices, max_iter < 1, a non-positive or non-finite learning rate, sigma outside (0, 0.5], a
-    negative weight, both weights zero, an unknown penalty or mode; ``PsiHipError`` for what the library refuses, CPU tensors included."""
+    negative weight, both weights zero, an unknown penalty or mode, a scene that is not such a tuple, a volume that is not cubic, D < 2,
+    a negative or non-finite w_scene, w_scene == 0 with a scene; ``PsiHipError`` for what the library refuses, CPU tensors included."""
     import math
     import numbers
     import numpy as np
@@ -2353,6 +2523,9 @@ def rigid_separate(base, overlap_handle_or_faces, crossings_handle_or_faces, gro
             raise ValueError('penalty is one of %s, got %r' % (sorted(BODY_DEPTH_PENALTIES), penalty))
         if mode not in ('pruned', 'brute'):
             raise ValueError("mode is 'pruned' or 'brute', got %r" % (mode,))
+        if scene is not None:
+            _check_w_scene(w_scene, positive=True)
+            _check_scene_tuple(scene, int(base.shape[0]), base.device)
         if base.shape[0] >= 1:
             if pivot is not None:
                 _check_rows(pivot, int(base.shape[0]), 3, 'pivot', base.device)
@@ -2368,18 +2541,30 @@ def rigid_separate(base, overlap_handle_or_faces, crossings_handle_or_faces, gro
             pivot = torch.from_numpy(base.detach().cpu().numpy().astype(np.float64).mean(1).astype(np.float32)).to(dev)
         state = rigid_state(pivot.clone())
         hist = {'triples': [], 'pairs': [], 'loss_pen': [], 'loss_cross': []}
+        table = None
+        if scene is not None:
+            table = _RigidScene(scene, B, dev, mask)
+            table.loss_rows = True
+            hist['scene_inside'], hist['loss_scene'] = [], []
         k, separated = 0, False
         with _overlap_handle(overlap_handle_or_faces, V) as oh, _crossings_handle(crossings_handle_or_faces, V) as ch:
             while True:
                 one = rigid_pass(base, state, k + 1, oh, ch, group=group, fixed_mask=mask, step=k < max_iter, lr_t=lr_t, lr_r=lr_r, betas=betas,
-                                 eps=eps, w_pen=w_pen, w_cross=w_cross, penalty=penalty, sigma=sigma, mode=mode)
+                                 eps=eps, w_pen=w_pen, w_cross=w_cross, penalty=penalty, sigma=sigma, mode=mode, scene=table, w_scene=w_scene)
                 verts = one.verts
                 hist['triples'].append(one.triples), hist['pairs'].append(one.pairs)
                 hist['loss_pen'].append(one.loss_pen), hist['loss_cross'].append(one.loss_cross)
                 separated = one.clean
+                if table is not None:
+                    hist['scene_inside'].append(one.scene_inside), hist['loss_scene'].append(one.loss_scene)
+                    separated = one.stop
                 if not one.stepped:
                     break
                 k += 1
         hist['loss_pen'], hist['loss_cross'] = torch.stack(hist['loss_pen']), torch.stack(hist['loss_cross'])
         M, shift, angle = _rigid_transform(state.quat, state.transl, state.pivot)
+        if table is not None:
+            hist['loss_scene'] = _chunk_order_sum(torch.stack(hist['loss_scene']))        # [passes,B,nchunk] -> [passes,B], in chunk order
+            return SceneSeparationResult(verts, state.quat, state.transl, state.pivot, M, k, separated, hist, shift, angle,
+                                         scene_inside=hist['scene_inside'][-1])
         return SeparationResult(verts, state.quat, state.transl, state.pivot, M, k, separated, hist, shift, angle)

@@ -2,6 +2,7 @@
 """python utils_separate_bodies.py GEN_FOLDER OUT_FOLDER [--human_model_path ... --vposer_ckpt_path ... | --synthetic DIR] [--no_flip]
                                                           [--fixed I,J,...] [--max_iter N] [--lr_t M] [--lr_r RAD] [--sigma S]
                                                           [--no_crossings] [--parts] [--out JSON]
+                                                          [--scene_sdf PATH [--w_scene W] | --scene_floor Z [--w_scene W]]
 
 Moves the bodies of GEN_FOLDER/body_gen_*.pkl apart: every body is placed as utils_eval_body_overlap.py places it, all bodies are separated
 as ONE batch (evaluation.BodySeparator, DESIGN.md section 10h: a rotation about the body's centre and a translation per body, until no
@@ -11,8 +12,12 @@ pairs before and after, the iterations, and the largest shift and angle.
 
 --fixed holds the listed rows where they are (two fixed bodies that overlap each other never separate); --no_crossings separates by the
 vertex test alone (w_cross = 0: surfaces may still cross afterwards); --parts hands the body parts to the crossings handle (they matter to
-self crossings only, which a rigid motion cannot change); --lr_t and --lr_r are the step lengths in metres and radians.  The room is not
-looked at: a body may be pushed into furniture."""
+self crossings only, which a rigid motion cannot change); --lr_t and --lr_r are the step lengths in metres and radians.
+
+Without --scene_sdf the room is not looked at: a body may be pushed into furniture.  --scene_sdf PATH names the signed distance volume
+of the room (PATH.json and PATH_sdf.npy, what scene_io.read_sdf reads; node-centred, free space positive): the bodies are then also moved
+out of it, with weight --w_scene, and the vertices in the scene before and after are printed and written.  With --synthetic, --scene_floor
+Z stands in for a room: the volume of s = z - Z over the bodies' box."""
 import argparse
 import json
 import math
@@ -42,6 +47,9 @@ def parse_args(argv=None):
     ap.add_argument('--max_files', type=int, default=8000)
     ap.add_argument('--chunk', type=int, default=512, help='bodies per skinning call')
     ap.add_argument('--out', default=None, metavar='JSON')
+    ap.add_argument('--scene_sdf', default=None, metavar='PATH', help='the signed distance volume of the room: PATH.json and PATH_sdf.npy')
+    ap.add_argument('--scene_floor', type=float, default=None, metavar='Z', help='with --synthetic: a floor at height Z as the scene')
+    ap.add_argument('--w_scene', type=float, default=1.0, metavar='W', help='the weight of the scene term')
     a = ap.parse_args(argv)
     try:
         a.fixed = [int(x) for x in a.fixed.split(',') if x.strip() != '']
@@ -58,6 +66,10 @@ def parse_args(argv=None):
         ap.error('--sigma must lie in (0, 0.5]')
     if a.chunk < 1:
         ap.error('--chunk must be at least 1')
+    if not (math.isfinite(a.w_scene) and a.w_scene > 0):
+        ap.error('--w_scene must be positive and finite')
+    if a.scene_floor is not None and (not math.isfinite(a.scene_floor) or not a.synthetic or a.scene_sdf):
+        ap.error('--scene_floor is a finite height, goes with --synthetic and not with --scene_sdf')
     return a
 
 
@@ -88,9 +100,22 @@ def pairs_of(counts):
     return [[i, j, int(c[i, j]), int(c[j, i])] for i in range(len(c)) for j in range(i + 1, len(c)) if c[i, j] or c[j, i]]
 
 
+def floor_scene(verts, z, dim=24):
+    """The SceneData of s = z' - z sampled at the nodes of a dim^3 grid over the box of ``verts`` [B,V,3] grown by 1 m (and down to 1 m
+    below the floor): linear, so its interpolation is the plane itself."""
+    from psi_release_amd import synth
+    v = verts.detach().cpu().numpy().reshape(-1, 3).astype(np.float64)
+    lo, hi = (v.min(0) - 1.0).astype(np.float32), (v.max(0) + 1.0).astype(np.float32)
+    lo[2] = min(lo[2], np.float32(z - 1.0))
+    hi[2] = max(hi[2], np.float32(z + 1.0))
+    zz = np.float64(lo[2]) + (np.float64(hi[2]) - np.float64(lo[2])) * np.arange(dim) / (dim - 1) - z
+    sdf = np.ascontiguousarray(np.broadcast_to(zz.astype(np.float32), (dim, dim, dim)))
+    return synth.SceneData(np.zeros((0, 3), np.float32), sdf, lo, hi, dim)
+
+
 def main(argv=None):
     a = parse_args(argv)
-    from psi_release_amd import synth
+    from psi_release_amd import evaluation, ops, scene_io, synth
     from psi_release_amd.evaluation import BodySeparator, PlausibilityEvaluator
     from utils_show_test_results import BodyDecoder, camera_pose
     device = torch.device('cuda', torch.cuda.current_device())
@@ -109,8 +134,22 @@ def main(argv=None):
         part, skip, rest = model_parts(smplx_src, decoder.faces.cpu().numpy())
     sep = BodySeparator(decoder.faces, device, order_verts=rest, face_part=part, part_skip=skip)
     pose = camera_pose(cam, a.no_flip)
+    table, scene_kw = None, {}
+    if a.scene_sdf or a.scene_floor is not None:
+        if a.scene_sdf:
+            sdf, lo, hi, dim = scene_io.read_sdf(a.scene_sdf)
+            scene = synth.SceneData(np.zeros((0, 3), np.float32), sdf, lo, hi, dim)
+        else:
+            scene = floor_scene(evaluation._verts_of_records(xh, pose, decoder, a.chunk, device, 'utils_separate_bodies'), a.scene_floor)
+        table = sep.scene_table(scene)
+        scene_kw = dict(scene=table, w_scene=a.w_scene)
+
+    def in_scene(p):
+        verts = evaluation._verts_of_records(xh, p, decoder, a.chunk, device, 'utils_separate_bodies')
+        return ops.rigid_scene_wrench(verts, verts.new_zeros(verts.shape[0], 3), *table)[1].cpu().tolist()
+
     res, _ = sep.separate_records(xh, pose, decoder, chunk=a.chunk, fixed=a.fixed or None, max_iter=a.max_iter, lr_t=a.lr_t, lr_r=a.lr_r,
-                                  sigma=a.sigma, w_cross=0.0 if a.no_crossings else 1.0)
+                                  sigma=a.sigma, w_cross=0.0 if a.no_crossings else 1.0, **scene_kw)
     M = res.transform.cpu().numpy()
     cam_new = np.matmul(M, np.asarray(cam, np.float64)).astype(np.float32)                  # the flip multiplies from the right: unaffected
     before_ov = sep.overlap.counts_of_records(xh, pose, decoder, chunk=a.chunk).counts.cpu().numpy()
@@ -124,6 +163,9 @@ def main(argv=None):
            'crossing_pairs_before': pairs_of(np.triu(before_cr, 1)), 'crossing_pairs_after': pairs_of(np.triu(after_cr, 1)),
            'triples': list(res.history['triples']), 'pairs': list(res.history['pairs']),
            'shift': shift.tolist(), 'angle': angle.tolist(), 'max_shift': float(shift.max()), 'max_angle': float(angle.max())}
+    if table is not None:
+        rep.update({'w_scene': float(a.w_scene), 'scene_inside_before': in_scene(pose), 'scene_inside_after': in_scene(after_pose),
+                    'scene_inside': [c.tolist() for c in res.history['scene_inside']]})
     os.makedirs(a.out_folder, exist_ok=True)
     for k, rec in enumerate(read_records(a.gen_folder, a.max_files)):
         rec['cam_ext'] = cam_new[k:k + 1]
@@ -132,6 +174,8 @@ def main(argv=None):
     print('[INFO] %d bodies, %d iterations, %s' % (rep['bodies'], rep['iterations'], 'separated' if rep['separated'] else 'NOT separated'))
     print('[INFO] overlapping pairs: %d before, %d after' % (len(rep['overlapping_pairs_before']), len(rep['overlapping_pairs_after'])))
     print('[INFO] crossing pairs of bodies: %d before, %d after' % (len(rep['crossing_pairs_before']), len(rep['crossing_pairs_after'])))
+    if table is not None:
+        print('[INFO] vertices in the scene: %d before, %d after' % (sum(rep['scene_inside_before']), sum(rep['scene_inside_after'])))
     print('[INFO] largest shift %.4f m, largest angle %.4f rad' % (rep['max_shift'], rep['max_angle']))
     sep.close()
     if a.out:

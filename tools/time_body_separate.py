@@ -18,7 +18,19 @@ its FIRST pass, on the same state, alternated over --rounds rounds (median and s
     torch      a plain torch composition of the same pose, reduction (fp64 sums) and Adam step on the same G: the comparator of `rigid`
     pass       one whole pass, ops.rigid_pass, from the same state every time
 
-The torch arm's wrench and state are compared with the kernels'."""
+The torch arm's wrench and state are compared with the kernels'.
+
+    python tools/time_body_separate.py --scene [--out FILE] [--dim 256] [--rounds 5] [--reps 3]      # profiles/body_separate_scene_times.json
+    python tools/time_body_separate.py --scene --trace [--calls 3]
+    python tools/time_body_separate.py --scene --merge STATS_CSV      # profiles/body_separate_scene_kernel_stats.csv
+
+The scene arm: the same batch in the --dim^3 signed distance volume of synth.make_oriented_room (scene_sdf.MeshSDF), alternated rounds:
+
+    scene        the scene kernel alone (psi_body_separate_scene: sample, hinge, wrench chunks, counts)
+    composition  what it replaces: ops.sdf_sample with its gradient rows, the mask sdf < 0 and -w * gradient in torch, and stage one of
+                 ops.rigid_wrench (the chunk sums)
+    pass         ops.rigid_pass without a scene, from the same state every time
+    pass_scene   ops.rigid_pass with the scene"""
 import argparse
 import csv
 import json
@@ -59,6 +71,97 @@ def torch_arm(torch, base, state, G, k, lr_t=0.01, lr_r=0.01, b1=0.9, b2=0.999, 
     return verts, g6, quat, transl, m, s
 
 
+def scene_arm(a):
+    verts, faces = make_batch(a.bodies, a.seed)
+    import torch
+    from psi_release_amd import evaluation, ops, scene_sdf, synth
+    import body_overlap_cases as C  # noqa: F401  (make_batch's mesh)
+    B, V = verts.shape[:2]
+    rest = synth.make_capsule_mesh(*C.WORKLOAD, C.RADIUS, C.HEIGHT)[0]
+    base = torch.tensor(verts, device='cuda')
+    room = synth.make_oriented_room()
+    lo, hi = scene_sdf.grid_box(room.verts, 0.5)
+    mesh = scene_sdf.MeshSDF(room.verts, room.faces, device='cuda')
+    sdf = mesh.compute(lo, hi, a.dim).reshape(1, a.dim, a.dim, a.dim).float().contiguous()
+    gmin, gmax = torch.tensor(lo, device='cuda').reshape(1, 3), torch.tensor(hi, device='cuda').reshape(1, 3)
+    scene = (sdf, gmin, gmax, None)
+    sep = evaluation.BodySeparator(faces, 'cuda', order_verts=rest)
+    oh, ch = sep.overlap._handle_for(V), sep.crossings._handle_for(V)
+    state0 = ops.rigid_state(torch.tensor(verts.astype('float64').mean(1).astype('float32'), device='cuda'))
+    scratch = ops.rigid_state(state0.pivot.clone())
+    p = state0.pivot + state0.transl
+
+    def kernel():
+        return ops._scene_launch(base, p, scene, 1.0)
+
+    def composition():
+        og = torch.empty(B, V, 3, device='cuda')
+        val = torch.empty(B, V, device='cuda')
+        ops.hip.check(ops.hip.lib().psi_sdf_sample_forward(ops.hip.ptr(sdf), None, ops.hip.ptr(gmin), ops.hip.ptr(gmax), ops.hip.ptr(base), B, V, a.dim,
+                                                           1, 1, ops.hip.ptr(val), ops.hip.ptr(og), ops.hip.stream()), 'psi_sdf_sample_forward')
+        inside = val < 0
+        G = torch.where(inside[..., None], -1.0 * og, torch.zeros_like(og))
+        return ops._rigid_chunks(base, G, p, None), inside.sum(1), torch.where(inside, -val, torch.zeros_like(val)).double().sum(1)
+
+    if a.trace:
+        for _ in range(a.calls):
+            kernel()
+            composition()
+        torch.cuda.synchronize()
+        return
+
+    def timed(fn, reps=a.reps):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(reps):
+            fn()
+        end.record()
+        end.synchronize()
+        return start.elapsed_time(end) / reps
+
+    def reset():
+        for dst, src in zip(scratch, state0):
+            dst.copy_(src)
+
+    def one_pass(**kw):
+        reset()
+        return ops.rigid_pass(base, scratch, 1, oh, ch, **kw)
+
+    table = ops._RigidScene(scene, B, base.device, None)
+    table.loss_rows = True                                 # as in the loop: the loss rows are added once after it
+    run = {'scene': kernel, 'composition': composition, 'pass': one_pass, 'pass_scene': lambda: one_pass(scene=table)}
+    res = {}
+    for k, fn in run.items():
+        res[k] = fn()
+        torch.cuda.synchronize()
+    ts = {k: [] for k in run}
+    for _ in range(a.rounds):
+        for k, fn in run.items():
+            ts[k].append(timed(fn))
+    s = {k: summary(v) for k, v in ts.items()}
+    spread = lambda k: s[k]['max_ms'] - s[k]['min_ms']
+    below = s['scene']['max_ms'] < s['composition']['min_ms'] and \
+        s['composition']['median_ms'] - s['scene']['median_ms'] > spread('scene') + spread('composition')
+    chunks, count, loss = res['scene']
+    c_chunks, c_count, c_loss = res['composition']
+    out = {'device': torch.cuda.get_device_name(0), 'rounds': a.rounds, 'reps': a.reps, 'bodies': B, 'seed': a.seed, 'vertices': V, 'dim': a.dim,
+           'what': 'the scene term of the separation on the batch of body_separate_times.json in the volume of synth.make_oriented_room, device '
+                   'events: scene = psi_body_separate_scene alone; composition = psi_sdf_sample_forward with gradient rows, the mask and the '
+                   'scaling in torch, psi_body_separate_wrench stage one; pass / pass_scene = ops.rigid_pass without / with the scene',
+           'vertices_in_the_scene': int(count.sum().item()), 'composition_vertices_in_the_scene': int(c_count.sum().item()),
+           'composition_chunks_max_abs_diff': float((chunks - c_chunks).abs().max().item()),
+           'composition_loss_max_abs_diff': float((ops._chunk_order_sum(loss) - c_loss).abs().max().item()),
+           **s, 'scene_share_of_pass_scene': s['scene']['median_ms'] / s['pass_scene']['median_ms'],
+           'pass_scene_over_pass': s['pass_scene']['median_ms'] / s['pass']['median_ms'],
+           'composition_over_scene': s['composition']['median_ms'] / s['scene']['median_ms'],
+           'scene_below_composition_by_more_than_both_spreads': bool(below)}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+    sep.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'body_separate_times.json'))
@@ -71,15 +174,23 @@ def main():
     ap.add_argument('--trace', action='store_true')
     ap.add_argument('--calls', type=int, default=3)
     ap.add_argument('--merge')
+    ap.add_argument('--scene', action='store_true', help='the scene arm: its own JSON and kernel rows')
+    ap.add_argument('--dim', type=int, default=256)
     a = ap.parse_args()
+    if a.scene:
+        if a.out == ap.get_default('out'):
+            a.out = os.path.join(ROOT, 'profiles', 'body_separate_scene_times.json')
+        if a.stats_out == ap.get_default('stats_out'):
+            a.stats_out = os.path.join(ROOT, 'profiles', 'body_separate_scene_kernel_stats.csv')
 
     if a.merge:
         out = json.load(open(a.out))
         kern = {}
         lines = open(a.merge).read().splitlines()
-        kept = [lines[0]] + [ln for ln in lines[1:] if any(k in ln for k in KERNELS)]       # this project's kernels, as rocprofv3 wrote them
+        names = KERNELS + ('bs_scene_kernel', 'sdf_sample') if a.scene else KERNELS
+        kept = [lines[0]] + [ln for ln in lines[1:] if any(k in ln for k in names)]         # this project's kernels, as rocprofv3 wrote them
         for row in csv.DictReader(kept):
-            for k in KERNELS:
+            for k in names:
                 if k in row['Name']:                   # the instances of a template are added up
                     calls, total = int(row['Calls']), float(row['TotalDurationNs']) / 1e3
                     if k in kern:
@@ -93,6 +204,8 @@ def main():
         print(json.dumps(out))
         return
 
+    if a.scene:
+        return scene_arm(a)
     verts, faces = make_batch(a.bodies, a.seed)
     import torch
     from psi_release_amd import evaluation, ops, synth
