@@ -269,6 +269,10 @@ int psi_fit_iterate_dp(psi_fit_engine *engine, psi_dp_comm *comm, int n_iter, in
 /* How this engine's data-parallel iterations have been launched so far: 0 = none yet, 1 = captured hipGraphs (the collective inside),
  * 2 = eager launches from C (capturing the collective was refused once; results are the same). */
 int psi_fit_dp_mode(const psi_fit_engine *engine);
+/* Where this engine runs the kinematic chain of the pose stage (the G / A transforms): 1 = as a role of blend_fwd's launch, beside its
+ * stream and off the iteration's critical path (cluster head kernels, B <= 64, a free compute unit for every links workgroup), 0 = in
+ * the head kernel (also with PSI_FIT_CHAIN_IN_HEAD=1 in the environment at creation).  The results are the same bit for bit. */
+int psi_fit_chain_mode(const psi_fit_engine *engine);
 /* Host-side wait for everything enqueued on `stream` with a bound (hipStreamQuery polls): 0 = done, PSI_ETIMEOUT = still busy after
  * timeout_ms — the watchdog of the data-parallel loop (a collective that cannot complete becomes an error, not a hang). */
 int psi_stream_wait(void *stream, int timeout_ms);
@@ -280,7 +284,8 @@ int psi_fit_profile(psi_fit_engine *engine, int n_rep, char *h_names, int name_s
                     int *h_n_stages, void *stream);
 /* Test/diagnostic copy of an engine-owned device buffer by name ("verts" [B,V,3], "pose" [B,165],
  * "g_pose", "g_rot" [B,55,9], "stats" [8], "adam_m"/"adam_v" [B,75]; the backward's intermediates "gA" [B,64,16], "gfeat" [B,Kpad],
- * "g_transl" [B,3], "gl" / "g_vp" / "v_posed" [B,Npad], and — engines whose per-vertex backward runs inside the scene launch — the
+ * "g_transl" [B,3], "gl" / "g_vp" / "v_posed" [B,Npad], the pose stage's "R" / "G" [B,55,12], "A" [B,55,12] + 16 zero rows of 12 and "feat"
+ * [ceil(B/32) 32, Kpad] (fp16 pairs in blend_fwd's operand order), and — engines whose per-vertex backward runs inside the scene launch — the
  * contact class of rows "glc" / "gvpc" / "vpc" [B,3 ncp] in slot order (ncp = n_contact rounded up to 256), "spb" [B] (independent
  * bodies: each body's penetration factor -w_collision / N_b), and "penmask" [B][Vpad/64] 64-bit words = 2 floats' worth of bits
  * each, Vpad = V rounded up to 256: bit v % 64 of word v / 64 is set when vertex v of the body had sdf < 0 in the last forward, i.e. when

@@ -42,6 +42,8 @@ __device__ int psi_dbg_sstop;            // dev: leave the skinning / scene kern
 #define PSI_SSTOP(k) do { if (psi_dbg_sstop == (k)) return; } while (0)
 __device__ int psi_dbg_pstop;            // dev: end the tail kernel inside the pose-backward stage (PSI_TAIL_STOP = 20 + k)
 #define PSI_PSTOP(k) do { if (psi_dbg_pstop == (k)) asm volatile("s_endpgm"); } while (0)
+__device__ int psi_dbg_cstop;            // dev: end the head kernel behind the feature row of psi_pose_fwd_chain (PSI_HEAD_STOP = 9)
+#define PSI_CSTOP() do { if (psi_dbg_cstop) asm volatile("s_endpgm"); } while (0)
 #define PSI_TRACE(lo, hi) PsiBlockTrace trace_((lo), (hi))
 // dev (PSI_SKIN_STOP=9): the workgroup timeline of the LAST fwd_scene launch — {start, end} in 10 ns wall-clock ticks, the hardware id
 // words and the kind of workgroup, one record per workgroup (tools/timeline.py draws it)
@@ -68,6 +70,7 @@ extern "C" int psi_dbg_timeline(unsigned long long *out, int nblocks)
 }
 #endif
 #include "lbs_device.h"
+#include "chain_plan.h"
 #include "lbs_joint_device.h"
 #include "sdf_device.h"
 #include "nnindex_device.h"
@@ -325,7 +328,10 @@ __device__ __forceinline__ float hx_value(unsigned long long *p, unsigned long l
 // they are issued at the top of the kernel, before the body vector is even read, so the weight fetch overlaps everything else.
 // C = 1 (B > 128: the grid fills the chip anyway) compiles to the exchange-free kernel.  Workgroup id = c * B + b: for B % 8 == 0 a
 // body's cluster shares an XCD (and its L2).
-template <int C>
+// LINKS_IN_HEAD = false: the pose stage ends at the feature row (psi_pose_fwd_rot) — all that blend_fwd, the next launch, reads of it.  The
+// kinematic chain and the G / A rows behind it are first read by the launch after that one, so they ride in blend_fwd's launch as a role of
+// their own (psi_lbs_blend_forward_links; when: chain_plan.h) instead of ending this latency-bound kernel.  true: the whole stage here.
+template <int C, bool LINKS_IN_HEAD>
 __global__ __launch_bounds__(HB) void head_fwd_kernel(FitDev f, PsiLbsView lv)
 {
     constexpr int NS = NH / C;              // fc2 outputs of this workgroup
@@ -368,7 +374,7 @@ __global__ __launch_bounds__(HB) void head_fwd_kernel(FitDev f, PsiLbsView lv)
         if (t < 22)
             for (int e = 0; e < 3; e++) pm[e] = f.pose_mean[t * 3 + e];
         if (t < 128) b3v = f.b3[t];
-        jp = psi_load_jump(lv.m);
+        if (LINKS_IN_HEAD) jp = psi_load_jump(lv.m);
     }
     __syncthreads();
     HSTOP(1);
@@ -492,7 +498,12 @@ __global__ __launch_bounds__(HB) void head_fwd_kernel(FitDev f, PsiLbsView lv)
     }
     __syncthreads();
     HSTOP(7);
-    psi_pose_fwd_chain(lv.m, spose, nullptr, f.B, b, sJ, jp, lv.feat, lv.R, lv.G, lv.A, nullptr);
+    if constexpr (LINKS_IN_HEAD) {
+        psi_pose_fwd_chain(lv.m, spose, nullptr, f.B, b, sJ, jp, lv.feat, lv.R, lv.G, lv.A, nullptr);
+    } else {
+        float R[9];
+        psi_pose_fwd_rot(lv.m, spose, b, t, lv.feat, lv.R, R);
+    }
     HSTOP(8);
     // what the skinning kernels and the backward read of the body-vector part
     psi_pose_fwd_rest_store(lv.m, sbetas, f.B, b, sJ, lv.feat, lv.Jl);
@@ -1681,7 +1692,7 @@ constexpr int GRAPH_UNROLL = PSI_GRAPH_UNROLL;
 // Every development switch of the engine, read ONCE per engine at psi_fit_create (README, "Environment knobs"); a value that is not
 // accepted leaves the default (0 in the int fields)
 struct FitKnobs {
-    bool split_scene, keep_verts, no_fused_bwd, sdf_linear, scene_skin_first, bwdv_mb, no_pen_skip, bwd_pf1;
+    bool split_scene, keep_verts, no_fused_bwd, sdf_linear, scene_skin_first, bwdv_mb, no_pen_skip, bwd_pf1, chain_in_head;
     int head_cluster, skin_nb, ska_nbody, search_lanes;
 #ifdef PSI_HEAD_STOPS
     int head_stop, tail_stop, skin_stop;      // tools/head_stops.sh
@@ -1698,6 +1709,7 @@ static FitKnobs fit_read_knobs()
     k.no_fused_bwd = is("PSI_FIT_FUSED_BWD", '0');
     k.no_pen_skip = is("PSI_FIT_PEN_SKIP", '0');
     k.bwd_pf1 = is("PSI_FIT_BWD_PF", '1');
+    k.chain_in_head = is("PSI_FIT_CHAIN_IN_HEAD", '1');
     k.sdf_linear = is("PSI_SDF_LINEAR", '1');
     k.scene_skin_first = is("PSI_SCENE_ORDER", '1');
     k.bwdv_mb = is("PSI_BWDV_MB", '1');
@@ -1726,10 +1738,12 @@ struct FitModes {
     int hc;                       // workgroups per body in the head / tail kernels (FitDev::hc)
     int gv_sps;                   // slots per body and class of the rows' maxima (FitDev::gv_sps)
     PsiStreamSplit split;         // column slices of the stream workgroups of fit_bwd_joint_kernel per row class, steps per slice (ska_plan.h)
+    PsiChainPlan chain;           // the pose stage's kinematic chain as a role of blend_fwd's launch (chain_plan.h); n_links_wg == 0: in the head kernel
 };
 
-// ncp3: the columns of the contact class (3 x n_c padded to whole 256-slot slices); mc: the model's counts at cfg->B (psi_lbs_counts)
-static FitModes fit_decide(const psi_fit_config *cfg, const FitKnobs &knobs, int J, int ncp3, const PsiLbsCounts &mc)
+// ncp3: the columns of the contact class (3 x n_c padded to whole 256-slot slices); mc: the model's counts at cfg->B (psi_lbs_counts);
+// cus: compute units of the device
+static FitModes fit_decide(const psi_fit_config *cfg, const FitKnobs &knobs, int J, int ncp3, const PsiLbsCounts &mc, int cus)
 {
     FitModes d = {};
     // one launch for both scene terms up to B = 128 (measured: 0.1695 -> 0.1611 ms per iteration at B = 32, 0.2342 -> 0.2258 at 64, 0.3957 ->
@@ -1768,6 +1782,9 @@ static FitModes fit_decide(const psi_fit_config *cfg, const FitKnobs &knobs, int
     // (compressed rows are read once per lane either way and measured 2-3 % slower with two bodies: 114.7 vs 112.3 us at B = 512)
     d.skin_nb = cfg->B > 128 && !mc.compressed_weights ? 2 : 1;
     if (knobs.skin_nb) d.skin_nb = knobs.skin_nb;
+    // the kinematic chain rides in blend_fwd's launch where that is free (the rule and its reasons: chain_plan.h; measured: DESIGN.md
+    // section 3, rule 12 — head_fwd 11.7 -> 10.4 us, blend_fwd unchanged); PSI_FIT_CHAIN_IN_HEAD=1 keeps it in the head kernel
+    d.chain = knobs.chain_in_head ? PsiChainPlan{0, 0} : psi_chain_plan(cfg->B, d.hc, mc.blend_wg, mc.blend_gy, cus);
     return d;
 }
 
@@ -1949,15 +1966,31 @@ struct psi_fit_engine {
 };
 
 // head / tail launches: grid = B bodies x hc workgroups per body (template instance per cluster width)
+template <bool LINKS_IN_HEAD>
 static void launch_head_fwd(const FitDev &f, const PsiLbsView &lv, hipStream_t st)
 {
     const dim3 g(f.B * f.hc), blk(HB);
     switch (f.hc) {
-    case 8: hipLaunchKernelGGL(head_fwd_kernel<8>, g, blk, 0, st, f, lv); break;
-    case 4: hipLaunchKernelGGL(head_fwd_kernel<4>, g, blk, 0, st, f, lv); break;
-    case 2: hipLaunchKernelGGL(head_fwd_kernel<2>, g, blk, 0, st, f, lv); break;
-    default: hipLaunchKernelGGL(head_fwd_kernel<1>, g, blk, 0, st, f, lv); break;
+    case 8: hipLaunchKernelGGL((head_fwd_kernel<8, LINKS_IN_HEAD>), g, blk, 0, st, f, lv); break;
+    case 4: hipLaunchKernelGGL((head_fwd_kernel<4, LINKS_IN_HEAD>), g, blk, 0, st, f, lv); break;
+    case 2: hipLaunchKernelGGL((head_fwd_kernel<2, LINKS_IN_HEAD>), g, blk, 0, st, f, lv); break;
+    default: hipLaunchKernelGGL((head_fwd_kernel<1, true>), g, blk, 0, st, f, lv); break;       // (no cluster: the rule keeps the chain here)
     }
+}
+
+// The head kernel and blend_fwd, as the pair the engine's mode selects: the head ending at the feature row + blend_fwd with the links role,
+// or the head with the whole pose stage + the plain blend_fwd
+static int fit_head_blend(psi_fit_engine *e, hipStream_t st)
+{
+    const FitDev &f = e->d;
+    const PsiChainPlan &cp = e->mode.chain;
+    const bool role = cp.n_links_wg > 0 && f.hc > 1;
+    if (role) launch_head_fwd<false>(f, e->lv, st);
+    else launch_head_fwd<true>(f, e->lv, st);
+    PSI_CHECK_LAUNCH("head_fwd_kernel");
+    psi_mark("head_fwd_kernel", st);
+    return role ? psi_lbs_blend_forward_links(e->lbs, f.B, e->lbs_ws, cp.n_links_wg, cp.bodies_per_wave, st)
+                : psi_lbs_blend_forward(e->lbs, f.B, e->lbs_ws, st);
 }
 
 template <bool ADAM>
@@ -2052,10 +2085,7 @@ static void fit_scene_dispatch(const psi_fit_engine *e, L &&launch)
 static int fit_forward(psi_fit_engine *e, float *stats, hipStream_t st, FitStats who)
 {
     FitDev &f = e->d;
-    launch_head_fwd(f, e->lv, st);
-    PSI_CHECK_LAUNCH("head_fwd_kernel");
-    psi_mark("head_fwd_kernel", st);
-    int rc = psi_lbs_blend_forward(e->lbs, f.B, e->lbs_ws, st);
+    int rc = fit_head_blend(e, st);
     if (rc) return rc;
     float gscale = f.w_contact / ((f.indep ? 1.0f : (float)f.B * (float)f.world) * (float)f.n_c);
     if (e->nn_index && e->mode.merged_scene) {
@@ -2241,7 +2271,10 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     f.scene = d_scene_verts;
     f.sdf = d_sdf;
     // ---- the decisions, and their copies where the kernels read them
-    const FitModes &mode = e->mode = fit_decide(cfg, knobs, J, f.ncp3, mc);
+    int dev = 0, cus = 0;
+    PSI_CHECK_HIP(hipGetDevice(&dev));
+    PSI_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const FitModes &mode = e->mode = fit_decide(cfg, knobs, J, f.ncp3, mc, cus);
     f.hc = mode.hc;
     f.gv_sps = mode.gv_sps;
     f.fused_bwd = mode.fused_bwd ? 1 : 0;
@@ -2252,6 +2285,8 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     f.stop_t = knobs.tail_stop;
     (void)hipMemcpyToSymbol(HIP_SYMBOL(psi_dbg_sstop), &knobs.skin_stop, sizeof(int));
     (void)hipMemcpyToSymbol(HIP_SYMBOL(psi_dbg_pstop), &f.stop_t, sizeof(int));
+    const int cstop = knobs.head_stop == 9;
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(psi_dbg_cstop), &cstop, sizeof(int));
 #endif
     const size_t B = (size_t)f.B;                                // (as size_t: the sizes below are products in bytes)
     // ---- host staging of constants
@@ -2654,6 +2689,11 @@ extern "C" int psi_fit_iterate_dp(psi_fit_engine *e, psi_dp_comm *comm, int n_it
     return eager(n_iter);
 }
 
+extern "C" int psi_fit_chain_mode(const psi_fit_engine *e)
+{
+    return e && e->mode.chain.n_links_wg > 0 && e->d.hc > 1 ? 1 : 0;
+}
+
 extern "C" int psi_fit_dp_mode(const psi_fit_engine *e)
 {
     if (!e || !e->dp_warm) return 0;
@@ -2669,9 +2709,7 @@ extern "C" int psi_fit_decode_forward(psi_fit_engine *e, const float *d_x75, con
     hipStream_t st = (hipStream_t)stream;
     PSI_CHECK_HIP(hipMemcpyAsync(f.x, d_x75, fit_x_bytes(f), hipMemcpyDeviceToDevice, st));
     PSI_CHECK_HIP(hipMemcpyAsync(f.cam, d_cam_ext, fit_cam_bytes(f), hipMemcpyDeviceToDevice, st));
-    launch_head_fwd(f, e->lv, st);
-    PSI_CHECK_LAUNCH("head_fwd_kernel");
-    int rc = psi_lbs_blend_forward(e->lbs, f.B, e->lbs_ws, st);
+    int rc = fit_head_blend(e, st);
     if (rc) return rc;
     hipLaunchKernelGGL(psi_skin_fwd_kernel<PsiSkinNoEpilogue>, dim3(f.nsdfblk, f.B), dim3(PSI_SKIN_BLK), 0, st, e->lv.m, e->lv.A,
                        e->lv.v_posed, f.transl, f.cam, f.B, d_verts, PsiSkinNoEpilogue());
@@ -2791,6 +2829,12 @@ extern "C" int psi_fit_copy_buffer(psi_fit_engine *e, const char *name, float *d
         {"gl", lv.gl, (long)f.B * lv.m.Npad},
         {"g_vp", lv.g_vp, (long)f.B * lv.m.Npad},
         {"v_posed", lv.v_posed, (long)f.B * lv.m.Npad},
+        // the pose stage's outputs: rotation rows, chain transforms, skinning transforms (with the PSI_A_TAIL zero rows behind the last
+        // body), and the feature rows as blend_fwd's fp16-pair operand (32-body tiles)
+        {"R", lv.R, (long)f.B * lv.m.J * 12},
+        {"G", lv.G, (long)f.B * lv.m.J * 12},
+        {"A", lv.A, (long)f.B * lv.m.J * 12 + PSI_A_TAIL * 12},
+        {"feat", lv.feat, (long)((f.B + 31) & ~31) * lv.m.Kpad},
     };
     for (const auto &b : more)
         if (!strcmp(name, b.name)) { src = b.src; cap = b.cap; }

@@ -30,6 +30,7 @@
 // The f32 MFMA (v_mfma_f32_16x16x4_f32) is bit-identical to an fmaf chain, so these are exact-f32 GEMMs.
 #include "psi_internal.h"
 #include "lbs_device.h"
+#include "chain_plan.h"
 #include <algorithm>
 #include <math.h>
 #include <stdlib.h>
@@ -132,11 +133,56 @@ __global__ __launch_bounds__(64) void pose_fwd_kernel(LbsDev m, const float *__r
 typedef _Float16 psi_h8 __attribute__((ext_vector_type(8)));
 typedef float psi_f16v __attribute__((ext_vector_type(16)));
 typedef unsigned int psi_u4 __attribute__((ext_vector_type(4)));
-template <int MTB, int NCH>
+//   LINKS (the fused fitting engine, psi_lbs_blend_forward_links): the launch carries a second ROLE behind the stream's workgroups.  Block
+// ids [0, n_stream) are the stream exactly as above; the n_links_wg <= 8 workgroups behind them run the kinematic chain of the pose stage
+// (psi_pose_fwd_links, lbs_device.h) — wave w of links workgroup g for the bodies (4 g + w) bpw .. + bpw - 1, one after the other, from the
+// R rows and rest joints the head kernel stored — and write G, A and A's tail rows.  Nothing in this launch reads them (the stream reads
+// `feat` only; their first reader is the skinning launch behind it), so the chain leaves the head kernel's critical path and runs in the
+// shadow of a launch that waits on HBM: the stream leaves 10 of the 256 CUs free, blocks are dealt round-robin over the XCDs, and the
+// rule of csrc/chain_plan.h only turns the role on when every workgroup of the launch is resident at once.  The role has LDS of its own per
+// wave and no workgroup barrier.
+template <bool LINKS> struct PsiLinksArgs {};
+template <> struct PsiLinksArgs<true> {
+    const float *Rs, *Jls;
+    float *Gs, *As;
+    int n_stream, bpw;
+};
+template <int MTB, int NCH, bool LINKS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void blend_fwd_h_kernel(LbsDev m, const float *__restrict__ feat, int B,
-                                                                                             float *__restrict__ v_posed)
+                                                                                             float *__restrict__ v_posed, PsiLinksArgs<LINKS> la)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if constexpr (LINKS) {
+        if ((int)blockIdx.x >= la.n_stream) {
+            __shared__ float sGw[4][PSI_JP][12];
+            __shared__ int sJmpw[4][PSI_NJUMP][PSI_JP];
+            const int b0 = psi_chain_first_body(PsiChainPlan{0, la.bpw}, (int)blockIdx.x - la.n_stream, w);
+            if (b0 >= B) return;
+            PsiJump jp;
+#pragma unroll
+            for (int r = 0; r < PSI_NJUMP; r++) {
+                jp.a[r] = (lane < m.J && r < m.njump) ? m.jump[r * PSI_JP + lane] : -1;
+                sJmpw[w][r][lane] = jp.a[r];
+            }
+            for (int b = b0; b < b0 + la.bpw && b < B; b++) {
+                float R[9];
+#pragma unroll
+                for (int e = 0; e < 9; e++) R[e] = 0.0f;
+                if (lane < m.J) {
+                    const psi_f4 *Rp = (const psi_f4 *)(la.Rs + ((size_t)b * m.J + lane) * 12);
+#pragma unroll
+                    for (int r = 0; r < 3; r++) {
+                        const psi_f4 rr = Rp[r];
+                        R[r * 3 + 0] = rr[0]; R[r * 3 + 1] = rr[1]; R[r * 3 + 2] = rr[2];
+                    }
+                }
+                psi_pose_fwd_links(m, nullptr, B, b, lane, 64, R, (const float (*)[3])(la.Jls + (size_t)b * m.J * 3), jp, sGw[w], sJmpw[w], la.Gs, la.As,
+                                   nullptr);
+                __builtin_amdgcn_wave_barrier();         // (the next body's first LDS writes stay behind this body's last reads)
+            }
+            return;
+        }
+    }
     // (body groups of one tile quad on ONE XCD, so that the quad comes from HBM once and from L2 for the other groups, was measured SLOWER — 199 vs 181 us
     // at B = 512, 52.1 vs 49.4 at 128: at large batches the launch reads more feature rows (every wave all of them: 1 GB at B = 512) than matrix)
     const int tq = blockIdx.x, y = blockIdx.y;
@@ -595,16 +641,33 @@ extern "C" size_t psi_lbs_workspace_floats(const psi_lbs_model *m, int B)
     return ws_layout(m->d, B).total;
 }
 
-static int lbs_launch_blend(const LbsDev &m, const WsLayout &L, int B, float *ws, hipStream_t st)
+// the stream's grid: workgroups of four 32-column waves x body groups
+static inline dim3 lbs_blend_grid(const LbsDev &m, int B)
 {
     const int bgroups = B > 32 ? psi_cdiv(B, 64) : 1;           // 32-body tiles per wave: 1, or 2 (every further group re-streams the matrix)
-    const dim3 grid(psi_cdiv(m.Npad / 32, 4), bgroups);
+    return dim3(psi_cdiv(m.Npad / 32, 4), bgroups);
+}
+
+// n_links_wg > 0: the launch with the links role (blend_fwd_h_kernel<.., true>) — n_links_wg workgroups behind the stream's, bpw bodies per wave
+static int lbs_launch_blend(const LbsDev &m, const WsLayout &L, int B, float *ws, hipStream_t st, int n_links_wg = 0, int bpw = 0)
+{
+    dim3 grid = lbs_blend_grid(m, B);
     static const bool loop_form = getenv("PSI_BLEND_FWD_LOOP") && getenv("PSI_BLEND_FWD_LOOP")[0] == '1';      // dev A/B: the chunk loop as a loop
-#define PSI_LAUNCH_BLEND(MT_, NCH_) hipLaunchKernelGGL((blend_fwd_h_kernel<MT_, NCH_>), grid, dim3(256), 0, st, m, ws + L.feat, B, ws + L.v_posed)
     const bool k8 = m.Kpad == 512 && !loop_form;              // SMPL-X: 506 feature rows -> 8 chunks
-    if (B > 32) { if (k8) PSI_LAUNCH_BLEND(2, 8); else PSI_LAUNCH_BLEND(2, 0); }
-    else { if (k8) PSI_LAUNCH_BLEND(1, 8); else PSI_LAUNCH_BLEND(1, 0); }
+    if (n_links_wg > 0) {
+        PSI_REQUIRE(grid.y == 1 && bpw >= 1 && (long)n_links_wg * 4 * bpw >= B, "the links role needs a one-row grid and a wave for every body");
+        const PsiLinksArgs<true> la = {ws + L.R, ws + L.Jl, ws + L.G, ws + L.A, (int)grid.x, bpw};
+        grid.x += n_links_wg;
+#define PSI_LAUNCH_BLEND_LINKS(MT_, NCH_) hipLaunchKernelGGL((blend_fwd_h_kernel<MT_, NCH_, true>), grid, dim3(256), 0, st, m, ws + L.feat, B, ws + L.v_posed, la)
+        if (B > 32) { if (k8) PSI_LAUNCH_BLEND_LINKS(2, 8); else PSI_LAUNCH_BLEND_LINKS(2, 0); }
+        else { if (k8) PSI_LAUNCH_BLEND_LINKS(1, 8); else PSI_LAUNCH_BLEND_LINKS(1, 0); }
+#undef PSI_LAUNCH_BLEND_LINKS
+    } else {
+#define PSI_LAUNCH_BLEND(MT_, NCH_) hipLaunchKernelGGL((blend_fwd_h_kernel<MT_, NCH_>), grid, dim3(256), 0, st, m, ws + L.feat, B, ws + L.v_posed, PsiLinksArgs<false>{})
+        if (B > 32) { if (k8) PSI_LAUNCH_BLEND(2, 8); else PSI_LAUNCH_BLEND(2, 0); }
+        else { if (k8) PSI_LAUNCH_BLEND(1, 8); else PSI_LAUNCH_BLEND(1, 0); }
 #undef PSI_LAUNCH_BLEND
+    }
     PSI_CHECK_LAUNCH("blend_fwd_kernel");
     psi_mark("blend_fwd_kernel", st);
     return 0;
@@ -657,7 +720,8 @@ int psi_lbs_counts(const psi_lbs_model *mdl, int B, PsiLbsCounts *out)
     PSI_REQUIRE(mdl && out && B > 0, "bad arguments");
     const LbsDev &m = mdl->d;
     const WsLayout L = ws_layout(m, B);
-    *out = PsiLbsCounts{L.nsv, L.nsn, m.Kpad, m.Npad, m.Wc != nullptr};
+    const dim3 bg = lbs_blend_grid(m, B);
+    *out = PsiLbsCounts{L.nsv, L.nsn, m.Kpad, m.Npad, m.Wc != nullptr, (int)bg.x, (int)bg.y};
     return 0;
 }
 
@@ -665,6 +729,15 @@ int psi_lbs_blend_forward(const psi_lbs_model *mdl, int B, float *ws, hipStream_
 {
     const LbsDev &m = mdl->d;
     return lbs_launch_blend(m, ws_layout(m, B), B, ws, st);
+}
+
+// ... with the links role behind the stream (blend_fwd_h_kernel): the chain stage of bodies whose R rows, rest joints and feature rows a
+// head kernel has stored; G, A and A's tail rows are complete when the launch ends.  n_links_wg / bodies_per_wave: csrc/chain_plan.h
+int psi_lbs_blend_forward_links(const psi_lbs_model *mdl, int B, float *ws, int n_links_wg, int bodies_per_wave, hipStream_t st)
+{
+    PSI_REQUIRE(mdl && ws && B > 0 && n_links_wg > 0 && bodies_per_wave > 0, "bad arguments");
+    const LbsDev &m = mdl->d;
+    return lbs_launch_blend(m, ws_layout(m, B), B, ws, st, n_links_wg, bodies_per_wave);
 }
 
 // the stages of psi_lbs_forward in front of its skinning kernel, for a caller that skins with an epilogue of its own (eval.hip): A and

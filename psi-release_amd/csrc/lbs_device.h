@@ -8,6 +8,9 @@
 #ifndef PSI_SSTOP
 #define PSI_SSTOP(k)
 #endif
+#ifndef PSI_CSTOP
+#define PSI_CSTOP()           // dev: leave the head kernel between the two halves of psi_pose_fwd_chain (fit.hip, -DPSI_HEAD_STOPS: stop 9)
+#endif
 #ifndef PSI_PSTOP
 #define PSI_PSTOP(k)          // dev: end the program inside the pose-backward stage at point k (fit.hip, -DPSI_HEAD_STOPS)
 #endif
@@ -52,19 +55,27 @@ struct PsiLbsView {
 __device__ __forceinline__ void psi_rodrigues(const float *aa, float *R)
 {
     // lbs.py:177-191: angle = ||aa + 1e-8||, dir = aa / angle, R = I + sin K + (1 - cos) K K
+    //   R[0] = 1 + c1 (-(ry ry + rz rz))   R[1] = s (-rz) + c1 (rx ry)   R[2] = s ry + c1 (rx rz)
+    //   R[3] = s rz + c1 (rx ry)           R[4] = 1 + c1 (-(rx rx + rz rz))   R[5] = s (-rx) + c1 (ry rz)
+    //   R[6] = s (-ry) + c1 (rx rz)        R[7] = s rx + c1 (ry rz)      R[8] = 1 + c1 (-(rx rx + ry ry))
+    // with every fused multiply-add spelled out (and nothing else fused): the function is inlined into kernels of different shapes whose
+    // copies must round identically (see psi_pose_fwd_links), in the association its single form had always been compiled to — the
+    // entries are NOT alike: R[1], R[5], R[6] and R[0] keep separately rounded products.
+#pragma clang fp contract(off)
     float x = aa[0] + 1e-8f, y = aa[1] + 1e-8f, z = aa[2] + 1e-8f;
-    float angle = sqrtf(x * x + y * y + z * z);
+    float angle = sqrtf(__builtin_fmaf(y, y, x * x) + z * z);
     float rx = aa[0] / angle, ry = aa[1] / angle, rz = aa[2] / angle;
     float s = sinf(angle), c1 = 1.0f - cosf(angle);
-    R[0] = 1.0f + c1 * (-(ry * ry + rz * rz));
-    R[1] = s * (-rz) + c1 * (rx * ry);
-    R[2] = s * ry + c1 * (rx * rz);
-    R[3] = s * rz + c1 * (rx * ry);
-    R[4] = 1.0f + c1 * (-(rx * rx + rz * rz));
-    R[5] = s * (-rx) + c1 * (ry * rz);
-    R[6] = s * (-ry) + c1 * (rx * rz);
-    R[7] = s * rx + c1 * (ry * rz);
-    R[8] = 1.0f + c1 * (-(rx * rx + ry * ry));
+    const float cxy = c1 * (rx * ry), cxz = c1 * (rx * rz), cyz = c1 * (ry * rz);
+    R[0] = 1.0f - c1 * __builtin_fmaf(ry, ry, rz * rz);
+    R[1] = cxy - rz * s;
+    R[2] = __builtin_fmaf(ry, s, cxz);
+    R[3] = __builtin_fmaf(rz, s, cxy);
+    R[4] = __builtin_fmaf(-(rx * rx + rz * rz), c1, 1.0f);
+    R[5] = cyz - rx * s;
+    R[6] = cxz - ry * s;
+    R[7] = __builtin_fmaf(rx, s, cyz);
+    R[8] = __builtin_fmaf(-__builtin_fmaf(ry, ry, rx * rx), c1, 1.0f);
 }
 
 // Pose-forward stage of body b, executed by a whole workgroup, in two parts so that a caller can run the first (which only needs
@@ -115,8 +126,16 @@ __device__ __forceinline__ void psi_pose_fwd_rest_store(const LbsDev &m, const f
 // when part 1 ran in the same workgroup just before).
 // The chain G_j = G_parent(j) [R_j | J_j - J_parent] is evaluated by POINTER JUMPING instead of a sweep over the tree levels: every
 // joint starts with its local transform and in round r multiplies it from the left by the current value of its 2^r-th ancestor, so
-// ceil(log2(depth)) = 4 rounds for SMPL-X's 11 levels instead of 10 (same products, associated differently).  All joints live in wave 0
+// ceil(log2(depth)) = 4 rounds for SMPL-X's 11 levels instead of 10 (same products, associated differently).  All joints live in ONE wave
 // (J <= 64) and a wave's LDS operations execute in order: reads of a round precede its writes, no workgroup barrier in the loop.
+//
+// Part 2 is itself two functions, cut at the feature row (psi_pose_fwd_chain = the two back to back, one workgroup barrier between them):
+//   psi_pose_fwd_rot    Rodrigues, the R rows, the pose entries of the feature row — everything blend_fwd reads of this stage;
+//   psi_pose_fwd_links  the kinematic chain and the G / A rows, whose first readers are the skinning kernels and the tail kernel.  It is
+//                       written for ONE wave and one body (lane j = joint j), with the wave's LDS supplied by the caller, so that a caller
+//                       that has the rotations and the rest joints in memory (R rows, Jl: the same fp32 values) can run it anywhere behind
+//                       the stores of the first function: the fused fitting engine runs it in workgroups of their own beside blend_fwd's
+//                       stream (lbs.hip: blend_fwd_h_kernel<.., LINKS = true>), off the iteration's critical path.
 struct PsiJump { int a[PSI_NJUMP]; };      // this thread's row of m.jump (a[0] = parent), loaded by the caller ahead of time
 
 __device__ __forceinline__ PsiJump psi_load_jump(const LbsDev &m)
@@ -127,20 +146,10 @@ __device__ __forceinline__ PsiJump psi_load_jump(const LbsDev &m)
     return jp;
 }
 
-__device__ __forceinline__ void psi_pose_fwd_chain(const LbsDev &m, const float *pose_b, const float *__restrict__ transl, int B, int b,
-                                                   const float (*sJ)[3], const PsiJump &jp, float *__restrict__ feat,
-                                                   float *__restrict__ Rs, float *__restrict__ Gs, float *__restrict__ As,
-                                                   float *__restrict__ joints)
+// thread j < m.J: R = Rodrigues(pose_b[3 j ..]) -> registers, Rs, feature row
+__device__ __forceinline__ void psi_pose_fwd_rot(const LbsDev &m, const float *pose_b, int b, int j, float *feat, float *Rs, float (&R)[9])
 {
-    const int j = threadIdx.x;
-    __shared__ float sG[PSI_JP][12];
-    __shared__ int sJmp[PSI_NJUMP][PSI_JP];          // the jump rows, so that the round loop below stays a (compact) loop
-    const bool act = j < m.J;
-    float R[9], Jl[3] = {0, 0, 0};
-    if (j < PSI_JP)
-#pragma unroll
-        for (int r = 0; r < PSI_NJUMP; r++) sJmp[r][j] = jp.a[r];
-    if (act) {
+    if (j < m.J) {
         psi_rodrigues(pose_b + j * 3, R);
         psi_f4 *Ro = (psi_f4 *)(Rs + ((size_t)b * m.J + j) * 12);      // rows padded to 4: three 16-byte stores
         Ro[0] = psi_f4{R[0], R[1], R[2], 0.0f};
@@ -152,14 +161,29 @@ __device__ __forceinline__ void psi_pose_fwd_chain(const LbsDev &m, const float 
                 psi_feat_store(m, feat, b, k, R[e] - ((e == 0 || e == 4 || e == 8) ? 1.0f : 0.0f));
             }
     }
-    __syncthreads();
+}
+
+// Lane j of the calling wave = joint j (threads j >= 64 of a wider caller only take part in the tail rows, nthr = the caller's thread
+// count).  R: the joint's rotation (psi_pose_fwd_rot's registers, or reloaded from its Rs row); J3: the body's rest joints [J][3], the
+// caller's LDS array or the body's Jl rows in memory; sG / sJmp: LDS of this wave alone, sJmp[r][j] = jp.a[r] written by the lane itself.
+__device__ __forceinline__ void psi_pose_fwd_links(const LbsDev &m, const float *transl, int B, int b, int j, int nthr, const float (&R)[9],
+                                                   const float (*J3)[3], const PsiJump &jp, float (*sG)[12], int (*sJmp)[PSI_JP], float *Gs,
+                                                   float *As, float *joints)
+{
+    // The products below are spelled out, fused multiply-add for fused multiply-add, and not left to the compiler's contraction: the
+    // function is inlined into kernels of different shapes (one workgroup per body, a wave per body beside a stream), whose copies must
+    // round identically.  The association of each entry is the one the single-copy form of this code had always been compiled to (the
+    // rows of a product are NOT alike: the third row of the rotation part and the translation column keep separately rounded products).
+#pragma clang fp contract(off)
+    const bool act = j < m.J;
+    float Jl[3] = {0, 0, 0};
     float G[12];   // row-major 3x4: [R | t]
     if (act) {
         const int par = jp.a[0];
-        for (int c = 0; c < 3; c++) Jl[c] = sJ[j][c];
+        for (int c = 0; c < 3; c++) Jl[c] = J3[j][c];
         for (int r = 0; r < 3; r++) {
             for (int c = 0; c < 3; c++) G[r * 4 + c] = R[r * 3 + c];
-            G[r * 4 + 3] = par >= 0 ? Jl[r] - sJ[par][r] : Jl[r];
+            G[r * 4 + 3] = par >= 0 ? Jl[r] - J3[par][r] : Jl[r];
         }
         for (int e = 0; e < 12; e++) sG[j][e] = G[e];
     }
@@ -172,10 +196,13 @@ __device__ __forceinline__ void psi_pose_fwd_chain(const LbsDev &m, const float 
             for (int e = 0; e < 12; e++) P[e] = sG[a][e];
         __builtin_amdgcn_wave_barrier();
         if (act && a >= 0) {
-            float N[12];
+            float N[12];       // N = P G: N[q][c] = P[q][0] G[0][c] + P[q][1] G[1][c] + P[q][2] G[2][c] (+ P[q][3] for c = 3)
             for (int q = 0; q < 3; q++) {
-                for (int c = 0; c < 3; c++) N[q * 4 + c] = P[q * 4 + 0] * G[0 * 4 + c] + P[q * 4 + 1] * G[1 * 4 + c] + P[q * 4 + 2] * G[2 * 4 + c];
-                N[q * 4 + 3] = P[q * 4 + 0] * G[3] + P[q * 4 + 1] * G[7] + P[q * 4 + 2] * G[11] + P[q * 4 + 3];
+                const float p0 = P[q * 4 + 0], p1 = P[q * 4 + 1], p2 = P[q * 4 + 2];
+                for (int c = 0; c < 2; c++) N[q * 4 + c] = __builtin_fmaf(p2, G[8 + c], __builtin_fmaf(p0, G[c], p1 * G[4 + c]));
+                N[q * 4 + 2] = p2 * G[10] + (q < 2 ? __builtin_fmaf(p0, G[2], p1 * G[6]) : p0 * G[2] + p1 * G[6]);
+                N[q * 4 + 3] = P[q * 4 + 3] + (q < 2 ? __builtin_fmaf(p2, G[11], __builtin_fmaf(p1, G[7], p0 * G[3]))
+                                                    : p2 * G[11] + __builtin_fmaf(p0, G[3], p1 * G[7]));
             }
             for (int e = 0; e < 12; e++) { G[e] = N[e]; sG[j][e] = N[e]; }
         }
@@ -186,7 +213,7 @@ __device__ __forceinline__ void psi_pose_fwd_chain(const LbsDev &m, const float 
             Go[r] = psi_f4{G[r * 4 + 0], G[r * 4 + 1], G[r * 4 + 2], G[r * 4 + 3]};
             // lbs.py:258-260: A = G - pad(G [J;0])
             Ao[r] = psi_f4{G[r * 4 + 0], G[r * 4 + 1], G[r * 4 + 2],
-                           G[r * 4 + 3] - (G[r * 4 + 0] * Jl[0] + G[r * 4 + 1] * Jl[1] + G[r * 4 + 2] * Jl[2])};
+                           G[r * 4 + 3] - (G[r * 4 + 2] * Jl[2] + __builtin_fmaf(G[r * 4 + 0], Jl[0], G[r * 4 + 1] * Jl[1]))};
         }
         if (joints)
             for (int r = 0; r < 3; r++) joints[((size_t)b * m.J + j) * 3 + r] = G[r * 4 + 3] + (transl ? transl[(size_t)b * 3 + r] : 0.0f);
@@ -195,7 +222,26 @@ __device__ __forceinline__ void psi_pose_fwd_chain(const LbsDev &m, const float 
     // of a group still reaches up to 2 rows past the padding: behind the last body's block those are PSI_A_TAIL rows that belong to the
     // array (ws_layout), so the load stays inside it, and are written here on every forward.
     if (b == B - 1)
-        for (int q = j; q < PSI_A_TAIL * 3; q += blockDim.x) ((psi_f4 *)(As + (size_t)B * m.J * 12))[q] = psi_f4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int q = j; q < PSI_A_TAIL * 3; q += nthr) ((psi_f4 *)(As + (size_t)B * m.J * 12))[q] = psi_f4{0.0f, 0.0f, 0.0f, 0.0f};
+}
+
+// (whole workgroup; all joints live in wave 0)
+__device__ __forceinline__ void psi_pose_fwd_chain(const LbsDev &m, const float *pose_b, const float *__restrict__ transl, int B, int b,
+                                                   const float (*sJ)[3], const PsiJump &jp, float *__restrict__ feat,
+                                                   float *__restrict__ Rs, float *__restrict__ Gs, float *__restrict__ As,
+                                                   float *__restrict__ joints)
+{
+    const int j = threadIdx.x;
+    __shared__ float sG[PSI_JP][12];
+    __shared__ int sJmp[PSI_NJUMP][PSI_JP];          // the jump rows, so that the round loop stays a (compact) loop
+    float R[9];
+    if (j < PSI_JP)
+#pragma unroll
+        for (int r = 0; r < PSI_NJUMP; r++) sJmp[r][j] = jp.a[r];
+    psi_pose_fwd_rot(m, pose_b, b, j, feat, Rs, R);
+    PSI_CSTOP();
+    __syncthreads();
+    psi_pose_fwd_links(m, transl, B, b, j, blockDim.x, R, sJ, jp, sG, sJmp, Gs, As, joints);
 }
 
 

@@ -60,9 +60,13 @@ int psi_lbs_view(const psi_lbs_model *mdl, int B, float *ws, PsiLbsView *out);
 // what the engine sizes its own buffers with before it has a workspace: the slice counts of the workspace layout at batch size B (256-vertex
 // slices of skin_bwd_A, column slices of blend_bwd), the padded feature and column counts, and whether the skinning weights are stored
 // as compressed rows (LbsDev::Wc)
-struct PsiLbsCounts { int nsv, nsn, Kpad, Npad; bool compressed_weights; };
+// ... and blend_fwd's grid: stream workgroups per row x body groups (gridDim.x, gridDim.y)
+struct PsiLbsCounts { int nsv, nsn, Kpad, Npad; bool compressed_weights; int blend_wg, blend_gy; };
 int psi_lbs_counts(const psi_lbs_model *mdl, int B, PsiLbsCounts *out);
 int psi_lbs_blend_forward(const psi_lbs_model *mdl, int B, float *ws, hipStream_t st);          // v_posed = v_t + feat @ dirs
+// ... with the pose stage's kinematic chain (G, A from the stored R rows and rest joints) as a second role of the same launch: n_links_wg
+// workgroups behind the stream's, bodies_per_wave bodies per wave (chain_plan.h)
+int psi_lbs_blend_forward_links(const psi_lbs_model *mdl, int B, float *ws, int n_links_wg, int bodies_per_wave, hipStream_t st);
 // pose_fwd + blend_fwd of psi_lbs_forward for given betas / pose: A and v_posed in the workspace, no vertices (eval.hip skins with its own epilogue)
 int psi_lbs_pose_blend_forward(const psi_lbs_model *mdl, const float *betas, const float *pose, const float *transl, int B, float *ws,
                                hipStream_t st);

@@ -542,6 +542,10 @@ class FusedEngine:
         inside, 2 eager launches from C (psi_fit_dp_mode)."""
         return int(hip.lib().psi_fit_dp_mode(self.handle))
 
+    def chain_mode(self):
+        """1: the kinematic chain of the pose stage runs as a role of blend_fwd's launch, 0: in the head kernel (psi_fit_chain_mode)."""
+        return int(hip.lib().psi_fit_chain_mode(self.handle))
+
     def watchdog(self):
         """Data-parallel runs: wait for the engine's stream with a bound (PSI_DP_WATCHDOG_S seconds, default 60) before a blocking read —
         a collective that can never complete (a rank that died, ranks that issued different numbers of collectives) becomes an error

@@ -99,6 +99,7 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p]),
     'psi_contact_slot_chain': (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     'psi_fit_dp_mode': (c_int, [c_void_p]),
+    'psi_fit_chain_mode': (c_int, [c_void_p]),
     'psi_stream_wait': (c_int, [c_void_p, c_int]),
     'psi_dp_unique_id': (c_int, [c_void_p]),
     'psi_dp_comm_create': (c_int, [c_void_p, c_void_p, c_int, c_int]),
