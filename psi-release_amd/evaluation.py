@@ -217,31 +217,24 @@ def _as_numpy(x, dtype):
 
 
 class _FacesHandleOwner:
-    """Owns the one topology ``faces`` [F,3] of the bodies of a batch and the library handle made of it for the vertex count last seen.
-    A subclass says how its handle is made (``_create(V)``) and freed (``_destroy(handle)``)."""
+    """Owns the one topology ``faces`` [F,3] of the bodies of a batch and holds the library handle (a ``hip.Handle``) made of it for the
+    vertex count last seen.  A subclass says how its handle is made (``_create(V)``).  The handle frees itself when its last holder lets
+    go: this object only ever drops its reference, so an autograd graph that still needs the handle keeps it."""
 
     def __init__(self, faces, device):
         self.device = torch.device(device)
         self.faces = _as_numpy(faces, np.int32)
-        self._handle, self._V = None, None
+        self._handle = None
 
     def _handle_for(self, V):
-        if self._handle is None or self._V != V:
+        if not self._handle or self._handle.V != V:
             self.close()
             with torch.cuda.device(self.device):
-                self._handle, self._V = self._create(V), V
+                self._handle = self._create(V)
         return self._handle
 
     def close(self):
-        if getattr(self, '_handle', None):
-            self._destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._handle = None
 
     @staticmethod
     def _group(group, verts):
@@ -258,8 +251,6 @@ class BodyOverlap(_FacesHandleOwner):
 
     def _create(self, V):
         return ops.body_overlap_create(self.faces, V)
-
-    _destroy = staticmethod(ops.body_overlap_destroy)
 
     @torch.no_grad()
     def counts(self, verts, group=None):
@@ -348,8 +339,6 @@ class SurfaceCrossings(_FacesHandleOwner):
 
     def _create(self, V):
         return ops.surface_crossings_create(self.faces, V, self._order_verts, self._face_part, self._part_skip)
-
-    _destroy = staticmethod(ops.surface_crossings_destroy)
 
     @torch.no_grad()
     def crossings(self, verts, group=None, self_pairs=True, between=True, mode='pruned'):

@@ -239,6 +239,31 @@ def ptr(t):
     return t.data_ptr()
 
 
+class Handle(ctypes.c_void_p):
+    """A library handle that owns itself: a ``c_void_p`` (so it goes wherever one goes: an argument, a ``byref`` out-parameter) that knows
+    the symbol that frees it and carries the integers its family asks for, filled in once by the ``*_create`` that made it: ``V`` vertices
+    per body, ``F`` faces, ``n_chunks`` face chunks.  Whoever needs the handle holds this object; ``close()``, or the last holder letting
+    go, frees it, once.  ``destroy`` None: a view of a handle someone else owns, never freed from here."""
+
+    def __init__(self, destroy):
+        super().__init__()
+        self.destroy, self.V, self.F, self.n_chunks = destroy, 0, 0, 0
+
+    def close(self):
+        if self.value:
+            try:
+                if self.destroy:
+                    getattr(lib(), self.destroy)(self)
+            finally:
+                self.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def stream():
     return torch.cuda.current_stream().cuda_stream
 

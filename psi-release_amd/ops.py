@@ -8,7 +8,9 @@ Inputs must live on the GPU; there is no CPU path (hip.ptr raises).
 """
 from __future__ import annotations
 
-import contextlib
+import ctypes
+import math
+import numbers
 from typing import NamedTuple
 
 import torch
@@ -1378,8 +1380,7 @@ def _batch_args(verts, group, name, then=None, max_B=None):
     """The checks of ``verts`` [B,V,3] fp32 and ``group`` [B] int32 or None, in the order that decides which exception a doubly-wrong call
     raises: verts, the caller's own argument checks (``then``), group, B <= ``max_B``, the device pointers (``PsiHipError`` for a CPU or
     non-contiguous tensor), B >= 1.  Returns B, V, dev, pv, pg."""
-    if not torch.is_tensor(verts) or verts.dtype != torch.float32 or verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
-        raise ValueError('expected verts [B,V,3] float32')
+    _check_batch_verts(verts)
     if then is not None:
         then()
     B, V = int(verts.shape[0]), int(verts.shape[1])
@@ -1394,15 +1395,45 @@ def _batch_args(verts, group, name, then=None, max_B=None):
     return B, V, dev, pv, pg
 
 
-@contextlib.contextmanager
-def _handle_or_made(given, own, create, destroy):
-    """``given`` itself when it is a handle; when ``own``, the handle ``create(given)`` makes of it, freed when the block ends."""
-    handle = create(given) if own else given
-    try:
-        yield handle
-    finally:
-        if own:
-            destroy(handle)
+def _check_batch_verts(verts):
+    if not torch.is_tensor(verts) or verts.dtype != torch.float32 or verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
+        raise ValueError('expected verts [B,V,3] float32')
+
+
+def _check_real(x, ok, message, *shown):
+    """``float(x)`` of a finite real number ``x``, not a bool, for which ``ok(x)`` holds; otherwise ``ValueError(message % shown)``."""
+    if isinstance(x, bool) or not isinstance(x, numbers.Real) or not math.isfinite(x) or not ok(x):
+        raise ValueError(message % shown)
+    return float(x)
+
+
+def _chunks_of(n, chunk):
+    """ceil(n / chunk) of a count or of a tensor of counts"""
+    return (n + (chunk - 1)) // chunk
+
+
+def _with_info(handle, kind):
+    """Fills in the integers of the ``hip.Handle`` of ``kind`` ('body_overlap' or 'surface_crossings') through psi_<kind>_info."""
+    info = (ctypes.c_int32 * 4)()               # body_overlap writes two of them
+    hip.check(getattr(hip.lib(), 'psi_%s_info' % kind)(handle, info), 'psi_%s_info' % kind)
+    handle.V, handle.F, handle.n_chunks = int(info[0]), int(info[1]), int(info[2])
+    return handle
+
+
+def _handle_of(handle_or_faces, V, kind):
+    """The ``hip.Handle`` of ``kind`` an operator works with: the one ``body_overlap_create`` / ``surface_crossings_create`` makes of faces
+    (it lives as long as somebody holds it), or the handle given, which must have been made for ``V`` vertices per body.  Any other
+    ``c_void_p`` is a handle its caller owns: it is viewed, with its integers read from the library, and never freed from here."""
+    if not isinstance(handle_or_faces, ctypes.c_void_p):
+        return (body_overlap_create if kind == 'body_overlap' else surface_crossings_create)(handle_or_faces, V)
+    handle = handle_or_faces
+    if not isinstance(handle, hip.Handle):
+        handle = hip.Handle(None)
+        handle.value = handle_or_faces.value
+        _with_info(handle, kind)
+    if handle.V != V:
+        raise ValueError('the handle was made for %d vertices per body, verts has %d' % (handle.V, V))
+    return handle
 
 
 def _unpack_bits(mask, n):
@@ -1420,22 +1451,20 @@ BODY_OVERLAP_MAX_CANDIDATES = 2 ** 31 - 1
 
 def body_overlap_create(faces, V):
     """faces [F,3] int32 (a tensor on any device, or an array), the one topology of every body, wound outwards; V vertices per body.  Returns
-    the ``psi_body_overlap`` handle (free it with ``body_overlap_destroy``).  ``ValueError`` for a wrong dtype or shape; ``PsiHipError``
-    for what the library refuses: F < 1, a face index outside [0, V)."""
-    import ctypes
+    the ``psi_body_overlap`` handle, a ``hip.Handle``: freed by ``body_overlap_destroy`` or when its last holder lets go of it.
+    ``ValueError`` for a wrong dtype or shape; ``PsiHipError`` for what the library refuses: F < 1, a face index outside [0, V)."""
     import numpy as np
     f = _host_array(faces, np.int32, 'faces [F,3]')
     if f.ndim != 2 or f.shape[1] != 3:
         raise ValueError('expected faces [F,3] int32')
-    h = ctypes.c_void_p()
+    h = hip.Handle('psi_body_overlap_destroy')
     hip.check(hip.lib().psi_body_overlap_create(ctypes.byref(h), f.ctypes.data_as(ctypes.c_void_p), int(V), int(f.shape[0])),
               'psi_body_overlap_create')
-    return h
+    return _with_info(h, 'body_overlap')
 
 
 def body_overlap_destroy(handle):
-    if handle:
-        hip.lib().psi_body_overlap_destroy(handle)
+    handle.close()
 
 
 def body_overlap(verts, faces_handle_or_tensor, group=None, return_candidates=False):
@@ -1450,47 +1479,41 @@ def body_overlap(verts, faces_handle_or_tensor, group=None, return_candidates=Fa
     candidates, the number of 256-candidate chunks and the non-finite flag: the call's only host synchronisation.  ``ValueError`` for
     wrong dtypes, shapes or devices, for a non-finite vertex (it names the first such body) and for more than 2^31 - 1 candidates;
     ``PsiHipError`` for what the library refuses, CPU tensors included."""
-    import ctypes
     B, V, dev, pv, pg = _batch_args(verts, group, 'body_overlap')
     L = hip.lib()
     with torch.cuda.device(dev):
-        with _handle_or_made(faces_handle_or_tensor, torch.is_tensor(faces_handle_or_tensor), lambda f: body_overlap_create(f, V),
-                             body_overlap_destroy) as handle:
-            info = (ctypes.c_int32 * 2)()
-            hip.check(L.psi_body_overlap_info(handle, info), 'psi_body_overlap_info')
-            if info[0] != V:
-                raise ValueError('the handle was made for %d vertices per body, verts has %d' % (info[0], V))
-            F = int(info[1])
-            st = hip.stream()
-            boxes = torch.empty(B, 6, dtype=torch.float32, device=dev)
-            bad = torch.empty(1, dtype=torch.int32, device=dev)
-            pair_count = torch.empty(B * B, dtype=torch.int32, device=dev)
-            hip.check(L.psi_body_overlap_boxes(handle, pv, B, hip.ptr(boxes), hip.ptr(bad), st), 'psi_body_overlap_boxes')
-            hip.check(L.psi_body_overlap_count(handle, pv, pg, B, hip.ptr(boxes), hip.ptr(pair_count), st), 'psi_body_overlap_count')
-            pair_chunks = (pair_count + (BODY_OVERLAP_CHUNK - 1)) // BODY_OVERLAP_CHUNK
-            cand_inc = torch.cumsum(pair_count, 0, dtype=torch.int64)
-            chunk_inc = torch.cumsum(pair_chunks, 0, dtype=torch.int64)
-            n_cand, n_chunks, first_bad = torch.stack([cand_inc[-1], chunk_inc[-1], bad[0].to(torch.int64)]).cpu().tolist()
-            if first_bad < B:
-                raise ValueError('body %d has a non-finite vertex coordinate' % first_bad)
-            if n_cand > BODY_OVERLAP_MAX_CANDIDATES:
-                raise ValueError('the batch has %d candidates: more than 2^31 - 1' % n_cand)
-            counts = torch.zeros(B, B, dtype=torch.int32, device=dev)
-            words = (V + 31) // 32
-            mask = torch.zeros(B, words, dtype=torch.int32, device=dev)
-            cand = torch.empty(n_cand, 3, dtype=torch.int32, device=dev)
-            w = torch.empty(n_cand, dtype=torch.float32, device=dev)
-            if n_cand > 0:                      # never an empty grid
-                cand_off, chunk_off = cand_inc - pair_count, chunk_inc - pair_chunks
-                chunks = torch.empty(n_chunks, 4, dtype=torch.int32, device=dev)
-                hip.check(L.psi_body_overlap_emit(handle, pv, pg, B, hip.ptr(boxes), hip.ptr(pair_count), hip.ptr(cand_off), hip.ptr(chunk_off),
-                                                  n_cand, n_chunks, hip.ptr(cand), hip.ptr(chunks), st), 'psi_body_overlap_emit')
-                ws_bytes = int(L.psi_body_overlap_workspace_bytes(n_cand, F))
-                ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
-                hip.check(L.psi_body_overlap_wind(handle, pv, B, hip.ptr(cand), n_cand, hip.ptr(chunks), n_chunks, hip.ptr(ws), ws_bytes, st),
-                          'psi_body_overlap_wind')
-                hip.check(L.psi_body_overlap_decide(handle, B, hip.ptr(cand), n_cand, hip.ptr(ws), ws_bytes, hip.ptr(w), hip.ptr(counts),
-                                                    hip.ptr(mask), st), 'psi_body_overlap_decide')
+        handle = _handle_of(faces_handle_or_tensor, V, 'body_overlap')
+        F = handle.F
+        st = hip.stream()
+        boxes = torch.empty(B, 6, dtype=torch.float32, device=dev)
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        pair_count = torch.empty(B * B, dtype=torch.int32, device=dev)
+        hip.check(L.psi_body_overlap_boxes(handle, pv, B, hip.ptr(boxes), hip.ptr(bad), st), 'psi_body_overlap_boxes')
+        hip.check(L.psi_body_overlap_count(handle, pv, pg, B, hip.ptr(boxes), hip.ptr(pair_count), st), 'psi_body_overlap_count')
+        pair_chunks = _chunks_of(pair_count, BODY_OVERLAP_CHUNK)
+        cand_inc = torch.cumsum(pair_count, 0, dtype=torch.int64)
+        chunk_inc = torch.cumsum(pair_chunks, 0, dtype=torch.int64)
+        n_cand, n_chunks, first_bad = torch.stack([cand_inc[-1], chunk_inc[-1], bad[0].to(torch.int64)]).cpu().tolist()
+        if first_bad < B:
+            raise ValueError('body %d has a non-finite vertex coordinate' % first_bad)
+        if n_cand > BODY_OVERLAP_MAX_CANDIDATES:
+            raise ValueError('the batch has %d candidates: more than 2^31 - 1' % n_cand)
+        counts = torch.zeros(B, B, dtype=torch.int32, device=dev)
+        words = (V + 31) // 32
+        mask = torch.zeros(B, words, dtype=torch.int32, device=dev)
+        cand = torch.empty(n_cand, 3, dtype=torch.int32, device=dev)
+        w = torch.empty(n_cand, dtype=torch.float32, device=dev)
+        if n_cand > 0:                      # never an empty grid
+            cand_off, chunk_off = cand_inc - pair_count, chunk_inc - pair_chunks
+            chunks = torch.empty(n_chunks, 4, dtype=torch.int32, device=dev)
+            hip.check(L.psi_body_overlap_emit(handle, pv, pg, B, hip.ptr(boxes), hip.ptr(pair_count), hip.ptr(cand_off), hip.ptr(chunk_off),
+                                              n_cand, n_chunks, hip.ptr(cand), hip.ptr(chunks), st), 'psi_body_overlap_emit')
+            ws_bytes = int(L.psi_body_overlap_workspace_bytes(n_cand, F))
+            ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+            hip.check(L.psi_body_overlap_wind(handle, pv, B, hip.ptr(cand), n_cand, hip.ptr(chunks), n_chunks, hip.ptr(ws), ws_bytes, st),
+                      'psi_body_overlap_wind')
+            hip.check(L.psi_body_overlap_decide(handle, B, hip.ptr(cand), n_cand, hip.ptr(ws), ws_bytes, hip.ptr(w), hip.ptr(counts),
+                                                hip.ptr(mask), st), 'psi_body_overlap_decide')
         inside = _unpack_bits(mask, V)
     if return_candidates:
         return counts, inside, cand, w
@@ -1524,23 +1547,10 @@ class PenetrationResult(NamedTuple):
     inside: torch.Tensor       # [B,V] bool: as body_overlap returns them
 
 
-def _overlap_handle(handle_or_faces, V):
-    return _handle_or_made(handle_or_faces, torch.is_tensor(handle_or_faces), lambda f: body_overlap_create(f, V), body_overlap_destroy)
-
-
-def _overlap_handle_F(handle, V):
-    import ctypes
-    info = (ctypes.c_int32 * 2)()
-    hip.check(hip.lib().psi_body_overlap_info(handle, info), 'psi_body_overlap_info')
-    if info[0] != V:
-        raise ValueError('the handle was made for %d vertices per body, verts has %d' % (info[0], V))
-    return int(info[1])
-
-
 def _depth_chunk_table(pair_count, B, n_chunks):
     """The chunk table of psi_body_overlap_emit, [n_chunks,4] int32 = (first triple, triples, i, j), for an ascending triple list with
     ``pair_count`` [B*B] int64 triples per ordered pair: plumbing, no host synchronisation."""
-    pair_chunks = (pair_count + (BODY_OVERLAP_CHUNK - 1)) // BODY_OVERLAP_CHUNK
+    pair_chunks = _chunks_of(pair_count, BODY_OVERLAP_CHUNK)
     chunk_inc, trip_inc = torch.cumsum(pair_chunks, 0), torch.cumsum(pair_count, 0)
     c = torch.arange(n_chunks, dtype=torch.int64, device=pair_count.device)
     p = torch.searchsorted(chunk_inc, c, right=True).clamp_(max=B * B - 1)
@@ -1550,27 +1560,25 @@ def _depth_chunk_table(pair_count, B, n_chunks):
     return torch.stack([first, cnt, p // B, p % B], 1).to(torch.int32).contiguous()
 
 
-def _depth_rows(handle, F, verts, trip, pair_count, n_chunks):
+def _new_depth_rows(n, dev):
+    return DepthRows(torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                     torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, 3, dtype=torch.float32, device=dev),
+                     torch.empty(n, 3, dtype=torch.float32, device=dev))
+
+
+def _depth_rows(handle, verts, trip, pair_count, n_chunks):
     """nearest and finish for the ascending triples ``trip`` [n,3], n >= 1."""
     L, st, dev = hip.lib(), hip.stream(), verts.device
     B, n = int(verts.shape[0]), int(trip.shape[0])
     chunks = _depth_chunk_table(pair_count, B, n_chunks)
-    ws_bytes = int(L.psi_body_depth_workspace_bytes(n, F))
+    ws_bytes = int(L.psi_body_depth_workspace_bytes(n, handle.F))
     ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
-    rows = DepthRows(torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
-                     torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, 3, dtype=torch.float32, device=dev),
-                     torch.empty(n, 3, dtype=torch.float32, device=dev))
+    rows = _new_depth_rows(n, dev)
     hip.check(L.psi_body_depth_nearest(handle, hip.ptr(verts), B, hip.ptr(trip), n, hip.ptr(chunks), n_chunks, hip.ptr(ws), ws_bytes, st),
               'psi_body_depth_nearest')
     hip.check(L.psi_body_depth_finish(handle, hip.ptr(verts), B, hip.ptr(trip), n, hip.ptr(ws), ws_bytes, hip.ptr(rows.face),
                                       hip.ptr(rows.region), hip.ptr(rows.depth), hip.ptr(rows.r), hip.ptr(rows.bary), st), 'psi_body_depth_finish')
     return rows
-
-
-def _empty_depth_rows(dev):
-    return DepthRows(torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
-                     torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, 3, dtype=torch.float32, device=dev),
-                     torch.empty(0, 3, dtype=torch.float32, device=dev))
 
 
 def body_depth(verts, handle_or_faces, triples):
@@ -1594,21 +1602,20 @@ def body_depth(verts, handle_or_faces, triples):
     B, V, dev, pv, _ = _batch_args(verts, None, 'body_depth', then=check_triples)
     n = int(triples.shape[0])
     with torch.cuda.device(dev), torch.no_grad():
-        with _overlap_handle(handle_or_faces, V) as handle:
-            F = _overlap_handle_F(handle, V)
-            if n == 0:
-                return _empty_depth_rows(dev)
-            trip = triples.contiguous()
-            t = trip.to(torch.int64)
-            i, j, v = t[:, 0], t[:, 1], t[:, 2]
-            key = (i * B + j) * V + v
-            bad = ((i < 0) | (i >= B) | (j < 0) | (j >= B) | (v < 0) | (v >= V) | (i == j)).any() | (key[1:] <= key[:-1]).any()
-            pair_count = torch.zeros(B * B, dtype=torch.int64, device=dev).scatter_add_(0, (i * B + j).clamp(0, B * B - 1), torch.ones_like(i))
-            n_chunks = ((pair_count + (BODY_OVERLAP_CHUNK - 1)) // BODY_OVERLAP_CHUNK).sum()
-            is_bad, n_chunks = torch.stack([bad.to(torch.int64), n_chunks]).cpu().tolist()
-            if is_bad:
-                raise ValueError('triples must be strictly ascending (i, j, v) rows with i != j, i and j in [0, %d) and v in [0, %d)' % (B, V))
-            return _depth_rows(handle, F, verts, trip, pair_count, n_chunks)
+        handle = _handle_of(handle_or_faces, V, 'body_overlap')
+        if n == 0:
+            return _new_depth_rows(0, dev)
+        trip = triples.contiguous()
+        t = trip.to(torch.int64)
+        i, j, v = t[:, 0], t[:, 1], t[:, 2]
+        key = (i * B + j) * V + v
+        bad = ((i < 0) | (i >= B) | (j < 0) | (j >= B) | (v < 0) | (v >= V) | (i == j)).any() | (key[1:] <= key[:-1]).any()
+        pair_count = torch.zeros(B * B, dtype=torch.int64, device=dev).scatter_add_(0, (i * B + j).clamp(0, B * B - 1), torch.ones_like(i))
+        n_chunks = _chunks_of(pair_count, BODY_OVERLAP_CHUNK).sum()
+        is_bad, n_chunks = torch.stack([bad.to(torch.int64), n_chunks]).cpu().tolist()
+        if is_bad:
+            raise ValueError('triples must be strictly ascending (i, j, v) rows with i != j, i and j in [0, %d) and v in [0, %d)' % (B, V))
+        return _depth_rows(handle, verts, trip, pair_count, n_chunks)
 
 
 def body_penetration(verts, handle_or_faces, group=None):
@@ -1621,30 +1628,29 @@ def body_penetration(verts, handle_or_faces, group=None):
     B, V, dev, pv, pg = _batch_args(verts, group, 'body_penetration')
     L = hip.lib()
     with torch.cuda.device(dev), torch.no_grad():
-        with _overlap_handle(handle_or_faces, V) as handle:
-            F = _overlap_handle_F(handle, V)
-            counts, inside, cand, w = body_overlap(verts, handle, group=group, return_candidates=True)
-            max_depth = torch.zeros(B, B, dtype=torch.float32, device=dev)
-            sum_depth, sum_sq = torch.zeros(B, B, dtype=torch.float64, device=dev), torch.zeros(B, B, dtype=torch.float64, device=dev)
-            depth_of = torch.zeros(B, V, dtype=torch.float32, device=dev)
-            loss = torch.zeros(2, B, dtype=torch.float32, device=dev)
-            n_in = n_chunks = 0
-            if cand.shape[0] > 0:
-                pair_count = counts.reshape(-1).to(torch.int64)
-                n_in, n_chunks = torch.stack([pair_count.sum(), ((pair_count + (BODY_OVERLAP_CHUNK - 1)) // BODY_OVERLAP_CHUNK).sum()]).cpu().tolist()
-            if n_in == 0:
-                return PenetrationResult(cand[:0], _empty_depth_rows(dev), max_depth, sum_depth, sum_sq, depth_of, loss, counts, inside)
-            if n_in > BODY_DEPTH_MAX_TRIPLES:
-                raise ValueError('the batch has %d inside triples: more than 2^29 - 1' % n_in)
-            keep = torch.sort((~(w > 0.5)).to(torch.uint8), stable=True).indices[:n_in]       # the triples with w > 0.5, in their order
-            trip = cand[keep].contiguous()
-            rows = _depth_rows(handle, F, verts, trip, pair_count, n_chunks)
-            row_start = torch.zeros(B + 1, dtype=torch.int64, device=dev)
-            row_start[1:] = torch.cumsum(pair_count.view(B, B).sum(1), 0)
-            hip.check(L.psi_body_depth_pairs(handle, B, hip.ptr(trip), n_in, hip.ptr(rows.depth), hip.ptr(row_start), hip.ptr(max_depth),
-                                             hip.ptr(sum_depth), hip.ptr(sum_sq), hip.ptr(depth_of), hip.ptr(loss), hip.stream()),
-                      'psi_body_depth_pairs')
-            return PenetrationResult(trip, rows, max_depth, sum_depth, sum_sq, depth_of, loss, counts, inside)
+        handle = _handle_of(handle_or_faces, V, 'body_overlap')
+        counts, inside, cand, w = body_overlap(verts, handle, group=group, return_candidates=True)
+        max_depth = torch.zeros(B, B, dtype=torch.float32, device=dev)
+        sum_depth, sum_sq = torch.zeros(B, B, dtype=torch.float64, device=dev), torch.zeros(B, B, dtype=torch.float64, device=dev)
+        depth_of = torch.zeros(B, V, dtype=torch.float32, device=dev)
+        loss = torch.zeros(2, B, dtype=torch.float32, device=dev)
+        n_in = n_chunks = 0
+        if cand.shape[0] > 0:
+            pair_count = counts.reshape(-1).to(torch.int64)
+            n_in, n_chunks = torch.stack([pair_count.sum(), _chunks_of(pair_count, BODY_OVERLAP_CHUNK).sum()]).cpu().tolist()
+        if n_in == 0:
+            return PenetrationResult(cand[:0], _new_depth_rows(0, dev), max_depth, sum_depth, sum_sq, depth_of, loss, counts, inside)
+        if n_in > BODY_DEPTH_MAX_TRIPLES:
+            raise ValueError('the batch has %d inside triples: more than 2^29 - 1' % n_in)
+        keep = torch.sort((~(w > 0.5)).to(torch.uint8), stable=True).indices[:n_in]       # the triples with w > 0.5, in their order
+        trip = cand[keep].contiguous()
+        rows = _depth_rows(handle, verts, trip, pair_count, n_chunks)
+        row_start = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        row_start[1:] = torch.cumsum(pair_count.view(B, B).sum(1), 0)
+        hip.check(L.psi_body_depth_pairs(handle, B, hip.ptr(trip), n_in, hip.ptr(rows.depth), hip.ptr(row_start), hip.ptr(max_depth),
+                                         hip.ptr(sum_depth), hip.ptr(sum_sq), hip.ptr(depth_of), hip.ptr(loss), hip.stream()),
+                  'psi_body_depth_pairs')
+        return PenetrationResult(trip, rows, max_depth, sum_depth, sum_sq, depth_of, loss, counts, inside)
 
 
 def segment_sum3(targets_sorted, rows, n_out, order=None):
@@ -1668,6 +1674,13 @@ def segment_sum3(targets_sorted, rows, n_out, order=None):
     return out
 
 
+def _sum_rows_by_target(targets, grows, B, V):
+    """G [B,V,3] fp32 of the gradient rows ``grows`` [m,3] and their target vertices ``targets`` [m] int64: a stable ``torch.sort`` of the
+    targets, then the rows of one target added in list order (``segment_sum3``)."""
+    srt = torch.sort(targets, stable=True)
+    return segment_sum3(srt.values, grows, B * V, order=srt.indices).view(B, V, 3)
+
+
 def body_penetration_grad(verts_shape, handle, triples, rows, g, penalty='depth'):
     """G [B,V,3] fp32: the gradient of sum_i g[i] loss[i] with respect to the vertices, for the inside ``triples`` and their ``rows``
     (``PenetrationResult``): grad_rows, a stable ``torch.sort`` of the targets, the segment sum.  No read-back."""
@@ -1686,28 +1699,14 @@ def body_penetration_grad(verts_shape, handle, triples, rows, g, penalty='depth'
         hip.check(hip.lib().psi_body_depth_grad_rows(handle, B, hip.ptr(triples), n, hip.ptr(rows.face), hip.ptr(rows.depth), hip.ptr(rows.r),
                                                      hip.ptr(rows.bary), hip.ptr(g), BODY_DEPTH_PENALTIES[penalty], hip.ptr(targets),
                                                      hip.ptr(grows), hip.stream()), 'psi_body_depth_grad_rows')
-        srt = torch.sort(targets, stable=True)
-        return segment_sum3(srt.values, grows, B * V, order=srt.indices).view(B, V, 3)
-
-
-class _OwnedOverlapHandle:
-    """A handle made for one call of ``body_penetration_loss`` from a faces tensor: it lives as long as the graph that needs it."""
-
-    def __init__(self, faces, V):
-        self.handle = body_overlap_create(faces, V)
-
-    def __del__(self):
-        try:
-            body_overlap_destroy(self.handle)
-        except Exception:
-            pass
+        return _sum_rows_by_target(targets, grows, B, V)
 
 
 class _BodyPenetrationLoss(Function):
     @staticmethod
-    def forward(ctx, verts, handle, owner, group, penalty):
+    def forward(ctx, verts, handle, group, penalty):
         res = body_penetration(verts, handle, group=group)
-        ctx.handle, ctx.owner, ctx.penalty, ctx.shape = handle, owner, penalty, tuple(verts.shape)
+        ctx.handle, ctx.penalty, ctx.shape = handle, penalty, tuple(verts.shape)        # the graph holds the handle it will need
         ctx.save_for_backward(res.triples, *res.rows)
         return res.loss[BODY_DEPTH_PENALTIES[penalty]].clone()
 
@@ -1715,7 +1714,7 @@ class _BodyPenetrationLoss(Function):
     def backward(ctx, g):
         trip, *rows = ctx.saved_tensors
         G = body_penetration_grad(ctx.shape, ctx.handle, trip, DepthRows(*rows), g.to(torch.float32).contiguous(), ctx.penalty)
-        return G, None, None, None, None
+        return G, None, None, None
 
 
 def body_penetration_loss(verts, handle_or_faces, group=None, penalty='depth'):
@@ -1728,11 +1727,9 @@ def body_penetration_loss(verts, handle_or_faces, group=None, penalty='depth'):
     zero gradient and no launch.  ``ValueError`` for an unknown penalty and for what ``body_overlap`` refuses."""
     if penalty not in BODY_DEPTH_PENALTIES:
         raise ValueError('penalty is one of %s, got %r' % (sorted(BODY_DEPTH_PENALTIES), penalty))
-    if not torch.is_tensor(verts) or verts.dtype != torch.float32 or verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
-        raise ValueError('expected verts [B,V,3] float32')
+    _check_batch_verts(verts)
     hip.ptr(verts)                              # a CPU or non-contiguous tensor is refused before a handle is made
-    owner = _OwnedOverlapHandle(handle_or_faces, int(verts.shape[1])) if torch.is_tensor(handle_or_faces) else None
-    return _BodyPenetrationLoss.apply(verts, owner.handle if owner else handle_or_faces, owner, group, penalty)
+    return _BodyPenetrationLoss.apply(verts, _handle_of(handle_or_faces, int(verts.shape[1]), 'body_overlap'), group, penalty)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1759,9 +1756,9 @@ def surface_crossings_create(faces, V, order_verts=None, face_part=None, part_sk
     fp32 or None: a representative pose (``v_template``); with it the faces are sorted once along a Morton curve of their centroids into the
     chunks of 256 the search prunes by (results are in the caller's face indices either way).  ``face_part`` [F] int32 and ``part_skip``
     [P,P] uint8 (symmetric; non-zero: self pairs of faces of these two parts are ignored) or both None.  Returns the
-    ``psi_surface_crossings`` handle (free it with ``surface_crossings_destroy``).  ``ValueError`` for wrong dtypes or shapes, F < 1,
-    F >= 2^21, V < 1, a face index outside [0, V), a part outside [0, P), an asymmetric matrix."""
-    import ctypes
+    ``psi_surface_crossings`` handle, a ``hip.Handle``: freed by ``surface_crossings_destroy`` or when its last holder lets go of it.
+    ``ValueError`` for wrong dtypes or shapes, F < 1, F >= 2^21, V < 1, a face index outside [0, V), a part outside [0, P), an
+    asymmetric matrix."""
     import numpy as np
     f = _host_array(faces, np.int32, 'faces [F,3]')
     if f.ndim != 2 or f.shape[1] != 3:
@@ -1789,15 +1786,14 @@ def surface_crossings_create(faces, V, order_verts=None, face_part=None, part_sk
         if not np.array_equal(ps != 0, (ps != 0).T):
             raise ValueError('surface_crossings_create: part_skip is not symmetric')
     as_p = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-    h = ctypes.c_void_p()
+    h = hip.Handle('psi_surface_crossings_destroy')
     hip.check(hip.lib().psi_surface_crossings_create(ctypes.byref(h), as_p(f), V, F, as_p(ov), as_p(fp), as_p(ps), P),
               'psi_surface_crossings_create')
-    return h
+    return _with_info(h, 'surface_crossings')
 
 
 def surface_crossings_destroy(handle):
-    if handle:
-        hip.lib().psi_surface_crossings_destroy(handle)
+    handle.close()
 
 
 def surface_crossings(verts, handle_or_faces, group=None, self_pairs=True, between=True, mode='pruned', return_stats=False):
@@ -1813,7 +1809,6 @@ def surface_crossings(verts, handle_or_faces, group=None, self_pairs=True, betwe
     plumbing.  Two read-backs: the number of tiles with the non-finite flag, and the number of pairs.  ``ValueError`` for wrong dtypes,
     shapes or devices, a non-finite vertex (it names the first such body), B > 46340, (B F)^2 >= 2^63 and more than 2^31 - 1 tiles or
     pairs; ``PsiHipError`` for what the library refuses, CPU tensors included."""
-    import ctypes
     def check_mode():
         if mode not in ('pruned', 'brute'):
             raise ValueError("mode is 'pruned' or 'brute', got %r" % (mode,))
@@ -1822,65 +1817,60 @@ def surface_crossings(verts, handle_or_faces, group=None, self_pairs=True, betwe
     flags = (1 if self_pairs else 0) | (2 if between else 0) | (4 if mode == 'brute' else 0)
     i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        with _handle_or_made(handle_or_faces, not isinstance(handle_or_faces, ctypes.c_void_p), lambda f: surface_crossings_create(f, V),
-                             surface_crossings_destroy) as handle:
-            info = (ctypes.c_int32 * 4)()
-            hip.check(L.psi_surface_crossings_info(handle, info), 'psi_surface_crossings_info')
-            if info[0] != V:
-                raise ValueError('the handle was made for %d vertices per body, verts has %d' % (info[0], V))
-            F, nC = int(info[1]), int(info[2])
-            if (B * F) ** 2 >= 2 ** 63:
-                raise ValueError('surface_crossings: (B F)^2 = (%d x %d)^2 does not fit the int64 pair key' % (B, F))
-            st = hip.stream()
-            words = (F + 31) // 32
-            counts = torch.zeros(B, B, **i32)
-            contour = torch.zeros(B, B, dtype=torch.float64, device=dev)
-            mask = torch.zeros(B, words, **i32)
-            irregular = torch.zeros(1, **i32)
-            pairs, events = torch.empty(0, 4, **i32), torch.empty(0, **i32)
-            length = torch.empty(0, dtype=torch.float32, device=dev)
-            n_tiles = n_pairs = 0
-            if flags & 3:
-                chunk_boxes = torch.empty(B, nC, 6, dtype=torch.float32, device=dev)
-                body_boxes = torch.empty(B, 6, dtype=torch.float32, device=dev)
-                bad = torch.empty(1, **i32)
-                job_tiles = torch.empty(B * B, **i32)
-                hip.check(L.psi_surface_crossings_boxes(handle, pv, B, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(bad), st),
-                          'psi_surface_crossings_boxes')
-                hip.check(L.psi_surface_crossings_tiles(handle, pg, B, flags, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles),
-                                                        None, 0, None, st), 'psi_surface_crossings_tiles')
-                job_inc = torch.cumsum(job_tiles, 0, dtype=torch.int64)
-                n_tiles, first_bad = torch.stack([job_inc[-1], bad[0].to(torch.int64)]).cpu().tolist()          # read-back 1
-                if first_bad < B:
-                    raise ValueError('body %d has a non-finite vertex coordinate' % first_bad)
-                if n_tiles > SURFACE_CROSSINGS_MAX:
-                    raise ValueError('the batch has %d tiles: more than 2^31 - 1' % n_tiles)
-            if n_tiles > 0:                     # never an empty grid
-                tiles = torch.empty(n_tiles, 4, **i32)
-                job_off = job_inc - job_tiles
-                hip.check(L.psi_surface_crossings_tiles(handle, pg, B, flags, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles),
-                                                        hip.ptr(job_off), n_tiles, hip.ptr(tiles), st), 'psi_surface_crossings_tiles')
-                tile_hits = torch.empty(n_tiles, **i32)
-                hip.check(L.psi_surface_crossings_test(handle, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), None, 0, None, None, None, st),
-                          'psi_surface_crossings_test')
-                tile_inc = torch.cumsum(tile_hits, 0, dtype=torch.int64)
-                n_pairs = int(tile_inc[-1].item())                                                            # read-back 2
-                if n_pairs > SURFACE_CROSSINGS_MAX:
-                    raise ValueError('the batch has %d crossing pairs: more than 2^31 - 1' % n_pairs)
-            if n_pairs > 0:
-                tile_off = tile_inc - tile_hits
-                keys = torch.empty(n_pairs, **i64)
-                ev_raw = torch.empty(n_pairs, **i32)
-                len_raw = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-                hip.check(L.psi_surface_crossings_test(handle, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), hip.ptr(tile_off), n_pairs,
-                                                       hip.ptr(keys), hip.ptr(ev_raw), hip.ptr(len_raw), st), 'psi_surface_crossings_test')
-                keys_sorted, order = torch.sort(keys)
-                row_start = torch.searchsorted(keys_sorted, torch.arange(B + 1, **i64) * (F * B * F)).contiguous()
-                pairs, events = torch.empty(n_pairs, 4, **i32), torch.empty(n_pairs, **i32)
-                length = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-                hip.check(L.psi_surface_crossings_finish(handle, B, hip.ptr(keys_sorted), hip.ptr(order), hip.ptr(ev_raw), hip.ptr(len_raw), n_pairs,
-                                                         hip.ptr(row_start), hip.ptr(pairs), hip.ptr(events), hip.ptr(length), hip.ptr(counts),
-                                                         hip.ptr(contour), hip.ptr(mask), hip.ptr(irregular), st), 'psi_surface_crossings_finish')
+        handle = _handle_of(handle_or_faces, V, 'surface_crossings')
+        F, nC = handle.F, handle.n_chunks
+        if (B * F) ** 2 >= 2 ** 63:
+            raise ValueError('surface_crossings: (B F)^2 = (%d x %d)^2 does not fit the int64 pair key' % (B, F))
+        st = hip.stream()
+        words = (F + 31) // 32
+        counts = torch.zeros(B, B, **i32)
+        contour = torch.zeros(B, B, dtype=torch.float64, device=dev)
+        mask = torch.zeros(B, words, **i32)
+        irregular = torch.zeros(1, **i32)
+        pairs, events = torch.empty(0, 4, **i32), torch.empty(0, **i32)
+        length = torch.empty(0, dtype=torch.float32, device=dev)
+        n_tiles = n_pairs = 0
+        if flags & 3:
+            chunk_boxes = torch.empty(B, nC, 6, dtype=torch.float32, device=dev)
+            body_boxes = torch.empty(B, 6, dtype=torch.float32, device=dev)
+            bad = torch.empty(1, **i32)
+            job_tiles = torch.empty(B * B, **i32)
+            hip.check(L.psi_surface_crossings_boxes(handle, pv, B, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(bad), st),
+                      'psi_surface_crossings_boxes')
+            hip.check(L.psi_surface_crossings_tiles(handle, pg, B, flags, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles),
+                                                    None, 0, None, st), 'psi_surface_crossings_tiles')
+            job_inc = torch.cumsum(job_tiles, 0, dtype=torch.int64)
+            n_tiles, first_bad = torch.stack([job_inc[-1], bad[0].to(torch.int64)]).cpu().tolist()          # read-back 1
+            if first_bad < B:
+                raise ValueError('body %d has a non-finite vertex coordinate' % first_bad)
+            if n_tiles > SURFACE_CROSSINGS_MAX:
+                raise ValueError('the batch has %d tiles: more than 2^31 - 1' % n_tiles)
+        if n_tiles > 0:                     # never an empty grid
+            tiles = torch.empty(n_tiles, 4, **i32)
+            job_off = job_inc - job_tiles
+            hip.check(L.psi_surface_crossings_tiles(handle, pg, B, flags, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles),
+                                                    hip.ptr(job_off), n_tiles, hip.ptr(tiles), st), 'psi_surface_crossings_tiles')
+            tile_hits = torch.empty(n_tiles, **i32)
+            hip.check(L.psi_surface_crossings_test(handle, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), None, 0, None, None, None, st),
+                      'psi_surface_crossings_test')
+            tile_inc = torch.cumsum(tile_hits, 0, dtype=torch.int64)
+            n_pairs = int(tile_inc[-1].item())                                                            # read-back 2
+            if n_pairs > SURFACE_CROSSINGS_MAX:
+                raise ValueError('the batch has %d crossing pairs: more than 2^31 - 1' % n_pairs)
+        if n_pairs > 0:
+            tile_off = tile_inc - tile_hits
+            keys = torch.empty(n_pairs, **i64)
+            ev_raw = torch.empty(n_pairs, **i32)
+            len_raw = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+            hip.check(L.psi_surface_crossings_test(handle, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), hip.ptr(tile_off), n_pairs,
+                                                   hip.ptr(keys), hip.ptr(ev_raw), hip.ptr(len_raw), st), 'psi_surface_crossings_test')
+            keys_sorted, order = torch.sort(keys)
+            row_start = torch.searchsorted(keys_sorted, torch.arange(B + 1, **i64) * (F * B * F)).contiguous()
+            pairs, events = torch.empty(n_pairs, 4, **i32), torch.empty(n_pairs, **i32)
+            length = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+            hip.check(L.psi_surface_crossings_finish(handle, B, hip.ptr(keys_sorted), hip.ptr(order), hip.ptr(ev_raw), hip.ptr(len_raw), n_pairs,
+                                                     hip.ptr(row_start), hip.ptr(pairs), hip.ptr(events), hip.ptr(length), hip.ptr(counts),
+                                                     hip.ptr(contour), hip.ptr(mask), hip.ptr(irregular), st), 'psi_surface_crossings_finish')
         face_hit = _unpack_bits(mask, F)
     res = CrossingsResult(pairs, events, length, counts, contour, face_hit, irregular[0])
     if not return_stats:
@@ -1914,39 +1904,20 @@ class CrossingFieldResult(NamedTuple):
 
 
 def _check_sigma(sigma):
-    import math
-    import numbers
-    if isinstance(sigma, bool) or not isinstance(sigma, numbers.Real) or not math.isfinite(sigma) or not 0.0 < sigma <= 0.5:
-        raise ValueError('sigma is a finite number in (0, 0.5], got %r' % (sigma,))
-    return float(sigma)
+    return _check_real(sigma, lambda s: 0.0 < s <= 0.5, 'sigma is a finite number in (0, 0.5], got %r', sigma)
 
 
-def _crossings_handle(handle_or_faces, V):
-    import ctypes
-    return _handle_or_made(handle_or_faces, not isinstance(handle_or_faces, ctypes.c_void_p), lambda f: surface_crossings_create(f, V),
-                           surface_crossings_destroy)
-
-
-def _crossings_handle_F(handle, V):
-    import ctypes
-    info = (ctypes.c_int32 * 4)()
-    hip.check(hip.lib().psi_surface_crossings_info(handle, info), 'psi_surface_crossings_info')
-    if info[0] != V:
-        raise ValueError('the handle was made for %d vertices per body, verts has %d' % (info[0], V))
-    return int(info[1])
+def _new_field_rows(n, dev):
+    return FieldRows(torch.empty(n, 2, dtype=torch.float32, device=dev), torch.empty(n, 2, 3, dtype=torch.float32, device=dev))
 
 
 def _field_rows(handle, verts, pairs, sigma):
     """eval for the pairs [n,4], n >= 1"""
-    B, n, dev = int(verts.shape[0]), int(pairs.shape[0]), verts.device
-    rows = FieldRows(torch.empty(n, 2, dtype=torch.float32, device=dev), torch.empty(n, 2, 3, dtype=torch.float32, device=dev))
+    B, n = int(verts.shape[0]), int(pairs.shape[0])
+    rows = _new_field_rows(n, verts.device)
     hip.check(hip.lib().psi_crossing_field_eval(handle, hip.ptr(verts), B, hip.ptr(pairs), n, sigma, hip.ptr(rows.psi), hip.ptr(rows.energy),
                                                 hip.stream()), 'psi_crossing_field_eval')
     return rows
-
-
-def _empty_field_rows(dev):
-    return FieldRows(torch.empty(0, 2, dtype=torch.float32, device=dev), torch.empty(0, 2, 3, dtype=torch.float32, device=dev))
 
 
 def _check_pairs_arg(pairs, verts):
@@ -1975,25 +1946,25 @@ def crossing_field(verts, handle_or_faces, pairs, sigma=CROSSING_FIELD_SIGMA):
     B, V, dev, pv, _ = _batch_args(verts, None, 'crossing_field', then=check, max_B=SURFACE_CROSSINGS_MAX_B)
     n = int(pairs.shape[0])
     with torch.cuda.device(dev), torch.no_grad():
-        with _crossings_handle(handle_or_faces, V) as handle:
-            F = _crossings_handle_F(handle, V)
-            if n == 0:
-                return _empty_field_rows(dev)
-            prs = pairs.contiguous()
-            p = prs.to(torch.int64)
-            i, s, j, t = p[:, 0], p[:, 1], p[:, 2], p[:, 3]
-            bad = ((i < 0) | (i >= B) | (j < i) | (j >= B) | (s < 0) | (s >= F) | (t < 0) | (t >= F)).any()
-            if (B * F) ** 2 < 2 ** 63:
-                key = ((i * F + s) * B + j) * F + t
-                bad = bad | (key[1:] <= key[:-1]).any()
-            else:                               # the key does not fit one int64: compare the rows lexicographically
-                d = p[1:] - p[:-1]
-                first = (d != 0).to(torch.int8).argmax(1)
-                bad = bad | ((d == 0).all(1) | (d.gather(1, first[:, None])[:, 0] < 0)).any()
-            if bool(bad.item()):                                                                            # the read-back
-                raise ValueError('pairs must be strictly ascending (i, s, j, t) rows with i <= j, i and j in [0, %d) and s and t in [0, %d)'
-                                 % (B, F))
-            return _field_rows(handle, verts, prs, float(sigma))
+        handle = _handle_of(handle_or_faces, V, 'surface_crossings')
+        F = handle.F
+        if n == 0:
+            return _new_field_rows(0, dev)
+        prs = pairs.contiguous()
+        p = prs.to(torch.int64)
+        i, s, j, t = p[:, 0], p[:, 1], p[:, 2], p[:, 3]
+        bad = ((i < 0) | (i >= B) | (j < i) | (j >= B) | (s < 0) | (s >= F) | (t < 0) | (t >= F)).any()
+        if (B * F) ** 2 < 2 ** 63:
+            key = ((i * F + s) * B + j) * F + t
+            bad = bad | (key[1:] <= key[:-1]).any()
+        else:                               # the key does not fit one int64: compare the rows lexicographically
+            d = p[1:] - p[:-1]
+            first = (d != 0).to(torch.int8).argmax(1)
+            bad = bad | ((d == 0).all(1) | (d.gather(1, first[:, None])[:, 0] < 0)).any()
+        if bool(bad.item()):                                                                            # the read-back
+            raise ValueError('pairs must be strictly ascending (i, s, j, t) rows with i <= j, i and j in [0, %d) and s and t in [0, %d)'
+                             % (B, F))
+        return _field_rows(handle, verts, prs, float(sigma))
 
 
 def _field_aggregates(handle, B, pairs, energy):
@@ -2021,17 +1992,17 @@ def crossing_penetration(verts, handle_or_faces, group=None, self_pairs=True, be
     _check_sigma(sigma)
     B, V, dev, pv, pg = _batch_args(verts, group, 'crossing_penetration', max_B=SURFACE_CROSSINGS_MAX_B)
     with torch.cuda.device(dev), torch.no_grad():
-        with _crossings_handle(handle_or_faces, V) as handle:
-            res = surface_crossings(verts, handle, group=group, self_pairs=self_pairs, between=between, mode=mode)
-            n = int(res.pairs.shape[0])
-            if n == 0:
-                return CrossingFieldResult(res, _empty_field_rows(dev), torch.zeros(B, B, dtype=torch.float64, device=dev),
-                                           torch.zeros(B, dtype=torch.float32, device=dev))
-            if n > CROSSING_FIELD_MAX_PAIRS:
-                raise ValueError('the batch has %d crossing pairs: more than 2^27 - 1' % n)
-            rows = _field_rows(handle, verts, res.pairs, float(sigma))
-            pair_energy, loss = _field_aggregates(handle, B, res.pairs, rows.energy)
-            return CrossingFieldResult(res, rows, pair_energy, loss)
+        handle = _handle_of(handle_or_faces, V, 'surface_crossings')
+        res = surface_crossings(verts, handle, group=group, self_pairs=self_pairs, between=between, mode=mode)
+        n = int(res.pairs.shape[0])
+        if n == 0:
+            return CrossingFieldResult(res, _new_field_rows(0, dev), torch.zeros(B, B, dtype=torch.float64, device=dev),
+                                       torch.zeros(B, dtype=torch.float32, device=dev))
+        if n > CROSSING_FIELD_MAX_PAIRS:
+            raise ValueError('the batch has %d crossing pairs: more than 2^27 - 1' % n)
+        rows = _field_rows(handle, verts, res.pairs, float(sigma))
+        pair_energy, loss = _field_aggregates(handle, B, res.pairs, rows.energy)
+        return CrossingFieldResult(res, rows, pair_energy, loss)
 
 
 def crossing_field_grad(verts, handle, pairs, g, sigma=CROSSING_FIELD_SIGMA):
@@ -2052,28 +2023,14 @@ def crossing_field_grad(verts, handle, pairs, g, sigma=CROSSING_FIELD_SIGMA):
         grows = torch.empty(12 * n, 3, dtype=torch.float32, device=dev)
         hip.check(hip.lib().psi_crossing_field_grad_rows(handle, hip.ptr(verts), B, hip.ptr(pairs), n, float(sigma), hip.ptr(g), hip.ptr(targets),
                                                          hip.ptr(grows), hip.stream()), 'psi_crossing_field_grad_rows')
-        srt = torch.sort(targets, stable=True)
-        return segment_sum3(srt.values, grows, B * V, order=srt.indices).view(B, V, 3)
-
-
-class _OwnedCrossingsHandle:
-    """A handle made for one call of ``crossing_penetration_loss`` from a faces tensor: it lives as long as the graph that needs it."""
-
-    def __init__(self, faces, V):
-        self.handle = surface_crossings_create(faces, V)
-
-    def __del__(self):
-        try:
-            surface_crossings_destroy(self.handle)
-        except Exception:
-            pass
+        return _sum_rows_by_target(targets, grows, B, V)
 
 
 class _CrossingPenetrationLoss(Function):
     @staticmethod
-    def forward(ctx, verts, handle, owner, group, self_pairs, between, sigma, mode):
+    def forward(ctx, verts, handle, group, self_pairs, between, sigma, mode):
         res = crossing_penetration(verts, handle, group=group, self_pairs=self_pairs, between=between, sigma=sigma, mode=mode)
-        ctx.handle, ctx.owner, ctx.sigma = handle, owner, sigma
+        ctx.handle, ctx.sigma = handle, sigma                                           # the graph holds the handle it will need
         ctx.save_for_backward(verts.detach(), res.crossings.pairs)
         return res.loss.clone()
 
@@ -2081,7 +2038,7 @@ class _CrossingPenetrationLoss(Function):
     def backward(ctx, g):
         verts, pairs = ctx.saved_tensors
         G = crossing_field_grad(verts, ctx.handle, pairs, g.to(torch.float32).contiguous(), ctx.sigma)
-        return G, None, None, None, None, None, None, None
+        return G, None, None, None, None, None, None
 
 
 def crossing_penetration_loss(verts, handle_or_faces, group=None, self_pairs=True, between=True, sigma=CROSSING_FIELD_SIGMA, mode='pruned'):
@@ -2094,13 +2051,10 @@ def crossing_penetration_loss(verts, handle_or_faces, group=None, self_pairs=Tru
     _check_sigma(sigma)
     if mode not in ('pruned', 'brute'):
         raise ValueError("mode is 'pruned' or 'brute', got %r" % (mode,))
-    if not torch.is_tensor(verts) or verts.dtype != torch.float32 or verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1:
-        raise ValueError('expected verts [B,V,3] float32')
-    import ctypes
+    _check_batch_verts(verts)
     hip.ptr(verts)                              # a CPU or non-contiguous tensor is refused before a handle is made
-    owner = None if isinstance(handle_or_faces, ctypes.c_void_p) else _OwnedCrossingsHandle(handle_or_faces, int(verts.shape[1]))
-    return _CrossingPenetrationLoss.apply(verts, owner.handle if owner else handle_or_faces, owner, group, bool(self_pairs), bool(between),
-                                          float(sigma), mode)
+    return _CrossingPenetrationLoss.apply(verts, _handle_of(handle_or_faces, int(verts.shape[1]), 'surface_crossings'), group, bool(self_pairs),
+                                          bool(between), float(sigma), mode)
 
 
 # ------------------------------------------------------------------------------------------
@@ -2178,7 +2132,7 @@ def rigid_pose(base, quat, transl, pivot):
 
 def _rigid_chunks(verts, G, p, g6):
     B, V = int(verts.shape[0]), int(verts.shape[1])
-    chunks = torch.empty(B, (V + RIGID_CHUNK - 1) // RIGID_CHUNK, 6, dtype=torch.float64, device=verts.device)
+    chunks = torch.empty(B, _chunks_of(V, RIGID_CHUNK), 6, dtype=torch.float64, device=verts.device)
     hip.check(hip.lib().psi_body_separate_wrench(hip.ptr(verts), hip.ptr(G), hip.ptr(p), B, V, hip.ptr(chunks), hip.ptr(g6), hip.stream()),
               'psi_body_separate_wrench')
     return chunks
@@ -2202,10 +2156,7 @@ def rigid_wrench(verts, G, pivot_plus_transl, return_chunks=False):
 
 
 def _check_w_scene(w_scene, positive=False):
-    import math
-    import numbers
-    if isinstance(w_scene, bool) or not isinstance(w_scene, numbers.Real) or not math.isfinite(w_scene) or w_scene < 0:
-        raise ValueError('w_scene is a finite number >= 0, got %r' % (w_scene,))
+    _check_real(w_scene, lambda w: w >= 0, 'w_scene is a finite number >= 0, got %r', w_scene)
     if positive and w_scene == 0:
         raise ValueError('w_scene is zero with a scene given: leave the scene out instead')
 
@@ -2230,7 +2181,7 @@ def _scene_launch(verts, p, scene, w_scene, value=None, G=None):
     """psi_body_separate_scene on checked arguments: chunks [B,nchunk,6] fp64, count [B,nchunk] int32, loss [B,nchunk] fp64."""
     sdf, gmin, gmax, scene_id = scene
     B, V, dev = int(verts.shape[0]), int(verts.shape[1]), verts.device
-    nchunk = (V + RIGID_CHUNK - 1) // RIGID_CHUNK
+    nchunk = _chunks_of(V, RIGID_CHUNK)
     chunks = torch.empty(B, nchunk, 6, dtype=torch.float64, device=dev)
     count = torch.empty(B, nchunk, dtype=torch.int32, device=dev)
     loss = torch.empty(B, nchunk, dtype=torch.float64, device=dev)
@@ -2295,19 +2246,11 @@ class _RigidScene:
 
 
 def _check_step_args(lr_t, lr_r, betas, eps):
-    import math
-    import numbers
-
-    def real(x):
-        return not isinstance(x, bool) and isinstance(x, numbers.Real) and math.isfinite(x)
-
     for name, lr in (('lr_t', lr_t), ('lr_r', lr_r)):
-        if not real(lr) or not lr > 0:
-            raise ValueError('%s is a finite positive number, got %r' % (name, lr))
-    if not isinstance(betas, (tuple, list)) or len(betas) != 2 or not all(real(b) and 0.0 <= b < 1.0 for b in betas):
-        raise ValueError('betas is a pair of numbers in [0, 1), got %r' % (betas,))
-    if not real(eps) or eps < 0:
-        raise ValueError('eps is a finite number >= 0, got %r' % (eps,))
+        _check_real(lr, lambda x: x > 0, '%s is a finite positive number, got %r', name, lr)
+    for b in betas if isinstance(betas, (tuple, list)) and len(betas) == 2 else (None,):        # None: not a pair, refused in the same words
+        _check_real(b, lambda x: 0.0 <= x < 1.0, 'betas is a pair of numbers in [0, 1), got %r', betas)
+    _check_real(eps, lambda x: x >= 0, 'eps is a finite number >= 0, got %r', eps)
 
 
 def _fixed_mask(fixed, B, dev):
@@ -2407,74 +2350,52 @@ def rigid_pass(base, state, k, overlap_handle, crossings_handle, group=None, fix
     returned without a read-back).  The pass stops when the bodies are clean and no body outside ``fixed_mask`` has a vertex in its
     scene; otherwise the bodies' chunk sums (zeros when they are clean) and the scene's are added in fp64 and go into the step."""
     B, dev = int(base.shape[0]), base.device
-    if scene is not None:
-        return _rigid_pass_scene(base, state, k, overlap_handle, crossings_handle, group, fixed_mask, step, lr_t, lr_r, betas, eps, w_pen,
-                                 w_cross, penalty, sigma, mode, scene if isinstance(scene, _RigidScene) else _RigidScene(scene, B, dev, fixed_mask),
-                                 w_scene)
+    if scene is not None and not isinstance(scene, _RigidScene):
+        scene = _RigidScene(scene, B, dev, fixed_mask)
     with torch.cuda.device(dev), torch.no_grad():
         verts = rigid_pose(base, state.quat, state.transl, state.pivot)
+        if scene is not None:
+            p = state.pivot + state.transl
+            chunks_scene, count, loss = _scene_launch(verts, p, scene.tensors, w_scene)
+            scene.host.copy_(count.to(torch.int64).sum(1), non_blocking=True)
+            scene.copied.record()
+            loss_scene = loss if scene.loss_rows else _chunk_order_sum(loss)
         pen = body_penetration(verts, overlap_handle, group=group) if w_pen != 0 else None
         cr = crossing_penetration(verts, crossings_handle, group=group, self_pairs=False, between=True, sigma=sigma, mode=mode) if w_cross != 0 else None
+        if scene is not None:
+            if not scene.copied.query():
+                scene.copied.synchronize()
+            inside = scene.host.clone()
         n_tri = -1 if pen is None else int(pen.triples.shape[0])
         n_pairs = -1 if cr is None else int(cr.crossings.pairs.shape[0])
         loss_pen = torch.zeros(B, dtype=torch.float32, device=dev) if pen is None else pen.loss[BODY_DEPTH_PENALTIES[penalty]]
         loss_cross = torch.zeros(B, dtype=torch.float32, device=dev) if cr is None else cr.loss
-        clean = n_tri <= 0 and n_pairs <= 0
-        if clean or not step:
-            return RigidPass(verts, n_tri, n_pairs, loss_pen, loss_cross, clean, False, None)
-        G = None
-        if pen is not None:
+        stop = clean = n_tri <= 0 and n_pairs <= 0
+        with_scene = ()                         # the fields of RigidPass that only a pass with a scene fills
+        if scene is not None:
+            stop = clean and int((inside if scene.free is None else inside[scene.free]).sum()) == 0
+            with_scene = (inside, stop, loss_scene)
+        if stop or not step:
+            return RigidPass(verts, n_tri, n_pairs, loss_pen, loss_cross, clean, False, None, *with_scene)
+        G = None                                # stays None for clean bodies, which only a scene makes step
+        if pen is not None and not clean:
             G = body_penetration_grad(verts.shape, overlap_handle, pen.triples, pen.rows, torch.full((B,), float(w_pen), dtype=torch.float32, device=dev),
                                       penalty)
-        if cr is not None:
+        if cr is not None and not clean:
             Gc = crossing_field_grad(verts, crossings_handle, cr.crossings.pairs, torch.full((B,), float(w_cross), dtype=torch.float32, device=dev),
                                      sigma)
             G = Gc if G is None else G + Gc
         g6 = torch.empty(B, 6, dtype=torch.float32, device=dev)
-        chunks = _rigid_chunks(verts, G, state.pivot + state.transl, None)
-        _rigid_step(state, g6, chunks, k, lr_t, lr_r, betas, eps, fixed_mask)
-        return RigidPass(verts, n_tri, n_pairs, loss_pen, loss_cross, False, True, g6)
-
-
-def _rigid_pass_scene(base, state, k, overlap_handle, crossings_handle, group, fixed_mask, step, lr_t, lr_r, betas, eps, w_pen, w_cross, penalty,
-                      sigma, mode, scene, w_scene):
-    B, dev = int(base.shape[0]), base.device
-    with torch.cuda.device(dev), torch.no_grad():
-        verts = rigid_pose(base, state.quat, state.transl, state.pivot)
-        p = state.pivot + state.transl
-        chunks_scene, count, loss = _scene_launch(verts, p, scene.tensors, w_scene)
-        scene.host.copy_(count.to(torch.int64).sum(1), non_blocking=True)
-        scene.copied.record()
-        loss_scene = loss if scene.loss_rows else _chunk_order_sum(loss)
-        pen = body_penetration(verts, overlap_handle, group=group) if w_pen != 0 else None
-        cr = crossing_penetration(verts, crossings_handle, group=group, self_pairs=False, between=True, sigma=sigma, mode=mode) if w_cross != 0 else None
-        if not scene.copied.query():
-            scene.copied.synchronize()
-        inside = scene.host.clone()
-        n_tri = -1 if pen is None else int(pen.triples.shape[0])
-        n_pairs = -1 if cr is None else int(cr.crossings.pairs.shape[0])
-        loss_pen = torch.zeros(B, dtype=torch.float32, device=dev) if pen is None else pen.loss[BODY_DEPTH_PENALTIES[penalty]]
-        loss_cross = torch.zeros(B, dtype=torch.float32, device=dev) if cr is None else cr.loss
-        clean = n_tri <= 0 and n_pairs <= 0
-        stop = clean and int((inside if scene.free is None else inside[scene.free]).sum()) == 0
-        if stop or not step:
-            return RigidPass(verts, n_tri, n_pairs, loss_pen, loss_cross, clean, False, None, inside, stop, loss_scene, None)
-        chunks = chunks_scene
-        if not clean:
-            G = None
-            if pen is not None:
-                G = body_penetration_grad(verts.shape, overlap_handle, pen.triples, pen.rows,
-                                          torch.full((B,), float(w_pen), dtype=torch.float32, device=dev), penalty)
-            if cr is not None:
-                Gc = crossing_field_grad(verts, crossings_handle, cr.crossings.pairs, torch.full((B,), float(w_cross), dtype=torch.float32, device=dev),
-                                         sigma)
-                G = Gc if G is None else G + Gc
-            chunks = _rigid_chunks(verts, G, p, None) + chunks_scene
-        else:
+        if scene is None:
+            chunks = _rigid_chunks(verts, G, state.pivot + state.transl, None)
+        elif clean:
             chunks = torch.zeros_like(chunks_scene) + chunks_scene         # the bodies' chunk sums are +0: the same fp64 add
-        g6 = torch.empty(B, 6, dtype=torch.float32, device=dev)
+        else:
+            chunks = _rigid_chunks(verts, G, p, None) + chunks_scene
         _rigid_step(state, g6, chunks, k, lr_t, lr_r, betas, eps, fixed_mask)
-        return RigidPass(verts, n_tri, n_pairs, loss_pen, loss_cross, clean, True, g6, inside, stop, loss_scene, chunks)
+        if scene is not None:
+            with_scene += (chunks,)
+        return RigidPass(verts, n_tri, n_pairs, loss_pen, loss_cross, clean, True, g6, *with_scene)
 
 
 def rigid_separate(base, overlap_handle_or_faces, crossings_handle_or_faces, group=None, fixed=None, pivot=None, max_iter=100, lr_t=0.01,
@@ -2505,8 +2426,6 @@ def rigid_separate(base, overlap_handle_or_faces, crossings_handle_or_faces, gro
     ``ValueError`` for wrong shapes, dtypes or devices, max_iter < 1, a non-positive or non-finite learning rate, sigma outside (0, 0.5], a
     negative weight, both weights zero, an unknown penalty or mode, a scene that is not such a tuple, a volume that is not cubic, D < 2,
     a negative or non-finite w_scene, w_scene == 0 with a scene; ``PsiHipError`` for what the library refuses, CPU tensors included."""
-    import math
-    import numbers
     import numpy as np
 
     def check():
@@ -2515,8 +2434,7 @@ def rigid_separate(base, overlap_handle_or_faces, crossings_handle_or_faces, gro
         _check_step_args(lr_t, lr_r, betas, eps)
         _check_sigma(sigma)
         for name, w in (('w_pen', w_pen), ('w_cross', w_cross)):
-            if isinstance(w, bool) or not isinstance(w, numbers.Real) or not math.isfinite(w) or w < 0:
-                raise ValueError('%s is a finite number >= 0, got %r' % (name, w))
+            _check_real(w, lambda x: x >= 0, '%s is a finite number >= 0, got %r', name, w)
         if w_pen == 0 and w_cross == 0:
             raise ValueError('w_pen and w_cross are both zero: nothing to separate by')
         if penalty not in BODY_DEPTH_PENALTIES:
@@ -2547,20 +2465,20 @@ def rigid_separate(base, overlap_handle_or_faces, crossings_handle_or_faces, gro
             table.loss_rows = True
             hist['scene_inside'], hist['loss_scene'] = [], []
         k, separated = 0, False
-        with _overlap_handle(overlap_handle_or_faces, V) as oh, _crossings_handle(crossings_handle_or_faces, V) as ch:
-            while True:
-                one = rigid_pass(base, state, k + 1, oh, ch, group=group, fixed_mask=mask, step=k < max_iter, lr_t=lr_t, lr_r=lr_r, betas=betas,
-                                 eps=eps, w_pen=w_pen, w_cross=w_cross, penalty=penalty, sigma=sigma, mode=mode, scene=table, w_scene=w_scene)
-                verts = one.verts
-                hist['triples'].append(one.triples), hist['pairs'].append(one.pairs)
-                hist['loss_pen'].append(one.loss_pen), hist['loss_cross'].append(one.loss_cross)
-                separated = one.clean
-                if table is not None:
-                    hist['scene_inside'].append(one.scene_inside), hist['loss_scene'].append(one.loss_scene)
-                    separated = one.stop
-                if not one.stepped:
-                    break
-                k += 1
+        oh, ch = _handle_of(overlap_handle_or_faces, V, 'body_overlap'), _handle_of(crossings_handle_or_faces, V, 'surface_crossings')
+        while True:
+            one = rigid_pass(base, state, k + 1, oh, ch, group=group, fixed_mask=mask, step=k < max_iter, lr_t=lr_t, lr_r=lr_r, betas=betas,
+                             eps=eps, w_pen=w_pen, w_cross=w_cross, penalty=penalty, sigma=sigma, mode=mode, scene=table, w_scene=w_scene)
+            verts = one.verts
+            hist['triples'].append(one.triples), hist['pairs'].append(one.pairs)
+            hist['loss_pen'].append(one.loss_pen), hist['loss_cross'].append(one.loss_cross)
+            separated = one.clean
+            if table is not None:
+                hist['scene_inside'].append(one.scene_inside), hist['loss_scene'].append(one.loss_scene)
+                separated = one.stop
+            if not one.stepped:
+                break
+            k += 1
         hist['loss_pen'], hist['loss_cross'] = torch.stack(hist['loss_pen']), torch.stack(hist['loss_cross'])
         M, shift, angle = _rigid_transform(state.quat, state.transl, state.pivot)
         if table is not None:

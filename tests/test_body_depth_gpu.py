@@ -15,6 +15,7 @@ import torch
 from conftest import ROOT
 import body_depth_cases as K
 import body_depth_ref as D
+import body_handles_cases as H
 import body_overlap_cases as C
 from psi_release_amd import evaluation, hip, ops, synth
 
@@ -86,7 +87,8 @@ def test_a_non_finite_face_loses():
 
 @pytest.fixture(scope='module')
 def penetration():
-    """name -> (PenetrationResult, handle owner): one forward run per case, shared, read-only."""
+    """name -> (PenetrationResult, its evaluator): one forward run per case, shared, read-only.  The evaluator comes along for the tests
+    that go on with its handle (``_handle_for``) or its methods; nothing here depends on it for the handle's lifetime."""
     cache = {}
 
     def get(name):
@@ -195,6 +197,17 @@ def test_autograd(penalty, penetration):
     ops.body_penetration_loss(leaf, torch.tensor(cs.faces), penalty=penalty).sum().backward()
     ones = ops.body_penetration_grad((B, V, 3), bo._handle_for(V), res.triples, res.rows, torch.ones(B, device=DEV), penalty)
     assert torch.equal(leaf.grad, ones)
+
+
+@pytest.mark.parametrize('what', H.LET_GO)
+def test_the_graph_keeps_the_handle_its_evaluator_let_go_of(what, monkeypatch):
+    """``BodyOverlap(faces).penetration_loss(verts)`` whose evaluator is deleted, closed or given a batch of another V before
+    ``.backward()`` (tests/body_handles_cases.py)."""
+    cs, other = C.case('c12x16'), C.case('c24x46')
+    assert cs.verts.shape[1] != other.verts.shape[1]
+    H.graph_outlives_evaluator(monkeypatch, 'psi_body_overlap_destroy', lambda: evaluation.BodyOverlap(cs.faces, DEV),
+                               lambda bo, leaf: bo.penetration_loss(leaf), lambda bo: bo.counts(_dev(other.verts)), _dev(cs.verts),
+                               _dev(G_UNEVEN), what)
 
 
 def test_nothing_inside_and_single_body():

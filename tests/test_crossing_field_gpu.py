@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+import body_handles_cases as H
 import crossing_field_cases as K
 import crossing_field_ref as FR
 import surface_crossings_cases as SC
@@ -197,6 +198,17 @@ def test_autograd(sigma):
     ops.crossing_penetration_loss(two, torch.tensor(cs.faces), between=False, sigma=sigma)[0].backward()
     assert K.same_bits(two.grad[0].cpu().numpy(), r.G['ones'][0]) and not two.grad[1].any().item()
     sc.close()
+
+
+@pytest.mark.parametrize('what', H.LET_GO)
+def test_the_graph_keeps_the_handle_its_evaluator_let_go_of(what, monkeypatch):
+    """``SurfaceCrossings(faces).penetration_loss(verts)`` whose evaluator is deleted, closed or given a batch of another V before
+    ``.backward()`` (tests/body_handles_cases.py)."""
+    cs, other = SC.case('six', '12x16'), SC.case('six', '24x46')
+    assert cs.verts.shape[1] != other.verts.shape[1]
+    H.graph_outlives_evaluator(monkeypatch, 'psi_surface_crossings_destroy', lambda: evaluation.SurfaceCrossings(cs.faces, DEV),
+                               lambda sc, leaf: sc.penetration_loss(leaf, self_pairs=False, sigma=0.5), lambda sc: sc.crossings(_t(other.verts)),
+                               _t(cs.verts), _t(K.uneven_g(6)), what)
 
 
 def test_empty_results_launch_nothing():
