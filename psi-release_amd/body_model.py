@@ -37,7 +37,7 @@ class LbsModel:
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise hip.PsiHipError('LbsModel needs a GPU device (no CPU implementation exists in this package)')
-        h = ctypes.c_void_p()
+        h = hip.Handle('psi_lbs_destroy')
         p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
         with torch.cuda.device(self.device):
             hip.check(hip.lib().psi_lbs_create(ctypes.byref(h), p(vt), p(sd), p(pd), p(jr), p(w), p(par),
@@ -52,14 +52,6 @@ class LbsModel:
             ws = torch.zeros(n, dtype=torch.float32, device=self.device)
             self._ws = {B: ws}          # keep one size resident
         return ws
-
-    def __del__(self):
-        try:
-            if getattr(self, 'handle', None):
-                hip.lib().psi_lbs_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 class _LbsFn(Function):

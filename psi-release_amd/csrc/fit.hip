@@ -37,6 +37,7 @@
 // the backward uses that R' == R on SO(3) and that Gram-Schmidt only moves along SO(3), so J_GS^T dL/dR' is the exact
 // gradient (requires pose_mean == 0 for global_orient/body joints, which holds for SMPL-X; checked at creation).
 #include "psi_internal.h"
+#include "blob.h"
 #ifdef PSI_HEAD_STOPS
 __device__ int psi_dbg_sstop;            // dev: leave the skinning / scene kernels at this point (tools/head_stops.sh)
 #define PSI_SSTOP(k) do { if (psi_dbg_sstop == (k)) return; } while (0)
@@ -1788,32 +1789,6 @@ static FitModes fit_decide(const psi_fit_config *cfg, const FitKnobs &knobs, int
     return d;
 }
 
-// The engine's blob: one device allocation for every buffer the engine owns.  A buffer is declared ONCE (fit_create) — the pointer field it
-// binds, its size, how it starts, and the name under which psi_fit_copy_buffer exposes it — and takes the next 256-byte-aligned offset.
-// After the allocation one loop binds the fields and does the uploads and the fills (fit_create); psi_fit_copy_buffer looks names and
-// capacities up here.
-struct FitBuf {
-    void *field;                  // address of the pointer field (of FitDev or of the engine) that points at the buffer
-    size_t off, bytes;
-    const void *src;              // uploaded from this host array (only until fit_create has done so); nullptr: filled
-    int fill;                     // byte the buffer starts as when it is not uploaded: 0, or 0xff
-    const char *name;             // psi_fit_copy_buffer's name for it, capacity bytes / 4 floats; nullptr: not exposed
-};
-struct FitBlob {
-    std::vector<FitBuf> bufs;
-    size_t size;                  // bytes declared so far
-    size_t zero_begin;            // the constants end here; everything behind is zeroed in one go before the other fills
-    template <class T>
-    void add(T *&field, size_t bytes, const void *src, int fill, const char *name)
-    {
-        bufs.push_back({&field, size, bytes, src, fill, name});
-        size += (bytes + 255) & ~(size_t)255;
-    }
-    template <class T> void upload(T *&field, const void *src, size_t bytes) { add(field, bytes, src, 0, nullptr); }
-    template <class T> void zero(T *&field, size_t bytes, const char *name = nullptr) { add(field, bytes, nullptr, 0, name); }
-    template <class T> void ones(T *&field, size_t bytes, const char *name = nullptr) { add(field, bytes, nullptr, 0xff, name); }
-};
-
 // Launch geometry of fit_bwd_joint_kernel: fixed by the model and the batch size, so derived once (fit_plan_make, at psi_fit_create)
 struct FitPlan {
     int mt;                       // 16-body tiles per stream workgroup (the template instance)
@@ -1942,7 +1917,7 @@ struct psi_fit_engine {
     PsiLbsView lv;                // pointers into lbs_ws for the pose stages fused into the head / tail kernels
     void *nn_ws;
     char *blob;
-    FitBlob table;                // what the blob holds (the declarations of fit_create)
+    PsiBlob table;                // what the blob holds (blob.h; the declarations of fit_create)
     float *stats_local;           // engine-owned stats buffer (single-GPU path)
     FitKnobs knobs;
     FitModes mode;
@@ -1952,6 +1927,7 @@ struct psi_fit_engine {
     int n_scenes;                 // 0: a psi_fit_create engine (one scene, the single-scene kernels)
     psi_nn_index **scene_index;   // [n_scenes]
     float **scene_vol;            // [n_scenes] device
+    char *scene_blob;             // the three tables below
     psikd::KdDev *d_kd_tab;       // device [n_scenes]
     PsiSdfGrid *d_grid_tab;       // device [n_scenes]
     int *d_slot;                  // device [B], every entry inside [0, n_scenes)
@@ -2308,7 +2284,7 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     // (sizes in bytes that several buffers share)
     const size_t hand_pca = (size_t)f.ncomp * 45 * 4, hidden = B * NH * 4, betas = B * NB * 4, pose = B * J * 3 * 4, transl = B * 3 * 4,
                  crows = B * f.n_c * 3 * 4, per_body = B * 4, slot_rows = B * f.ncp3 * 4;
-    FitBlob &T = e->table;
+    PsiBlob &T = e->table;
     // constants
     T.upload(f.W1T, W1T.data(), W1T.size() * 4);
     T.upload(f.b1, h_b1, NH * 4);
@@ -2385,23 +2361,7 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     T.zero(e->lbs_ws, psi_lbs_workspace_floats(lbs, f.B) * 4);
     T.zero(e->nn_ws, psi_nn_ws_bytes(f.B, f.n_c, f.m));
     // ---- allocate, bind, upload, fill
-    hipError_t err = hipMalloc((void **)&e->blob, T.size);
-    if (err != hipSuccess) {
-        psi_set_error("psi_fit_create: hipMalloc(%zu) failed: %s", T.size, hipGetErrorString(err));
-        return (int)err;
-    }
-    err = hipMemset(e->blob + T.zero_begin, 0, T.size - T.zero_begin);
-    for (FitBuf &b : T.bufs) {
-        char *p = e->blob + b.off;
-        memcpy(b.field, &p, sizeof(p));                          // (the fields are object pointers of several types: one representation)
-        if (err == hipSuccess && b.src) err = hipMemcpy(p, b.src, b.bytes, hipMemcpyHostToDevice);
-        else if (err == hipSuccess && b.fill) err = hipMemset(p, b.fill, b.bytes);
-        b.src = nullptr;                                         // the host arrays do not outlive this call
-    }
-    if (err != hipSuccess) {
-        psi_set_error("psi_fit_create: upload failed: %s", hipGetErrorString(err));
-        return (int)err;
-    }
+    if (int rc = psi_blob_realise(T, &e->blob, "psi_fit_create")) return rc;
     f.hx_err = f.step + 1;
     if (int rcv = psi_lbs_view(lbs, f.B, e->lbs_ws, &e->lv)) return rcv;
     e->plan = fit_plan_make(f, e->lv.m, knobs.ska_nbody, knobs.bwd_pf1);
@@ -2415,7 +2375,7 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     }
     if (cells) sdf_cells_fill(d_sdf, (float *)f.sdf_cells, f.D);
     e->grid = psi_sdf_grid_make(f.sdf_cells, h_gmin, h_gmax, f.D, f.align_corners);
-    err = hipDeviceSynchronize();                                // the one-off layout kernels above ran on the NULL stream
+    hipError_t err = hipDeviceSynchronize();                     // the one-off layout kernels above ran on the NULL stream
     if (err == hipSuccess) err = hipGetLastError();
     if (err != hipSuccess) {
         psi_set_error("psi_fit_create: layout kernels failed: %s", hipGetErrorString(err));
@@ -2472,21 +2432,15 @@ static int fit_build_scenes(psi_fit_engine *e, const psi_fit_scene *h_scenes, in
         e->kd_rows = std::max(e->kd_rows, kd[s].rows);
     }
     e->nn_index = e->scene_index[0];
-    hipError_t err = hipMalloc((void **)&e->d_kd_tab, sizeof(psikd::KdDev) * S);
-    if (err == hipSuccess) err = hipMalloc((void **)&e->d_grid_tab, sizeof(PsiSdfGrid) * S);
-    if (err == hipSuccess) err = hipMalloc((void **)&e->d_slot, sizeof(int) * (size_t)f.B);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        psi_set_error("psi_fit_create_scenes: no memory for the scene tables: %s", hipGetErrorString(err));
-        return PSI_ENOMEM;
-    }
-    err = hipMemcpy(e->d_kd_tab, kd.data(), sizeof(psikd::KdDev) * S, hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(e->d_grid_tab, grids.data(), sizeof(PsiSdfGrid) * S, hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemset(e->d_slot, 0, sizeof(int) * (size_t)f.B);
-    if (err == hipSuccess) err = hipDeviceSynchronize();         // the layout kernels above ran on the NULL stream
+    PsiBlob T;
+    T.upload(e->d_kd_tab, kd.data(), sizeof(psikd::KdDev) * S);
+    T.upload(e->d_grid_tab, grids.data(), sizeof(PsiSdfGrid) * S);
+    T.zero(e->d_slot, sizeof(int) * (size_t)f.B);
+    if (int rc = psi_blob_realise(T, &e->scene_blob, "psi_fit_create_scenes")) return rc;
+    hipError_t err = hipDeviceSynchronize();                     // the layout kernels above ran on the NULL stream
     if (err == hipSuccess) err = hipGetLastError();
     if (err != hipSuccess) {
-        psi_set_error("psi_fit_create_scenes: scene tables / layout kernels failed: %s", hipGetErrorString(err));
+        psi_set_error("psi_fit_create_scenes: layout kernels failed: %s", hipGetErrorString(err));
         return (int)err;
     }
     return 0;
@@ -2554,9 +2508,7 @@ extern "C" void psi_fit_destroy(psi_fit_engine *e)
         for (int s = 0; s < e->n_scenes; s++) (void)hipFree(e->scene_vol[s]);
         delete[] e->scene_vol;
     }
-    (void)hipFree(e->d_kd_tab);
-    (void)hipFree(e->d_grid_tab);
-    (void)hipFree(e->d_slot);
+    (void)hipFree(e->scene_blob);
     for (FitGraph &G : e->graphs) fit_graph_drop(&G);
     (void)hipFree(e->blob);
     delete e;
@@ -2818,8 +2770,7 @@ extern "C" int psi_fit_copy_buffer(psi_fit_engine *e, const char *name, float *d
     const float *src = nullptr;
     long cap = 0;
     // the blob's named buffers (fit_create: the names of a fused_bwd engine's own buffers exist only there) ...
-    for (const FitBuf &b : e->table.bufs)
-        if (b.name && !strcmp(name, b.name)) { src = (const float *)(e->blob + b.off); cap = (long)(b.bytes / 4); }
+    if (const PsiBuf *b = e->table.find(name)) { src = (const float *)(e->blob + b->off); cap = (long)(b->bytes / 4); }
     // ... the statistics, and what lives in the LBS workspace: the reduced gradients the tail kernel reads, the per-vertex rows of the
     // skinning backward (fused_bwd: the UNSCALED penetration part) and the posed vertices
     const struct { const char *name; const float *src; long cap; } more[] = {

@@ -13,6 +13,7 @@
 // and avg in fp64 / integers, combined in a fixed order: no floating-point atomics, bit-identical from run to run and independent of
 // how the iterations are split into psi_kmeans_iterate calls.  A converged restart is frozen: its workgroups return at once.
 #include "psi_common.h"
+#include "blob.h"
 #include <math.h>
 #include <vector>
 
@@ -23,7 +24,7 @@ struct psi_kmeans {
     int N, d, k, R;
     float thresh;
     int P, CH, NWA;       // update slices (of 256 * CH points), assign workgroups
-    void *blob;
+    char *blob;
     float *obsT;          // [d][N]: the assign kernel's loads are coalesced over the points
     float *book;          // [R][k][d], first k_eff[r] rows valid
     int *k_eff, *iters, *conv;     // [R]
@@ -235,6 +236,8 @@ extern "C" int psi_kmeans_create(psi_kmeans **out, const float *obs, int N, int 
     PSI_REQUIRE(out && obs && guess, "null pointer");
     PSI_REQUIRE(d >= 1 && d <= 128 && k >= 1 && k <= 64 && R >= 1 && R <= 64, "d <= 128, k <= 64, R <= 64");
     PSI_REQUIRE(N >= k && (long)N * d < (1L << 31), "N >= k");
+    // a one-off on the default stream, between two device synchronisations: obs / guess may have been produced on any stream
+    PSI_CHECK_HIP(hipDeviceSynchronize());
     psi_kmeans *km = new psi_kmeans();
     km->obs = obs;
     km->N = N; km->d = d; km->k = k; km->R = R;
@@ -242,36 +245,31 @@ extern "C" int psi_kmeans_create(psi_kmeans **out, const float *obs, int N, int 
     km->CH = psi_cdiv(psi_cdiv(N, 64), KB);                          // at most 64 slices
     km->P = psi_cdiv(N, (long)KB * km->CH);
     km->NWA = psi_cdiv(N, KB);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_obsT = take((size_t)N * d * 4), o_book = take((size_t)R * k * d * 4), o_ke = take((size_t)R * 4), o_it = take((size_t)R * 4),
-                 o_cv = take((size_t)R * 4), o_prev = take((size_t)R * 8), o_avg = take((size_t)R * 8), o_code = take((size_t)R * N * 4),
-                 o_psum = take((size_t)R * km->P * k * d * 8), o_pcnt = take((size_t)R * km->P * k * 4),
-                 o_pdist = take((size_t)R * km->NWA * 8);
-    hipError_t e = hipMalloc(&km->blob, o);
-    if (e != hipSuccess) {
-        psi_set_error("psi_kmeans_create: hipMalloc of %zu bytes failed: %s", o, hipGetErrorString(e));
+    const size_t Rz = (size_t)R;
+    PsiBlob T;                                                   // all but the codebook start uninitialised: the two kernels below write them
+    T.raw(km->obsT, (size_t)N * d * 4);
+    T.copy(km->book, guess, Rz * k * d * 4);
+    T.raw(km->k_eff, Rz * 4);
+    T.raw(km->iters, Rz * 4);
+    T.raw(km->conv, Rz * 4);
+    T.raw(km->prev, Rz * 8);
+    T.raw(km->avg, Rz * 8);
+    T.raw(km->code, Rz * N * 4);
+    T.raw(km->psum, Rz * km->P * k * d * 8);
+    T.raw(km->pcnt, Rz * km->P * k * 4);
+    T.raw(km->pdist, Rz * km->NWA * 8);
+    if (int rc = psi_blob_realise(T, &km->blob, "psi_kmeans_create")) {
         delete km;
-        return (int)e;
+        return rc;
     }
-    char *b = (char *)km->blob;
-    km->obsT = (float *)(b + o_obsT); km->book = (float *)(b + o_book); km->k_eff = (int *)(b + o_ke); km->iters = (int *)(b + o_it);
-    km->conv = (int *)(b + o_cv); km->prev = (double *)(b + o_prev); km->avg = (double *)(b + o_avg); km->code = (int *)(b + o_code);
-    km->psum = (double *)(b + o_psum); km->pcnt = (int *)(b + o_pcnt); km->pdist = (double *)(b + o_pdist);
-    // a one-off on the default stream, between two device synchronisations: obs / guess may have been produced on any stream
-    e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(km->book, guess, (size_t)R * k * d * 4, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) {
-        const long n = (long)N * d;
-        hipLaunchKernelGGL(km_transpose_kernel, dim3(psi_cdiv(n, KB)), dim3(KB), 0, 0, obs, n, N, d, km->obsT);
-        hipLaunchKernelGGL(km_init_kernel, dim3(1), dim3(64), 0, 0, *km);
-        e = hipGetLastError();
-    }
+    const long n = (long)N * d;
+    hipLaunchKernelGGL(km_transpose_kernel, dim3(psi_cdiv(n, KB)), dim3(KB), 0, 0, obs, n, N, d, km->obsT);
+    hipLaunchKernelGGL(km_init_kernel, dim3(1), dim3(64), 0, 0, *km);
+    hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         psi_set_error("psi_kmeans_create failed: %s", hipGetErrorString(e));
-        (void)hipFree(km->blob);
-        delete km;
+        psi_kmeans_destroy(km);
         return (int)e;
     }
     *out = km;

@@ -29,6 +29,7 @@
 // re-instantiates them with its own hooks.
 // The f32 MFMA (v_mfma_f32_16x16x4_f32) is bit-identical to an fmaf chain, so these are exact-f32 GEMMs.
 #include "psi_internal.h"
+#include "blob.h"
 #include "lbs_device.h"
 #include "chain_plan.h"
 #include <algorithm>
@@ -579,48 +580,28 @@ extern "C" int psi_lbs_create(psi_lbs_model **out, const float *h_v_template, co
             }
         }
     }
-    // one device blob
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
-    size_t o_dirs = take(dirs.size() * 4), o_dirs_bh = take(dirs_bh.size() * 4), o_vt = take(vt.size() * 4), o_wt = take(WT.size() * 4), o_wtt = take(WTt.size() * 4), o_jt = take(Jt.size() * 4),
-           o_js = take(Js.size() * 4), o_wc = take(Wc.size() * 4 + 4), o_wj = take(Wj.size() * 4 + 4), o_par = take(J * 4), o_lvl = take(J * 4), o_cp = take((J + 1) * 4), o_ci = take(cidx.size() * 4),
-           o_jump = take(jump.size() * 4), o_sl = take(sub_list.size()), o_si = take(sub_item.size() * 4), o_sf = take(sub_first.size());
-    char *blob = nullptr;
-    PSI_CHECK_HIP(hipMalloc((void **)&blob, o));
+    // one device blob (blob.h): the ORDER is the layout
     std::vector<int> par(h_parents, h_parents + J);
-    struct { size_t off; const void *src; size_t bytes; } cp[] = {
-        {o_dirs, dirs.data(), dirs.size() * 4}, {o_dirs_bh, dirs_bh.data(), dirs_bh.size() * 4}, {o_vt, vt.data(), vt.size() * 4}, {o_wt, WT.data(), WT.size() * 4}, {o_wtt, WTt.data(), WTt.size() * 4},
-        {o_jt, Jt.data(), Jt.size() * 4}, {o_js, Js.data(), Js.size() * 4}, {o_wc, Wc.data(), Wc.size() * 4}, {o_wj, Wj.data(), Wj.size() * 4},
-        {o_par, par.data(), (size_t)J * 4},
-        {o_lvl, level.data(), (size_t)J * 4}, {o_cp, cptr.data(), (size_t)(J + 1) * 4}, {o_ci, cidx.data(), cidx.size() * 4},
-        {o_jump, jump.data(), jump.size() * 4}, {o_sl, sub_list.data(), sub_list.size()}, {o_si, sub_item.data(), sub_item.size() * 4},
-        {o_sf, sub_first.data(), sub_first.size()}};
-    for (auto &c : cp) {
-        if (!c.bytes) continue;
-        hipError_t e = hipMemcpy(blob + c.off, c.src, c.bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(blob);
-            psi_set_error("hipMemcpy failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-    }
-    d.dirs = (const float *)(blob + o_dirs);
-    d.dirs_bh = (const float *)(blob + o_dirs_bh);
-    d.v_template = (const float *)(blob + o_vt);
-    d.WT = (const float *)(blob + o_wt);
-    d.WTt = (const float *)(blob + o_wtt);
-    d.Wc = Wc.empty() ? nullptr : (const float *)(blob + o_wc);
-    d.Wj = Wj.empty() ? nullptr : (const unsigned *)(blob + o_wj);
-    d.J_t = (const float *)(blob + o_jt);
-    d.J_s = (const float *)(blob + o_js);
-    d.parents = (const int *)(blob + o_par);
-    d.level = (const int *)(blob + o_lvl);
-    d.child_ptr = (const int *)(blob + o_cp);
-    d.child_idx = (const int *)(blob + o_ci);
-    d.jump = (const int *)(blob + o_jump);
-    d.sub_list = (const unsigned char *)(blob + o_sl);
-    d.sub_item = (const unsigned int *)(blob + o_si);
-    d.sub_first = (const unsigned char *)(blob + o_sf);
+    PsiBlob T;
+    T.upload(d.dirs, dirs.data(), dirs.size() * 4);
+    T.upload(d.dirs_bh, dirs_bh.data(), dirs_bh.size() * 4);
+    T.upload(d.v_template, vt.data(), vt.size() * 4);
+    T.upload(d.WT, WT.data(), WT.size() * 4);
+    T.upload(d.WTt, WTt.data(), WTt.size() * 4);
+    T.upload(d.J_t, Jt.data(), Jt.size() * 4);
+    T.upload(d.J_s, Js.data(), Js.size() * 4);
+    T.upload(d.Wc, Wc.data(), Wc.size() * 4, Wc.size() * 4 + 4).or_null();
+    T.upload(d.Wj, Wj.data(), Wj.size() * 4, Wj.size() * 4 + 4).or_null();
+    T.upload(d.parents, par.data(), (size_t)J * 4);
+    T.upload(d.level, level.data(), (size_t)J * 4);
+    T.upload(d.child_ptr, cptr.data(), (size_t)(J + 1) * 4);
+    T.upload(d.child_idx, cidx.data(), cidx.size() * 4);
+    T.upload(d.jump, jump.data(), jump.size() * 4);
+    T.upload(d.sub_list, sub_list.data(), sub_list.size());
+    T.upload(d.sub_item, sub_item.data(), sub_item.size() * 4);
+    T.upload(d.sub_first, sub_first.data(), sub_first.size());
+    char *blob = nullptr;
+    if (int rc = psi_blob_realise(T, &blob, "psi_lbs_create")) return rc;
     psi_lbs_model *mdl = new psi_lbs_model;
     mdl->d = d;
     mdl->blob = blob;

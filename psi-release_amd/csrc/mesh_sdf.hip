@@ -22,6 +22,7 @@
 // No floating-point atomics, no communication between workgroups, no spinning: the volume is bit-identical from run to run, and pruning
 // changes no bit (the bounds carry an explicit slack, below).
 #include "mesh_sdf_shared.h"
+#include "blob.h"
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -631,28 +632,19 @@ extern "C" int psi_mesh_sdf_create(psi_mesh_sdf **out, const float *d_verts, con
     m->kept.swap(hm.kept);
     m->aux = psi_mesh_aux{nullptr, nullptr};
     for (int k = 0; k < 4; k++) m->info[k] = hm.info[k];
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_rec = pad((size_t)nk * sizeof(TriRec)), b_nrm = pad((size_t)nk * sizeof(NrmRec)), b_start = pad((ncell + 1) * 4),
-                 b_bins = pad(hb.size() * 4);
-    hipError_t e = hipMalloc((void **)&m->blob, b_rec + b_nrm + b_start + b_bins);
-    if (e != hipSuccess) {
-        psi_set_error("psi_mesh_sdf_create: hipMalloc failed: %s", hipGetErrorString(e));
+    PsiBlob T;
+    T.upload(m->recs, hr.data(), (size_t)nk * sizeof(TriRec));
+    T.upload(m->nrm, hn.data(), (size_t)nk * sizeof(NrmRec));
+    T.upload(m->cell_start, start.data(), (ncell + 1) * 4);
+    T.upload(m->bins, hb.data(), hb.size() * 4);
+    if (int rc = psi_blob_realise(T, &m->blob, "psi_mesh_sdf_create")) {
         delete m;
-        return PSI_ENOMEM;
+        return rc == (int)hipErrorOutOfMemory ? PSI_ENOMEM : rc;
     }
-    m->recs = (TriRec *)m->blob;
-    m->nrm = (NrmRec *)(m->blob + b_rec);
-    m->cell_start = (int *)(m->blob + b_rec + b_nrm);
-    m->bins = (int *)(m->blob + b_rec + b_nrm + b_start);
-    e = hipMemcpy(m->recs, hr.data(), (size_t)nk * sizeof(TriRec), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->nrm, hn.data(), (size_t)nk * sizeof(NrmRec), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->cell_start, start.data(), (ncell + 1) * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->bins, hb.data(), hb.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
+    hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         psi_set_error("psi_mesh_sdf_create failed: %s", hipGetErrorString(e));
-        (void)hipFree(m->blob);
-        delete m;
+        psi_mesh_sdf_destroy(m);
         return (int)e;
     }
     *out = m;

@@ -17,6 +17,7 @@
 // In the reference the scene cloud is static per FittingOP (fitting_proxe.py:93-96), so the tree is built once at
 // construction; the brute-force op remains the general `chamfer.forward` replacement (arbitrary, per-sample clouds).
 #include "psi_internal.h"
+#include "blob.h"
 #include "nnindex_device.h"
 #include <algorithm>
 #include <math.h>
@@ -139,7 +140,7 @@ struct Builder {
 
 struct psi_nn_index {
     KdDev d;
-    void *blob;
+    char *blob;
     int lanes;              // lanes per query of this index's own launches (kd_lanes_from_env)
 };
 
@@ -251,35 +252,22 @@ extern "C" int psi_nn_index_create(psi_nn_index **out, const float *h_points, in
             if (k & 1) memcpy(&b.w, &none, 4); else memcpy(&b.z, &none, 4);
         }
     }
-    size_t nb_nodes = bd.nodes.size() * sizeof(KdNode), nb_pts = pts.size() * sizeof(float4), nb_opts = opts.size() * sizeof(float4);
-    size_t nb_cs = use_grid ? cell_start.size() * sizeof(int) : 0, nb_gp = gpts.size() * sizeof(float4);
-    size_t off_pts = (nb_nodes + 255) & ~(size_t)255;
-    size_t off_opts = (off_pts + nb_pts + 255) & ~(size_t)255;
-    size_t off_cs = (off_opts + nb_opts + 255) & ~(size_t)255;
-    size_t off_gp = (off_cs + nb_cs + 255) & ~(size_t)255;
-    char *blob = nullptr;
-    PSI_CHECK_HIP(hipMalloc((void **)&blob, off_gp + nb_gp + 64));
-    hipError_t e = hipMemcpy(blob, bd.nodes.data(), nb_nodes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(blob + off_pts, pts.data(), nb_pts, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(blob + off_opts, opts.data(), nb_opts, hipMemcpyHostToDevice);
-    if (e == hipSuccess && use_grid) e = hipMemcpy(blob + off_cs, cell_start.data(), nb_cs, hipMemcpyHostToDevice);
-    if (e == hipSuccess && use_grid) e = hipMemcpy(blob + off_gp, gpts.data(), nb_gp, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(blob);
-        psi_set_error("psi_nn_index_create: upload failed: %s", hipGetErrorString(e));
-        return (int)e;
-    }
+    // one device blob (blob.h): the ORDER is the layout; the grid's two buffers are empty without a grid
     psi_nn_index *ix = new psi_nn_index;
-    ix->blob = blob;
+    PsiBlob T;
+    T.upload(ix->d.nodes, bd.nodes.data(), bd.nodes.size() * sizeof(KdNode));
+    T.upload(ix->d.pts, pts.data(), pts.size() * sizeof(float4));
+    T.upload(ix->d.opts, opts.data(), opts.size() * sizeof(float4));
+    T.upload(ix->d.cell_start, cell_start.data(), use_grid ? cell_start.size() * sizeof(int) : 0).or_null();
+    T.upload(ix->d.gpts, gpts.data(), gpts.size() * sizeof(float4), gpts.size() * sizeof(float4) + 64);
+    if (int rc = psi_blob_realise(T, &ix->blob, "psi_nn_index_create")) {
+        delete ix;
+        return rc;
+    }
     ix->lanes = kd_lanes_from_env();
-    ix->d.nodes = (const KdNode *)blob;
-    ix->d.pts = (const float4 *)(blob + off_pts);
-    ix->d.opts = (const float4 *)(blob + off_opts);
     ix->d.root = root;
     ix->d.m = m;
     ix->d.rows = rows;
-    ix->d.cell_start = use_grid ? (const int *)(blob + off_cs) : nullptr;
-    ix->d.gpts = (const float4 *)(blob + off_gp);
     for (int a = 0; a < 3; a++) { ix->d.gorg[a] = gmn[a]; ix->d.gn[a] = gn[a]; }
     ix->d.ginv = ginv;
     *out = ix;

@@ -25,6 +25,7 @@
 //               the same pieces) and interpolating the piece that covers the pixel.
 // No floating-point atomics and no global atomics on the pixel path.
 #include "raster_device.h"
+#include "blob.h"
 #include <vector>
 
 namespace {
@@ -175,39 +176,31 @@ extern "C" int psi_raster_mesh_create(psi_raster_mesh **out, const float *d_vert
 {
     PSI_REQUIRE(out && d_verts && d_faces, "null pointer");
     PSI_REQUIRE(nv >= 1 && nf >= 1 && (long)nf * 2 < (1L << 30), "nv >= 1, 1 <= nf < 2^29");
+    // a one-off between two device synchronisations: the inputs may have been produced on any stream
+    PSI_CHECK_HIP(hipDeviceSynchronize());
     psi_raster_mesh *m = new psi_raster_mesh();
     m->nv = nv;
     m->nf = nf;
-    const size_t bv = ((size_t)nv * 12 + 255) & ~(size_t)255, bf = ((size_t)nf * 12 + 255) & ~(size_t)255, bl = ((size_t)nv * 4 + 255) & ~(size_t)255;
-    char *blob = nullptr;
+    int *d_bad = nullptr;
     int bad = 0;
-    // a one-off between two device synchronisations: the inputs may have been produced on any stream
-    hipError_t e = hipMalloc((void **)&blob, bv + bf + bl + 256);
-    if (e != hipSuccess) {
-        psi_set_error("psi_raster_mesh_create: hipMalloc failed: %s", hipGetErrorString(e));
+    // room for the labels and the flag word whether or not labels are given
+    PsiBlob T;
+    T.copy(m->verts, d_verts, (size_t)nv * 12);
+    T.copy(m->faces, d_faces, (size_t)nf * 12);
+    T.copy(m->vlabel, d_vlabel, d_vlabel ? (size_t)nv * 4 : 0, (size_t)nv * 4).or_null();
+    T.zero(d_bad, 4);
+    if (int rc = psi_blob_realise(T, &m->blob, "psi_raster_mesh_create")) {
         delete m;
-        return (int)e;
+        return rc;
     }
-    m->verts = (float *)blob;
-    m->faces = (int *)(blob + bv);
-    m->vlabel = d_vlabel ? (float *)(blob + bv + bf) : nullptr;
-    int *d_bad = (int *)(blob + bv + bf + bl);
-    e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(m->verts, d_verts, (size_t)nv * 12, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m->faces, d_faces, (size_t)nf * 12, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess && d_vlabel) e = hipMemcpy(m->vlabel, d_vlabel, (size_t)nv * 4, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemset(d_bad, 0, 4);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(rs_check_faces_kernel, dim3(psi_cdiv((long)nf * 3, 256)), dim3(256), 0, 0, m->faces, (long)nf * 3, nv, d_bad);
-        e = hipGetLastError();
-    }
+    hipLaunchKernelGGL(rs_check_faces_kernel, dim3(psi_cdiv((long)nf * 3, 256)), dim3(256), 0, 0, m->faces, (long)nf * 3, nv, d_bad);
+    hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess || bad) {
         if (bad) psi_set_error("psi_raster_mesh_create: a face index lies outside [0, nv)");
         else psi_set_error("psi_raster_mesh_create failed: %s", hipGetErrorString(e));
-        (void)hipFree(blob);
-        delete m;
+        psi_raster_mesh_destroy(m);
         return bad ? PSI_EINVAL : (int)e;
     }
     *out = m;
@@ -217,7 +210,7 @@ extern "C" int psi_raster_mesh_create(psi_raster_mesh **out, const float *d_vert
 extern "C" void psi_raster_mesh_destroy(psi_raster_mesh *m)
 {
     if (!m) return;
-    (void)hipFree(m->verts);             // the blob's first member
+    (void)hipFree(m->blob);
     if (m->bins_extra) (void)hipFree(m->bins_extra);
     delete m;
 }

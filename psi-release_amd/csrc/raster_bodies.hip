@@ -20,16 +20,18 @@
 //   rb_compose       one lane per pixel: owner, shading (the winning triangle set up again with three attributes), colours, counts
 // No floating-point atomics; integer atomics only for the bin counts and the per-draw pixel counts.
 #include "raster_device.h"
+#include "blob.h"
 #include <algorithm>
 #include <vector>
 
 struct psi_raster_bodies {
-    int *faces;        // [F][3]    device; the first member of one blob
+    int *faces;        // [F][3]    device
     int *voff;         // [V + 1]   CSR: the faces of vertex v are vface[voff[v] .. voff[v + 1]), ascending
     int *vface;        // [3 F]
     int V, F;
     void *bins_extra;  // as psi_raster_mesh: grown when a pass's (tile, piece) pairs exceed the workspace's bins
     size_t bins_extra_bytes;
+    char *blob;        // the one allocation behind faces, voff and vface
 };
 
 namespace {
@@ -372,22 +374,18 @@ extern "C" int psi_raster_bodies_create(psi_raster_bodies **out, const int32_t *
     psi_raster_bodies *b = new psi_raster_bodies();
     b->V = V;
     b->F = F;
-    const size_t bf = ((size_t)F * 12 + 255) & ~(size_t)255, bo = (((size_t)V + 1) * 4 + 255) & ~(size_t)255;
-    char *blob = nullptr;
-    hipError_t e = hipMalloc((void **)&blob, bf + bo + bf);
-    if (e == hipSuccess) {
-        b->faces = (int *)blob;
-        b->voff = (int *)(blob + bf);
-        b->vface = (int *)(blob + bf + bo);
-        e = hipMemcpy(b->faces, hf.data(), (size_t)F * 12, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(b->voff, voff.data(), ((size_t)V + 1) * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(b->vface, vface.data(), (size_t)F * 12, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
+    PsiBlob T;
+    T.upload(b->faces, hf.data(), (size_t)F * 12);
+    T.upload(b->voff, voff.data(), ((size_t)V + 1) * 4);
+    T.upload(b->vface, vface.data(), (size_t)F * 12);
+    if (int rc = psi_blob_realise(T, &b->blob, "psi_raster_bodies_create")) {
+        delete b;
+        return rc;
     }
+    hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         psi_set_error("psi_raster_bodies_create failed: %s", hipGetErrorString(e));
-        if (blob) (void)hipFree(blob);
-        delete b;
+        psi_raster_bodies_destroy(b);
         return (int)e;
     }
     *out = b;
@@ -397,7 +395,7 @@ extern "C" int psi_raster_bodies_create(psi_raster_bodies **out, const int32_t *
 extern "C" void psi_raster_bodies_destroy(psi_raster_bodies *b)
 {
     if (!b) return;
-    (void)hipFree(b->faces);             // the blob's first member
+    (void)hipFree(b->blob);
     if (b->bins_extra) (void)hipFree(b->bins_extra);
     delete b;
 }

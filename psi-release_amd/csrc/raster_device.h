@@ -17,6 +17,7 @@ struct psi_raster_mesh {
     int nv, nf;
     void *bins_extra;  // grown on demand when a call's (tile, piece) pairs exceed what its workspace holds
     size_t bins_extra_bytes;
+    char *blob;        // the one allocation behind verts, faces and vlabel
 };
 
 namespace {

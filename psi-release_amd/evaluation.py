@@ -497,7 +497,7 @@ class KMeansRestarts:
         self.R, self.k = guess.shape[0], guess.shape[1]
         if guess.dim() != 3 or guess.shape[2] != self.d:
             raise ValueError('KMeansRestarts: guess must be [R,k,%d], got %s' % (self.d, tuple(guess.shape)))
-        h = ctypes.c_void_p()
+        h = hip.Handle('psi_kmeans_destroy')
         with torch.cuda.device(self.obs.device):
             hip.check(hip.lib().psi_kmeans_create(ctypes.byref(h), hip.ptr(self.obs), self.N, self.d, hip.ptr(guess), self.k, self.R,
                                                   float(thresh)), 'psi_kmeans_create')
@@ -530,8 +530,7 @@ class KMeansRestarts:
     def close(self):
         if getattr(self, 'handle', None):
             torch.cuda.synchronize(self.obs.device)
-            hip.lib().psi_kmeans_destroy(self.handle)
-            self.handle = None
+            self.handle.close()
 
     def __del__(self):
         try:

@@ -468,7 +468,7 @@ class FusedEngine:
                             concurrent_engines=int(getattr(op, 'concurrent_engines', 1)))
         self.concurrent_engines = int(getattr(op, 'concurrent_engines', 1))
         self._keep = (op.s_verts, op.s_sdf)                    # device arrays the engine points into
-        h = ctypes.c_void_p()
+        h = hip.Handle('psi_fit_destroy')
         p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
         # several scenes (or scene_table_engine=True: the same engine over a table of one): psi_fit_create_scenes, scene selected per body
         tab = getattr(op, '_scene_tab', None)
@@ -593,12 +593,15 @@ class FusedEngine:
         self.stream.synchronize()
         return out
 
+    def close(self):
+        """Frees the engine once the device is idle (its launches may still be running)."""
+        if getattr(self, 'handle', None):
+            torch.cuda.synchronize()
+            self.handle.close()
+
     def __del__(self):
         try:
-            if getattr(self, 'handle', None):
-                torch.cuda.synchronize()
-                hip.lib().psi_fit_destroy(self.handle)
-                self.handle = None
+            self.close()
         except Exception:
             pass
 

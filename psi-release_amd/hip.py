@@ -241,9 +241,10 @@ def ptr(t):
 
 class Handle(ctypes.c_void_p):
     """A library handle that owns itself: a ``c_void_p`` (so it goes wherever one goes: an argument, a ``byref`` out-parameter) that knows
-    the symbol that frees it and carries the integers its family asks for, filled in once by the ``*_create`` that made it: ``V`` vertices
-    per body, ``F`` faces, ``n_chunks`` face chunks.  Whoever needs the handle holds this object; ``close()``, or the last holder letting
-    go, frees it, once.  ``destroy`` None: a view of a handle someone else owns, never freed from here."""
+    the symbol that frees it and carries the integers the body-against-body family asks for, filled in once by the ``*_create`` that made
+    it: ``V`` vertices per body, ``F`` faces, ``n_chunks`` face chunks.  Every owner of a library object holds one as ``.handle``.  Whoever
+    needs the handle holds this object; ``close()``, or the last holder letting go, frees it, once (an owner that must wait for the device
+    first does so in a ``close()`` of its own).  ``destroy`` None: a view of a handle someone else owns, never freed from here."""
 
     def __init__(self, destroy):
         super().__init__()

@@ -185,7 +185,7 @@ class SceneNNIndex:
         self.m = pts.shape[0]
         self.device = torch.device(device)
         self.points = torch.tensor(pts, device=self.device)           # for the backward gather
-        h = ctypes.c_void_p()
+        h = hip.Handle('psi_nn_index_destroy')
         with torch.cuda.device(self.device):
             hip.check(hip.lib().psi_nn_index_create(ctypes.byref(h), pts.ctypes.data_as(ctypes.c_void_p), self.m),
                       'psi_nn_index_create')
@@ -200,14 +200,6 @@ class SceneNNIndex:
         hip.check(hip.lib().psi_nn_index_query(self.handle, hip.ptr(xyz1), B, n, hip.ptr(dist), hip.ptr(idx), hip.ptr(hint),
                                                hip.stream()), 'psi_nn_index_query')
         return dist, idx
-
-    def __del__(self):
-        try:
-            if getattr(self, 'handle', None):
-                hip.lib().psi_nn_index_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 class _IndexedChamfer(Function):
@@ -242,7 +234,7 @@ class SceneSet:
         self.device = torch.device(device)
         self.indices = [SceneNNIndex(self.verts_table[s], self.device) for s in range(self.verts_table.shape[0])]
         arr = (ctypes.c_void_p * len(self.indices))(*[ix.handle.value for ix in self.indices])
-        h = ctypes.c_void_p()
+        h = hip.Handle('psi_nn_index_set_destroy')
         with torch.cuda.device(self.device):
             hip.check(hip.lib().psi_nn_index_set_create(ctypes.byref(h), arr, len(self.indices)), 'psi_nn_index_set_create')
         self.handle = h
@@ -255,14 +247,6 @@ class SceneSet:
         hip.check(hip.lib().psi_nn_index_set_query(self.handle, hip.ptr(slot), hip.ptr(xyz1), B, n, hip.ptr(dist), hip.ptr(idx),
                                                    hip.stream()), 'psi_nn_index_set_query')
         return dist, idx
-
-    def __del__(self):
-        try:
-            if getattr(self, 'handle', None):
-                hip.lib().psi_nn_index_set_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 class _SceneSetChamfer(Function):
@@ -943,22 +927,29 @@ def scene_losses(body_verts, vid, scenes: SceneSet, slot, sdf, grid_min, grid_ma
 # ------------------------------------------------------------------------------------------
 def raster_mesh_create(verts, faces, vertex_labels=None):
     """Upload-side half of ``rendering.SceneMesh``: verts [nv,3] fp32, faces [nf,3] int32, vertex_labels [nv] fp32 or None, all on the GPU.
-    Returns the ``psi_raster_mesh`` handle (free it with ``raster_mesh_destroy``)."""
+    Returns the ``psi_raster_mesh`` handle, a ``hip.Handle``: freed by ``raster_mesh_destroy`` or when its last holder lets go of it."""
     import ctypes
     if verts.dtype != torch.float32 or faces.dtype != torch.int32 or verts.dim() != 2 or faces.dim() != 2 or verts.shape[1] != 3 or faces.shape[1] != 3:
         raise ValueError('expected verts [nv,3] float32 and faces [nf,3] int32')
     if vertex_labels is not None and (vertex_labels.dtype != torch.float32 or vertex_labels.shape != (verts.shape[0],)):
         raise ValueError('expected vertex_labels [nv] float32')
-    h = ctypes.c_void_p()
+    h = hip.Handle('psi_raster_mesh_destroy')
     pv, pf, pl = hip.ptr(verts), hip.ptr(faces), hip.ptr(vertex_labels)
     with torch.cuda.device(verts.device):
         hip.check(hip.lib().psi_raster_mesh_create(ctypes.byref(h), pv, pf, pl, verts.shape[0], faces.shape[0]), 'psi_raster_mesh_create')
     return h
 
 
+def _destroy(handle, symbol):
+    """``close()`` of a ``hip.Handle``; any other ``c_void_p`` is a handle its caller owns and frees here, through the library's ``symbol``."""
+    if isinstance(handle, hip.Handle):
+        handle.close()
+    elif handle:
+        getattr(hip.lib(), symbol)(handle)
+
+
 def raster_mesh_destroy(handle):
-    if handle:
-        hip.lib().psi_raster_mesh_destroy(handle)
+    _destroy(handle, 'psi_raster_mesh_destroy')
 
 
 def raster_render(handle, nf, w2c, intr, size, near=0.05, with_seg=True):
@@ -986,21 +977,20 @@ def raster_render(handle, nf, w2c, intr, size, near=0.05, with_seg=True):
 # Result images (psi_raster_bodies_*)
 # ------------------------------------------------------------------------------------------
 def raster_bodies_create(faces, V):
-    """faces [F,3] int32 on the GPU, the one topology of every body; V vertices per body.  Returns the ``psi_raster_bodies`` handle (free it
-    with ``raster_bodies_destroy``); a face index outside [0, V) is refused."""
+    """faces [F,3] int32 on the GPU, the one topology of every body; V vertices per body.  Returns the ``psi_raster_bodies`` handle, a
+    ``hip.Handle`` (``raster_bodies_destroy``, or its last holder letting go, frees it); a face index outside [0, V) is refused."""
     import ctypes
     pf = hip.ptr(faces)
     if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
         raise ValueError('expected faces [F,3] int32')
-    h = ctypes.c_void_p()
+    h = hip.Handle('psi_raster_bodies_destroy')
     with torch.cuda.device(faces.device):
         hip.check(hip.lib().psi_raster_bodies_create(ctypes.byref(h), pf, int(V), faces.shape[0]), 'psi_raster_bodies_create')
     return h
 
 
 def raster_bodies_destroy(handle):
-    if handle:
-        hip.lib().psi_raster_bodies_destroy(handle)
+    _destroy(handle, 'psi_raster_bodies_destroy')
 
 
 def _body_verts_ptr(bverts, V):
@@ -1071,21 +1061,20 @@ def raster_bodies_render(bodies, V, F, bverts, draw_body, draw_view, draw_rgb, w
 # Mesh -> signed distance volume (psi_mesh_sdf_*)
 # ------------------------------------------------------------------------------------------
 def mesh_sdf_create(verts, faces):
-    """Upload-side half of ``scene_sdf.MeshSDF``: verts [nv,3] fp32 and faces [nf,3] int32 on the GPU.  Returns the ``psi_mesh_sdf`` handle
-    (free it with ``mesh_sdf_destroy``); a face index out of range, a non-finite vertex or a mesh of degenerate triangles only is refused."""
+    """Upload-side half of ``scene_sdf.MeshSDF``: verts [nv,3] fp32 and faces [nf,3] int32 on the GPU.  Returns the ``psi_mesh_sdf`` handle,
+    a ``hip.Handle`` (``mesh_sdf_destroy``, or its last holder letting go, frees it); a face index out of range, a non-finite vertex or a mesh of degenerate triangles only is refused."""
     import ctypes
     pv, pf = hip.ptr(verts), hip.ptr(faces)
     if verts.dtype != torch.float32 or faces.dtype != torch.int32 or verts.dim() != 2 or faces.dim() != 2 or verts.shape[1] != 3 or faces.shape[1] != 3:
         raise ValueError('expected verts [nv,3] float32 and faces [nf,3] int32')
-    h = ctypes.c_void_p()
+    h = hip.Handle('psi_mesh_sdf_destroy')
     with torch.cuda.device(verts.device):
         hip.check(hip.lib().psi_mesh_sdf_create(ctypes.byref(h), pv, pf, verts.shape[0], faces.shape[0]), 'psi_mesh_sdf_create')
     return h
 
 
 def mesh_sdf_destroy(handle):
-    if handle:
-        hip.lib().psi_mesh_sdf_destroy(handle)
+    _destroy(handle, 'psi_mesh_sdf_destroy')
 
 
 def mesh_sdf_info(handle):

@@ -57,14 +57,6 @@ class SceneMesh:
         verts, faces, rgb = scene_io.read_ply_mesh(path)
         return cls(verts, faces, None if rgb is None else scene_io.labels_from_colors(rgb), device=device, vertex_rgb=rgb)
 
-    def __del__(self):
-        try:
-            if getattr(self, 'handle', None):
-                ops.raster_mesh_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
-
 
 def world_to_camera(cam_ext) -> np.ndarray:
     """[n,3,4] fp32 rows of the inverse of camera-to-world ``cam_ext`` [n,4,4]: inverted in fp64, rounded to fp32 once."""
@@ -298,14 +290,6 @@ class ResultRenderer:
         for view in np.nonzero(self.last_stats[:, 1])[0]:
             warnings.warn('view %d: %d body triangle pieces project beyond the 2^28 sub-pixel range and were not drawn' % (view, self.last_stats[view, 1]))
         return ResultImages(*out[:6])
-
-    def __del__(self):
-        try:
-            if getattr(self, 'handle', None):
-                ops.raster_bodies_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 def write_png(path, rgb_uint8):

@@ -50,7 +50,6 @@ class MeshSDF:
         if np.abs(f).max() >= 2 ** 31:
             raise ops.hip.PsiHipError('a face index lies outside [0, nv)')
         self.nv, self.nf = len(v), len(f)
-        self.handle = None
         self.handle = ops.mesh_sdf_create(torch.tensor(v, device=self.device), torch.tensor(f.astype(np.int32), device=self.device))
         self.info = ops.mesh_sdf_info(self.handle)
         self._warned = False
@@ -88,14 +87,6 @@ class MeshSDF:
             warnings.warn('mesh is not closed: the sign follows the triangle orientation (%d edges are not shared by exactly two triangles)'
                           % self.info[3])
         return ops.mesh_sdf_compute(self.handle, grid_min, grid_max, dim, MODES[mode], device=self.device)
-
-    def __del__(self):
-        try:
-            if getattr(self, 'handle', None):
-                ops.mesh_sdf_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 def scene_cloud(verts, voxel=None) -> np.ndarray:

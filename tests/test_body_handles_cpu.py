@@ -2,29 +2,37 @@
 ops._handle_of; evaluation.BodyOverlap, SurfaceCrossings, BodySeparator): the library is replaced by a fake that hands out addresses and
 counts what it is asked to free.  A handle is freed exactly once, when its last holder lets go or at ``close()``; a holder standing in for
 an autograd graph keeps it alive whatever the evaluator does; the integers come from one query at creation.  And the one range check of
-the family's real arguments, with the message of each of its callers."""
+the family's real arguments, with the message of each of its callers.
+
+The library's other owners go through the same fake (ops.raster_mesh_create, raster_bodies_create, mesh_sdf_create; ops.SceneNNIndex,
+SceneSet; body_model.LbsModel; fitting.FusedEngine; evaluation.KMeansRestarts; rendering.SceneMesh, ResultRenderer; scene_sdf.MeshSDF):
+nothing is freed while a holder lives, everything once when the last goes or at ``close()``, a second ``close()`` does nothing, and the
+two owners that wait for the device do so before their destroy."""
 import contextlib
 import ctypes
 import gc
+import re
 import weakref
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from psi_release_amd import evaluation, hip, ops
+from psi_release_amd import body_model, evaluation, fitting, hip, ops, rendering, scene_sdf
 
 FACES = np.array([[0, 1, 2], [1, 2, 4]], np.int32)
 KINDS = ('body_overlap', 'surface_crossings')
 CREATE = {'body_overlap': ops.body_overlap_create, 'surface_crossings': ops.surface_crossings_create}
 DESTROY = {'body_overlap': ops.body_overlap_destroy, 'surface_crossings': ops.surface_crossings_destroy}
+OWNED = ('nn_index_set', 'nn_index', 'lbs', 'fit', 'kmeans', 'raster_mesh', 'raster_bodies', 'mesh_sdf')
 
 
 class FakeLib:
     """The create, info and destroy symbols of both kinds; ``freed`` lists (symbol, address) in call order."""
 
     def __init__(self):
-        self.made, self.freed, self.info_calls, self.live, self._next = {}, [], 0, [], 0x1000
+        self.made, self.freed, self.events, self.info_calls, self.live, self._next = {}, [], [], 0, [], 0x1000
 
     def _create(self, out, V, F, n_chunks):
         self._next += 0x100
@@ -51,6 +59,18 @@ class FakeLib:
 
     def psi_surface_crossings_destroy(self, handle):
         self.freed.append(('psi_surface_crossings_destroy', handle.value))
+
+    def __getattr__(self, name):
+        """The other families: ``made`` maps an address to the family that created it; ``events`` adds the device synchronisations to the
+        destroys.  Every further symbol succeeds and does nothing."""
+        m = re.fullmatch(r'psi_(%s)_(create|create_scenes|destroy)' % '|'.join(OWNED), name)
+        if not name.startswith('psi_'):
+            raise AttributeError(name)
+        if not m:
+            return lambda *args: 0
+        if m.group(2) == 'destroy':
+            return lambda handle: (self.freed.append((name, handle.value)), self.events.append((name, handle.value)))[0]
+        return lambda out, *args: self._create(out, m.group(1), 0, 0)
 
 
 @pytest.fixture
@@ -223,3 +243,148 @@ def test_the_range_check_and_the_messages_of_its_callers():
     for bad in ((0.9,), (0.9, 0.999, 0.5), [0.9, 1.0], (True, 0.5), (0.9, float('nan')), (-0.1, 0.5), 0.9, None, 'ab', (0.9, None)):
         _refused(lambda b: ops._check_step_args(**dict(step, betas=b)), bad, 'betas is a pair of numbers in [0, 1), got %r')
     ops._check_step_args(**dict(step, betas=[0, 0.5]))
+
+
+# ------------------------------------------------------------------------------------------
+# The library's other owners
+# ------------------------------------------------------------------------------------------
+class _OnGpu(torch.Tensor):
+    """A CPU tensor that says it is on the GPU and stays where it is: what the owners' argument checks ask of their inputs."""
+    is_cuda = True
+
+    def to(self, *args, **kwargs):
+        return self
+
+
+def _gpu(*shape, dtype=torch.float32):
+    return torch.zeros(*shape, dtype=dtype).as_subclass(_OnGpu)
+
+
+@pytest.fixture
+def no_gpu(lib, monkeypatch):
+    """The fake library, and a device to match: tensors made "on the GPU" land on the CPU, a pointer is a number, the stream an object,
+    and ``torch.cuda.synchronize`` is an event in ``lib.events``."""
+    real = torch.tensor
+    monkeypatch.setattr(torch, 'tensor', lambda data, *args, device=None, **kwargs: real(data, *args, **kwargs))
+    monkeypatch.setattr(hip, 'ptr', lambda t: None if t is None else 0x40)
+    monkeypatch.setattr(torch.cuda, 'Stream', lambda device=None: SimpleNamespace(cuda_stream=0))
+    monkeypatch.setattr(torch.cuda, 'synchronize', lambda device=None: lib.events.append(('synchronize', None)))
+    return lib
+
+
+TRIANGLES = dict(verts=np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0]], np.float32), faces=np.array([[0, 1, 2], [1, 3, 2]], np.int64))
+
+
+def _lbs_model():
+    V, J, NB = 4, 2, 1
+    return body_model.LbsModel(np.zeros((V, 3)), np.zeros((V, 3, NB)), np.zeros(((J - 1) * 9, 3 * V)), np.zeros((J, V)), np.zeros((V, J)),
+                               np.array([-1, 0]), 'cuda')
+
+
+def _engine():
+    dec = {'bodyprior_dec_fc1': (512, 32), 'bodyprior_dec_fc2': (512, 512), 'bodyprior_dec_out': (126, 512)}
+    sd = {k + '.weight': torch.zeros(*s) for k, s in dec.items()}
+    sd.update({k + '.bias': torch.zeros(s[0]) for k, s in dec.items()})
+    bm = SimpleNamespace(left_hand_components=torch.zeros(6, 45), right_hand_components=torch.zeros(6, 45), pose_mean=torch.zeros(165),
+                         lbs_model=SimpleNamespace(handle=ctypes.c_void_p(0x80)))
+    op = SimpleNamespace(device='cpu', vposer=SimpleNamespace(state_dict=lambda: sd), body_mesh_model=bm, batch_size=2, align_corners=False,
+                         contact_vertex_ids=lambda: torch.zeros(4, dtype=torch.int64), s_grid_min_batch=torch.zeros(1, 3),
+                         s_grid_max_batch=torch.ones(1, 3), s_verts=torch.zeros(1, 8, 3), s_sdf=torch.zeros(1, 4, 4, 4), weight_loss_rec=1.0,
+                         weight_loss_vposer=0.01, weight_contact=0.1, weight_collision=0.5, contact_const=0.0, init_lr_h=0.1, nn_mode='kdtree')
+    return fitting.FusedEngine(op)
+
+
+def _result_renderer():
+    r = rendering.ResultRenderer(None, TRIANGLES['faces'])
+    r._bodies(_gpu(1, 4, 3))                                                             # the handle is made for the first bodies' V
+    return r
+
+
+# owner -> (what makes one, the families of the handles it then holds)
+OWNERS = {
+    'SceneNNIndex': (lambda: ops.SceneNNIndex(np.zeros((65, 3), np.float32), device='cpu'), ['nn_index']),
+    'SceneSet': (lambda: ops.SceneSet(torch.zeros(2, 65, 3), device='cpu'), ['nn_index', 'nn_index', 'nn_index_set']),
+    'LbsModel': (_lbs_model, ['lbs']),
+    'FusedEngine': (_engine, ['fit']),
+    'KMeansRestarts': (lambda: evaluation.KMeansRestarts(_gpu(64, 3), _gpu(1, 2, 3)), ['kmeans']),
+    'SceneMesh': (lambda: rendering.SceneMesh(**TRIANGLES), ['raster_mesh']),
+    'ResultRenderer': (_result_renderer, ['raster_bodies']),
+    'MeshSDF': (lambda: scene_sdf.MeshSDF(**TRIANGLES), ['mesh_sdf']),
+}
+WAITS_FOR_THE_DEVICE = ('FusedEngine', 'KMeansRestarts')
+
+
+def _made_by(lib, owner):
+    """What ``owner`` must free: (destroy symbol, address) of every handle the fake made, sorted."""
+    assert isinstance(owner.handle, hip.Handle) and owner.handle.value in lib.made
+    return sorted(('psi_%s_destroy' % family, address) for address, (family, _, _) in lib.made.items())
+
+
+@pytest.mark.parametrize('name', sorted(OWNERS))
+def test_an_owner_frees_its_handle_once_when_its_last_holder_goes(no_gpu, name):
+    make, families = OWNERS[name]
+    owner = make()
+    made = _made_by(no_gpu, owner)
+    assert [symbol for symbol, _ in made] == sorted('psi_%s_destroy' % f for f in families)
+    assert owner.handle.destroy == 'psi_%s_destroy' % families[-1]
+    second = owner
+    del owner
+    assert _freed(no_gpu) == []
+    if name not in WAITS_FOR_THE_DEVICE:                                                 # (their ``__del__`` is their ``close()``)
+        second = second.handle                                                           # the owner is gone, its handle has a holder
+        assert sorted(_freed(no_gpu)) == [f for f in made if f[1] != second.value]       # (a set's indices go with the set)
+    del second
+    assert sorted(_freed(no_gpu)) == made
+    if name in WAITS_FOR_THE_DEVICE:
+        assert no_gpu.events == [('synchronize', None), made[0]]
+    else:
+        assert ('synchronize', None) not in no_gpu.events
+
+
+@pytest.mark.parametrize('name', sorted(OWNERS))
+def test_closing_an_owners_handle_twice_frees_it_once(no_gpu, name):
+    owner = OWNERS[name][0]()
+    mine = ('psi_%s_destroy' % OWNERS[name][1][-1], owner.handle.value)
+    close = owner.close if name in WAITS_FOR_THE_DEVICE else owner.handle.close
+    close()
+    assert _freed(no_gpu) == [mine] and not owner.handle and isinstance(owner.handle, hip.Handle)
+    close()
+    assert _freed(no_gpu) == [mine]
+    if name in WAITS_FOR_THE_DEVICE:
+        assert no_gpu.events == [('synchronize', None), mine]                            # the device is idle before the destroy, and asked once
+    made = sorted(('psi_%s_destroy' % family, address) for address, (family, _, _) in no_gpu.made.items())
+    del owner
+    assert sorted(_freed(no_gpu)) == made and no_gpu.events.count(('synchronize', None)) == (1 if name in WAITS_FOR_THE_DEVICE else 0)
+
+
+OPS_CREATE = {
+    'raster_mesh': lambda: ops.raster_mesh_create(_gpu(4, 3), _gpu(2, 3, dtype=torch.int32), _gpu(4)),
+    'raster_bodies': lambda: ops.raster_bodies_create(_gpu(2, 3, dtype=torch.int32), 4),
+    'mesh_sdf': lambda: ops.mesh_sdf_create(_gpu(4, 3), _gpu(2, 3, dtype=torch.int32)),
+}
+OPS_DESTROY = {'raster_mesh': ops.raster_mesh_destroy, 'raster_bodies': ops.raster_bodies_destroy, 'mesh_sdf': ops.mesh_sdf_destroy}
+
+
+@pytest.mark.parametrize('kind', sorted(OPS_CREATE))
+def test_the_create_operators_hand_out_handles_that_own_themselves(no_gpu, kind):
+    symbol = 'psi_%s_destroy' % kind
+    h = OPS_CREATE[kind]()
+    assert isinstance(h, hip.Handle) and h.destroy == symbol and no_gpu.made[h.value][0] == kind
+    address, second = h.value, h
+    del h
+    assert _freed(no_gpu) == []
+    del second
+    assert _freed(no_gpu) == [(symbol, address)]
+    g = OPS_CREATE[kind]()
+    other = g.value
+    OPS_DESTROY[kind](g)                                                                 # the operators' own names: the same close
+    assert not g and _freed(no_gpu) == [(symbol, address), (symbol, other)]
+    OPS_DESTROY[kind](g)
+    g.close()
+    del g
+    assert _freed(no_gpu) == [(symbol, address), (symbol, other)]
+    raw = ctypes.c_void_p(0x7700)                                                        # a handle its caller owns: freed through the library, as before
+    OPS_DESTROY[kind](raw)
+    OPS_DESTROY[kind](ctypes.c_void_p())
+    OPS_DESTROY[kind](None)
+    assert _freed(no_gpu)[2:] == [(symbol, 0x7700)]

@@ -29,6 +29,8 @@ def test_knob_and_buffer_are_declared():
     create = src.split('static int fit_create(')[1].split('extern "C" int psi_fit_create(')[0]
     assert 'T.zero(f.penmask, ' in create.split('if (mode.fused_bwd) {')[1].split('}')[0] and '"penmask");' in create
     copy = src.split('extern "C" int psi_fit_copy_buffer')[1]
-    assert 'e->table.bufs' in copy and '!strcmp(name, b.name)' in copy
+    assert 'e->table.find(name)' in copy                             # the table's own lookup (csrc/blob.h): whole names only
+    find = open(os.path.join(ROOT, 'psi-release_amd', 'csrc', 'blob.h')).read().split('const PsiBuf *find(const char *name) const')[1].split('return nullptr;')[0]
+    assert 'for (const PsiBuf &b : bufs)' in find and '!strcmp(b.name, name)' in find
     assert 'PSI_FIT_PEN_SKIP' in open(os.path.join(ROOT, 'README.md')).read()
     assert 'penmask' in open(os.path.join(ROOT, 'include', 'psi_hip.h')).read()
