@@ -936,6 +936,50 @@ int psi_body_separate_scene(const float *d_verts, const float *d_p, const float 
                             const int32_t *d_scene_id, int B, int V, int D, int S, float w_scene, double *d_chunks, int32_t *d_count,
                             double *d_loss, float *d_sdf_out, float *d_G_out, void *stream);
 
+/* ---- Scene crossings: which body triangles of a batch properly intersect which triangles of a static scene mesh (csrc/scene_crossings.hip) ----
+ * Contract (the per-pair statements are csrc/surface_crossings_shared.h, the key and the host half of create
+ * csrc/scene_crossings_shared.h).  The scene: h_verts HOST [nv,3] fp32 and h_faces HOST [nf,3] int32, fixed for the life of the handle;
+ * degenerate triangles are kept.  The bodies: d_verts [B,V,3] fp32, world frame, with the topology of the psi_surface_crossings handle
+ * `body`.
+ *   candidate  a body face (i, s) and a scene triangle t whose closed exact face boxes meet
+ *   decision   sc_pair(P = body face, Q = scene triangle), both in the caller's corner order: crosses iff events >= 1; length as in
+ *              psi_surface_crossings_*
+ *   create     HOST work only, no kernel: the triangles sorted along a Morton curve (10 bits per axis) of their centroid sums (fp64) over
+ *              the box of those sums, ties to the lower index; chunks of 256 positions; the exact box of every chunk and of the scene by
+ *              comparisons; uploaded per position: the nine coordinates and the caller's index
+ *   info       info[4] = nv, nf, scene chunks, 0
+ *   tiles      a job is a body chunk (i, c), a tile (i, c, k) a job and a scene chunk whose boxes meet (brute = 1: every (i, c, k)); a
+ *              body or body chunk whose box misses the scene's box has none.  d_chunk_boxes [B, body chunks, 6] and d_body_boxes [B,6]
+ *              are what psi_surface_crossings_boxes wrote for `body`.  Called twice: with d_job_off = d_tiles = NULL, n_tiles = 0 it
+ *              writes d_job_tiles [B, body chunks]; with d_job_off (the caller's exclusive scan of d_job_tiles, int64) it writes d_tiles
+ *              [n_tiles,4] int32 (i, c, k, 0), the tiles of a job in ascending k
+ *   test       one workgroup per tile.  With d_keys = NULL (and d_tile_off, d_events, d_length NULL, n_pairs = 0) it writes d_tile_hits
+ *              [n_tiles]; with d_tile_off (the exclusive scan, int64) it writes the key (i F + s) nf + t (s, t: the caller's indices),
+ *              events and length of every crossing pair from d_tile_off[tile] on, in any order within the tile
+ *   finish     d_keys_sorted and d_order: the caller's sort of d_keys; d_row_start [B+1] int64: the first row of every body.  Writes
+ *              d_pairs [n,3] int32 (i, s, t), d_events [n], d_length [n]; adds into d_counts [B] int32, ors into d_face_mask
+ *              [B, ceil(F / 32)] and d_tri_mask [ceil(nf / 32)] (bit k of word k >> 5 at position k & 31), counts d_irregular (events
+ *              != 2), and writes d_contour [B] fp64 of the bodies with rows: their lengths added one after the other in row order.  The
+ *              five ZEROED BY THE CALLER
+ * No floating-point atomics: every output is bit-identical from run to run, and the rows of a body depend neither on the rest of the batch
+ * nor on the order of the body faces or of the scene triangles.  No pass launches an empty grid: with n_tiles = 0 or n_pairs = 0 the
+ * caller stops.  PSI_EINVAL: a null pointer; create: nv < 1, nf < 1, a face index outside [0, nv), a non-finite referenced vertex; B < 1
+ * or B > 46340; B F nf >= 2^63 (the key is one int64); n_tiles or n_pairs outside [1, 2^31). */
+typedef struct psi_scene_crossings psi_scene_crossings;
+int psi_scene_crossings_create(psi_scene_crossings **out, const float *h_verts, int nv, const int32_t *h_faces, int nf);
+void psi_scene_crossings_destroy(psi_scene_crossings *h);
+int psi_scene_crossings_info(const psi_scene_crossings *h, int32_t info[4]);
+int psi_scene_crossings_tiles(const psi_scene_crossings *h, const psi_surface_crossings *body, int B, int brute, const float *d_chunk_boxes,
+                              const float *d_body_boxes, int32_t *d_job_tiles, const int64_t *d_job_off, long long n_tiles, int32_t *d_tiles,
+                              void *stream);
+int psi_scene_crossings_test(const psi_scene_crossings *h, const psi_surface_crossings *body, const float *d_verts, int B,
+                             const int32_t *d_tiles, long long n_tiles, int32_t *d_tile_hits, const int64_t *d_tile_off, long long n_pairs,
+                             int64_t *d_keys, int32_t *d_events, float *d_length, void *stream);
+int psi_scene_crossings_finish(const psi_scene_crossings *h, const psi_surface_crossings *body, int B, const int64_t *d_keys_sorted,
+                               const int64_t *d_order, const int32_t *d_events_in, const float *d_length_in, long long n_pairs,
+                               const int64_t *d_row_start, int32_t *d_pairs, int32_t *d_events, float *d_length, int32_t *d_counts,
+                               double *d_contour, uint32_t *d_face_mask, uint32_t *d_tri_mask, int32_t *d_irregular, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,8 @@ PER_FILE = {'chamfer.hip': ['-ffp-contract=off', '-fno-slp-vectorize'], 'nnindex
             'crossing_field.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
             # the pose, the wrench terms, the Adam step and the quaternion update, rounding for rounding
             'body_separate.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
+            # the same fifteen values against a scene triangle, rounding for rounding
+            'scene_crossings.hip': ['-ffp-contract=off', '-fhip-fp32-correctly-rounded-divide-sqrt'],
             'body_overlap.hip': []}            # default contraction: the contract on w is a tolerance, and
                                                         # everything that decides membership (box, threshold) is a comparison
 

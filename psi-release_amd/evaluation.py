@@ -13,6 +13,8 @@ DESIGN.md section 10d), and ``select_disjoint`` picks a greedy set of bodies tha
 counterpart on the path (its BodyInterpenetration needs an external CUDA package).  ``SurfaceCrossings`` lists the pairs of triangles of
 the bodies' surfaces that intersect, between bodies and within one body (psi_surface_crossings_*), with
 ``face_parts`` / ``part_skip_matrix`` for that class's body-part filter and ``select_uncrossed`` for the greedy choice.
+Body against the room's mesh: ``SceneCrossings`` lists the pairs of a body triangle and a scene triangle that intersect, with no distance
+volume (psi_scene_crossings_*), and ``select_clear`` keeps the bodies that stand clear.
 
 Diversity: utils/utils_eval_diversity.py:93-104 — ``diversity_reference`` runs the reference's ``scipy.cluster.vq.kmeans`` protocol
 on the GPU (psi_kmeans_*, psi_vq); ``diversity_scores`` is the older k-means++ variant (a different algorithm, kept as it is).
@@ -375,6 +377,54 @@ class SurfaceCrossings(_FacesHandleOwner):
         """``field`` of the bodies ``xh72`` [N,72], skinned exactly as ``crossings_of_records`` skins them, in ONE call over all N."""
         verts = _verts_of_records(xh72, cam_ext, evaluator_or_decoder, chunk, self.device, 'field_of_records')
         return self.field(verts, group, self_pairs, between, sigma)
+
+
+class SceneCrossings(_FacesHandleOwner):
+    """Which triangles of the body surfaces of a batch properly intersect which triangles of a scene mesh (``ops.scene_crossings``;
+    DESIGN.md section 10i): the one body-against-room question that needs no distance volume, so it sees geometry thinner than the
+    volume's node spacing and open, unoriented scans.  ``scene_verts`` [nv,3] and ``scene_faces`` [nf,3], or a ``rendering.SceneMesh`` as
+    ``scene_verts`` with ``scene_faces`` None; ``body_faces`` [F,3]: the one topology of every body; ``order_verts`` [V,3]: a
+    representative pose the body faces are sorted along once.  The scene handle (``.scene``) is made at construction and lives as long as this
+    object; ``close()`` lets go of the body handle only."""
+
+    def __init__(self, scene_verts, scene_faces, body_faces, device='cuda', order_verts=None):
+        super().__init__(body_faces, device)
+        if scene_faces is None and hasattr(scene_verts, 'verts') and hasattr(scene_verts, 'faces'):
+            scene_verts, scene_faces = scene_verts.verts, scene_verts.faces
+        self._order_verts = _as_numpy(order_verts, np.float32)
+        with torch.cuda.device(self.device):
+            self.scene = ops.scene_crossings_create(_as_numpy(scene_verts, np.float32), _as_numpy(scene_faces, np.int32))
+
+    def _create(self, V):
+        return ops.surface_crossings_create(self.faces, V, self._order_verts)
+
+    @torch.no_grad()
+    def crossings(self, verts, mode='pruned'):
+        """verts [B,V,3] fp32 on the device, world frame.  Returns ``ops.SceneCrossingsResult``."""
+        return ops.scene_crossings(verts.contiguous(), self.scene, self._handle_for(int(verts.shape[1])), mode=mode)
+
+    @torch.no_grad()
+    def crossings_of_records(self, xh72, cam_ext, evaluator_or_decoder, chunk=512):
+        """The bodies ``xh72`` [N,72] with cameras ``cam_ext``, skinned in chunks of ``chunk`` exactly as
+        ``BodyOverlap.counts_of_records`` skins them, then ONE crossings call over all N."""
+        verts = _verts_of_records(xh72, cam_ext, evaluator_or_decoder, chunk, self.device, 'crossings_of_records')
+        return self.crossings(verts)
+
+
+def select_clear(order, counts, max_pairs=0):
+    """The bodies that stand clear of the scene, on the host: those of ``order``, in its order and each once, with at most ``max_pairs``
+    scene crossings.  ``counts`` [B]: ``SceneCrossingsResult.counts`` (a tensor or an array)."""
+    c = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+    if c.ndim != 1:
+        raise ValueError('select_clear: counts is [B], got %s' % (c.shape,))
+    kept = []
+    for i in order:
+        i = int(i)
+        if not 0 <= i < c.shape[0]:
+            raise ValueError('select_clear: body %d outside [0, %d)' % (i, c.shape[0]))
+        if int(c[i]) <= max_pairs and i not in kept:
+            kept.append(i)
+    return kept
 
 
 class BodySeparator:

@@ -178,6 +178,13 @@ SIGNATURES = {
     'psi_body_separate_wrench': (c_int, [c_void_p] * 3 + [c_int] * 2 + [c_void_p] * 3),
     'psi_body_separate_step': (c_int, [c_void_p, c_int] + [c_void_p] * 6 + [c_int] + [c_float] * 7 + [c_void_p]),
     'psi_body_separate_scene': (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_float] + [c_void_p] * 6),
+    'psi_scene_crossings_create': (c_int, [c_void_p] * 2 + [c_int, c_void_p, c_int]),
+    'psi_scene_crossings_destroy': (None, [c_void_p]),
+    'psi_scene_crossings_info': (c_int, [c_void_p] * 2),
+    'psi_scene_crossings_tiles': (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 4 + [ctypes.c_longlong] + [c_void_p] * 2),
+    'psi_scene_crossings_test': (c_int, [c_void_p] * 3 + [c_int, c_void_p, ctypes.c_longlong] + [c_void_p] * 2 + [ctypes.c_longlong]
+                                 + [c_void_p] * 4),
+    'psi_scene_crossings_finish': (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 4 + [ctypes.c_longlong] + [c_void_p] * 10),
 }
 
 

@@ -1874,6 +1874,137 @@ def surface_crossings(verts, handle_or_faces, group=None, self_pairs=True, betwe
 
 
 # ------------------------------------------------------------------------------------------
+# Scene crossings: body triangles of a batch that intersect triangles of a static scene mesh (psi_scene_crossings_*)
+# ------------------------------------------------------------------------------------------
+class SceneCrossingsResult(NamedTuple):
+    pairs: torch.Tensor        # [n,3] int32 (i, s, t), strictly ascending: face s of body i crosses scene triangle t (the caller's indices)
+    events: torch.Tensor       # [n] int32: piercing edges of the pair, 1 to 6; 2 is the regular case
+    length: torch.Tensor       # [n] fp32: the length of the pair's intersection segment (0 unless events == 2)
+    counts: torch.Tensor       # [B] int32: crossing pairs of body i
+    contour: torch.Tensor      # [B] fp64: the lengths of body i added one after the other in pair order
+    face_hit: torch.Tensor     # [B,F] bool: the body face is in a crossing pair
+    tri_hit: torch.Tensor      # [nf] bool: the scene triangle is crossed by some body
+    irregular: torch.Tensor    # [] int32: pairs with events != 2
+
+
+def scene_crossings_create(scene_verts, scene_faces):
+    """scene_verts [nv,3] fp32 and scene_faces [nf,3] int32 (tensors on any device, or arrays): the scene mesh, fixed for the life of the
+    handle; degenerate triangles are kept.  The triangles are sorted once on the host along a Morton curve of their centroids into chunks of
+    256 with exact boxes; no kernel runs.  Returns the ``psi_scene_crossings`` handle, a ``hip.Handle`` (``V`` = nv, ``F`` = nf,
+    ``n_chunks`` scene chunks): freed by ``scene_crossings_destroy`` or when its last holder lets go of it.  ``ValueError`` for wrong
+    dtypes or shapes, nf < 1, a face index outside [0, nv), a non-finite referenced vertex."""
+    import numpy as np
+    v, f = _host_array(scene_verts, np.float32, 'scene_verts [nv,3]'), _host_array(scene_faces, np.int32, 'scene_faces [nf,3]')
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError('expected scene_verts [nv,3] float32 and scene_faces [nf,3] int32')
+    nv, nf = int(v.shape[0]), int(f.shape[0])
+    if nf < 1 or nf >= 2 ** 31 or nv < 1:
+        raise ValueError('scene_crossings_create: 1 <= nf < 2^31 and nv >= 1, got nf = %d, nv = %d' % (nf, nv))
+    if f.min() < 0 or f.max() >= nv:
+        raise ValueError('scene_crossings_create: a face index outside [0, %d)' % nv)
+    used = np.zeros(nv, bool)
+    used[f.ravel()] = True
+    if not np.isfinite(v[used]).all():
+        raise ValueError('scene_crossings_create: vertex %d, which a triangle refers to, is not finite'
+                         % int(np.nonzero(used & ~np.isfinite(v).all(1))[0][0]))
+    h = hip.Handle('psi_scene_crossings_destroy')
+    hip.check(hip.lib().psi_scene_crossings_create(ctypes.byref(h), v.ctypes.data_as(ctypes.c_void_p), nv, f.ctypes.data_as(ctypes.c_void_p), nf),
+              'psi_scene_crossings_create')
+    return _with_info(h, 'scene_crossings')
+
+
+def scene_crossings_destroy(handle):
+    handle.close()
+
+
+def scene_crossings(verts, scene_handle, body_handle_or_faces, mode='pruned', return_stats=False):
+    """Which triangles of the body surfaces of a batch properly intersect which triangles of a scene mesh (include/psi_hip.h:
+    psi_scene_crossings_*).  verts [B,V,3] fp32 on the GPU, world frame; ``scene_handle``: a handle of
+    ``scene_crossings_create``; ``body_handle_or_faces``: a handle of ``surface_crossings_create`` or faces [F,3] int32 (a handle is then
+    made and freed by the call); ``mode``: 'pruned', or 'brute', which tests every body chunk against every scene chunk and gives the same
+    bits.  Returns a ``SceneCrossingsResult`` on the device (with ``return_stats`` also {'tiles', 'pairs', 'box_tests'}, at the price of
+    one more read-back).
+
+    The kernels run on the current stream; two scans (``torch.cumsum``), one sort of the int64 pair keys and one ``searchsorted`` are
+    plumbing.  Two read-backs: the number of tiles with the non-finite flag, and the number of pairs; no empty grid is launched.
+    ``ValueError`` for wrong dtypes, shapes or devices, a non-finite vertex (it names the first such body), B > 46340, B F nf >= 2^63 and
+    more than 2^31 - 1 tiles or pairs; ``PsiHipError`` for what the library refuses, CPU tensors included."""
+    def check():
+        if mode not in ('pruned', 'brute'):
+            raise ValueError("mode is 'pruned' or 'brute', got %r" % (mode,))
+        if not isinstance(scene_handle, hip.Handle) or scene_handle.destroy != 'psi_scene_crossings_destroy' or not scene_handle:
+            raise ValueError('scene_crossings: scene_handle is a live handle of scene_crossings_create')
+    B, V, dev, pv, _ = _batch_args(verts, None, 'scene_crossings', then=check, max_B=SURFACE_CROSSINGS_MAX_B)
+    L = hip.lib()
+    brute = 1 if mode == 'brute' else 0
+    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        body = _handle_of(body_handle_or_faces, V, 'surface_crossings')
+        F, nC, nf = body.F, body.n_chunks, scene_handle.F
+        if B * F * nf >= 2 ** 63:
+            raise ValueError('scene_crossings: B F nf = %d x %d x %d does not fit the int64 pair key' % (B, F, nf))
+        st = hip.stream()
+        counts = torch.zeros(B, **i32)
+        contour = torch.zeros(B, dtype=torch.float64, device=dev)
+        face_mask = torch.zeros(B, (F + 31) // 32, **i32)
+        tri_mask = torch.zeros(1, (nf + 31) // 32, **i32)
+        irregular = torch.zeros(1, **i32)
+        pairs, events = torch.empty(0, 3, **i32), torch.empty(0, **i32)
+        length = torch.empty(0, dtype=torch.float32, device=dev)
+        n_pairs = 0
+        chunk_boxes = torch.empty(B, nC, 6, dtype=torch.float32, device=dev)
+        body_boxes = torch.empty(B, 6, dtype=torch.float32, device=dev)
+        bad = torch.empty(1, **i32)
+        job_tiles = torch.empty(B * nC, **i32)
+        hip.check(L.psi_surface_crossings_boxes(body, pv, B, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(bad), st),
+                  'psi_surface_crossings_boxes')
+        hip.check(L.psi_scene_crossings_tiles(scene_handle, body, B, brute, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles),
+                                              None, 0, None, st), 'psi_scene_crossings_tiles')
+        job_inc = torch.cumsum(job_tiles, 0, dtype=torch.int64)
+        n_tiles, first_bad = torch.stack([job_inc[-1], bad[0].to(torch.int64)]).cpu().tolist()              # read-back 1
+        if first_bad < B:
+            raise ValueError('body %d has a non-finite vertex coordinate' % first_bad)
+        if n_tiles > SURFACE_CROSSINGS_MAX:
+            raise ValueError('the batch has %d tiles: more than 2^31 - 1' % n_tiles)
+        if n_tiles > 0:                     # never an empty grid
+            tiles = torch.empty(n_tiles, 4, **i32)
+            job_off = job_inc - job_tiles
+            hip.check(L.psi_scene_crossings_tiles(scene_handle, body, B, brute, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles),
+                                                  hip.ptr(job_off), n_tiles, hip.ptr(tiles), st), 'psi_scene_crossings_tiles')
+            tile_hits = torch.empty(n_tiles, **i32)
+            hip.check(L.psi_scene_crossings_test(scene_handle, body, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), None, 0, None, None,
+                                                 None, st), 'psi_scene_crossings_test')
+            tile_inc = torch.cumsum(tile_hits, 0, dtype=torch.int64)
+            n_pairs = int(tile_inc[-1].item())                                                            # read-back 2
+            if n_pairs > SURFACE_CROSSINGS_MAX:
+                raise ValueError('the batch has %d crossing pairs: more than 2^31 - 1' % n_pairs)
+        if n_pairs > 0:
+            tile_off = tile_inc - tile_hits
+            keys = torch.empty(n_pairs, **i64)
+            ev_raw = torch.empty(n_pairs, **i32)
+            len_raw = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+            hip.check(L.psi_scene_crossings_test(scene_handle, body, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), hip.ptr(tile_off),
+                                                 n_pairs, hip.ptr(keys), hip.ptr(ev_raw), hip.ptr(len_raw), st), 'psi_scene_crossings_test')
+            keys_sorted, order = torch.sort(keys)
+            row_start = torch.searchsorted(keys_sorted, torch.arange(B + 1, **i64) * (F * nf)).contiguous()
+            pairs, events = torch.empty(n_pairs, 3, **i32), torch.empty(n_pairs, **i32)
+            length = torch.empty(n_pairs, dtype=torch.float32, device=dev)
+            hip.check(L.psi_scene_crossings_finish(scene_handle, body, B, hip.ptr(keys_sorted), hip.ptr(order), hip.ptr(ev_raw),
+                                                   hip.ptr(len_raw), n_pairs, hip.ptr(row_start), hip.ptr(pairs), hip.ptr(events),
+                                                   hip.ptr(length), hip.ptr(counts), hip.ptr(contour), hip.ptr(face_mask), hip.ptr(tri_mask),
+                                                   hip.ptr(irregular), st), 'psi_scene_crossings_finish')
+        res = SceneCrossingsResult(pairs, events, length, counts, contour, _unpack_bits(face_mask, F), _unpack_bits(tri_mask, nf)[0], irregular[0])
+    if not return_stats:
+        return res
+    box_tests = 0
+    if n_tiles > 0:                             # the (face, triangle) box tests the test pass executes, counted from the tile table
+        t = tiles.long()
+        na, nb = (F - t[:, 1] * SURFACE_CROSSINGS_CHUNK).clamp(max=SURFACE_CROSSINGS_CHUNK), (nf - t[:, 2] * SURFACE_CROSSINGS_CHUNK).clamp(max=SURFACE_CROSSINGS_CHUNK)
+        box_tests = int((na * nb).sum().item())
+    return res, {'tiles': int(n_tiles), 'pairs': int(n_pairs), 'box_tests': box_tests}
+
+
+# ------------------------------------------------------------------------------------------
 # Surface crossings: the conic distance field of triangle pairs, its loss and gradient (psi_crossing_field_*)
 # ------------------------------------------------------------------------------------------
 CROSSING_FIELD_MAX_PAIRS = 2 ** 27 - 1

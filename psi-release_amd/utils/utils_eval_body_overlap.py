@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """python utils_eval_body_overlap.py GEN_FOLDER [--human_model_path ... --vposer_ckpt_path ... | --synthetic DIR] [--no_flip]
                                                  [--max_inside 0] [--out JSON] [--crossings [--self] [--parts] [--field [--sigma S]]]
-                                                 [--depth [--tol M]]
+                                                 [--depth [--tol M]] [--scene_mesh PLY [--max_scene_pairs 0]]
 
 Which bodies of GEN_FOLDER/body_gen_*.pkl stand in each other: every body is placed as utils_show_test_results.py places it (cam_ext .
 T_mat for Habitat trees, cam_ext with --no_flip for PROX-E), and every vertex of every body is tested against every other body
@@ -25,7 +25,13 @@ every JSON field is what it was.
 --depth adds how far in the vertices are (evaluation.BodyOverlap.depths: the distance of every inside vertex to the nearest triangle of
 the body it is in): the largest and the mean depth of every overlapping ordered pair, the bodies ranked by their deepest vertex, and the
 greedy set of bodies that stand no deeper than --tol metres in each other (evaluation.select_shallow, in file order).  Without --depth
-every printed line and every JSON field is what it was."""
+every printed line and every JSON field is what it was.
+
+--scene_mesh PLY adds the bodies against the room's mesh itself (evaluation.SceneCrossings, DESIGN.md section 10i: which body triangles
+cut which scene triangles, with no distance volume, so a table top thinner than the volume's node spacing is seen): per body the crossing
+pairs and the contour length, the bodies ranked by contour, the irregular pairs, the crossed scene triangles and the bodies that stand
+clear in file order (evaluation.select_clear with --max_scene_pairs).  With --synthetic, --scene_mesh - is the stand-in room
+synth.make_room_mesh().  Without --scene_mesh every printed line and every JSON field is what it was."""
 import argparse
 import json
 
@@ -52,7 +58,15 @@ def parse_args(argv=None):
     ap.add_argument('--sigma', type=float, default=None, metavar='S', help='with --field: the height of the cones, in (0, 0.5]; default 1e-3')
     ap.add_argument('--depth', action='store_true', help='also report how deep the inside vertices are')
     ap.add_argument('--tol', type=float, default=0.0, metavar='M', help='with --depth: the depth two kept bodies may reach in each other, in metres')
+    ap.add_argument('--scene_mesh', default=None, metavar='PLY', help="also test the bodies against this scene mesh ('-' with --synthetic: the stand-in room)")
+    ap.add_argument('--max_scene_pairs', type=int, default=0, help='with --scene_mesh: scene crossings a body of the clear set may have')
     a = ap.parse_args(argv)
+    if a.scene_mesh == '-' and not a.synthetic:
+        ap.error('--scene_mesh - needs --synthetic')
+    if a.max_scene_pairs != 0 and not a.scene_mesh:
+        ap.error('--max_scene_pairs needs --scene_mesh')
+    if a.max_scene_pairs < 0:
+        ap.error('--max_scene_pairs must not be negative')
     if a.tol != 0.0 and not a.depth:
         ap.error('--tol needs --depth')
     if not a.tol >= 0.0:
@@ -142,6 +156,17 @@ def depth_report(max_depth, sum_depth, counts, depth_of, tol):
             'shallow': select_shallow(range(B), max_depth, tol)}
 
 
+def scene_report(res, max_pairs):
+    """The JSON fields of --scene_mesh: ``res`` a SceneCrossingsResult."""
+    from psi_release_amd.evaluation import select_clear
+    counts, contour = res.counts.cpu().numpy().astype(np.int64), res.contour.cpu().numpy()
+    B = len(counts)
+    return {'scene_crossings': counts.tolist(), 'scene_contour': contour.tolist(),
+            'scene_ranked': sorted(range(B), key=lambda i: (-float(contour[i]), i)), 'scene_irregular': int(res.irregular.item()),
+            'scene_triangle_pairs': int(res.pairs.shape[0]), 'scene_triangles_crossed': int(res.tri_hit.sum().item()),
+            'max_scene_pairs': int(max_pairs), 'clear': select_clear(range(B), counts, max_pairs)}
+
+
 def main(argv=None):
     a = parse_args(argv)
     from psi_release_amd import synth
@@ -204,6 +229,23 @@ def main(argv=None):
         for i in drep['deepest_ranked']:
             print('body %6d: deepest vertex %.4f m' % (i, drep['deepest'][i]))
         print('--shallow=' + ','.join(str(i) for i in drep['shallow']))
+    if a.scene_mesh:
+        from psi_release_amd import scene_io
+        from psi_release_amd.evaluation import SceneCrossings
+        if a.scene_mesh == '-':
+            room = synth.make_room_mesh()
+            sverts, sfaces = room.verts, room.faces
+        else:
+            sverts, sfaces, _ = scene_io.read_ply_mesh(a.scene_mesh)
+        scn = SceneCrossings(sverts, sfaces, decoder.faces, device)
+        srep = scene_report(scn.crossings_of_records(xh, camera_pose(cam, a.no_flip), decoder, chunk=a.chunk), a.max_scene_pairs)
+        rep.update(srep)
+        print('[INFO] scene mesh of %d triangles: %d pairs of triangles cross (%d irregular), %d scene triangles crossed' % (
+            len(sfaces), srep['scene_triangle_pairs'], srep['scene_irregular'], srep['scene_triangles_crossed']))
+        for i in range(rep['bodies']):
+            print('body %6d: %6d scene crossings, contour %.4f m' % (i, srep['scene_crossings'][i], srep['scene_contour'][i]))
+        print('--scene_ranked=' + ','.join(str(i) for i in srep['scene_ranked']))
+        print('--clear=' + ','.join(str(i) for i in srep['clear']))
     if a.out:
         with open(a.out, 'w') as f:
             json.dump(rep, f, indent=1)

@@ -9,7 +9,10 @@ from that overview camera; --together adds img_together.png, all bodies from the
 body, the pixels it covers and the pixels of those that the scene does not hide.  With --disjoint [MAX_INSIDE] (it needs --together)
 img_together.png draws only the greedy set of bodies that do not stand in each other (evaluation.BodyOverlap and select_disjoint in file
 order; MAX_INSIDE vertices, default 0, are tolerated per pair), and every row of visibility.json gains ``inside_others``, the number of
-the body's vertices inside other bodies, and ``disjoint``, whether it was drawn.  The reference's interactive window is not included."""
+the body's vertices inside other bodies, and ``disjoint``, whether it was drawn.  With --scene_crossings (it needs a scene mesh) every row of
+visibility.json gains ``scene_crossings``, the pairs of a body triangle and a scene triangle that intersect, and ``scene_contour``, the
+length of their contour in metres (evaluation.SceneCrossings: the mesh itself, no distance volume).  The reference's interactive window is
+not included."""
 import argparse
 import json
 import os
@@ -57,7 +60,10 @@ def parse_args(argv=None):
     ap.add_argument('--human_model_path', default='/is/ps2/yzhang/body_models/VPoser')
     ap.add_argument('--vposer_ckpt_path', default='/is/ps2/yzhang/body_models/VPoser/vposer_v1_0')
     ap.add_argument('--synthetic', default=None, help="stand-in body model and VPoser; with SCENE_PLY '-' also a stand-in room, written to DIR/room.ply")
+    ap.add_argument('--scene_crossings', action='store_true', help='also count, per body, the triangle pairs of the body and the scene mesh that intersect')
     a = ap.parse_args(argv)
+    if a.scene_crossings and a.scene_ply == '-' and not a.synthetic:
+        ap.error('--scene_crossings needs a scene mesh')
     if a.fixed_cam is not None and len(a.fixed_cam) not in (1, 16):
         ap.error('--fixed_cam takes 16 numbers or one .npy file')
     if a.together and a.fixed_cam is None:
@@ -126,6 +132,10 @@ def main(argv=None):
     fixed = None if a.fixed_cam is None else fixed_camera(a.fixed_cam)
     os.makedirs(a.out_dir, exist_ok=True)
     report, all_verts = [], []
+    scene_crossings = None
+    if a.scene_crossings:
+        from psi_release_amd.evaluation import SceneCrossings
+        scene_crossings = SceneCrossings(scene, None, decoder.faces, device)
     for lo in range(0, len(xh), a.pack):
         hi = min(len(xh), lo + a.pack)
         verts = decoder.verts(xh[lo:hi], pose[lo:hi])
@@ -139,6 +149,10 @@ def main(argv=None):
             for i in range(lo, hi):
                 rendering.write_png(os.path.join(a.out_dir, 'img_%06d_%s.png' % (i, name)), rgb[i - lo])
                 rows[i - lo][name] = {'covered': int(counts[i - lo, 0]), 'visible': int(counts[i - lo, 1])}
+        if scene_crossings is not None:
+            sres = scene_crossings.crossings(verts)
+            for row, n, length in zip(rows, sres.counts.cpu().tolist(), sres.contour.cpu().tolist()):
+                row['scene_crossings'], row['scene_contour'] = int(n), float(length)
         report += rows
     if a.together:
         verts = torch.cat(all_verts)
