@@ -294,6 +294,12 @@ int psi_fit_profile(psi_fit_engine *engine, int n_rep, char *h_names, int name_s
  * (int32 bits; at least [B, n_contact], -1 = none) — into d_out (device).  n_floats above a buffer's size, or an unknown name: PSI_EINVAL. */
 int psi_fit_copy_buffer(psi_fit_engine *engine, const char *name, float *d_out, long n_floats, void *stream);
 
+/* The shape of the search role of the engine's shared scene launch: lanes per contact query (2 or 4), slices of 64 contact queries per
+ * search workgroup (1 or 2) and the number of search workgroups of a launch, B * ceil(ceil(n_contact / 64) / slices).  All 0 on an engine
+ * that runs the search as a launch of its own.  Two slices are chosen with 2 lanes unless PSI_FIT_SEARCH_SPW=1 was set when the engine was
+ * created, or the scene's tree is so deep that the shape would lower the number of workgroups a compute unit holds. */
+int psi_fit_search_shape(const psi_fit_engine *engine, int *lanes, int *slices, int *workgroups);
+
 /* ---------------------------------------------------------------------------------------------
  * Dense layers of the CVAEs on the matrix cores — replaces nn.Linear (+ LeakyReLU, + skip connection) of
  *   ResBlock                 net_layers.py:28-43  (fc1 -> LeakyReLU -> fc2 -> LeakyReLU -> + x0)

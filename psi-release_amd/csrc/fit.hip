@@ -49,6 +49,9 @@ __device__ int psi_dbg_cstop;            // dev: end the head kernel behind the 
 // dev (PSI_SKIN_STOP=9): the workgroup timeline of the LAST fwd_scene launch — {start, end} in 10 ns wall-clock ticks, the hardware id
 // words and the kind of workgroup, one record per workgroup (tools/timeline.py draws it)
 __device__ unsigned long long psi_dbg_tl[4 * 8192];
+// ... and one record per WAVE of the workgroup: {end, HW_ID word} — a wave that retires early (waves 2-3 of a 2-lane search workgroup) ends
+// early, and bits 4-5 of the word are the SIMD it ran on
+__device__ unsigned long long psi_dbg_tlw[2 * 4 * 8192];
 struct PsiBlockTrace {
     unsigned long long t0;
     int kind;
@@ -57,7 +60,13 @@ struct PsiBlockTrace {
     __device__ ~PsiBlockTrace()
     {
         const unsigned bid = blockIdx.y * gridDim.x + blockIdx.x;
-        if (psi_dbg_sstop < sel_lo || psi_dbg_sstop > sel_hi || threadIdx.x != 0 || bid >= 8192) return;
+        if (psi_dbg_sstop < sel_lo || psi_dbg_sstop > sel_hi || bid >= 8192) return;
+        if ((threadIdx.x & 63) == 0 && threadIdx.x < 256) {
+            unsigned long long *w = psi_dbg_tlw + 2 * (4 * (size_t)bid + (threadIdx.x >> 6));
+            w[0] = wall_clock64();
+            w[1] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);
+        }
+        if (threadIdx.x != 0) return;
         unsigned long long *o = psi_dbg_tl + 4 * (size_t)bid;
         o[0] = t0;
         o[1] = wall_clock64();
@@ -68,6 +77,10 @@ struct PsiBlockTrace {
 extern "C" int psi_dbg_timeline(unsigned long long *out, int nblocks)
 {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(psi_dbg_tl), sizeof(unsigned long long) * 4 * (size_t)(nblocks < 8192 ? nblocks : 8192));
+}
+extern "C" int psi_dbg_timeline_waves(unsigned long long *out, int nblocks)
+{
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(psi_dbg_tlw), sizeof(unsigned long long) * 8 * (size_t)(nblocks < 8192 ? nblocks : 8192));
 }
 #endif
 #include "lbs_device.h"
@@ -727,12 +740,15 @@ __device__ __forceinline__ void psi_contact_part_sums(float x, float (&out)[psi_
 //   LPQ = 2 (two lanes per query, 128 threads of the workgroup: nnindex_device.h): lane 0 builds rows 0 AND 2, lane 1 row 1 — the same
 // ascending-joint chains, so the query point, the gradient rows and the hints are bit-identical to the 4-lane form; the 128 threads stage the
 // transforms in three pieces each.
-template <int LPQ>
+// SPW = 2 (two slices per workgroup, nnindex_device.h: kd_query_body): all 256 threads are present and stage the transforms ONCE for both wave
+// pairs, in two pieces each as the 4-lane form does; each pair reduces its own slice (contact_finish) in its own slots.
+template <int LPQ, int SPW = 1>
 struct ContactSkinSrc {
     static_assert(LPQ == 2 || LPQ == 4, "the query's lane group skins its own vertex with 2 or 4 lanes");
-    static constexpr int NT = psikd::kd_threads(LPQ);             // threads of the workgroup that are present
+    static_assert(SPW == 1 || (SPW == 2 && LPQ == 2), "two slices per workgroup: the 2-lane search");
+    static constexpr int NT = SPW * psikd::kd_threads(LPQ);       // threads of the workgroup that are present
     static constexpr int NST = (PSI_JP * 6 + NT - 1) / NT;        // pieces of the body's transforms per thread: 2 (256 threads) or 3 (128)
-    static constexpr int CT0 = LPQ == 2 ? 80 : 128;               // first of the 15 threads that fetch the camera / translation: their last piece is beyond J <= 56
+    static constexpr int CT0 = NT == 128 ? 80 : 128;              // first of the 15 threads that fetch the camera / translation: their last piece is beyond J <= 56
     FitDev f;
     LbsDev m;
     const float *As, *v_posed;
@@ -791,7 +807,7 @@ struct ContactSkinSrc {
     {
         psi_f2 (*sA_)[6] = psi_transform_stage<1>()[0];           // (shared with the skinning workgroups of the launch: lbs_device.h)
         __shared__ float sCT_[16];
-        __shared__ float sTR_[psikd::kd_qpb(LPQ)][9];
+        __shared__ float sTR_[SPW * psikd::kd_qpb(LPQ)][9];
 #pragma unroll
         for (int q = 0; q < NST; q++) {
             const int idx = threadIdx.x + q * NT;
@@ -884,13 +900,25 @@ struct ContactSkinSrc {
         if constexpr (LPQ != 2) psi_st(f.vpc + row, off, psi_p3{px, py, pz});
         gs[0] = lx; gs[1] = ly; gs[2] = lz;
     }
+    // (SPW == 2: bx is the SLICE of this thread's wave pair and nbx the body's slice count; each pair has its own slots)
     __device__ __forceinline__ void contact_finish(int b, int bx, int nbx)
     {
         if (!f.fused_bwd) return;
         // the three sums per part and slot of search_sum_order.h (the slice's value does not depend on LPQ); the maximum in any order
         constexpr int PPW = psi_sum_parts_per_wave(LPQ);
-        __shared__ float wsum3[psi_sum_parts(LPQ)][3];
-        __shared__ float wmax[psi_sum_waves(LPQ)];
+        // (SPW == 2: both tables of both pairs lie in the transforms' staging area, which no wave reads any more — every live wave has passed
+        // kd_block_fsum's barrier, behind point() — so that the workgroup's LDS stays under the step at which a CU holds five, not six)
+        __shared__ float wsum3_[SPW == 2 ? 1 : psi_sum_parts(LPQ)][3];
+        __shared__ float wmax_[SPW == 2 ? 1 : psi_sum_waves(LPQ)];
+        float (*wsum3)[3] = wsum3_;
+        float *wmax = wmax_;
+        if constexpr (SPW == 2) {
+            static_assert(sizeof(psi_f2) * 6 * PSI_JP >= sizeof(float) * (SPW * psi_sum_parts(LPQ) * 3 + SPW * psi_sum_waves(LPQ)), "the staging area holds both tables");
+            float *dead = (float *)&psi_transform_stage<1>()[0][0][0];
+            wsum3 = (float (*)[3])dead;
+            wmax = dead + SPW * psi_sum_parts(LPQ) * 3;
+        }
+        const int pr = SPW == 2 ? (bx & 1) : 0, t0 = pr * psi_sum_wg_pair_threads(LPQ);       // my pair (slice 2 bx' + pair), its first thread (0, 0 when SPW == 1)
         float sx[PPW], sy[PPW], sz[PPW];
         psi_contact_part_sums<LPQ>(gs[0], sx);
         psi_contact_part_sums<LPQ>(gs[1], sy);
@@ -901,24 +929,25 @@ struct ContactSkinSrc {
         if ((threadIdx.x & 63) == 0) {
 #pragma unroll
             for (int p = 0; p < PPW; p++) {
-                wsum3[psi_sum_slot(LPQ, threadIdx.x >> 6, p)][0] = sx[p];
-                wsum3[psi_sum_slot(LPQ, threadIdx.x >> 6, p)][1] = sy[p];
-                wsum3[psi_sum_slot(LPQ, threadIdx.x >> 6, p)][2] = sz[p];
+                const unsigned s = SPW == 2 ? psi_sum_wg_slot(LPQ, SPW, threadIdx.x >> 6, p) : psi_sum_slot(LPQ, threadIdx.x >> 6, p);
+                wsum3[s][0] = sx[p];
+                wsum3[s][1] = sy[p];
+                wsum3[s][2] = sz[p];
             }
             wmax[threadIdx.x >> 6] = mx;
         }
         __syncthreads();
-        if (threadIdx.x == 64) {
-            float m2 = wmax[0];
+        if ((int)threadIdx.x == t0 + 64) {
+            float m2 = wmax[pr * psi_sum_waves(LPQ)];
 #pragma unroll
-            for (int w = 1; w < psi_sum_waves(LPQ); w++) m2 = fmaxf(m2, wmax[w]);
+            for (int w = 1; w < psi_sum_waves(LPQ); w++) m2 = fmaxf(m2, wmax[pr * psi_sum_waves(LPQ) + w]);
             if (m2 > 0.0f) atomicMax(f.gvbits + PSI_GV_SLOTS + (size_t)b * f.gv_sps + (bx & (f.gv_sps - 1)), __float_as_uint(m2));
         }
-        if (threadIdx.x < 3) {
+        if ((int)threadIdx.x >= t0 && (int)threadIdx.x < t0 + 3) {
             float a = 0.0f;
 #pragma unroll
-            for (int w = 0; w < psi_sum_parts(LPQ); w++) a += wsum3[w][threadIdx.x];
-            f.gtc_part[((size_t)b * nbx + bx) * 4 + threadIdx.x] = a;
+            for (int w = 0; w < psi_sum_parts(LPQ); w++) a += wsum3[pr * psi_sum_parts(LPQ) + w][(int)threadIdx.x - t0];
+            f.gtc_part[((size_t)b * nbx + bx) * 4 + ((int)threadIdx.x - t0)] = a;
         }
     }
 };
@@ -934,7 +963,7 @@ extern "C" int psi_dbg_kd_stat(int *out, int nblocks)
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(psi_kd_stat), sizeof(int) * 4 * (size_t)(nblocks < 8192 ? nblocks : 8192));
 }
 #endif
-// ONE launch for the two scene terms of the forward pass: block ids [0, n_kd) are the NN-search workgroups (64 contact queries of
+// ONE launch for the two scene terms of the forward pass: block ids [0, n_kd) are the NN-search workgroups (SPW slices of 64 contact queries of
 // one body each; long, VALU-issue-bound pointer chases — dispatched first), the rest are the skinning + SDF workgroups (256
 // vertices of one body each; gather-latency-bound).  As two launches they ran back to back (23 + 18 us); they depend on the same
 // inputs only, so in one grid their waves share the SIMDs and hide each other's stalls.
@@ -948,9 +977,15 @@ template <bool SCENES>
 using SceneTrees = std::conditional_t<SCENES, const psikd::KdDev *__restrict__, psikd::KdDev>;      // one tree in the arguments / a table on the device
 
 // LPQ: lanes per contact query of the search role (2 or 4: fit_decide)
-template <int NB, bool SCENES, int LPQ>
+// SPW: slices of 64 contact queries per search workgroup (1, or 2 with LPQ = 2: fit_decide).  With two, all four waves of a search workgroup
+// carry queries — n_kd = B * nqb workgroups, nqb = cdiv(nfp, 2) per body — where the 2-lane search with one slice left waves 2 and 3 dead
+// while the workgroup's LDS stayed allocated: half as many search workgroups hold the same live waves, and the slots they free take skinning
+// workgroups from the start of the launch (profiles/search_shape_ab.txt).  The dynamic LDS is the same 64 * rows * 8 bytes, now the column
+// lists of 128 queries; the rare tree walk keeps its stack in kd_stack (global memory).
+template <int NB, bool SCENES, int LPQ, int SPW>
 __global__ __launch_bounds__(256, 6) void fwd_scene_kernel(FitDev f, LbsDev m, const float *__restrict__ As, const float *__restrict__ v_posed,
-                                                           SceneTrees<SCENES> T, int n_kd, int nqb, int rows, float gscale, int skin_first, SdfEpilogue<SCENES> epi)
+                                                           SceneTrees<SCENES> T, int n_kd, int nqb, int rows, float gscale, int skin_first, SdfEpilogue<SCENES> epi,
+                                                           int *__restrict__ kd_stack)
 {
     extern __shared__ int smem_i[];
 #ifdef PSI_HEAD_STOPS
@@ -983,8 +1018,9 @@ __global__ __launch_bounds__(256, 6) void fwd_scene_kernel(FitDev f, LbsDev m, c
             tab = T;
             slot = epi.slot;
         } else tree = T;
-        psikd::kd_query_body<LPQ, true, SCENES>(tree, ContactSkinSrc<LPQ>{f, m, As, v_posed, nullptr, {}, 0.0f, 0, 0.0f, 0.0f, 0.0f, nullptr, {}, 0}, f.n_c, (float *)nullptr, (int *)nullptr,
-                                           f.cconst, gscale, f.fused_bwd ? (float *)nullptr : f.gq, f.fpart, f.nn_hint, rows, tab, slot, bx, b, nqb, smem_i);
+        // (nbx of the search body counts SLICES: f.nfp; nqb == f.nfp when SPW == 1)
+        psikd::kd_query_body<LPQ, true, SCENES, SPW>(tree, ContactSkinSrc<LPQ, SPW>{f, m, As, v_posed, nullptr, {}, 0.0f, 0, 0.0f, 0.0f, 0.0f, nullptr, {}, 0}, f.n_c, (float *)nullptr, (int *)nullptr,
+                                           f.cconst, gscale, f.fused_bwd ? (float *)nullptr : f.gq, f.fpart, f.nn_hint, rows, tab, slot, bx, b, SPW == 2 ? f.nfp : nqb, smem_i, kd_stack);
     } else {
         const int i = bid;
         if constexpr (SCENES) epi.template load_grids<NB>((i / f.nsdfblk) * NB, f.B);
@@ -1694,7 +1730,7 @@ constexpr int GRAPH_UNROLL = PSI_GRAPH_UNROLL;
 // accepted leaves the default (0 in the int fields)
 struct FitKnobs {
     bool split_scene, keep_verts, no_fused_bwd, sdf_linear, scene_skin_first, bwdv_mb, no_pen_skip, bwd_pf1, chain_in_head;
-    int head_cluster, skin_nb, ska_nbody, search_lanes;
+    int head_cluster, skin_nb, ska_nbody, search_lanes, search_spw;
 #ifdef PSI_HEAD_STOPS
     int head_stop, tail_stop, skin_stop;      // tools/head_stops.sh
 #endif
@@ -1720,6 +1756,7 @@ static FitKnobs fit_read_knobs()
     k.ska_nbody = psi_ska_nbody_override(SKA_NBODY);
     const int sl = num("PSI_FIT_SEARCH_LANES");
     if (sl == 2 || sl == 4) k.search_lanes = sl;
+    if (num("PSI_FIT_SEARCH_SPW") == 1) k.search_spw = 1;
 #ifdef PSI_HEAD_STOPS
     k.head_stop = num("PSI_HEAD_STOP");
     k.tail_stop = num("PSI_TAIL_STOP");
@@ -1736,6 +1773,7 @@ struct FitModes {
     bool fused_bwd;               // the skinning backward rides on fwd_scene (see fit_bwd_joint_kernel): six launches per iteration, no per-vertex backward launch
     int skin_nb;                  // bodies per workgroup of the forward skinning + SDF kernel (1 or 2: lbs_device.h)
     int search_lanes;             // lanes per contact query of the search role of the shared launch (2 or 4: nnindex_device.h)
+    int search_spw;               // slices of 64 contact queries per search workgroup of the shared launch (2 with 2 lanes, else 1)
     int hc;                       // workgroups per body in the head / tail kernels (FitDev::hc)
     int gv_sps;                   // slots per body and class of the rows' maxima (FitDev::gv_sps)
     PsiStreamSplit split;         // column slices of the stream workgroups of fit_bwd_joint_kernel per row class, steps per slice (ska_plan.h)
@@ -1761,6 +1799,9 @@ static FitModes fit_decide(const psi_fit_config *cfg, const FitKnobs &knobs, int
     // PSI_FIT_SEARCH_LANES=2|4 overrides.
     d.search_lanes = knobs.search_lanes ? knobs.search_lanes : mc.compressed_weights ? 4 : PSI_FIT_SEARCH_LANES_DEFAULT;
     d.merged_scene = d.self_skin && cfg->B <= 128 && !knobs.split_scene;
+    // Slices per search workgroup: two wherever the search has 2 lanes — all four waves of a search workgroup live, half as many of them
+    // (fwd_scene_kernel; profiles/search_shape_ab.txt).  PSI_FIT_SEARCH_SPW=1: one, waves 2 and 3 retire at once (the shape before).
+    d.search_spw = d.search_lanes == 2 && !knobs.search_spw ? 2 : 1;
     // the vertices themselves are an output nobody reads when the search skins its own queries (the shared launch): not stored there
     // (psi_fit_copy_buffer("verts") produces them on demand); with separate launches the search reads its contact rows, which are the
     // only ones stored (fit_forward); PSI_KEEP_VERTS=1 stores all of them in every iteration
@@ -1932,6 +1973,10 @@ struct psi_fit_engine {
     PsiSdfGrid *d_grid_tab;       // device [n_scenes]
     int *d_slot;                  // device [B], every entry inside [0, n_scenes)
     int kd_rows;                  // the largest traversal stack of the set (the search's LDS)
+    // two slices per search workgroup (mode.search_spw == 2, settled by fit_search_shape): the tree walk's stacks, [B][n_c][2][rows] words, a
+    // blob of their own because the rows are known only once the index is built; null otherwise
+    char *search_blob;
+    int *kd_stack;
     FitGraph graphs[FIT_N_GRAPHS];
     // the captured graphs bake the statistics pointer (and the data-parallel ones the communicator) in
     const float *half_stats[2];
@@ -2014,11 +2059,11 @@ static int fit_launch_stats(psi_fit_engine *e, float *stats, hipStream_t st)
 
 // The scene stage's two launch kinds, each for one (bodies per skinning workgroup, one scene / a table of scenes); fit_scene_dispatch
 // picks the instance of an engine
-template <int NB, bool SCENES, int LPQ>
+template <int NB, bool SCENES, int LPQ, int SPW>
 static void launch_fwd_scene(const psi_fit_engine *e, float gscale, hipStream_t st)
 {
     const FitDev &f = e->d;
-    const int nqb = f.nfp, n_kd = nqb * f.B, skin_first = e->knobs.scene_skin_first ? 1 : 0;
+    const int nqb = psi_cdiv(f.nfp, SPW), n_kd = nqb * f.B, skin_first = e->knobs.scene_skin_first ? 1 : 0;
     const dim3 grid(n_kd + f.nsdfblk * psi_cdiv(f.B, NB));
     FitDev fk = f;
     if (!e->mode.keep_verts) fk.verts = nullptr;
@@ -2032,8 +2077,8 @@ static void launch_fwd_scene(const psi_fit_engine *e, float gscale, hipStream_t 
         T = psi_nn_index_dev(e->nn_index);
         rows = T.rows;
     }
-    hipLaunchKernelGGL((fwd_scene_kernel<NB, SCENES, LPQ>), grid, dim3(256), psikd::kd_lds_bytes(LPQ, rows), st, fk, e->lv.m, e->lv.A, e->lv.v_posed, T, n_kd, nqb, rows,
-                       gscale, skin_first, epi);
+    hipLaunchKernelGGL((fwd_scene_kernel<NB, SCENES, LPQ, SPW>), grid, dim3(256), psikd::kd_lds_bytes(LPQ, rows), st, fk, e->lv.m, e->lv.A, e->lv.v_posed, T, n_kd, nqb, rows,
+                       gscale, skin_first, epi, e->kd_stack);
 }
 
 template <int NB, bool SCENES>
@@ -2067,8 +2112,9 @@ static int fit_forward(psi_fit_engine *e, float *stats, hipStream_t st, FitStats
     if (e->nn_index && e->mode.merged_scene) {
         // skinning + SDF and the NN search of the contact vertices as ONE launch (fwd_scene_kernel)
         fit_scene_dispatch(e, [&](auto nb, auto scenes) {
-            if (e->mode.search_lanes == 2) launch_fwd_scene<decltype(nb)::value, decltype(scenes)::value, 2>(e, gscale, st);
-            else launch_fwd_scene<decltype(nb)::value, decltype(scenes)::value, 4>(e, gscale, st);
+            if (e->mode.search_lanes == 2 && e->mode.search_spw == 2) launch_fwd_scene<decltype(nb)::value, decltype(scenes)::value, 2, 2>(e, gscale, st);
+            else if (e->mode.search_lanes == 2) launch_fwd_scene<decltype(nb)::value, decltype(scenes)::value, 2, 1>(e, gscale, st);
+            else launch_fwd_scene<decltype(nb)::value, decltype(scenes)::value, 4, 1>(e, gscale, st);
         });
         PSI_CHECK_LAUNCH("fwd_scene_kernel");
         psi_mark("fwd_scene_kernel", st);
@@ -2195,6 +2241,44 @@ static int fit_scene_index(psi_nn_index **out, const float *d_verts, int m, hipE
     std::vector<float> hs((size_t)m * 3);
     *err = hipMemcpy(hs.data(), d_verts, hs.size() * 4, hipMemcpyDeviceToHost);
     return *err == hipSuccess ? psi_nn_index_create(out, hs.data(), m) : (int)*err;
+}
+
+// Two slices per search workgroup, once the index exists (its rows size the launch's dynamic LDS and the walk's stacks): the shape is kept only
+// where it costs no residency (search_shape.h: psi_search_spw_for, with the static LDS of the engine's two instances as the runtime reports
+// it) and a body's stacks stay inside a 32-bit offset; else the engine falls back to one slice.  The stacks (nnindex_device.h:
+// kd_query_round<.., SPW = 2>): a region of 2 rows words per contact query of every body.  Nothing reads an entry the same query has not
+// written in the same launch: no fill.
+template <int NB, bool SCENES, int SPW>
+static size_t fwd_scene_static_lds()
+{
+    hipFuncAttributes a;
+    if (hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&fwd_scene_kernel<NB, SCENES, 2, SPW>)) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return a.sharedSizeBytes;
+}
+static int fit_search_shape(psi_fit_engine *e)
+{
+    const FitDev &f = e->d;
+    const char *who = e->n_scenes ? "psi_fit_create_scenes" : "psi_fit_create";
+    const int rows = e->n_scenes ? e->kd_rows : psi_nn_index_dev(e->nn_index).rows;
+    int dev = 0, lds_cu = 0;
+    PSI_CHECK_HIP(hipGetDevice(&dev));
+    if (hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess) {
+        (void)hipGetLastError();
+        lds_cu = 0;
+    }
+    size_t s1 = 0, s2 = 0;
+    fit_scene_dispatch(e, [&](auto nb, auto scenes) {
+        s1 = fwd_scene_static_lds<decltype(nb)::value, decltype(scenes)::value, 1>();
+        s2 = fwd_scene_static_lds<decltype(nb)::value, decltype(scenes)::value, 2>();
+    });
+    e->mode.search_spw = psi_search_stack_fits(f.n_c, rows) ? psi_search_spw_for((size_t)lds_cu, s1, s2, psikd::kd_lds_bytes(2, rows), 6) : 1;
+    if (e->mode.search_spw != 2) return 0;
+    PsiBlob T;
+    T.raw(e->kd_stack, psi_search_stack_bytes(f.B, f.n_c, rows));
+    return psi_blob_realise(T, &e->search_blob, who);
 }
 
 // psi_fit_create (h_scenes == nullptr: the one scene of the four scene arguments) and psi_fit_create_scenes (the four arguments are those of
@@ -2386,6 +2470,8 @@ static int fit_create(psi_fit_engine **out, const psi_lbs_model *lbs, const psi_
     } else if (cfg->nn_mode == 1) {
         if (int rc = fit_scene_index(&e->nn_index, d_scene_verts, f.m, &err)) return rc;
     }
+    if (e->nn_index && mode.merged_scene && mode.search_spw == 2)
+        if (int rc = fit_search_shape(e)) return rc;
     owner.release();
     *out = e;
     return 0;
@@ -2509,6 +2595,7 @@ extern "C" void psi_fit_destroy(psi_fit_engine *e)
         delete[] e->scene_vol;
     }
     (void)hipFree(e->scene_blob);
+    (void)hipFree(e->search_blob);
     for (FitGraph &G : e->graphs) fit_graph_drop(&G);
     (void)hipFree(e->blob);
     delete e;
@@ -2759,6 +2846,16 @@ extern "C" int psi_fit_read_losses(psi_fit_engine *e, int adam_step, float *d_ou
     PSI_REQUIRE(e && d_out4 && adam_step >= 1, "bad arguments");
     FitDev &f = e->d;
     PSI_CHECK_HIP(hipMemcpyAsync(d_out4, f.history + (size_t)((adam_step - 1) % f.max_hist) * 4, 16, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int psi_fit_search_shape(const psi_fit_engine *e, int *lanes, int *slices, int *workgroups)
+{
+    PSI_REQUIRE(e && lanes && slices && workgroups, "null pointer");
+    const bool shared = e->nn_index && e->mode.merged_scene;
+    *lanes = shared ? e->mode.search_lanes : 0;
+    *slices = shared ? e->mode.search_spw : 0;
+    *workgroups = shared ? e->d.B * psi_cdiv(e->d.nfp, e->mode.search_spw) : 0;
     return 0;
 }
 

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(QBLK) void kd_query_kernel(KdDev T0, const float *_
                                                         const int *__restrict__ slot = nullptr)
 {
     extern __shared__ int smem_i[];
-    kd_query_body<LPQ, CONTACT, MULTI>(T0, KdQueryFromMemory{xyz1, qidx, qstride}, n, dist, idx, cconst, gscale, gq, fpart, hint, rows, tab, slot,
+    kd_query_body<LPQ, CONTACT, MULTI, 1>(T0, KdQueryFromMemory{xyz1, qidx, qstride}, n, dist, idx, cconst, gscale, gq, fpart, hint, rows, tab, slot,
                                   (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, smem_i);
 }
 

@@ -6,6 +6,7 @@
 #include <math.h>
 #include "psi_common.h"
 #include "search_sum_order.h"
+#include "search_shape.h"
 
 #ifndef PSI_SSTOP
 #define PSI_SSTOP(k)
@@ -170,25 +171,49 @@ struct KdQueryFromMemory {
 
 // sum of the per-group contact terms over the workgroup -> *out: the halving tree and the slots of search_sum_order.h, i.e. the same
 // association for every LPQ that shares the slice (2 and 4)
-template <int LPQ>
-__device__ __forceinline__ void kd_block_fsum(float fval, float *__restrict__ out)
+// SPW = 2 (two slices per workgroup, search_sum_order.h): every wave pair reduces its own slice into its own four slots, and the first thread of
+// each pair writes its slice's value to ITS `out`
+// (pr: the caller's pair, uniform over its waves)
+template <int LPQ, int SPW = 1>
+__device__ __forceinline__ void kd_block_fsum(float fval, float *__restrict__ out, int pr = 0)
 {
-    __shared__ float wsum[psi_sum_parts(LPQ)];
+    __shared__ float wsum[SPW * psi_sum_parts(LPQ)];
     const int tid = threadIdx.x;
     float v = fval;
 #pragma unroll
     for (int o2 = psi_sum_part_lanes(LPQ) / 2; o2 > 0; o2 >>= 1) v += __shfl_down(v, o2, 64);
 #pragma unroll
     for (int p = 0; p < psi_sum_parts_per_wave(LPQ); p++)
-        if ((tid & 63) == psi_sum_first_lane(LPQ, p)) wsum[(int)psi_sum_slot(LPQ, tid >> 6, p)] = v;
+        if ((tid & 63) == psi_sum_first_lane(LPQ, p)) wsum[(int)(SPW == 2 ? psi_sum_wg_slot(LPQ, SPW, tid >> 6, p) : psi_sum_slot(LPQ, tid >> 6, p))] = v;
     __syncthreads();
-    if (tid == 0) {
+    if (tid == pr * psi_sum_wg_pair_threads(LPQ)) {
         float t = 0.0f;
 #pragma unroll
-        for (int w = 0; w < psi_sum_parts(LPQ); w++) t += wsum[w];
+        for (int w = 0; w < psi_sum_parts(LPQ); w++) t += wsum[pr * psi_sum_parts(LPQ) + w];
         *out = t;
     }
 }
+
+// The traversal stack of the tree walk.  SPW == 1: the query's LDS rows (plain accesses).  SPW == 2: the query's region of an engine-owned
+// buffer in global memory (the LDS rows hold the grid scan's column list only).  Entries are written by one lane of the query's group and read
+// by all of them, so with global memory the pushes are completed (release) before the next pop is requested, and a pop's values are
+// acquired, at workgroup scope: the lanes of a group are lanes of one wave, whose vector memory operations issue in order.
+template <int SPW, class T>
+__device__ __forceinline__ T kd_stack_ld(const T *p)
+{
+    if constexpr (SPW == 2) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else return *p;
+}
+template <int SPW, class T>
+__device__ __forceinline__ void kd_stack_st(T *p, T v)
+{
+    if constexpr (SPW == 2) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else *p = v;
+}
+template <int SPW>
+__device__ __forceinline__ void kd_stack_pushed() { if constexpr (SPW == 2) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); }
+template <int SPW>
+__device__ __forceinline__ void kd_stack_popped() { if constexpr (SPW == 2) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
 
 // The warm-start candidate of a query: last iteration's winner (hint[o], -1 = none) and its coordinates.  Two dependent loads that need
 // nothing but the query's slot, as two calls: callers issue the first together with their own first loads and the second together with
@@ -214,17 +239,18 @@ __device__ __forceinline__ T &kd_slot(T *tab, size_t obase, int jq, int K, int k
 // term s / (s + c) of the query in lane 0 of its group (0 elsewhere) when CONTACT.  No barriers inside: groups are independent.
 // o == obase + jq, obase uniform over the workgroup: with two lanes per query the outputs are addressed as (uniform base) + (32-bit lane
 // offset), so that no 64-bit lane address waits in registers across the search (kd_slot).
-template <int LPQ, int RPL, bool CONTACT, class QSrc>
+// SPW = 2: the workgroup carries 128 queries; stk_n is the query's [rows] column list in LDS and the walk's stack lives in gstk (kd_stack_*)
+template <int LPQ, int RPL, bool CONTACT, int SPW, class QSrc>
 __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, float qx, float qy, float qz, bool active, size_t o, float *__restrict__ dist,
                                                 int *__restrict__ idx, float cconst, float gscale, float *__restrict__ gq, int *__restrict__ hint,
-                                                int rows, int *smem_i, int h, const float4 &hp, size_t obase, int jq)
+                                                int rows, int *smem_i, int h, const float4 &hp, size_t obase, int jq, int *__restrict__ gstk)
 {
 #pragma clang fp contract(off)    // the distance expression (PSI_SQ3) must not be re-contracted in translation units built with contraction on
     constexpr int CPL = kd_cpl(LPQ);
     const int tid = threadIdx.x;
     const int c = tid & (LPQ - 1);                            // my first child / leaf slot (the others: c + LPQ, ...)
     const int g = tid / LPQ;                                  // query group inside the workgroup
-    int *stk_n = smem_i + (size_t)g * rows * 2;               // [rows] child references
+    int *stk_n = smem_i + (size_t)g * rows * (SPW == 2 ? 1 : 2);      // [rows] child references (SPW == 2: the column list only)
     float *stk_d = (float *)(stk_n + rows);                   // [rows] box distances
     kd_key bestk = kd_pack(INFINITY, 0x7fffffff);
     float best = INFINITY;                                    // == kd_key_d(bestk)
@@ -305,7 +331,7 @@ __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, floa
         if (fncand <= (float)GRID_MAX_CAND) {
             const int ncand = (int)fncand;
             const float rny = __builtin_amdgcn_rcpf(fny);
-            const int list_max = min(GRID_LIST_MAX, 2 * rows);  // the list lives in the group's stack rows
+            const int list_max = min(GRID_LIST_MAX, SPW == 2 ? rows : 2 * rows);  // the list lives in the group's stack rows
             int nsurv = 0;
             for (int c0 = 0; c0 < ncand; c0 += LPQ) {          // (uniform over the group)
                 const float fcol = (float)(c0 + c);
@@ -402,11 +428,23 @@ __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, floa
             } else { PSI_KD_STAT(if (c == 0 && psi_dbg_sstop == 10) { atomicAdd(psi_kd_reason + 1, 1); atomicMax(psi_kd_reason + 5, nsurv); }) }
         } else { PSI_KD_STAT(if (c == 0 && psi_dbg_sstop == 10) { atomicAdd(psi_kd_reason + 0, 1); atomicMax(psi_kd_reason + 4, (int)fminf(fncand, 1e6f)); }) }
     } else { PSI_KD_STAT(if (have && c == 0 && psi_dbg_sstop == 10) atomicAdd(psi_kd_reason + 3, 1);) }
+    // the walk's stack, entry i: the query's LDS rows, or (SPW == 2) the query's 8 rows bytes of gstk as uniform base + 32-bit lane offset
+    // (search_shape.h; obase = b * n)
+    char *const gbase = SPW == 2 ? (char *)gstk + obase * (size_t)rows * 8 : nullptr;
+    auto ref_at = [&](int i) -> int * {
+        if constexpr (SPW == 2) return (int *)(gbase + psi_search_stack_entry(jq, rows, 0, i));
+        else return stk_n + i;
+    };
+    auto dist_at = [&](int i) -> float * {
+        if constexpr (SPW == 2) return (float *)(gbase + psi_search_stack_entry(jq, rows, 1, i));
+        else return stk_d + i;
+    };
     while (true) {
         while (!have && sp > 0) {                             // pop until something survives the current bound (group-uniform)
             --sp;
-            cur = stk_n[sp];
-            curd = stk_d[sp];
+            cur = kd_stack_ld<SPW>(ref_at(sp));
+            curd = kd_stack_ld<SPW>(dist_at(sp));
+            kd_stack_popped<SPW>();
             have = !(curd * 0.999999f > best);
         }
         if (!have) break;
@@ -440,11 +478,12 @@ __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, floa
                 const unsigned gm = (unsigned)(__ballot(push) >> gshift) & ((1u << LPQ) - 1u);
                 if (push) {
                     const int pos = sp + __popc(gm & ((1u << c) - 1u));
-                    stk_n[pos] = ref[u];
-                    stk_d[pos] = dc[u];
+                    kd_stack_st<SPW>(ref_at(pos), ref[u]);
+                    kd_stack_st<SPW>(dist_at(pos), dc[u]);
                 }
                 sp += __popc(gm);
             }
+            kd_stack_pushed<SPW>();
             int rsel = ref[0];
 #pragma unroll
             for (int u = 1; u < CPL; u++) rsel = (cmin / LPQ == u) ? ref[u] : rsel;
@@ -513,15 +552,22 @@ __device__ __forceinline__ float kd_query_round(const KdDev &T, QSrc &qsrc, floa
 // body of the search for workgroup (bx, b) of an (nbx, B) grid; smem_i: kd_qpb(LPQ) * rows * 8 bytes of LDS for the traversal stacks
 // (launched with QBLK threads for every LPQ; the threads beyond kd_threads(LPQ) — waves 2 and 3 with 2 lanes per query — leave before the
 // source's first load: the workgroup's barriers count the waves that are left)
-template <int LPQ, bool CONTACT, bool MULTI, class QSrc>
+// SPW = 2 (LPQ = 2 only): all four waves carry queries — waves 0-1 slice 2 bx, waves 2-3 slice 2 bx + 1 of body b, nbx counting SLICES; the
+// second pair of a body's last workgroup leaves behind the source's workgroup phase when the slice count is odd.  smem_i then holds
+// kd_qpb(LPQ) * rows * 8 bytes for 128 queries (the column lists), gstk the walk's stacks: B * n * rows * 8 bytes.
+template <int LPQ, bool CONTACT, bool MULTI, int SPW, class QSrc>
 __device__ __forceinline__ void kd_query_body(KdDev T0, QSrc qsrc, int n, float *__restrict__ dist, int *__restrict__ idx, float cconst,
                                               float gscale, float *__restrict__ gq, float *__restrict__ fpart, int *__restrict__ hint,
                                               int rows, const KdDev *__restrict__ tab, const int *__restrict__ slot, int bx, int b, int nbx,
-                                              int *smem_i)
+                                              int *smem_i, int *__restrict__ gstk = nullptr)
 {
-    constexpr int QPB = kd_qpb(LPQ);
+    static_assert(SPW == 1 || (SPW == 2 && 2 * kd_threads(LPQ) == QBLK), "two slices per workgroup: two wave pairs of 64 queries");
+    constexpr int QPB = SPW * kd_qpb(LPQ);
     const int tid = threadIdx.x;
-    if (kd_threads(LPQ) < QBLK && tid >= kd_threads(LPQ)) return;
+    if (SPW == 1 && kd_threads(LPQ) < QBLK && tid >= kd_threads(LPQ)) return;
+    // my pair (uniform over a wave: a scalar) and my slice of the body (== bx when SPW == 1)
+    const int pr = SPW == 2 ? __builtin_amdgcn_readfirstlane(psi_sum_wg_pair(LPQ, SPW, tid)) : 0;
+    const int sl = psi_sum_wg_slice(SPW, bx, pr);
     const int c = tid & (LPQ - 1), g = tid / LPQ;
     const KdDev T = MULTI ? tab[slot[b]] : T0;
     const int j = bx * QPB + g;
@@ -538,13 +584,14 @@ __device__ __forceinline__ void kd_query_body(KdDev T0, QSrc qsrc, int n, float 
     qsrc.fetch(b);
     const int h = kd_warm_candidate(T, h0, hp);
     qsrc.prepare(b);
+    if (SPW == 2 && sl >= nbx) return;                           // odd slice count: no second slice (the barriers from here on count the live waves)
     qsrc.point(b, active ? j : 0, c, qx, qy, qz);                // every lane of the group ends up with the same point
     PSI_SSTOP(4);                                                // (dev: differential timing — the query source alone)
     PSI_KD_MARK(0);
-    const float fval = kd_query_round<LPQ, kd_rpl(LPQ), CONTACT>(T, qsrc, qx, qy, qz, active, o, dist, idx, cconst, gscale, gq, hint, rows, smem_i, h, hp, obase, jq);
+    const float fval = kd_query_round<LPQ, kd_rpl(LPQ), CONTACT, SPW>(T, qsrc, qx, qy, qz, active, o, dist, idx, cconst, gscale, gq, hint, rows, smem_i, h, hp, obase, jq, gstk);
     if (CONTACT) {
-        kd_block_fsum<LPQ>(fval, fpart + (size_t)b * nbx + bx);
-        qsrc.contact_finish(b, bx, nbx);
+        kd_block_fsum<LPQ, SPW>(fval, fpart + (size_t)b * nbx + sl, pr);
+        qsrc.contact_finish(b, sl, nbx);
     }
 }
 

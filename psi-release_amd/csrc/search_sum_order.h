@@ -34,6 +34,18 @@ PSI_SUM_HD constexpr unsigned psi_sum_slot(int lpq, unsigned w, int p) { return 
 PSI_SUM_HD constexpr int psi_sum_first_lane(int lpq, int p) { return p * psi_sum_part_lanes(lpq); }
 // pair tree: the lane of part p in which the part's sum ends (its last)
 PSI_SUM_HD constexpr int psi_sum_last_lane(int lpq, int p) { return (p + 1) * psi_sum_part_lanes(lpq) - 1; }
+// TWO SLICES PER WORKGROUP (spw = 2; 2 lanes per query): the workgroup's four waves are two PAIRS, pair r = waves 2r, 2r + 1 carries slice
+// 2 bx + r of the body with exactly the lanes, trees and slot order above, in a slot table of its own: slots 4r .. 4r + 3.  A body with an odd
+// number of slices gives the second pair of its last workgroup no slice.  spw = 1: one pair (all waves), pair 0.
+PSI_SUM_HD constexpr int psi_sum_wg_pair_threads(int lpq) { return psi_sum_waves(lpq) * 64; }                             // threads that carry one slice
+PSI_SUM_HD constexpr int psi_sum_wg_pair(int lpq, int spw, int tid) { return spw == 2 ? tid / psi_sum_wg_pair_threads(lpq) : 0; }
+PSI_SUM_HD constexpr int psi_sum_wg_slice(int spw, int bx, int pair) { return spw * bx + pair; }
+// slot of part p of wave w (of the workgroup) in the workgroup's spw * psi_sum_parts slots
+PSI_SUM_HD constexpr unsigned psi_sum_wg_slot(int lpq, int spw, unsigned w, int p)
+{
+    return spw == 2 ? (w / (unsigned)psi_sum_waves(lpq)) * (unsigned)psi_sum_parts(lpq) + psi_sum_slot(lpq, w % (unsigned)psi_sum_waves(lpq), p)
+                    : psi_sum_slot(lpq, w, p);
+}
 // the slice's value from the workgroup's slots, in slot order from +0
 PSI_SUM_HD inline float psi_sum_slots(const float *slot, int stride, int lpq)
 {

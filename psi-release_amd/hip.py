@@ -113,6 +113,7 @@ SIGNATURES = {
     'psi_fit_decode_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     'psi_fit_profile': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'psi_fit_copy_buffer': (c_int, [c_void_p, ctypes.c_char_p, c_void_p, c_long, c_void_p]),
+    'psi_fit_search_shape': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     'psi_lbs_sdf_counts': (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 3),
     'psi_kmeans_create': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float]),
     'psi_kmeans_destroy': (None, [c_void_p]),

@@ -10,6 +10,7 @@
 // (v[l] += v[l + d], the __shfl_down semantics: a lane whose partner lies beyond the wave adds itself) and by the pair tree (v[l] += v[l ^ d]),
 // the parts go to their slots, the slots are added in order.  Every slice below cdiv(n_c, 64) must be written exactly once, none beyond it
 // (the output is a heap array of exactly that many floats: the sanitizer sees a write outside), and its bits must equal the reference's.
+// With 2 lanes per query the grid is walked a second time with two slices per workgroup (the wave pairs and slot tables of the header).
 // Exit status 1 at the first difference.  It does not cover the kernels' own shuffles and barriers: those need the GPU tests.
 #include <math.h>
 #include <stdio.h>
@@ -89,16 +90,20 @@ struct Out {
     int *writes;
     int n;
 };
-static int run_grid(int lpq, const float *q, int n, bool pairs, Out &out)
+// spw: slices per workgroup (1; or 2 with 2 lanes per query: wave pair r of workgroup bx carries slice 2 bx + r in slots 4 r .. 4 r + 3, and
+// the second pair of the last workgroup has no slice when the slice count is odd)
+static int run_grid(int lpq, const float *q, int n, bool pairs, Out &out, int spw = 1)
 {
-    const int slice_q = psi_sum_slice_queries(lpq), nbx = (n + slice_q - 1) / slice_q;
+    const int slice_q = psi_sum_slice_queries(lpq), nslices = (n + slice_q - 1) / slice_q, nbx = (nslices + spw - 1) / spw;
     for (int bx = 0; bx < nbx; bx++) {
-        float slot[4];
-        int slot_writes[4] = {0, 0, 0, 0};
-        for (int w = 0; w < psi_sum_waves(lpq); w++) {
+        float slot[8];
+        int slot_writes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int w = 0; w < spw * psi_sum_waves(lpq); w++) {
+            const int pair = psi_sum_wg_pair(lpq, spw, 64 * w);
+            if (psi_sum_wg_slice(spw, bx, pair) >= nslices) continue;     // (the pair retires behind the source's workgroup phase)
             float v[64];
             for (int l = 0; l < 64; l++) {
-                const int tid = 64 * w + l, g = tid / lpq, c = tid % lpq, j = bx * slice_q + g;
+                const int tid = 64 * w + l, g = tid / lpq, c = tid % lpq, j = bx * spw * slice_q + g;
                 v[l] = (c == 0 && j < n) ? q[j] : 0.0f;
             }
             const int pl = psi_sum_part_lanes(lpq);
@@ -116,16 +121,24 @@ static int run_grid(int lpq, const float *q, int n, bool pairs, Out &out)
                 }
             }
             for (int p = 0; p < psi_sum_parts_per_wave(lpq); p++) {
-                const int s = psi_sum_slot(lpq, w, p);
-                if (s < 0 || s >= psi_sum_parts(lpq)) { printf("lpq %d: slot %d of wave %d part %d\n", lpq, s, w, p); return 1; }
+                const int s = spw == 2 ? psi_sum_wg_slot(lpq, spw, w, p) : psi_sum_slot(lpq, w, p);
+                if (s < pair * psi_sum_parts(lpq) || s >= (pair + 1) * psi_sum_parts(lpq)) { printf("lpq %d: slot %d of wave %d part %d\n", lpq, s, w, p); return 1; }
                 slot[s] = v[pairs ? psi_sum_last_lane(lpq, p) : psi_sum_first_lane(lpq, p)];
                 slot_writes[s]++;
             }
         }
-        for (int s = 0; s < psi_sum_parts(lpq); s++)
-            if (slot_writes[s] != 1) { printf("lpq %d: slot %d written %d times\n", lpq, s, slot_writes[s]); return 1; }
-        out.v[bx] = psi_sum_slots(slot, 1, lpq);       // (a write beyond the heap array: the sanitizer's)
-        out.writes[bx]++;
+        for (int pair = 0; pair < spw; pair++) {
+            const int sl = psi_sum_wg_slice(spw, bx, pair);
+            if (sl >= nslices) {
+                for (int s = 0; s < psi_sum_parts(lpq); s++)
+                    if (slot_writes[pair * psi_sum_parts(lpq) + s]) { printf("lpq %d: a pair without a slice wrote slot %d\n", lpq, s); return 1; }
+                continue;
+            }
+            for (int s = 0; s < psi_sum_parts(lpq); s++)
+                if (slot_writes[pair * psi_sum_parts(lpq) + s] != 1) { printf("lpq %d: slot %d written %d times\n", lpq, s, slot_writes[pair * psi_sum_parts(lpq) + s]); return 1; }
+            out.v[sl] = psi_sum_slots(slot + pair * psi_sum_parts(lpq), 1, lpq);       // (a write beyond the heap array: the sanitizer's)
+            out.writes[sl]++;
+        }
     }
     return 0;
 }
@@ -143,14 +156,15 @@ static int check(int n, int kind)
             printf("lpq %d: slice of %d queries, %d waves\n", lpq, psi_sum_slice_queries(lpq), psi_sum_waves(lpq));
             return 1;
         }
-        for (int pairs = 0; pairs < 2; pairs++) {
+        for (int shape = 0; shape < 2 * (lpq == 2 ? 2 : 1); shape++) {      // both trees; with 2 lanes also two slices per workgroup
+            const int pairs = shape & 1, spw = 1 + (shape >> 1);
             Out out = {(float *)malloc(sizeof(float) * nfp), (int *)calloc(nfp, sizeof(int)), nfp};
-            int bad = run_grid(lpq, q.data(), n, pairs != 0, out);
+            int bad = run_grid(lpq, q.data(), n, pairs != 0, out, spw);
             for (int bx = 0; bx < nfp && !bad; bx++) {
                 const float want = pairs ? ref_pairs(q.data(), n, bx) : ref_halving(q.data(), n, bx);
                 checked++;
                 if (out.writes[bx] != 1) {
-                    printf("n_c %d lpq %d: slice %d written %d times\n", n, lpq, bx, out.writes[bx]);
+                    printf("n_c %d lpq %d spw %d: slice %d written %d times\n", n, lpq, spw, bx, out.writes[bx]);
                     bad = 1;
                 } else if (bits(out.v[bx]) != bits(want)) {
                     printf("n_c %d lpq %d %s tree kind %d: slice %d = %08x, the 4-lane association gives %08x\n", n, lpq, pairs ? "pair" : "halving", kind, bx,
@@ -173,5 +187,6 @@ int main()
             for (int rep = 0; rep < (kind == 2 ? 1 : 4); rep++)
                 if (check(n, kind)) return 1;
     printf("search_sum_order: %ld slices of n_c = 1 .. 300 equal the 4-lane association bit for bit at 2 and 4 lanes per query, each written exactly once\n", checked);
+    printf("search_sum_order: among them the two-slice workgroups of the 2-lane search (slots 4 r .. 4 r + 3 of wave pair r), odd slice counts included\n");
     return 0;
 }

@@ -23,9 +23,10 @@ mb = (ctypes.c_ulonglong * (4 * N))()
 rc |= lib.psi_dbg_kd_mark(mb, N)
 marks = np.frombuffer(mb, dtype=np.uint64).reshape(N, 4).astype(np.int64)
 a = np.frombuffer(buf, dtype=np.uint64).reshape(N, 4).astype(np.int64)
-marks = marks[a[:, 1] > 0]
-stat = np.frombuffer(sb, dtype=np.int32).reshape(N, 4)[a[:, 1] > 0]
-a = a[a[:, 1] > 0]
+keep = a[:, 1] > 0                                             # the workgroups of the launch
+marks = marks[keep]
+stat = np.frombuffer(sb, dtype=np.int32).reshape(N, 4)[keep]
+a = a[keep]
 t0 = a[:, 0].min()
 st, en = (a[:, 0] - t0) * 0.01, (a[:, 1] - t0) * 0.01          # us
 print('rc', rc, 'workgroups', len(a), 'span us', en.max())
@@ -46,11 +47,38 @@ for k in (1, 0):
     m = a[:, 3] == k
     print('resident kind', k, ' '.join('%d' % int(((st[m] <= t) & (en[m] > t)).sum()) for t in T))
 
+# per 1 us bin: resident workgroups per kind and CU, and the live search waves on each SIMD of a CU (a wave's record: its own end and its
+# HW_ID word, bits 4-5 = SIMD; it starts with its workgroup).  A search wave that retires before its first load ends within a microsecond.
+if hasattr(lib, 'psi_dbg_timeline_waves'):
+    wb = (ctypes.c_ulonglong * (8 * N))()
+    rc = lib.psi_dbg_timeline_waves(wb, N)
+    W = np.frombuffer(wb, dtype=np.uint64).reshape(N, 4, 2).astype(np.int64)[keep]
+    wen = (W[:, :, 0] - t0) * 0.01
+    wsimd = (W[:, :, 1] >> 4) & 3
+    ncu = len(np.unique(cuid))
+    print('per-wave records rc', rc, ' CUs', ncu)
+    for k in (1, 0):
+        m = a[:, 3] == k
+        if not m.any(): continue
+        wd = wen[m] - st[m][:, None]
+        print('kind', k, 'wave life us by wave 0..3: median', ' '.join('%.2f' % np.median(wd[:, w]) for w in range(4)),
+              ' SIMD of wave 0..3 (share of workgroups with SIMD == wave index):', ' '.join('%.2f' % (wsimd[m][:, w] == w).mean() for w in range(4)))
+        print('kind', k, 'workgroups by (SIMD of wave 0, SIMD of wave 1):', np.bincount(wsimd[m][:, 0] * 4 + wsimd[m][:, 1], minlength=16).reshape(4, 4).tolist())
+    print('bin_us  resident per CU: search skinning | live search waves per CU on SIMD 0 1 2 3 (mean over CUs; largest on one SIMD of one CU)')
+    cu_ix = np.unique(cuid, return_inverse=True)[1]
+    ms = a[:, 3] == 1
+    for t in T:
+        res = [(((st[a[:, 3] == k] <= t) & (en[a[:, 3] == k] > t)).sum() / ncu) for k in (1, 0)]
+        live = (st[ms][:, None] <= t) & (wen[ms] > t)                     # [search workgroups][4 waves]
+        cnt = np.zeros((ncu, 4), dtype=np.int64)
+        np.add.at(cnt, (np.repeat(cu_ix[ms], 4)[live.ravel()], wsimd[ms].ravel()[live.ravel()]), 1)
+        print('%5.0f   %5.2f %5.2f | %5.2f %5.2f %5.2f %5.2f  (%d)' % ((t, res[0], res[1]) + tuple(cnt.mean(axis=0)) + (int(cnt.max()),)))
+
 if (a[:, 3] == 1).any():
     m = a[:, 3] == 1
     d = en[m] - st[m]
     S = stat[m]
-    print('search workgroups: tree-walk queries per workgroup (of 64) mean %.1f max %d; workgroups with none %d' % (S[:, 0].mean(), S[:, 0].max(), int((S[:, 0] == 0).sum())))
+    print('search workgroups: tree-walk queries per workgroup (of its 64 or, with two slices, 128; counted under PSI_SKIN_STOP=10 only) mean %.1f max %d; workgroups with none %d' % (S[:, 0].mean(), S[:, 0].max(), int((S[:, 0] == 0).sum())))
     print('most visits of one query: quantiles', np.quantile(S[:, 1], [0, .5, .9, .99, 1]), ' grid rounds (max per lane)', np.quantile(S[:, 3], [0, .5, .9, .99, 1]))
     order = np.argsort(d)
     for lo_, hi_ in ((0, 0.1), (0.45, 0.55), (0.9, 1.0), (0.99, 1.0)):
