@@ -1,6 +1,6 @@
 // Body against body: which vertices of one body of a batch lie inside another body of the batch, for gfx950 (wave64).  The contract is
 // DESIGN.md "Body against body"; the per-triple statements are csrc/body_overlap_shared.h and csrc/geom_shared.h (boxes, normal, half_omega),
-// the workgroup sum, box and ordered rank csrc/wg_device.h.
+// the workgroup sum, box and the ordered emit pass (wg_emit, which the crossing searches use too) csrc/wg_device.h.
 //
 //   box        of body j: the exact min / max of its V vertices per axis
 //   candidate  an ordered triple (i, j, v), i != j, group[i] == group[j], vertex v of body i inside the closed box of j; ascending (i, j, v)
@@ -15,10 +15,9 @@
 // candidates belong to ONE pair, so all lanes stage the same body j; per 256 faces every lane builds one triangle record in LDS, then every
 // lane reads every record: identical addresses broadcast), decide (the slice sums in order, w, integer atomics into counts and the bit mask).
 #include "body_overlap_shared.h"
-#include "psi_common.h"
+#include "blob.h"
 #include "wg_device.h"
 #include <limits.h>
-#include <vector>
 
 namespace psi_bo {
 
@@ -85,19 +84,12 @@ __global__ __launch_bounds__(WG) void bo_emit_kernel(const float *__restrict__ v
     for (int c = t; c * BO_CHUNK < pc; c += WG)
         if (coff + c < n_chunks) chunks[coff + c] = Chunk{(int)(off + (long long)c * BO_CHUNK), min(BO_CHUNK, pc - c * BO_CHUNK), i, j};
     const float *v = verts + (size_t)i * V * 3;
-    int done = 0;                                           // candidates of the vertices before this round
-    for (int k0 = 0; k0 < V; k0 += WG) {
-        const int k = k0 + t;
-        const bool in = k < V && geom_in_box(v[(size_t)k * 3], v[(size_t)k * 3 + 1], v[(size_t)k * 3 + 2], lo, hi);
-        const int idx = wg_rank(in, s_wcnt, &done);         // this vertex's place among the pair's candidates
-        const long long pos = off + idx;
-        if (in && idx < pc && pos < n_cand) {
-            cand[pos * 3] = i;
-            cand[pos * 3 + 1] = j;
-            cand[pos * 3 + 2] = k;
-        }
-        __syncthreads();                                    // s_wcnt is read by every wave before the next round writes it
-    }
+    wg_emit(V, pc, off, n_cand, s_wcnt, [&](int k) { return geom_in_box(v[(size_t)k * 3], v[(size_t)k * 3 + 1], v[(size_t)k * 3 + 2], lo, hi); },
+            [&](long long pos, int k) {                     // vertex k at its place among the pair's candidates
+                cand[pos * 3] = i;
+                cand[pos * 3 + 1] = j;
+                cand[pos * 3 + 2] = k;
+            });
 }
 
 // part [n_slices, n_cand] fp64: the slice sums of every candidate.  grid = (chunk, slice).
@@ -171,17 +163,21 @@ extern "C" int psi_body_overlap_create(psi_body_overlap **out, const int32_t *h_
     PSI_REQUIRE((long long)F * 3 < (1ll << 31), "F * 3 < 2^31");
     int rc = psi_check_faces(h_faces, V, F);
     if (rc) return rc;
-    int32_t *d = nullptr;
-    rc = psi_upload(&d, h_faces, (size_t)F * 3, "psi_body_overlap_create");
-    if (rc) return rc;
-    *out = new psi_body_overlap{d, V, F};
+    psi_body_overlap *h = new psi_body_overlap{nullptr, nullptr, V, F};
+    PsiBlob T;
+    T.upload(h->d_faces, h_faces, (size_t)F * 3 * sizeof(int32_t));
+    if (int e = psi_blob_realise(T, &h->blob, "psi_body_overlap_create")) {
+        delete h;
+        return e;
+    }
+    *out = h;
     return 0;
 }
 
 extern "C" void psi_body_overlap_destroy(psi_body_overlap *h)
 {
     if (!h) return;
-    (void)hipFree(h->d_faces);
+    (void)hipFree(h->blob);
     delete h;
 }
 

@@ -8,7 +8,8 @@
 
 // The handle of psi_body_overlap_create, which csrc/body_depth.hip takes as well: the one topology of every body, on the device
 struct psi_body_overlap {
-    int32_t *d_faces;
+    char *blob;                // the one allocation (csrc/blob.h)
+    int32_t *d_faces;          // [F,3]
     int V, F;
 };
 

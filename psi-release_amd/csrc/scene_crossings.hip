@@ -1,7 +1,8 @@
 // Scene crossings: which triangles of the posed body surfaces of a batch properly intersect which triangles of a static scene mesh, for
-// gfx950 (wave64).  The contract is DESIGN.md section 10i; the per-pair statements are csrc/surface_crossings_shared.h, the key and the
-// host half of create csrc/scene_crossings_shared.h, the closed-box test csrc/geom_shared.h, the workgroup sum and ordered rank
-// csrc/wg_device.h.  This file is compiled with -ffp-contract=off.
+// gfx950 (wave64).  The contract is DESIGN.md section 10i; the per-pair statements and the Morton order are csrc/surface_crossings_shared.h,
+// the key and the host half of create csrc/scene_crossings_shared.h, the closed-box test csrc/geom_shared.h, the workgroup sum and the two
+// passes of a count-or-emit job csrc/wg_device.h, the argument rules of the count-or-emit entry points and the launch of a test kernel's
+// two forms, as in the body search, csrc/crossings_common.h.  This file is compiled with -ffp-contract=off.
 //
 //   candidate  a body face (i, s) and a scene triangle t whose closed exact face boxes meet
 //   decision   sc_pair(P = body face, Q = scene triangle): the pair crosses iff at least one edge of one pierces the other
@@ -15,9 +16,9 @@
 // atomics, which commute) and contour (one workgroup per body adds the lengths of its rows in fp64, one after the other in row order).
 // No floating-point atomics.
 #include "scene_crossings_shared.h"
+#include "crossings_common.h"
 #include "surface_crossings_handle.h"
 #include "blob.h"
-#include "wg_device.h"
 
 struct psi_scene_crossings {
     char *blob;                // records | chunk boxes
@@ -53,26 +54,17 @@ __global__ __launch_bounds__(WG) void scn_tile_kernel(const float *__restrict__ 
         if (!tiles && t == 0) job_tiles[job] = 0;
         return;
     }
+    const auto meets = [&](int k) {
+        return brute || geom_boxes_meet(cb, cb + 3, scene_chunk_boxes + (size_t)k * 6, scene_chunk_boxes + (size_t)k * 6 + 3);
+    };
     if (!tiles) {
-        int n = 0;
-        for (int k = t; k < nK; k += WG)
-            n += (brute || geom_boxes_meet(cb, cb + 3, scene_chunk_boxes + (size_t)k * 6, scene_chunk_boxes + (size_t)k * 6 + 3)) ? 1 : 0;
-        n = wg_sum(n, s_w);
+        const int n = wg_count(nK, s_w, meets);
         if (t == 0) job_tiles[job] = n;
         return;
     }
     const int want = job_tiles[job];
     if (want == 0) return;
-    const long long off = job_off[job];
-    int done = 0;
-    for (int k0 = 0; k0 < nK; k0 += WG) {
-        const int k = k0 + t;
-        const bool in = k < nK && (brute || geom_boxes_meet(cb, cb + 3, scene_chunk_boxes + (size_t)k * 6, scene_chunk_boxes + (size_t)k * 6 + 3));
-        const int idx = wg_rank(in, s_w, &done);
-        const long long pos = off + idx;
-        if (in && idx < want && pos >= 0 && pos < n_tiles) tiles[pos] = Tile{i, c, k, 0};
-        __syncthreads();                                    // s_w is read by every wave before the next round writes it
-    }
+    wg_emit(nK, want, job_off[job], n_tiles, s_w, meets, [&](long long pos, int k) { tiles[pos] = Tile{i, c, k, 0}; });
 }
 
 // The hot pass.  EMIT = false: tile_hits[tile] = the crossing pairs of the tile.  EMIT = true: key, events and length of every crossing
@@ -257,8 +249,7 @@ extern "C" int psi_scene_crossings_tiles(const psi_scene_crossings *h, const psi
                                          long long n_tiles, int32_t *d_tiles, void *stream)
 {
     PSI_REQUIRE(h && body && d_chunk_boxes && d_body_boxes && d_job_tiles, "null pointer");
-    PSI_REQUIRE((d_tiles == nullptr) == (d_job_off == nullptr), "the emit pass takes d_job_off and d_tiles, the count pass neither");
-    PSI_REQUIRE(d_tiles ? (n_tiles >= 1 && n_tiles < (1ll << 31)) : n_tiles == 0, "1 <= n_tiles < 2^31 to emit, 0 to count");
+    SC_REQUIRE_TILE_PASS(d_job_off, n_tiles, d_tiles);
     PSI_REQUIRE(brute == 0 || brute == 1, "brute is 0 or 1");
     SCN_REQUIRE_B(h, B, body->F);
     psi_scn::Box6 scene;
@@ -275,19 +266,10 @@ extern "C" int psi_scene_crossings_test(const psi_scene_crossings *h, const psi_
                                         long long n_pairs, int64_t *d_keys, int32_t *d_events, float *d_length, void *stream)
 {
     PSI_REQUIRE(h && body && d_verts && d_tiles && d_tile_hits, "null pointer");
-    PSI_REQUIRE(n_tiles >= 1 && n_tiles < (1ll << 31), "1 <= n_tiles < 2^31");
-    SCN_REQUIRE_B(h, B, body->F);
-    const bool emit = d_keys != nullptr;
-    PSI_REQUIRE(emit ? (d_tile_off && d_events && d_length && n_pairs >= 1 && n_pairs < (1ll << 31)) : (!d_tile_off && !d_events && !d_length && n_pairs == 0),
-                "the emit pass takes d_tile_off, d_keys, d_events, d_length and 1 <= n_pairs < 2^31; the count pass none of them");
-    if (emit)
-        hipLaunchKernelGGL(psi_scn::scn_test_kernel<true>, dim3((unsigned)n_tiles), dim3(psi_scn::WG), 0, (hipStream_t)stream, h->d_recs, h->nf,
-                           h->nK, d_verts, body->d_faces, body->d_orig, B, body->V, body->F, (const psi_scn::Tile *)d_tiles, d_tile_hits,
-                           (const long long *)d_tile_off, n_pairs, (long long *)d_keys, d_events, d_length);
-    else
-        hipLaunchKernelGGL(psi_scn::scn_test_kernel<false>, dim3((unsigned)n_tiles), dim3(psi_scn::WG), 0, (hipStream_t)stream, h->d_recs, h->nf,
-                           h->nK, d_verts, body->d_faces, body->d_orig, B, body->V, body->F, (const psi_scn::Tile *)d_tiles, d_tile_hits,
-                           (const long long *)nullptr, 0ll, (long long *)nullptr, (int *)nullptr, (float *)nullptr);
+    SC_REQUIRE_TEST_PASS(n_tiles, SCN_REQUIRE_B(h, B, body->F), d_tile_off, n_pairs, d_keys, d_events, d_length);
+    SC_LAUNCH_TEST(psi_scn::scn_test_kernel, n_tiles, stream, d_keys, h->d_recs, h->nf, h->nK, d_verts, body->d_faces, body->d_orig, B, body->V,
+                   body->F, (const psi_scn::Tile *)d_tiles, d_tile_hits, (const long long *)d_tile_off, n_pairs, (long long *)d_keys, d_events,
+                   d_length);
     PSI_CHECK_LAUNCH("scn_test_kernel");
     return 0;
 }

@@ -1,13 +1,10 @@
 // What csrc/scene_crossings.hip shares with its host rehearsal tools/scene_crossings_host_check.hip: the sort key
 // of a pair (body i, body face s, scene triangle t) and the host half of psi_scene_crossings_create, which is plain C++ without a HIP
-// call: the Morton order of the scene's triangles, the records of the chunk order, the chunk boxes and the scene's box.  The per-pair
-// statements (sc_pair, sc_face_box, sc_spread10) are csrc/surface_crossings_shared.h, the closed-box test csrc/geom_shared.h.
+// call: the records of the chunk order, the chunk boxes and the scene's box.  The per-pair statements (sc_pair, sc_face_box) and the
+// Morton order of the triangles (sc_morton_order) are csrc/surface_crossings_shared.h, the closed-box test csrc/geom_shared.h.
 #pragma once
 #include "surface_crossings_shared.h"
 #include <string.h>
-#include <algorithm>
-#include <numeric>
-#include <vector>
 
 constexpr int SCN_REC_ROWS = 3;         // float4 rows of a record: q0.xyz q1.x | q1.yz q2.xy | q2.z caller's index 0 0
 
@@ -38,8 +35,8 @@ struct ScnBuilt {
 
 enum { SCN_OK = 0, SCN_NO_FACES = 1, SCN_BAD_INDEX = 2, SCN_NOT_FINITE = 3 };
 
-// The host half of create.  Morton curve (10 bits per axis) of the centroid sums in fp64 over their bounding box, ties to the lower
-// index; chunks of SC_CHUNK positions; boxes by comparisons only.  *bad: the first offending triangle.
+// The host half of create.  The triangles in Morton order (sc_morton_order); chunks of SC_CHUNK positions; boxes by comparisons only.
+// *bad: the first offending triangle.
 static inline int scn_build(const float *v, int nv, const int32_t *f, long long nf, ScnBuilt *o, long long *bad)
 {
     *bad = -1;
@@ -51,29 +48,8 @@ static inline int scn_build(const float *v, int nv, const int32_t *f, long long 
             for (int a = 0; a < 3; a++)
                 if (!std::isfinite(v[(size_t)id * 3 + a])) { *bad = t; return SCN_NOT_FINITE; }
         }
-    std::vector<double> c((size_t)nf * 3);
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (long long t = 0; t < nf; t++)
-        for (int a = 0; a < 3; a++) {
-            double s = 0.0;
-            for (int k = 0; k < 3; k++) s += (double)v[(size_t)f[t * 3 + k] * 3 + a];
-            c[(size_t)t * 3 + a] = s;
-            lo[a] = std::min(lo[a], s);
-            hi[a] = std::max(hi[a], s);
-        }
-    std::vector<uint32_t> code((size_t)nf);
-    for (long long t = 0; t < nf; t++) {
-        uint32_t m = 0;
-        for (int a = 0; a < 3; a++) {
-            const double w = hi[a] - lo[a];
-            const uint32_t q = w > 0.0 ? (uint32_t)std::min(1023.0, (c[(size_t)t * 3 + a] - lo[a]) / w * 1024.0) : 0u;
-            m |= sc_spread10(q) << a;
-        }
-        code[t] = m;
-    }
     o->order.resize((size_t)nf);
-    std::iota(o->order.begin(), o->order.end(), 0);
-    std::stable_sort(o->order.begin(), o->order.end(), [&](int32_t a, int32_t b) { return code[a] < code[b]; });
+    sc_morton_order(v, f, nf, o->order.data());             // (every referenced coordinate is finite: so are the sums of three in fp64)
     const long long nK = (nf + SC_CHUNK - 1) / SC_CHUNK;
     o->recs.assign((size_t)nf * SCN_REC_ROWS * 4, 0.0f);
     o->chunk_boxes.resize((size_t)nK * 6);

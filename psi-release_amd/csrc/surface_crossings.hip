@@ -1,6 +1,8 @@
 // Surface crossings: which pairs of triangles of the posed body surfaces of a batch properly intersect, for gfx950 (wave64).  The contract is
-// DESIGN.md section 10e; the per-pair statements are csrc/surface_crossings_shared.h, the closed-box test csrc/geom_shared.h, the workgroup
-// sum, box and ordered rank csrc/wg_device.h.  This file is compiled with -ffp-contract=off.
+// DESIGN.md section 10e; the per-pair statements and the Morton order of the faces are csrc/surface_crossings_shared.h, the closed-box test
+// csrc/geom_shared.h, the workgroup sum, box and the two passes of a count-or-emit job csrc/wg_device.h, the argument rules of the
+// count-or-emit entry points and the launch of a test kernel's two forms, as in the scene search, csrc/crossings_common.h.  Compiled with
+// -ffp-contract=off.
 //
 //   candidate  an unordered pair of faces ((i, s), (j, t)), (i, s) < (j, t): bodies i < j of one group (between), or two faces s < t of one
 //              body that share no vertex index and whose parts are not skipped (self); and the closed face boxes meet
@@ -14,13 +16,10 @@
 // sort of the keys: pairs, counts, face mask and irregular count by integer atomics) and contour (one workgroup per job adds the lengths
 // of its pairs in fp64, sequentially in pair order).  No floating-point atomics.
 #include "surface_crossings_shared.h"
+#include "crossings_common.h"
 #include "surface_crossings_handle.h"
-#include "psi_common.h"
-#include "wg_device.h"
+#include "blob.h"
 #include <limits.h>
-#include <algorithm>
-#include <numeric>
-#include <vector>
 
 namespace psi_sc {
 
@@ -93,26 +92,15 @@ __global__ __launch_bounds__(WG) void sc_tile_kernel(const float *__restrict__ c
         if (!tiles && t == 0) job_tiles[blockIdx.x] = 0;
         return;
     }
-    const int total = nC * nC;
+    const auto live = [&](int k) { return tile_live(chunk_boxes, nC, flags, i, j, k / nC, k % nC); };
     if (!tiles) {
-        int n = 0;
-        for (int k = t; k < total; k += WG) n += tile_live(chunk_boxes, nC, flags, i, j, k / nC, k % nC) ? 1 : 0;
-        n = wg_sum(n, s_w);
+        const int n = wg_count(nC * nC, s_w, live);
         if (t == 0) job_tiles[blockIdx.x] = n;
         return;
     }
     const int want = job_tiles[blockIdx.x];
     if (want == 0) return;
-    const long long off = job_off[blockIdx.x];
-    int done = 0;
-    for (int k0 = 0; k0 < total; k0 += WG) {
-        const int k = k0 + t;
-        const bool in = k < total && tile_live(chunk_boxes, nC, flags, i, j, k / nC, k % nC);
-        const int idx = wg_rank(in, s_w, &done);
-        const long long pos = off + idx;
-        if (in && idx < want && pos < n_tiles) tiles[pos] = Tile{i, j, k / nC, k % nC};
-        __syncthreads();                                    // s_w is read by every wave before the next round writes it
-    }
+    wg_emit(nC * nC, want, job_off[blockIdx.x], n_tiles, s_w, live, [&](long long pos, int k) { tiles[pos] = Tile{i, j, k / nC, k % nC}; });
 }
 
 // The hot pass.  EMIT = false: tile_hits[tile] = the crossing pairs of the tile.  EMIT = true: key, events and length of every crossing
@@ -259,31 +247,11 @@ extern "C" int psi_surface_crossings_face_order(const int32_t *h_faces, int V, i
     PSI_REQUIRE(V >= 1 && F >= 1 && F < SC_MAX_F, "V >= 1 and 1 <= F < 2^21");
     const int rc = psi_check_faces(h_faces, V, F);
     if (rc) return rc;
-    std::iota(h_order, h_order + F, 0);
-    if (!h_order_verts) return 0;
-    // centroids in fp64, quantised to 10 bits per axis of their bounding box; ties keep face order
-    std::vector<double> c((size_t)F * 3);
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int f = 0; f < F; f++)
-        for (int a = 0; a < 3; a++) {
-            double s = 0.0;
-            for (int k = 0; k < 3; k++) s += (double)h_order_verts[(size_t)h_faces[(size_t)f * 3 + k] * 3 + a];
-            PSI_REQUIRE(std::isfinite(s), "order_verts is finite");
-            c[(size_t)f * 3 + a] = s;
-            lo[a] = std::min(lo[a], s);
-            hi[a] = std::max(hi[a], s);
-        }
-    std::vector<uint32_t> code((size_t)F);
-    for (int f = 0; f < F; f++) {
-        uint32_t m = 0;
-        for (int a = 0; a < 3; a++) {
-            const double w = hi[a] - lo[a];
-            const uint32_t q = w > 0.0 ? (uint32_t)std::min(1023.0, (c[(size_t)f * 3 + a] - lo[a]) / w * 1024.0) : 0u;
-            m |= sc_spread10(q) << a;
-        }
-        code[f] = m;
+    if (!h_order_verts) {
+        for (int f = 0; f < F; f++) h_order[f] = f;
+        return 0;
     }
-    std::stable_sort(h_order, h_order + F, [&](int32_t a, int32_t b) { return code[a] < code[b]; });
+    PSI_REQUIRE(sc_morton_order(h_order_verts, h_faces, F, h_order), "order_verts is finite");
     return 0;
 }
 
@@ -314,25 +282,25 @@ extern "C" int psi_surface_crossings_create(psi_surface_crossings **out, const i
             for (int b = 0; b < P; b++)
                 PSI_REQUIRE((h_part_skip[(size_t)a * P + b] != 0) == (h_part_skip[(size_t)b * P + a] != 0), "part_skip is symmetric");
     }
-    psi_surface_crossings h{nullptr, nullptr, nullptr, nullptr, V, F, P, nullptr};
-    const char *who = "psi_surface_crossings_create";
-    int e = psi_upload(&h.d_faces, faces.data(), faces.size(), who);
-    if (!e) e = psi_upload(&h.d_orig, order.data(), order.size(), who);
-    if (!e && h_face_part) e = psi_upload(&h.d_part, part.data(), part.size(), who);
-    if (!e && h_face_part) e = psi_upload(&h.d_skip, h_part_skip, (size_t)P * P, who);
-    if (!e) e = psi_upload(&h.d_caller, h_faces, (size_t)F * 3, who);
-    if (e) {
-        (void)hipFree(h.d_faces), (void)hipFree(h.d_orig), (void)hipFree(h.d_part), (void)hipFree(h.d_skip), (void)hipFree(h.d_caller);
+    psi_surface_crossings *h = new psi_surface_crossings{nullptr, nullptr, nullptr, nullptr, nullptr, V, F, P, nullptr};
+    PsiBlob T;
+    T.upload(h->d_faces, faces.data(), faces.size() * sizeof(int32_t));
+    T.upload(h->d_orig, order.data(), order.size() * sizeof(int32_t));
+    T.upload(h->d_part, part.data(), part.size() * sizeof(int32_t)).or_null();
+    T.upload(h->d_skip, h_part_skip, (size_t)P * P).or_null();
+    T.upload(h->d_caller, h_faces, (size_t)F * 3 * sizeof(int32_t));
+    if (int e = psi_blob_realise(T, &h->blob, "psi_surface_crossings_create")) {
+        delete h;
         return e;
     }
-    *out = new psi_surface_crossings(h);
+    *out = h;
     return 0;
 }
 
 extern "C" void psi_surface_crossings_destroy(psi_surface_crossings *h)
 {
     if (!h) return;
-    (void)hipFree(h->d_faces), (void)hipFree(h->d_orig), (void)hipFree(h->d_part), (void)hipFree(h->d_skip), (void)hipFree(h->d_caller);
+    (void)hipFree(h->blob);
     delete h;
 }
 
@@ -370,8 +338,7 @@ extern "C" int psi_surface_crossings_tiles(const psi_surface_crossings *h, const
                                            int32_t *d_tiles, void *stream)
 {
     PSI_REQUIRE(h && d_chunk_boxes && d_body_boxes && d_job_tiles, "null pointer");
-    PSI_REQUIRE((d_tiles == nullptr) == (d_job_off == nullptr), "the emit pass takes d_job_off and d_tiles, the count pass neither");
-    PSI_REQUIRE(d_tiles ? (n_tiles >= 1 && n_tiles < (1ll << 31)) : n_tiles == 0, "1 <= n_tiles < 2^31 to emit, 0 to count");
+    SC_REQUIRE_TILE_PASS(d_job_off, n_tiles, d_tiles);
     PSI_REQUIRE(flags >= 0 && flags < 8, "flags");
     SC_REQUIRE_B(h, B);
     hipLaunchKernelGGL(psi_sc::sc_tile_kernel, dim3(B * B), dim3(psi_sc::WG), 0, (hipStream_t)stream, d_chunk_boxes, d_body_boxes, d_group, B,
@@ -385,19 +352,9 @@ extern "C" int psi_surface_crossings_test(const psi_surface_crossings *h, const 
                                           int32_t *d_events, float *d_length, void *stream)
 {
     PSI_REQUIRE(h && d_verts && d_tiles && d_tile_hits, "null pointer");
-    PSI_REQUIRE(n_tiles >= 1 && n_tiles < (1ll << 31), "1 <= n_tiles < 2^31");
-    SC_REQUIRE_B(h, B);
-    const bool emit = d_keys != nullptr;
-    PSI_REQUIRE(emit ? (d_tile_off && d_events && d_length && n_pairs >= 1 && n_pairs < (1ll << 31)) : (!d_tile_off && !d_events && !d_length && n_pairs == 0),
-                "the emit pass takes d_tile_off, d_keys, d_events, d_length and 1 <= n_pairs < 2^31; the count pass none of them");
-    if (emit)
-        hipLaunchKernelGGL(psi_sc::sc_test_kernel<true>, dim3((unsigned)n_tiles), dim3(psi_sc::WG), 0, (hipStream_t)stream, d_verts, h->d_faces,
-                           h->d_orig, h->d_part, h->d_skip, h->P, B, h->V, h->F, (const psi_sc::Tile *)d_tiles, d_tile_hits,
-                           (const long long *)d_tile_off, n_pairs, (long long *)d_keys, d_events, d_length);
-    else
-        hipLaunchKernelGGL(psi_sc::sc_test_kernel<false>, dim3((unsigned)n_tiles), dim3(psi_sc::WG), 0, (hipStream_t)stream, d_verts, h->d_faces,
-                           h->d_orig, h->d_part, h->d_skip, h->P, B, h->V, h->F, (const psi_sc::Tile *)d_tiles, d_tile_hits,
-                           (const long long *)nullptr, 0ll, (long long *)nullptr, (int *)nullptr, (float *)nullptr);
+    SC_REQUIRE_TEST_PASS(n_tiles, SC_REQUIRE_B(h, B), d_tile_off, n_pairs, d_keys, d_events, d_length);
+    SC_LAUNCH_TEST(psi_sc::sc_test_kernel, n_tiles, stream, d_keys, d_verts, h->d_faces, h->d_orig, h->d_part, h->d_skip, h->P, B, h->V, h->F,
+                   (const psi_sc::Tile *)d_tiles, d_tile_hits, (const long long *)d_tile_off, n_pairs, (long long *)d_keys, d_events, d_length);
     PSI_CHECK_LAUNCH("sc_test_kernel");
     return 0;
 }

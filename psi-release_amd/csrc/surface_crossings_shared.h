@@ -12,9 +12,15 @@
 // Event: edge i of P pierces Q iff sP[i] and sP[i+1] are strictly of opposite sign (two comparisons, no product) and D[i][0], D[i][1],
 // D[i][2] are all > 0 or all < 0; the edges of Q against P alike with sQ and the columns of D.  A zero anywhere is no event.
 // The closed-box overlap test (geom_boxes_meet) and the bound on the bodies of a batch (GEOM_MAX_B) are csrc/geom_shared.h.
+// Also here, on the host only: the Morton order of a mesh's triangles (sc_morton_order), the one statement behind the chunk order of the
+// body handle and of the scene handle (csrc/scene_crossings_shared.h), which tests/scene_crossings_ref.py restates.
 #pragma once
 #include "geom_shared.h"
 #include <stdint.h>
+#include <algorithm>
+#include <cmath>
+#include <numeric>
+#include <vector>
 
 #define SC_FN __host__ __device__ __forceinline__
 
@@ -151,4 +157,37 @@ SC_FN uint32_t sc_spread10(uint32_t x)
     x = (x | (x << 4)) & 0x030c30c3u;
     x = (x | (x << 2)) & 0x09249249u;
     return x;
+}
+
+// The Morton order of nf < 2^31 triangles f [nf,3] over the vertices v: order[k] = the triangle at position k.  The centroid sums
+// ((v0 + v1) + v2 per axis) in fp64, quantised to 10 bits per axis of their own bounding box (0 on an axis without extent), bits
+// interleaved x lowest, a stable sort: ties keep triangle order.  Plain C++, no HIP call; the body handle's face order
+// (psi_surface_crossings_face_order) and the scene handle's (scn_build).  false, with order untouched, when a sum is not finite.
+static inline bool sc_morton_order(const float *v, const int32_t *f, long long nf, int32_t *order)
+{
+    const size_t n = (size_t)nf;
+    std::vector<double> c(n * 3);
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (size_t t = 0; t < n; t++)
+        for (int a = 0; a < 3; a++) {
+            double s = 0.0;
+            for (int k = 0; k < 3; k++) s += (double)v[(size_t)f[t * 3 + k] * 3 + a];
+            if (!std::isfinite(s)) return false;
+            c[t * 3 + a] = s;
+            lo[a] = std::min(lo[a], s);
+            hi[a] = std::max(hi[a], s);
+        }
+    std::vector<uint32_t> code(n);
+    for (size_t t = 0; t < n; t++) {
+        uint32_t m = 0;
+        for (int a = 0; a < 3; a++) {
+            const double w = hi[a] - lo[a];
+            const uint32_t q = w > 0.0 ? (uint32_t)std::min(1023.0, (c[t * 3 + a] - lo[a]) / w * 1024.0) : 0u;
+            m |= sc_spread10(q) << a;
+        }
+        code[t] = m;
+    }
+    std::iota(order, order + n, 0);
+    std::stable_sort(order, order + n, [&](int32_t a, int32_t b) { return code[a] < code[b]; });
+    return true;
 }

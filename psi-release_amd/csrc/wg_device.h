@@ -1,5 +1,6 @@
-// Workgroup helpers of the geometry passes (csrc/body_overlap.hip, csrc/surface_crossings.hip), device only: a workgroup is WG_LANES = 256
-// lanes, four waves of 64 (gfx950).  Every helper must be reached by all 256 lanes: each contains a barrier.
+// Workgroup helpers of the geometry passes (csrc/body_overlap.hip, csrc/surface_crossings.hip, csrc/scene_crossings.hip), device only: a
+// workgroup is WG_LANES = 256 lanes, four waves of 64 (gfx950).  Every helper must be reached by all 256 lanes: each contains a barrier.
+// The sum, the box, the ordered rank, and on top of them the two passes of a count-or-emit job (wg_count, wg_emit).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -64,6 +65,32 @@ __device__ __forceinline__ int wg_rank(bool in, int *s_w, int *done)
     const int idx = *done + before + __popcll(m & ((1ull << lane) - 1ull));
     *done += total;
     return idx;
+}
+
+// The count pass of a count-or-emit job over the items 0 .. total-1 of one workgroup: how many have live(k) set, in every lane.
+template <class Live>
+__device__ __forceinline__ int wg_count(int total, int *s_w, Live live)
+{
+    int n = 0;
+    for (int k = threadIdx.x; k < total; k += WG_LANES) n += live(k) ? 1 : 0;
+    return wg_sum(n, s_w);
+}
+
+// The emit pass of the same job: rounds of 256 items; write(pos, k) for every live item k, pos = off + its place among the live items in
+// ascending k.  want: the count pass's result for this job, limit: the rows of the output table; a place beyond either, or a pos outside
+// [0, limit), is not written (the caller's scan is not trusted).
+template <class Live, class Write>
+__device__ __forceinline__ void wg_emit(int total, int want, long long off, long long limit, int *s_w, Live live, Write write)
+{
+    int done = 0;                              // live items of the rounds before this one
+    for (int k0 = 0; k0 < total; k0 += WG_LANES) {
+        const int k = k0 + threadIdx.x;
+        const bool in = k < total && live(k);
+        const int idx = wg_rank(in, s_w, &done);
+        const long long pos = off + idx;
+        if (in && idx < want && pos >= 0 && pos < limit) write(pos, k);
+        __syncthreads();                       // s_w is read by every wave before the next round writes it
+    }
 }
 
 // The box of body b = blockIdx.x over its V vertices, box [6] = min xyz, max xyz (exact: comparisons only), and the non-finite flag: *bad

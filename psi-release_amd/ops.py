@@ -1401,8 +1401,17 @@ def _chunks_of(n, chunk):
     return (n + (chunk - 1)) // chunk
 
 
+# kind of handle -> how an operator makes one of faces [F,3] and V when it is given no handle (None: only its own constructor makes one,
+# scene_crossings_create of a scene mesh); psi_<kind>_info reads the integers of every kind
+_HANDLE_KINDS = {'body_overlap': lambda faces, V: body_overlap_create(faces, V),
+                 'surface_crossings': lambda faces, V: surface_crossings_create(faces, V),
+                 'scene_crossings': None}
+
+
 def _with_info(handle, kind):
-    """Fills in the integers of the ``hip.Handle`` of ``kind`` ('body_overlap' or 'surface_crossings') through psi_<kind>_info."""
+    """Fills in the integers of the ``hip.Handle`` of ``kind`` (a key of ``_HANDLE_KINDS``) through psi_<kind>_info: ``V``, ``F`` and
+    ``n_chunks`` (vertices, faces and 256-face chunks; of the scene mesh for 'scene_crossings'; 'body_overlap' has no chunks: 0)."""
+    assert kind in _HANDLE_KINDS, kind
     info = (ctypes.c_int32 * 4)()               # body_overlap writes two of them
     hip.check(getattr(hip.lib(), 'psi_%s_info' % kind)(handle, info), 'psi_%s_info' % kind)
     handle.V, handle.F, handle.n_chunks = int(info[0]), int(info[1]), int(info[2])
@@ -1410,11 +1419,11 @@ def _with_info(handle, kind):
 
 
 def _handle_of(handle_or_faces, V, kind):
-    """The ``hip.Handle`` of ``kind`` an operator works with: the one ``body_overlap_create`` / ``surface_crossings_create`` makes of faces
-    (it lives as long as somebody holds it), or the handle given, which must have been made for ``V`` vertices per body.  Any other
-    ``c_void_p`` is a handle its caller owns: it is viewed, with its integers read from the library, and never freed from here."""
+    """The ``hip.Handle`` of ``kind`` an operator works with: the one the kind's constructor in ``_HANDLE_KINDS`` makes of faces (it lives
+    as long as somebody holds it), or the handle given, which must have been made for ``V`` vertices per body.  Any other ``c_void_p``
+    is a handle its caller owns: it is viewed, with its integers read from the library, and never freed from here."""
     if not isinstance(handle_or_faces, ctypes.c_void_p):
-        return (body_overlap_create if kind == 'body_overlap' else surface_crossings_create)(handle_or_faces, V)
+        return _HANDLE_KINDS[kind](handle_or_faces, V)
     handle = handle_or_faces
     if not isinstance(handle, hip.Handle):
         handle = hip.Handle(None)
@@ -1785,6 +1794,67 @@ def surface_crossings_destroy(handle):
     handle.close()
 
 
+def _faces_in_chunk(n, chunk):
+    """how many of n faces lie in 256-face chunk ``chunk`` (a tensor of chunk indices): 256 but for a partial last chunk"""
+    return (n - chunk * SURFACE_CROSSINGS_CHUNK).clamp(max=SURFACE_CROSSINGS_CHUNK)
+
+
+def _crossings_search(kind, lead, tile_args, body, pv, B, n_jobs, key_stride, width, outs):
+    """The passes of a crossing search, psi_<kind>_{tiles,test,finish} of ``kind`` 'surface_crossings' or 'scene_crossings', on the current
+    stream and device of the caller: the boxes of the ``body`` handle's chunks and bodies, the tile count pass, a scan, read-back 1 (the
+    tiles with the non-finite flag), the tile emit pass, the test count pass, a scan, read-back 2 (the pairs), the test emit pass, the
+    sort of the int64 keys, the row starts of the bodies (``key_stride`` keys per body) and finish, which fills the caller's zeroed
+    ``outs`` (counts, contour, the bit masks, irregular, as psi_<kind>_finish takes them).  ``lead``: the handles that lead every
+    argument list of the kind; ``tile_args``: what follows them in tiles; ``n_jobs``: the workgroups of the tile passes (0: nothing is
+    admitted and nothing is launched); ``width``: the columns of a pair row.  A pass with nothing to do is not launched: no tile ends
+    after read-back 1, no pair after read-back 2.  Returns pairs [n,width] int32, events [n] int32, length [n] fp32, n_tiles, n_pairs
+    and the tile table [n_tiles,4] int32 (None without tiles).  ``ValueError`` for a non-finite vertex and for more than 2^31 - 1
+    tiles or pairs."""
+    L, st, dev = hip.lib(), hip.stream(), outs[0].device
+    i32, i64, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev), dict(dtype=torch.float32, device=dev)
+
+    def run(name, *args):
+        hip.check(getattr(L, name)(*args, st), name)
+
+    tiles_pass, test_pass, finish = ('psi_%s_%s' % (kind, p) for p in ('tiles', 'test', 'finish'))
+    pairs, events, length = torch.empty(0, width, **i32), torch.empty(0, **i32), torch.empty(0, **f32)
+    if n_jobs == 0:
+        return pairs, events, length, 0, 0, None
+    chunk_boxes, body_boxes = torch.empty(B, body.n_chunks, 6, **f32), torch.empty(B, 6, **f32)
+    bad, job_tiles = torch.empty(1, **i32), torch.empty(n_jobs, **i32)
+    cb, bb, jt = hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles)
+    run('psi_surface_crossings_boxes', body, pv, B, cb, bb, hip.ptr(bad))
+    run(tiles_pass, *lead, *tile_args, cb, bb, jt, None, 0, None)
+    job_inc = torch.cumsum(job_tiles, 0, dtype=torch.int64)
+    n_tiles, first_bad = torch.stack([job_inc[-1], bad[0].to(torch.int64)]).cpu().tolist()                  # read-back 1
+    if first_bad < B:
+        raise ValueError('body %d has a non-finite vertex coordinate' % first_bad)
+    if n_tiles > SURFACE_CROSSINGS_MAX:
+        raise ValueError('the batch has %d tiles: more than 2^31 - 1' % n_tiles)
+    if n_tiles == 0:                            # never an empty grid
+        return pairs, events, length, 0, 0, None
+    tiles, job_off = torch.empty(n_tiles, 4, **i32), job_inc - job_tiles
+    run(tiles_pass, *lead, *tile_args, cb, bb, jt, hip.ptr(job_off), n_tiles, hip.ptr(tiles))
+    tile_hits = torch.empty(n_tiles, **i32)
+    run(test_pass, *lead, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), None, 0, None, None, None)
+    tile_inc = torch.cumsum(tile_hits, 0, dtype=torch.int64)
+    n_pairs = int(tile_inc[-1].item())                                                                      # read-back 2
+    if n_pairs > SURFACE_CROSSINGS_MAX:
+        raise ValueError('the batch has %d crossing pairs: more than 2^31 - 1' % n_pairs)
+    if n_pairs == 0:
+        return pairs, events, length, n_tiles, 0, tiles
+    keys, ev_raw, len_raw = torch.empty(n_pairs, **i64), torch.empty(n_pairs, **i32), torch.empty(n_pairs, **f32)
+    tile_off = tile_inc - tile_hits
+    run(test_pass, *lead, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), hip.ptr(tile_off), n_pairs, hip.ptr(keys), hip.ptr(ev_raw),
+        hip.ptr(len_raw))
+    keys_sorted, order = torch.sort(keys)
+    row_start = torch.searchsorted(keys_sorted, torch.arange(B + 1, **i64) * key_stride).contiguous()
+    pairs, events, length = torch.empty(n_pairs, width, **i32), torch.empty(n_pairs, **i32), torch.empty(n_pairs, **f32)
+    run(finish, *lead, B, hip.ptr(keys_sorted), hip.ptr(order), hip.ptr(ev_raw), hip.ptr(len_raw), n_pairs, hip.ptr(row_start), hip.ptr(pairs),
+        hip.ptr(events), hip.ptr(length), *(hip.ptr(o) for o in outs))
+    return pairs, events, length, n_tiles, n_pairs, tiles
+
+
 def surface_crossings(verts, handle_or_faces, group=None, self_pairs=True, between=True, mode='pruned', return_stats=False):
     """Which pairs of triangles of the body surfaces of a batch properly intersect (include/psi_hip.h: psi_surface_crossings_*; DESIGN.md
     section 10e).  verts [B,V,3] fp32 on the GPU, world frame; ``handle_or_faces``: a handle of ``surface_crossings_create`` or faces [F,3]
@@ -1802,64 +1872,20 @@ def surface_crossings(verts, handle_or_faces, group=None, self_pairs=True, betwe
         if mode not in ('pruned', 'brute'):
             raise ValueError("mode is 'pruned' or 'brute', got %r" % (mode,))
     B, V, dev, pv, pg = _batch_args(verts, group, 'surface_crossings', then=check_mode, max_B=SURFACE_CROSSINGS_MAX_B)
-    L = hip.lib()
     flags = (1 if self_pairs else 0) | (2 if between else 0) | (4 if mode == 'brute' else 0)
-    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         handle = _handle_of(handle_or_faces, V, 'surface_crossings')
-        F, nC = handle.F, handle.n_chunks
+        F = handle.F
         if (B * F) ** 2 >= 2 ** 63:
             raise ValueError('surface_crossings: (B F)^2 = (%d x %d)^2 does not fit the int64 pair key' % (B, F))
-        st = hip.stream()
-        words = (F + 31) // 32
         counts = torch.zeros(B, B, **i32)
         contour = torch.zeros(B, B, dtype=torch.float64, device=dev)
-        mask = torch.zeros(B, words, **i32)
+        mask = torch.zeros(B, (F + 31) // 32, **i32)
         irregular = torch.zeros(1, **i32)
-        pairs, events = torch.empty(0, 4, **i32), torch.empty(0, **i32)
-        length = torch.empty(0, dtype=torch.float32, device=dev)
-        n_tiles = n_pairs = 0
-        if flags & 3:
-            chunk_boxes = torch.empty(B, nC, 6, dtype=torch.float32, device=dev)
-            body_boxes = torch.empty(B, 6, dtype=torch.float32, device=dev)
-            bad = torch.empty(1, **i32)
-            job_tiles = torch.empty(B * B, **i32)
-            hip.check(L.psi_surface_crossings_boxes(handle, pv, B, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(bad), st),
-                      'psi_surface_crossings_boxes')
-            hip.check(L.psi_surface_crossings_tiles(handle, pg, B, flags, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles),
-                                                    None, 0, None, st), 'psi_surface_crossings_tiles')
-            job_inc = torch.cumsum(job_tiles, 0, dtype=torch.int64)
-            n_tiles, first_bad = torch.stack([job_inc[-1], bad[0].to(torch.int64)]).cpu().tolist()          # read-back 1
-            if first_bad < B:
-                raise ValueError('body %d has a non-finite vertex coordinate' % first_bad)
-            if n_tiles > SURFACE_CROSSINGS_MAX:
-                raise ValueError('the batch has %d tiles: more than 2^31 - 1' % n_tiles)
-        if n_tiles > 0:                     # never an empty grid
-            tiles = torch.empty(n_tiles, 4, **i32)
-            job_off = job_inc - job_tiles
-            hip.check(L.psi_surface_crossings_tiles(handle, pg, B, flags, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles),
-                                                    hip.ptr(job_off), n_tiles, hip.ptr(tiles), st), 'psi_surface_crossings_tiles')
-            tile_hits = torch.empty(n_tiles, **i32)
-            hip.check(L.psi_surface_crossings_test(handle, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), None, 0, None, None, None, st),
-                      'psi_surface_crossings_test')
-            tile_inc = torch.cumsum(tile_hits, 0, dtype=torch.int64)
-            n_pairs = int(tile_inc[-1].item())                                                            # read-back 2
-            if n_pairs > SURFACE_CROSSINGS_MAX:
-                raise ValueError('the batch has %d crossing pairs: more than 2^31 - 1' % n_pairs)
-        if n_pairs > 0:
-            tile_off = tile_inc - tile_hits
-            keys = torch.empty(n_pairs, **i64)
-            ev_raw = torch.empty(n_pairs, **i32)
-            len_raw = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-            hip.check(L.psi_surface_crossings_test(handle, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), hip.ptr(tile_off), n_pairs,
-                                                   hip.ptr(keys), hip.ptr(ev_raw), hip.ptr(len_raw), st), 'psi_surface_crossings_test')
-            keys_sorted, order = torch.sort(keys)
-            row_start = torch.searchsorted(keys_sorted, torch.arange(B + 1, **i64) * (F * B * F)).contiguous()
-            pairs, events = torch.empty(n_pairs, 4, **i32), torch.empty(n_pairs, **i32)
-            length = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-            hip.check(L.psi_surface_crossings_finish(handle, B, hip.ptr(keys_sorted), hip.ptr(order), hip.ptr(ev_raw), hip.ptr(len_raw), n_pairs,
-                                                     hip.ptr(row_start), hip.ptr(pairs), hip.ptr(events), hip.ptr(length), hip.ptr(counts),
-                                                     hip.ptr(contour), hip.ptr(mask), hip.ptr(irregular), st), 'psi_surface_crossings_finish')
+        pairs, events, length, n_tiles, n_pairs, tiles = _crossings_search(
+            'surface_crossings', (handle,), (pg, B, flags), handle, pv, B, n_jobs=B * B if flags & 3 else 0, key_stride=F * B * F, width=4,
+            outs=(counts, contour, mask, irregular))
         face_hit = _unpack_bits(mask, F)
     res = CrossingsResult(pairs, events, length, counts, contour, face_hit, irregular[0])
     if not return_stats:
@@ -1867,7 +1893,7 @@ def surface_crossings(verts, handle_or_faces, group=None, self_pairs=True, betwe
     box_tests = 0
     if n_tiles > 0:                             # the (pair, box) tests the test pass executes, counted from the tile table
         t = tiles.long()
-        na, nb = (F - t[:, 2] * SURFACE_CROSSINGS_CHUNK).clamp(max=SURFACE_CROSSINGS_CHUNK), (F - t[:, 3] * SURFACE_CROSSINGS_CHUNK).clamp(max=SURFACE_CROSSINGS_CHUNK)
+        na, nb = _faces_in_chunk(F, t[:, 2]), _faces_in_chunk(F, t[:, 3])
         diagonal = (t[:, 0] == t[:, 1]) & (t[:, 2] == t[:, 3])
         box_tests = int(torch.where(diagonal, na * (na - 1) // 2, na * nb).sum().item())
     return res, {'tiles': int(n_tiles), 'pairs': int(n_pairs), 'box_tests': box_tests}
@@ -1935,72 +1961,27 @@ def scene_crossings(verts, scene_handle, body_handle_or_faces, mode='pruned', re
         if not isinstance(scene_handle, hip.Handle) or scene_handle.destroy != 'psi_scene_crossings_destroy' or not scene_handle:
             raise ValueError('scene_crossings: scene_handle is a live handle of scene_crossings_create')
     B, V, dev, pv, _ = _batch_args(verts, None, 'scene_crossings', then=check, max_B=SURFACE_CROSSINGS_MAX_B)
-    L = hip.lib()
-    brute = 1 if mode == 'brute' else 0
-    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         body = _handle_of(body_handle_or_faces, V, 'surface_crossings')
         F, nC, nf = body.F, body.n_chunks, scene_handle.F
         if B * F * nf >= 2 ** 63:
             raise ValueError('scene_crossings: B F nf = %d x %d x %d does not fit the int64 pair key' % (B, F, nf))
-        st = hip.stream()
         counts = torch.zeros(B, **i32)
         contour = torch.zeros(B, dtype=torch.float64, device=dev)
         face_mask = torch.zeros(B, (F + 31) // 32, **i32)
         tri_mask = torch.zeros(1, (nf + 31) // 32, **i32)
         irregular = torch.zeros(1, **i32)
-        pairs, events = torch.empty(0, 3, **i32), torch.empty(0, **i32)
-        length = torch.empty(0, dtype=torch.float32, device=dev)
-        n_pairs = 0
-        chunk_boxes = torch.empty(B, nC, 6, dtype=torch.float32, device=dev)
-        body_boxes = torch.empty(B, 6, dtype=torch.float32, device=dev)
-        bad = torch.empty(1, **i32)
-        job_tiles = torch.empty(B * nC, **i32)
-        hip.check(L.psi_surface_crossings_boxes(body, pv, B, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(bad), st),
-                  'psi_surface_crossings_boxes')
-        hip.check(L.psi_scene_crossings_tiles(scene_handle, body, B, brute, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles),
-                                              None, 0, None, st), 'psi_scene_crossings_tiles')
-        job_inc = torch.cumsum(job_tiles, 0, dtype=torch.int64)
-        n_tiles, first_bad = torch.stack([job_inc[-1], bad[0].to(torch.int64)]).cpu().tolist()              # read-back 1
-        if first_bad < B:
-            raise ValueError('body %d has a non-finite vertex coordinate' % first_bad)
-        if n_tiles > SURFACE_CROSSINGS_MAX:
-            raise ValueError('the batch has %d tiles: more than 2^31 - 1' % n_tiles)
-        if n_tiles > 0:                     # never an empty grid
-            tiles = torch.empty(n_tiles, 4, **i32)
-            job_off = job_inc - job_tiles
-            hip.check(L.psi_scene_crossings_tiles(scene_handle, body, B, brute, hip.ptr(chunk_boxes), hip.ptr(body_boxes), hip.ptr(job_tiles),
-                                                  hip.ptr(job_off), n_tiles, hip.ptr(tiles), st), 'psi_scene_crossings_tiles')
-            tile_hits = torch.empty(n_tiles, **i32)
-            hip.check(L.psi_scene_crossings_test(scene_handle, body, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), None, 0, None, None,
-                                                 None, st), 'psi_scene_crossings_test')
-            tile_inc = torch.cumsum(tile_hits, 0, dtype=torch.int64)
-            n_pairs = int(tile_inc[-1].item())                                                            # read-back 2
-            if n_pairs > SURFACE_CROSSINGS_MAX:
-                raise ValueError('the batch has %d crossing pairs: more than 2^31 - 1' % n_pairs)
-        if n_pairs > 0:
-            tile_off = tile_inc - tile_hits
-            keys = torch.empty(n_pairs, **i64)
-            ev_raw = torch.empty(n_pairs, **i32)
-            len_raw = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-            hip.check(L.psi_scene_crossings_test(scene_handle, body, pv, B, hip.ptr(tiles), n_tiles, hip.ptr(tile_hits), hip.ptr(tile_off),
-                                                 n_pairs, hip.ptr(keys), hip.ptr(ev_raw), hip.ptr(len_raw), st), 'psi_scene_crossings_test')
-            keys_sorted, order = torch.sort(keys)
-            row_start = torch.searchsorted(keys_sorted, torch.arange(B + 1, **i64) * (F * nf)).contiguous()
-            pairs, events = torch.empty(n_pairs, 3, **i32), torch.empty(n_pairs, **i32)
-            length = torch.empty(n_pairs, dtype=torch.float32, device=dev)
-            hip.check(L.psi_scene_crossings_finish(scene_handle, body, B, hip.ptr(keys_sorted), hip.ptr(order), hip.ptr(ev_raw),
-                                                   hip.ptr(len_raw), n_pairs, hip.ptr(row_start), hip.ptr(pairs), hip.ptr(events),
-                                                   hip.ptr(length), hip.ptr(counts), hip.ptr(contour), hip.ptr(face_mask), hip.ptr(tri_mask),
-                                                   hip.ptr(irregular), st), 'psi_scene_crossings_finish')
+        pairs, events, length, n_tiles, n_pairs, tiles = _crossings_search(
+            'scene_crossings', (scene_handle, body), (B, 1 if mode == 'brute' else 0), body, pv, B, n_jobs=B * nC, key_stride=F * nf, width=3,
+            outs=(counts, contour, face_mask, tri_mask, irregular))
         res = SceneCrossingsResult(pairs, events, length, counts, contour, _unpack_bits(face_mask, F), _unpack_bits(tri_mask, nf)[0], irregular[0])
     if not return_stats:
         return res
     box_tests = 0
     if n_tiles > 0:                             # the (face, triangle) box tests the test pass executes, counted from the tile table
         t = tiles.long()
-        na, nb = (F - t[:, 1] * SURFACE_CROSSINGS_CHUNK).clamp(max=SURFACE_CROSSINGS_CHUNK), (nf - t[:, 2] * SURFACE_CROSSINGS_CHUNK).clamp(max=SURFACE_CROSSINGS_CHUNK)
-        box_tests = int((na * nb).sum().item())
+        box_tests = int((_faces_in_chunk(F, t[:, 1]) * _faces_in_chunk(nf, t[:, 2])).sum().item())
     return res, {'tiles': int(n_tiles), 'pairs': int(n_pairs), 'box_tests': box_tests}
 
 

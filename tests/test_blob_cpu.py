@@ -14,7 +14,8 @@ CSRC = os.path.join(ROOT, 'psi-release_amd', 'csrc')
 CONSTRUCTORS = {
     'psi_lbs_create': ('lbs.hip', 17), 'psi_nn_index_create': ('nnindex.hip', 5), 'psi_mesh_sdf_create': ('mesh_sdf.hip', 4),
     'psi_raster_mesh_create': ('raster.hip', 4), 'psi_raster_bodies_create': ('raster_bodies.hip', 3), 'psi_kmeans_create': ('kmeans.hip', 11),
-    'fit_build_scenes': ('fit.hip', 3),
+    'fit_build_scenes': ('fit.hip', 3), 'psi_body_overlap_create': ('body_overlap.hip', 1),
+    'psi_surface_crossings_create': ('surface_crossings.hip', 5),
 }
 
 
@@ -38,7 +39,9 @@ def test_every_constructors_buffers_lie_where_the_rule_puts_them(host_check):
     print(rr.stdout.strip())
     assert rr.returncode == 0, rr.stdout[-2000:] + rr.stderr[-4000:]
     assert 'runtime error' not in rr.stderr and 'AddressSanitizer' not in rr.stderr and 'FAILED' not in rr.stdout
-    assert 'all 12 blobs laid out as declared' in rr.stdout
+    assert 'all 15 blobs laid out as declared' in rr.stdout
+    # without parts the two optional buffers of the crossings handle reserve nothing: three 256-byte-padded buffers of 352 faces
+    assert re.search(r'^psi_surface_crossings_create F 352, no parts +5 buffers, +%d bytes' % (2 * 4352 + 1536), rr.stdout, re.M)
     counted = {m.group(1): int(m.group(2)) for m in re.finditer(r'^(\w+)[^\n]*? +(\d+) buffers,', rr.stdout, re.M)}
     for who, (_, n) in CONSTRUCTORS.items():
         assert counted[who] == n, (who, counted)

@@ -128,6 +128,35 @@ def test_handle_builder_against_the_numpy_statement(host_check, tmp_path, name, 
     assert np.array_equal(box, np.concatenate([pts.min(0), pts.max(0)]))
 
 
+def _flat_plate_face():
+    """The 50 triangles of the plate's face of constant z = 0.9: their centroid sums have no extent along z."""
+    v, f = C.plate_mesh()
+    flat = np.ascontiguousarray(f[200:250])
+    assert (v[flat][:, :, 2] == v[flat][0, 0, 2]).all()
+    return v, flat
+
+
+@pytest.mark.parametrize('name', ['capsule_24x46', 'plate_only', 'flat_plate_face'])
+def test_one_morton_order_for_body_handle_scene_handle_and_restatement(host_check, tmp_path, name):
+    """One mesh as a body topology with a pose and as a scene: the face order of psi_surface_crossings_face_order, the triangle order of
+    scn_build (through tools/scene_crossings_host_check.hip) and ``morton_chunks`` are equal element for element.  The 24 x 46 capsule has
+    F = 2116, nine chunks; on the flat face one axis has zero width."""
+    import surface_crossings_cases as SC
+    from psi_release_amd import hip
+    v, f = {'capsule_24x46': lambda: SC.mesh('24x46'), 'plate_only': C.plate_mesh, 'flat_plate_face': _flat_plate_face}[name]()
+    v, f = np.ascontiguousarray(v, np.float32), np.ascontiguousarray(f, np.int32)
+    V, F = len(v), len(f)
+    assert F == {'capsule_24x46': 2116, 'plate_only': 300, 'flat_plate_face': 50}[name]
+    as_p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    body_order = np.full(F, -1, np.int32)
+    assert hip.lib().psi_surface_crossings_face_order(as_p(f), V, F, as_p(v), as_p(body_order)) == 0, hip.last_error()
+    sc = C.scene('plate_only')
+    _, (scene_order, _, _) = C.run_host_check(host_check, tmp_path, sc.body_verts[:1], sc.body_faces, v, f)
+    want = SR.morton_chunks(v, f)[0]
+    assert np.array_equal(np.sort(want), np.arange(F)) and not np.array_equal(want, np.arange(F))
+    assert np.array_equal(body_order, want) and np.array_equal(scene_order, want)
+
+
 def test_morton_order_tightens_the_chunks():
     """On a shuffled room the chunk boxes of the Morton order are far smaller than those of the given order."""
     from psi_release_amd import synth

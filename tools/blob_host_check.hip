@@ -132,6 +132,13 @@ static Case nn_case(const char *who, size_t m, size_t nodes, size_t leaves, size
     return {who, {up(nodes * 256), up(leaves * 8 * 16), up(m * 16), up(cs, cs, true), up(gp, gp + 64, false)}, -1};
 }
 
+// psi_surface_crossings_create: F faces in chunk order, their caller's indices, the parts of the faces and the P x P skip matrix (or
+// neither: both fields null), the faces in the caller's order
+static Case crossings_case(const char *who, size_t F, size_t P)
+{
+    return {who, {up(F * 12), up(F * 4), up(P ? F * 4 : 0, P ? F * 4 : 0, true), up(P * P, P * P, true), up(F * 12)}, -1};
+}
+
 int main()
 {
     const size_t B = 2, n_c = 256, hint = B * n_c * 4;
@@ -144,6 +151,9 @@ int main()
         {"psi_raster_mesh_create nv 4 nf 2, labels", {dev(4 * 12), dev(2 * 12), {4 * 4, 4 * 4, DEVICE, true, nullptr}, zero(4)}, -1},
         {"psi_raster_mesh_create nv 4 nf 2, no labels", {dev(4 * 12), dev(2 * 12), {0, 4 * 4, DEVICE, true, nullptr}, zero(4)}, -1},
         {"psi_raster_bodies_create V 5 F 2", {up(2 * 12), up((5 + 1) * 4), up(2 * 12)}, -1},
+        {"psi_body_overlap_create F 352", {up(352 * 12)}, -1},
+        crossings_case("psi_surface_crossings_create F 352, 2 parts", 352, 2),
+        crossings_case("psi_surface_crossings_create F 352, no parts", 352, 0),
         // N = 64 points of d = 3, k = 2 centres, R = 1 restart: P = 1 update slice, NWA = 1 assign workgroup
         {"psi_kmeans_create N 64 d 3 k 2 R 1", {raw(64 * 3 * 4), dev(1 * 2 * 3 * 4), raw(4), raw(4), raw(4), raw(8), raw(8), raw(64 * 4), raw(2 * 3 * 8), raw(2 * 4), raw(8)}, -1},
         // S = 2 scenes of B = 2 bodies: KdDev is 88 bytes, PsiSdfGrid 40
