@@ -342,6 +342,9 @@ int psi_linear_backward(const float *gy, const float *act_out, const void *x, in
  * x, residual (nullable), y: bf16 feature maps [M, C] with the channel fastest (M = N*H*W: an NHWC / torch channels_last tensor),
  * C % 8 == 0, C <= 256.  y = act(gamma * (x - mean) * invstd + beta (+ residual)), act = ReLU when relu != 0.  save_mean / save_invstd
  * [C] fp32 are kept for the backward.  running_mean / running_var / num_batches_tracked (int64) may be NULL.
+ * The batch statistics are fp32 sums of x - x[0][c] and of its square, combined in double (mean = x[0][c] + S/M, var = Q/M - (S/M)^2): the
+ * error of the variance is a few fp32 roundings of the variance itself (tests: 64 * 2^-24 * (var + eps)) whatever the ratio of a channel's
+ * mean to its standard deviation, and a constant channel has variance 0 exactly.
  * Backward: dy [M,C] bf16 = dL/dy -> dx [M,C] bf16, dresidual [M,C] bf16 (nullable: the gradient of the skip input = dy masked by the
  * ReLU), dgamma / dbeta [C] fp32 (OVERWRITTEN).  y is the forward output (needed only when relu != 0, for the mask).
  * ws: psi_bn_workspace_floats(M, C) floats of device scratch per call (per-block partial sums; deterministic summation order).

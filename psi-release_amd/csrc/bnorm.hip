@@ -13,11 +13,14 @@
 // a plain bandwidth-bound pass is ~6 us.
 //   forward : stats (read x) -> finalize (C values) -> apply (read x [+ residual], write y)
 //   backward: reduce (read dy, y|x) -> finalize -> apply (read dy, x, y, write dx [, d_residual])
-// The reductions are deterministic: fixed per-block partials, summed in order by the finalize kernels (16 channels per block).  The partials
-// are fp32 sums of x and x^2; the finalize step combines them in double precision, which keeps the COMBINATION exact but not the partials:
-// for a channel whose |mean| is far above its standard deviation (mean 10, variance 0.01) E[x^2] - mean^2 loses the digits the fp32 partials
-// no longer hold and the variance can be off by about a percent, where the library's Welford pass is not.  Convolution outputs of this
-// trunk have |mean| of the order of their standard deviation (the parity tests against the library path hold to bf16 rounding).
+// The reductions are deterministic: fixed per-block partials, summed in order by the finalize kernels (16 channels per block).  The forward
+// partials are fp32 sums of d = x - p_c and d^2, where the pivot p_c = x[0][c] is the channel's value in row 0 of the map: a sample of the
+// channel, so |mean_c - p_c| is of the order of the standard deviation whatever the mean is.  The finalize step combines the partials in
+// double precision: mean = p + S/M, var = Q/M - (S/M)^2.  The cancellation in that difference is the one of a channel with |mean| ~ std (a
+// few units of the fp32 rounding of the partials, about 1e-7 of the variance), independent of mean / std; a constant channel has d = 0 in
+// every row and a variance of exactly 0.  (Sums of x and x^2 themselves lose var * (mean / std)^2 * 2^-24 and more: 8e-5 of the variance at
+// mean / std = 64, 3e-2 at 1024 — tools/bnorm_stats_sim.py, profiles/bnorm_fp64_errors.json.)  x - p is one more VALU operation per element
+// of a pass that waits for HBM, and p is one 16-byte load per thread of a line every thread of the grid shares.
 #include "psi_internal.h"
 #include <hip/hip_bf16.h>
 
@@ -104,25 +107,37 @@ __global__ __launch_bounds__(BN_BLK) void bn_stats_kernel(const void *__restrict
     typedef Map8<MT> V;
     const int ngrp = C / 8, rpb = BN_BLK / ngrp;
     const int g = threadIdx.x % ngrp, rr = threadIdx.x / ngrp;
-    float acc[2][8];
+    float acc[2][8], pv[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) acc[0][i] = acc[1][i] = 0.0f;
     const long stride = (long)gridDim.x * rpb;
     long r = (long)blockIdx.x * rpb + rr;
-    // four rows in flight per thread
-    for (; r + 3 * stride < M; r += 4 * stride) {
-        typename V::raw v[4];
+    // four rows in flight per thread.  The pivot (row 0 of the map; bn_fwd_finalize_kernel reads the same values) is requested BEHIND the
+    // first four rows: asked for first, it is waited for before any row is requested, a trip to memory of its own (profiles/bnorm_shifted_stats_ab.txt)
+    typename V::raw v[4];
+    bool more = r + 3 * stride < M;
+    if (more) {
 #pragma unroll
         for (int u = 0; u < 4; u++) v[u] = V::ld(x, (r + u * stride) * ngrp + g);
+    }
+    V::unpack(V::ld(x, g), pv);
+    while (more) {
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             float f[8];
             V::unpack(v[u], f);
 #pragma unroll
             for (int i = 0; i < 8; i++) {
-                acc[0][i] += f[i];
-                acc[1][i] += f[i] * f[i];
+                const float d = f[i] - pv[i];
+                acc[0][i] += d;
+                acc[1][i] += d * d;
             }
+        }
+        r += 4 * stride;
+        more = r + 3 * stride < M;
+        if (more) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) v[u] = V::ld(x, (r + u * stride) * ngrp + g);
         }
     }
     for (; r < M; r += stride) {
@@ -130,8 +145,9 @@ __global__ __launch_bounds__(BN_BLK) void bn_stats_kernel(const void *__restrict
         V::unpack(V::ld(x, r * ngrp + g), fa);
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-            acc[0][i] += fa[i];
-            acc[1][i] += fa[i] * fa[i];
+            const float d = fa[i] - pv[i];
+            acc[0][i] += d;
+            acc[1][i] += d * d;
         }
     }
     block_reduce_store<2>(acc, C, g, rr, rpb, part);
@@ -181,9 +197,13 @@ __device__ __forceinline__ void sum_partials(const float *__restrict__ part, int
     }
 }
 
-// sums the per-block partials in order (16 channels per block); mean / invstd / scale / shift; running statistics (nn.BatchNorm2d semantics:
+// sums the per-block partials in order (16 channels per block): S = sum (x - p), Q = sum (x - p)^2 with the pivot p = x[0][c] of
+// bn_stats_kernel, read here from the map itself (requested before the partials, so that it adds no trip to memory of its own);
+// mean = p + S/M, var = Q/M - (S/M)^2 in double; invstd / scale / shift; running statistics (nn.BatchNorm2d semantics:
 // running = (1 - momentum) * running + momentum * batch, the variance unbiased) and the batch counter
-__global__ __launch_bounds__(1024) void bn_fwd_finalize_kernel(const float *__restrict__ part, int nblk, long M, int C, const float *__restrict__ gamma,
+template <typename MT>
+__global__ __launch_bounds__(1024) void bn_fwd_finalize_kernel(const void *__restrict__ x, const float *__restrict__ part, int nblk, long M, int C,
+                                                                 const float *__restrict__ gamma,
                                                                  const float *__restrict__ beta, float eps, float momentum,
                                                                  float *__restrict__ running_mean, float *__restrict__ running_var,
                                                                  long long *__restrict__ num_batches, float *__restrict__ save_mean,
@@ -191,12 +211,14 @@ __global__ __launch_bounds__(1024) void bn_fwd_finalize_kernel(const float *__re
 {
     __shared__ double shd[1024];
     if (blockIdx.x == 0 && threadIdx.x == 0 && num_batches) *num_batches += 1;
+    const int Cb = C > BN_FIN_CH ? BN_FIN_CH : C, cp = threadIdx.x < Cb ? blockIdx.x * Cb + threadIdx.x : 0;    // (sum_partials: c)
+    const double pivot = sizeof(MT) == 2 ? (double)bf2f(((const bf16raw *)x)[cp]) : (double)((const float *)x)[cp];
     double s, q;
     int c;
     sum_partials(part, nblk, C, shd, s, q, c);
     if (c < 0) return;
-    const double mean = s / (double)M;
-    double var = q / (double)M - mean * mean;
+    const double ds = s / (double)M, mean = pivot + ds;
+    double var = q / (double)M - ds * ds;
     if (var < 0.0) var = 0.0;
     const float invstd = (float)(1.0 / sqrt(var + (double)eps));
     save_mean[c] = (float)mean;
@@ -498,7 +520,7 @@ static int bn_forward_t(const void *x, const void *residual, const float *gamma,
         hipLaunchKernelGGL(bn_stats_kernel<MT>, dim3(nb), dim3(BN_BLK), 0, st, x, M, C, part);
         PSI_CHECK_LAUNCH("bn_stats_kernel");
         psi_mark("bn_stats_kernel", st);
-        hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3(bn_fin_blocks(C)), dim3(1024), 0, st, part, nb, M, C, gamma, beta, eps, momentum, running_mean,
+        hipLaunchKernelGGL(bn_fwd_finalize_kernel<MT>, dim3(bn_fin_blocks(C)), dim3(1024), 0, st, x, part, nb, M, C, gamma, beta, eps, momentum, running_mean,
                            running_var, num_batches_tracked, save_mean, save_invstd, ss);
         PSI_CHECK_LAUNCH("bn_fwd_finalize_kernel");
     }
