@@ -16,20 +16,18 @@
 //
 // Launches of one psi_raster_render call (all views at once; the view is a grid dimension):
 //   rs_setup    one lane per (view, triangle): pieces -> 48-byte records, their tile boxes, per-tile counts (integer atomics)
-//   rs_scan     one workgroup per view: exclusive prefix sum of the view's tile counts, the view's number of (tile, piece) pairs
-//   rs_fill     one lane per (view, piece slot): piece ids into the bins (integer atomics; the order inside a bin is free)
+//   rs_scan, rs_view_base, the one host read of the call (the views' pair counts), rs_fill: the binning pass both rasterisers share
+//               (raster_bins.h: rs_bin_pass); a row of rs_fill is a view, the bin entry the piece slot within the view
 //   rs_tile     one workgroup per (view, 16x16 tile): the z-buffer of the tile as 256 64-bit keys in LDS; the bin is streamed in chunks
 //               of 256 pieces, one record per lane, read once.  A piece whose box covers few pixels of the tile is rasterised by its own
 //               lane (LDS atomic minimum); the others are put in an LDS list and rasterised by the whole workgroup, one lane per pixel.
 //               Then the resolve: depth and id from the key; the label by setting the winning triangle up again (same arithmetic, so
 //               the same pieces) and interpolating the piece that covers the pixel.
 // No floating-point atomics and no global atomics on the pixel path.
-#include "raster_device.h"
+#include "raster_bins.h"
 #include "blob.h"
-#include <vector>
 
 namespace {
-
 
 typedef CamVertT<1> CamVert;   // the one attribute of a snapshot vertex is its label
 
@@ -76,30 +74,10 @@ __global__ __launch_bounds__(256) void rs_setup_kernel(psi_raster_mesh mesh, con
         const unsigned box = k < n ? piece_record(pc[k], t, W, H, r) : NOBOX;
         if (box != NOBOX) {
             recs[slot] = r;
-            const int tx0 = box & 255, ty0 = (box >> 8) & 255, tx1 = (box >> 16) & 255, ty1 = box >> 24;
-            for (int ty = ty0; ty <= ty1; ty++)
-                for (int tx = tx0; tx <= tx1; tx++) atomicAdd(&tcount[(size_t)view * ntiles + ty * tiles_x + tx], 1);
+            count_box_tiles(box, view, tiles_x, ntiles, tcount);
         }
         pbox[slot] = box;
     }
-}
-
-__global__ __launch_bounds__(256) void rs_fill_kernel(int nf, int tiles_x, int ntiles, const unsigned *__restrict__ pbox, const int *__restrict__ toff,
-                                                      const long long *__restrict__ vbase, int *__restrict__ tcursor, int *__restrict__ bins)
-{
-    const int view = blockIdx.y;
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= 2 * nf) return;
-    const unsigned box = pbox[(size_t)view * 2 * nf + s];
-    if (box == NOBOX) return;
-    const int tx0 = box & 255, ty0 = (box >> 8) & 255, tx1 = (box >> 16) & 255, ty1 = box >> 24;
-    int *base = bins + vbase[view];
-    for (int ty = ty0; ty <= ty1; ty++)
-        for (int tx = tx0; tx <= tx1; tx++) {
-            const size_t tile = (size_t)view * ntiles + ty * tiles_x + tx;
-            const int pos = atomicAdd(&tcursor[tile], 1);
-            base[toff[tile] + pos] = s;
-        }
 }
 
 __global__ __launch_bounds__(WG) void rs_tile_kernel(psi_raster_mesh mesh, const float *__restrict__ w2c, const float *__restrict__ intr, int W, int H,
@@ -141,32 +119,11 @@ __global__ __launch_bounds__(256) void rs_check_faces_kernel(const int *__restri
     if (i < n && (faces[i] < 0 || faces[i] >= nv)) atomicOr(bad, 1);
 }
 
-struct Layout {
-    size_t o_recs, o_pbox, o_tcount, o_toff, o_tcursor, o_vbase, o_bins, bytes;
-    size_t pair_cap;
-    int tiles_x, tiles_y, ntiles;
-};
-
-Layout layout(int nf, int n_views, int W, int H)
+BinLayout layout(int nf, int n_views, int W, int H)
 {
-    Layout L;
-    L.tiles_x = psi_cdiv(W, TILE);
-    L.tiles_y = psi_cdiv(H, TILE);
-    L.ntiles = L.tiles_x * L.tiles_y;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t slots = (size_t)n_views * 2 * nf, vt = (size_t)n_views * L.ntiles;
-    L.o_recs = take(slots * sizeof(PieceRec));
-    L.o_pbox = take(slots * 4);
-    L.o_tcount = take(vt * 4);           // tcount and tcursor are adjacent: one memset clears both
-    L.o_tcursor = take(vt * 4);
-    L.o_toff = take(vt * 4);
-    L.o_vbase = take((size_t)n_views * 8);
-    // room for the bins: every piece in one tile, plus 64 pieces in every tile (large triangles cover many tiles); a call that needs more
-    // takes the bins from a buffer the mesh object owns
-    L.pair_cap = (size_t)n_views * ((size_t)2 * nf + (size_t)64 * L.ntiles);
-    L.o_bins = take(L.pair_cap * 4);
-    L.bytes = o;
+    BinLayout L;
+    L.begin((size_t)n_views * 2 * nf, n_views, W, H);
+    L.place_bins();
     return L;
 }
 
@@ -211,7 +168,7 @@ extern "C" void psi_raster_mesh_destroy(psi_raster_mesh *m)
 {
     if (!m) return;
     (void)hipFree(m->blob);
-    if (m->bins_extra) (void)hipFree(m->bins_extra);
+    rs_free_grown_bins(m->bins_extra);
     delete m;
 }
 
@@ -229,56 +186,24 @@ extern "C" int psi_raster_render(psi_raster_mesh *m, const float *d_w2c, const f
     PSI_REQUIRE(W >= 1 && H >= 1 && W <= 4096 && H <= 4096, "image sizes 1..4096");
     PSI_REQUIRE(near_ > 0.0f, "near > 0");
     hipStream_t st = (hipStream_t)stream;
-    const Layout L = layout(m->nf, n_views, W, H);
+    const BinLayout L = layout(m->nf, n_views, W, H);
     char *ws = (char *)d_workspace;
     if (!ws) {
         ws = (char *)psi_scratch(L.bytes, st);
         if (!ws) return PSI_ENOMEM;
     }
-    PieceRec *recs = (PieceRec *)(ws + L.o_recs);
-    unsigned *pbox = (unsigned *)(ws + L.o_pbox);
-    int *tcount = (int *)(ws + L.o_tcount), *tcursor = (int *)(ws + L.o_tcursor), *toff = (int *)(ws + L.o_toff);
-    long long *vbase = (long long *)(ws + L.o_vbase);
-    int *bins = (int *)(ws + L.o_bins);
+    const BinRegions R(L, ws);
 
-    PSI_CHECK_HIP(hipMemsetAsync(tcount, 0, L.o_toff - L.o_tcount, st));
+    PSI_CHECK_HIP(hipMemsetAsync(R.tcount, 0, L.count_bytes(), st));
     PSI_CHECK_HIP(hipMemsetAsync(d_stats, 0, (size_t)n_views * 8, st));
     hipLaunchKernelGGL(rs_setup_kernel, dim3(psi_cdiv(m->nf, 256), n_views), dim3(256), 0, st, *m, d_w2c, d_intr, W, H, near_, L.tiles_x, L.ntiles,
-                       recs, pbox, tcount, d_stats);
+                       R.recs, R.pbox, R.tcount, d_stats);
     PSI_CHECK_LAUNCH("rs_setup_kernel");
-    hipLaunchKernelGGL(rs_scan_kernel, dim3(n_views), dim3(256), 0, st, tcount, L.ntiles, toff, d_stats);
-    PSI_CHECK_LAUNCH("rs_scan_kernel");
-    hipLaunchKernelGGL(rs_view_base_kernel, dim3(1), dim3(64), 0, st, d_stats, n_views, vbase);
-    PSI_CHECK_LAUNCH("rs_view_base_kernel");
-    // the bins are sized from the counts: the one host read of the call
-    std::vector<int> h_stats((size_t)n_views * 2);
-    PSI_CHECK_HIP(hipMemcpyAsync(h_stats.data(), d_stats, (size_t)n_views * 8, hipMemcpyDeviceToHost, st));
-    PSI_CHECK_HIP(hipStreamSynchronize(st));
-    size_t pairs = 0;
-    for (int v = 0; v < n_views; v++) {
-        PSI_REQUIRE(h_stats[(size_t)v * 2] >= 0, "a view's (tile, piece) pairs exceed 2^31");
-        pairs += (size_t)h_stats[(size_t)v * 2];
-    }
-    if (pairs > L.pair_cap) {
-        if (m->bins_extra_bytes < pairs * 4) {
-            if (m->bins_extra) (void)hipFree(m->bins_extra);  // one call at a time per mesh (psi_hip.h) and this call's stream is idle: nothing reads the old buffer
-            m->bins_extra = nullptr;
-            m->bins_extra_bytes = 0;
-            const size_t want = pairs * 4 + pairs;
-            hipError_t e = hipMalloc(&m->bins_extra, want);
-            if (e != hipSuccess) {
-                psi_set_error("psi_raster_render: hipMalloc of %zu bytes for the bins failed: %s", want, hipGetErrorString(e));
-                return PSI_ENOMEM;
-            }
-            m->bins_extra_bytes = want;
-        }
-        bins = (int *)m->bins_extra;
-    }
-    hipLaunchKernelGGL(rs_fill_kernel, dim3(psi_cdiv(2L * m->nf, 256), n_views), dim3(256), 0, st, m->nf, L.tiles_x, L.ntiles, pbox, toff, vbase, tcursor,
-                       bins);
-    PSI_CHECK_LAUNCH("rs_fill_kernel");
-    hipLaunchKernelGGL(rs_tile_kernel, dim3(L.ntiles, n_views), dim3(WG), 0, st, *m, d_w2c, d_intr, W, H, near_, L.tiles_x, L.ntiles, recs, tcount, toff,
-                       vbase, bins, d_depth, d_tri, d_seg);
+    int *bins = nullptr;
+    if (int rc = rs_bin_pass("psi_raster_render", L, R, m->bins_extra, n_views, d_stats, nullptr, nullptr, n_views, 2 * m->nf, nullptr, 0, st, &bins))
+        return rc;
+    hipLaunchKernelGGL(rs_tile_kernel, dim3(L.ntiles, n_views), dim3(WG), 0, st, *m, d_w2c, d_intr, W, H, near_, L.tiles_x, L.ntiles, R.recs, R.tcount,
+                       R.toff, R.vbase, bins, d_depth, d_tri, d_seg);
     PSI_CHECK_LAUNCH("rs_tile_kernel");
     return 0;
 }

@@ -13,13 +13,14 @@
 //   rb_check_draws   one lane per draw: body and view indices in range
 //   per pass of at most draws_per_pass draws (the piece records of a pass are what the workspace holds):
 //     rb_setup       one lane per (draw, face): pieces -> records, tile boxes, per-(view, tile) counts
-//     rs_scan, rs_view_base   as psi_raster_render; then the host reads the pass's pair counts
-//     rb_fill        one lane per (draw, piece slot): slots into the bins of the draw's view
+//     rs_scan, rs_view_base, the one host read of the pass (the views' pair counts; the first pass also brings rb_check_draws' verdict),
+//     rs_fill        the binning pass both rasterisers share (raster_bins.h: rs_bin_pass); a row of rs_fill is a draw, the bin entry the
+//                    piece slot within the pass, in the bins of the draw's view
 //     rb_tile        one workgroup per (view, tile): raster.hip's LDS z-buffer over the bin, min-combined into the body key image by a plain
 //                    load / min / store (one workgroup owns a tile within a pass, and the passes are stream-ordered)
 //   rb_compose       one lane per pixel: owner, shading (the winning triangle set up again with three attributes), colours, counts
 // No floating-point atomics; integer atomics only for the bin counts and the per-draw pixel counts.
-#include "raster_device.h"
+#include "raster_bins.h"
 #include "blob.h"
 #include <algorithm>
 #include <vector>
@@ -29,8 +30,7 @@ struct psi_raster_bodies {
     int *voff;         // [V + 1]   CSR: the faces of vertex v are vface[voff[v] .. voff[v + 1]), ascending
     int *vface;        // [3 F]
     int V, F;
-    void *bins_extra;  // as psi_raster_mesh: grown when a pass's (tile, piece) pairs exceed the workspace's bins
-    size_t bins_extra_bytes;
+    RsGrownBins bins_extra;  // as psi_raster_mesh's, for a pass
     char *blob;        // the one allocation behind faces, voff and vface
 };
 
@@ -217,33 +217,10 @@ __global__ __launch_bounds__(256) void rb_setup_kernel(psi_raster_bodies tp, Dra
         const size_t slot = ((size_t)j * 2 + k) * tp.F + f;
         if (box[k] != NOBOX) {
             recs[slot] = r[k];
-            const int tx0 = box[k] & 255, ty0 = (box[k] >> 8) & 255, tx1 = (box[k] >> 16) & 255, ty1 = box[k] >> 24;
-            for (int ty = ty0; ty <= ty1; ty++)
-                for (int tx = tx0; tx <= tx1; tx++) atomicAdd(&tcount[(size_t)view * ntiles + ty * tiles_x + tx], 1);
+            count_box_tiles(box[k], view, tiles_x, ntiles, tcount);
         }
         pbox[slot] = box[k];
     }
-}
-
-__global__ __launch_bounds__(256) void rb_fill_kernel(int F, const int *__restrict__ draw_view, int d0, int tiles_x, int ntiles,
-                                                      const unsigned *__restrict__ pbox, const int *__restrict__ toff, const long long *__restrict__ vbase,
-                                                      int *__restrict__ tcursor, int *__restrict__ bins)
-{
-    const int j = blockIdx.y;
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= 2 * F) return;
-    const size_t slot = (size_t)j * 2 * F + s;
-    const unsigned box = pbox[slot];
-    if (box == NOBOX) return;                                 // every slot of a draw with a bad view is empty
-    const int view = draw_view[d0 + j];
-    const int tx0 = box & 255, ty0 = (box >> 8) & 255, tx1 = (box >> 16) & 255, ty1 = box >> 24;
-    int *base = bins + vbase[view];
-    for (int ty = ty0; ty <= ty1; ty++)
-        for (int tx = tx0; tx <= tx1; tx++) {
-            const size_t tile = (size_t)view * ntiles + ty * tiles_x + tx;
-            const int pos = atomicAdd(&tcursor[tile], 1);
-            base[toff[tile] + pos] = (int)slot;
-        }
 }
 
 __global__ __launch_bounds__(WG) void rb_tile_kernel(int W, int H, int tiles_x, int ntiles, const PieceRec *__restrict__ recs, const int *__restrict__ tcount,
@@ -305,10 +282,9 @@ __global__ __launch_bounds__(256) void rb_compose_kernel(Scene sc, psi_raster_bo
     }
 }
 
-struct Layout {
-    size_t o_recs, o_pbox, o_tcount, o_tcursor, o_toff, o_vbase, o_pstats, o_bad, o_keys, o_bins, bytes;
-    size_t pair_cap;
-    int dpp, tiles_x, tiles_y, ntiles;
+struct Layout : BinLayout {
+    size_t o_pstats, o_bad, o_keys;
+    int dpp;
 };
 
 // dpp * F < 2^30: a pass's 2 * dpp * F piece slots are ints in the bins
@@ -317,26 +293,11 @@ bool layout(int F, int draws_per_pass, int n_views, int W, int H, Layout &L)
     if (F <= 0 || draws_per_pass <= 0 || n_views <= 0 || n_views > 65535 || W <= 0 || H <= 0 || W > 4096 || H > 4096) return false;
     L.dpp = std::min(draws_per_pass, MAX_PASS_DRAWS);
     if ((long long)L.dpp * F >= (1LL << 30)) return false;
-    L.tiles_x = psi_cdiv(W, TILE);
-    L.tiles_y = psi_cdiv(H, TILE);
-    L.ntiles = L.tiles_x * L.tiles_y;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-    const size_t slots = (size_t)L.dpp * 2 * F, vt = (size_t)n_views * L.ntiles;
-    L.o_recs = take(slots * sizeof(PieceRec));
-    L.o_pbox = take(slots * 4);
-    L.o_tcount = take(vt * 4);           // tcount and tcursor are adjacent: one memset clears both
-    L.o_tcursor = take(vt * 4);
-    L.o_toff = take(vt * 4);
-    L.o_vbase = take((size_t)n_views * 8);
-    L.o_pstats = take((size_t)n_views * 8);
-    L.o_bad = take(4);
-    L.o_keys = take((size_t)n_views * W * H * 8);
-    // room for a pass's bins: every piece in one tile, plus 64 pieces in every tile; a pass that needs more takes the bins from a buffer the
-    // bodies object owns
-    L.pair_cap = slots + (size_t)64 * vt;
-    L.o_bins = take(L.pair_cap * 4);
-    L.bytes = o;
+    L.begin((size_t)L.dpp * 2 * F, n_views, W, H);
+    L.o_pstats = L.take((size_t)n_views * 8);
+    L.o_bad = L.take(4);
+    L.o_keys = L.take((size_t)n_views * W * H * 8);
+    L.place_bins();
     return true;
 }
 
@@ -396,7 +357,7 @@ extern "C" void psi_raster_bodies_destroy(psi_raster_bodies *b)
 {
     if (!b) return;
     (void)hipFree(b->blob);
-    if (b->bins_extra) (void)hipFree(b->bins_extra);
+    rs_free_grown_bins(b->bins_extra);
     delete b;
 }
 
@@ -439,13 +400,9 @@ extern "C" int psi_raster_bodies_render(psi_raster_mesh *scene, const float *d_v
         ws = (char *)psi_scratch(L.bytes, st);
         if (!ws) return PSI_ENOMEM;
     }
-    PieceRec *recs = (PieceRec *)(ws + L.o_recs);
-    unsigned *pbox = (unsigned *)(ws + L.o_pbox);
-    int *tcount = (int *)(ws + L.o_tcount), *tcursor = (int *)(ws + L.o_tcursor), *toff = (int *)(ws + L.o_toff);
-    long long *vbase = (long long *)(ws + L.o_vbase);
+    const BinRegions R(L, ws);
     int *pstats = (int *)(ws + L.o_pstats), *d_bad = (int *)(ws + L.o_bad);
     unsigned long long *keys = (unsigned long long *)(ws + L.o_keys);
-    int *bins = (int *)(ws + L.o_bins);
     const Draws dr = {d_draw_body, d_draw_view, d_draw_rgb, d_bverts};
 
     PSI_CHECK_HIP(hipMemsetAsync(keys, 0xff, (size_t)n_views * W * H * 8, st));
@@ -456,49 +413,18 @@ extern "C" int psi_raster_bodies_render(psi_raster_mesh *scene, const float *d_v
         hipLaunchKernelGGL(rb_check_draws_kernel, dim3(psi_cdiv(M, 256)), dim3(256), 0, st, d_draw_body, d_draw_view, M, B, n_views, d_bad);
         PSI_CHECK_LAUNCH("rb_check_draws_kernel");
     }
-    std::vector<int> h_stats((size_t)n_views * 2);
     for (int d0 = 0; d0 < M; d0 += L.dpp) {
         const int nd = std::min(L.dpp, M - d0);
-        PSI_CHECK_HIP(hipMemsetAsync(tcount, 0, L.o_toff - L.o_tcount, st));
+        PSI_CHECK_HIP(hipMemsetAsync(R.tcount, 0, L.count_bytes(), st));
         hipLaunchKernelGGL(rb_setup_kernel, dim3(psi_cdiv(b->F, 256), nd), dim3(256), 0, st, *b, dr, d0, B, n_views, d_w2c, d_intr, W, H, near_, L.tiles_x,
-                           L.ntiles, recs, pbox, tcount, d_stats);
+                           L.ntiles, R.recs, R.pbox, R.tcount, d_stats);
         PSI_CHECK_LAUNCH("rb_setup_kernel");
-        hipLaunchKernelGGL(rs_scan_kernel, dim3(n_views), dim3(256), 0, st, tcount, L.ntiles, toff, pstats);
-        PSI_CHECK_LAUNCH("rs_scan_kernel");
-        hipLaunchKernelGGL(rs_view_base_kernel, dim3(1), dim3(64), 0, st, pstats, n_views, vbase);
-        PSI_CHECK_LAUNCH("rs_view_base_kernel");
-        // the bins are sized from the counts: the one host read of the pass (the first also brings the verdict on the draws)
-        int bad = 0;
-        PSI_CHECK_HIP(hipMemcpyAsync(h_stats.data(), pstats, (size_t)n_views * 8, hipMemcpyDeviceToHost, st));
-        if (d0 == 0) PSI_CHECK_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
-        PSI_CHECK_HIP(hipStreamSynchronize(st));
-        PSI_REQUIRE(!bad, "a draw's body lies outside [0, B) or its view outside [0, n_views)");
-        size_t pairs = 0;
-        for (int v = 0; v < n_views; v++) {
-            PSI_REQUIRE(h_stats[(size_t)v * 2] >= 0, "a view's (tile, piece) pairs exceed 2^31");
-            pairs += (size_t)h_stats[(size_t)v * 2];
-        }
-        int *pass_bins = bins;
-        if (pairs > L.pair_cap) {
-            if (b->bins_extra_bytes < pairs * 4) {
-                if (b->bins_extra) (void)hipFree(b->bins_extra);  // one call at a time per bodies object and this call's stream is idle
-                b->bins_extra = nullptr;
-                b->bins_extra_bytes = 0;
-                const size_t want = pairs * 4 + pairs;
-                hipError_t e = hipMalloc(&b->bins_extra, want);
-                if (e != hipSuccess) {
-                    psi_set_error("psi_raster_bodies_render: hipMalloc of %zu bytes for the bins failed: %s", want, hipGetErrorString(e));
-                    return PSI_ENOMEM;
-                }
-                b->bins_extra_bytes = want;
-            }
-            pass_bins = (int *)b->bins_extra;
-        }
-        hipLaunchKernelGGL(rb_fill_kernel, dim3(psi_cdiv(2L * b->F, 256), nd), dim3(256), 0, st, b->F, d_draw_view, d0, L.tiles_x, L.ntiles, pbox, toff, vbase,
-                           tcursor, pass_bins);
-        PSI_CHECK_LAUNCH("rb_fill_kernel");
-        hipLaunchKernelGGL(rb_tile_kernel, dim3(L.ntiles, n_views), dim3(WG), 0, st, W, H, L.tiles_x, L.ntiles, recs, tcount, toff, vbase, pass_bins, pstats,
-                           d_stats, keys);
+        int *pass_bins = nullptr;
+        if (int rc = rs_bin_pass("psi_raster_bodies_render", L, R, b->bins_extra, n_views, pstats, d0 == 0 ? d_bad : nullptr,
+                                 "a draw's body lies outside [0, B) or its view outside [0, n_views)", nd, 2 * b->F, d_draw_view, d0, st, &pass_bins))
+            return rc;
+        hipLaunchKernelGGL(rb_tile_kernel, dim3(L.ntiles, n_views), dim3(WG), 0, st, W, H, L.tiles_x, L.ntiles, R.recs, R.tcount, R.toff, R.vbase, pass_bins,
+                           pstats, d_stats, keys);
         PSI_CHECK_LAUNCH("rb_tile_kernel");
     }
     Scene sc;

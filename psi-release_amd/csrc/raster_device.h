@@ -10,13 +10,26 @@
 
 #pragma clang fp contract(off)
 
+// Bins that a handle owns: grown on demand (raster_bins.h: rs_bin_pass) when the (tile, piece) pairs of a call or pass exceed what its
+// workspace holds, kept for the next one, freed with the handle.
+struct RsGrownBins {
+    void *ptr;
+    size_t bytes;
+};
+
+static inline void rs_free_grown_bins(RsGrownBins &g)
+{
+    if (g.ptr) (void)hipFree(g.ptr);
+    g.ptr = nullptr;
+    g.bytes = 0;
+}
+
 struct psi_raster_mesh {
     float *verts;      // [nv][3]   owned copies
     int *faces;        // [nf][3]
     float *vlabel;     // [nv] or nullptr
     int nv, nf;
-    void *bins_extra;  // grown on demand when a call's (tile, piece) pairs exceed what its workspace holds
-    size_t bins_extra_bytes;
+    RsGrownBins bins_extra;  // for a call whose (tile, piece) pairs exceed its workspace's bins
     char *blob;        // the one allocation behind verts, faces and vlabel
 };
 

@@ -952,15 +952,20 @@ def raster_mesh_destroy(handle):
     _destroy(handle, 'psi_raster_mesh_destroy')
 
 
+def _check_views(w2c, intr, size):
+    """n, H, W and the device of w2c [n,3,4] / intr [n,4] fp32 and size = (H, W)."""
+    if w2c.dtype != torch.float32 or intr.dtype != torch.float32 or w2c.dim() != 3 or tuple(w2c.shape[1:]) != (3, 4) or tuple(intr.shape) != (w2c.shape[0], 4):
+        raise ValueError('expected w2c [n,3,4] and intr [n,4], float32')
+    return w2c.shape[0], int(size[0]), int(size[1]), w2c.device
+
+
 def raster_render(handle, nf, w2c, intr, size, near=0.05, with_seg=True):
     """All views of one call through the tile-binned rasteriser (include/psi_hip.h: psi_raster_render).
 
     w2c [n,3,4] fp32 world-to-camera rows, intr [n,4] fp32 = fx, fy, cx, cy, size = (H, W).  Returns depth [n,H,W] fp32 (0 = no hit),
     tri [n,H,W] int32 (-1 = no hit), seg [n,H,W] fp32 or None, stats [n,2] int32 (binned pairs, pieces dropped by the 2^28 guard)."""
     pw, pi = hip.ptr(w2c), hip.ptr(intr)
-    if w2c.dtype != torch.float32 or intr.dtype != torch.float32 or w2c.dim() != 3 or tuple(w2c.shape[1:]) != (3, 4) or tuple(intr.shape) != (w2c.shape[0], 4):
-        raise ValueError('expected w2c [n,3,4] and intr [n,4], float32')
-    n, (H, W), dev = w2c.shape[0], (int(size[0]), int(size[1])), w2c.device
+    n, H, W, dev = _check_views(w2c, intr, size)
     depth = torch.empty(n, H, W, device=dev)
     tri = torch.empty(n, H, W, dtype=torch.int32, device=dev)
     seg = torch.empty(n, H, W, device=dev) if with_seg else None
@@ -1029,15 +1034,13 @@ def raster_bodies_render(bodies, V, F, bverts, draw_body, draw_view, draw_rgb, w
     body_id (int32) [n,H,W], counts [M,2] int32, stats [n,2] int32."""
     pv = _body_verts_ptr(bverts, V)
     pw, pi = hip.ptr(w2c), hip.ptr(intr)
-    if w2c.dtype != torch.float32 or intr.dtype != torch.float32 or w2c.dim() != 3 or tuple(w2c.shape[1:]) != (3, 4) or tuple(intr.shape) != (w2c.shape[0], 4):
-        raise ValueError('expected w2c [n,3,4] and intr [n,4], float32')
+    n, H, W, dev = _check_views(w2c, intr, size)
     M = draw_body.shape[0]
     if draw_body.dtype != torch.int32 or draw_view.dtype != torch.int32 or draw_rgb.dtype != torch.float32 or tuple(draw_view.shape) != (M,) \
             or tuple(draw_rgb.shape) != (M, 3) or draw_body.dim() != 1:
         raise ValueError('expected draw_body, draw_view [M] int32 and draw_rgb [M,3] float32')
     if M * F >= 2 ** 31:
         raise ValueError('M * F = %d: the piece index d * F + face must stay below 2^31' % (M * F))
-    n, (H, W), dev = w2c.shape[0], (int(size[0]), int(size[1])), w2c.device
     if scene is not None and (tuple(sdepth.shape) != (n, H, W) or tuple(stri.shape) != (n, H, W) or sdepth.dtype != torch.float32
                               or stri.dtype != torch.int32):
         raise ValueError("expected the scene's depth (float32) and tri (int32) images [n,H,W] of the same views")

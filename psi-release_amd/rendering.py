@@ -71,6 +71,14 @@ def intrinsics_rows(cam_int, n) -> np.ndarray:
     return np.ascontiguousarray(np.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], -1), dtype=np.float32)
 
 
+def camera_rows(cam_ext, cam_int, device):
+    """The cameras as the rasterisers take them: ``world_to_camera`` [n,3,4] and ``intrinsics_rows`` [n,4], uploaded to ``device``."""
+    ext = cam_ext.detach().cpu().numpy() if torch.is_tensor(cam_ext) else cam_ext
+    K = cam_int.detach().cpu().numpy() if torch.is_tensor(cam_int) else cam_int
+    w2c = world_to_camera(ext)
+    return torch.tensor(w2c, device=device), torch.tensor(intrinsics_rows(K, len(w2c)), device=device)
+
+
 class SnapshotRenderer:
     def __init__(self, mesh: SceneMesh):
         self.mesh = mesh
@@ -80,12 +88,11 @@ class SnapshotRenderer:
         """All views in one call: cam_ext [n,4,4] camera-to-world, cam_int [n,3,3] or [3,3], size = (H, W).  Returns GPU tensors
         depth [n,H,W] fp32 (0 where nothing is hit, like a depth sensor's hole), seg [n,H,W] fp32 (the interpolated vertex label,
         0 where nothing is hit) and tri [n,H,W] int32 (the triangle index, -1 where nothing is hit)."""
-        ext = cam_ext.detach().cpu().numpy() if torch.is_tensor(cam_ext) else cam_ext
-        K = cam_int.detach().cpu().numpy() if torch.is_tensor(cam_int) else cam_int
-        w2c = world_to_camera(ext)
-        dev = self.mesh.device
-        depth, tri, seg, stats = ops.raster_render(self.mesh.handle, self.mesh.nf, torch.tensor(w2c, device=dev),
-                                                   torch.tensor(intrinsics_rows(K, len(w2c)), device=dev), size, near)
+        return self._render_rows(*camera_rows(cam_ext, cam_int, self.mesh.device), size, near)
+
+    def _render_rows(self, w2c, intr, size, near):
+        """``render`` with the cameras as ``camera_rows`` prepares them (``ResultRenderer.render`` makes them once for both of its calls)."""
+        depth, tri, seg, stats = ops.raster_render(self.mesh.handle, self.mesh.nf, w2c, intr, size, near)
         self.last_stats = stats.cpu().numpy()
         for view in np.nonzero(self.last_stats[:, 1])[0]:
             warnings.warn('view %d: %d triangle pieces project beyond the 2^28 sub-pixel range and were not drawn (a vertex very close to '
@@ -256,10 +263,8 @@ class ResultRenderer:
         draw_view[i] with the colour body_rgb[i] ([M,3] or one colour for all, in [0,1]); by default draw i is (body i, view i), the
         reference's cam1 picture, which needs B == n.  Returns ``ResultImages``."""
         bv = self._bodies(body_verts)
-        ext = cam_ext.detach().cpu().numpy() if torch.is_tensor(cam_ext) else cam_ext
-        K = cam_int.detach().cpu().numpy() if torch.is_tensor(cam_int) else cam_int
-        w2c = world_to_camera(ext)
-        n, B, dev = len(w2c), bv.shape[0], self.device
+        t_w2c, t_intr = camera_rows(cam_ext, cam_int, self.device)
+        n, B, dev = len(t_w2c), bv.shape[0], self.device
         if (draw_body is None) != (draw_view is None):
             raise ValueError('draw_body and draw_view come together')
         if draw_body is None:
@@ -278,10 +283,9 @@ class ResultRenderer:
                                          dtype=np.float32), (M, 3))
         if draws_per_pass is None:
             draws_per_pass = self.pick_draws_per_pass(M, n, size)
-        t_w2c, t_intr = torch.tensor(w2c, device=dev), torch.tensor(intrinsics_rows(K, n), device=dev)
         scene = {}
         if self.scene is not None:
-            sdepth, _, stri = self.snapshots.render(ext, K, size, near)
+            sdepth, _, stri = self.snapshots._render_rows(t_w2c, t_intr, size, near)
             scene = dict(scene=self.scene.handle, vrgb=self.scene.rgb, sdepth=sdepth, stri=stri)
         out = ops.raster_bodies_render(self.handle, self.V, self.F, bv, torch.tensor(db, dtype=torch.int32, device=dev),
                                        torch.tensor(dv, dtype=torch.int32, device=dev), torch.tensor(np.ascontiguousarray(rgb), device=dev), t_w2c,

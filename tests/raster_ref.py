@@ -188,3 +188,22 @@ def raycast_fp64(verts, faces, cam_ext, cam_int, size, near=0.05, offset=(0.0, 0
         res['depth'].append(dd1.reshape(H, W))
         res['depth2'].append(dd2.reshape(H, W))
     return {k: np.stack(v) for k, v in res.items()}
+
+
+def triangle_soup(seed, n, reach, z_lo, z_hi, cam_int, size):
+    """n loose triangles in front of an identity camera, from RandomState(seed): centres uniform over the image of size = (H, W), every
+    vertex offset by uniform +-reach pixels in u and in v, at its own depth uniform in z_lo .. z_hi.  Returns verts [3n,3] fp32 (the points
+    that project to those pixel coordinates at those depths), faces [n,3] int32 = (3i, 3i+1, 3i+2), labels [3n] fp32 in 0 .. 41 and the
+    number of (tile, triangle) pairs of the triangles' pixel boxes, clipped to the image: a box estimate of the bin entries of either
+    rasteriser (16-pixel tiles).  Large triangles in a small image put more entries into the bins than their workspace
+    holds: 2 n for the piece slots + 64 per tile."""
+    (H, W), K, rs = size, np.asarray(cam_int, np.float64), np.random.RandomState(seed)
+    c = np.stack([rs.uniform(0, W, (n, 1)), rs.uniform(0, H, (n, 1))], -1) + rs.uniform(-reach, reach, (n, 3, 2))
+    z = rs.uniform(z_lo, z_hi, (n, 3))
+    verts = np.stack([(c[..., 0] - K[0, 2]) * z / K[0, 0], (c[..., 1] - K[1, 2]) * z / K[1, 1], z], -1).reshape(-1, 3).astype(F)
+    labels = rs.randint(0, 42, 3 * n).astype(F)
+    lo, hi = np.floor(c.min(1)), np.ceil(c.max(1))
+    seen = (c[..., 0].max(1) >= 0) & (c[..., 0].min(1) < W) & (c[..., 1].max(1) >= 0) & (c[..., 1].min(1) < H)
+    tx = np.clip(hi[:, 0], 0, W - 1) // 16 - np.clip(lo[:, 0], 0, W - 1) // 16 + 1
+    ty = np.clip(hi[:, 1], 0, H - 1) // 16 - np.clip(lo[:, 1], 0, H - 1) // 16 + 1
+    return verts, np.arange(3 * n, dtype=np.int32).reshape(n, 3), labels, int((tx * ty * seen).sum())

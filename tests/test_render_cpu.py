@@ -31,6 +31,24 @@ def test_raster_symbols_declared_and_exported():
     assert small >= 2 * 1000 * 48 and 3 * small < big <= 4 * small
 
 
+def test_workspace_bytes_region_by_region():
+    """psi_raster_workspace_bytes is the sum of its regions, each rounded up to 256 bytes: two piece slots per (view, triangle) of a 48-byte
+    record and a 4-byte tile box, three ints per (view, tile) (count, cursor, offset), a 64-bit bin base per view, and 4-byte bin entries
+    for every slot plus 64 per tile.  Zero for arguments the call refuses."""
+    from psi_release_amd import build, hip
+    build.build()
+    L = hip.lib()
+    r = lambda x: (x + 255) & ~255
+    for nf in (1, 7, 1000, 123457):
+        for n in (1, 3, 65535):
+            for W, H in ((64, 48), (70, 45), (1, 1), (17, 33), (4096, 4096)):
+                nt = -(-W // 16) * -(-H // 16)
+                want = r(96 * n * nf) + r(8 * n * nf) + 3 * r(4 * n * nt) + r(8 * n) + r(4 * n * (2 * nf + 64 * nt))
+                assert L.psi_raster_workspace_bytes(nf, n, W, H) == want, (nf, n, W, H)
+    for args in ((0, 1, 64, 48), (10, 0, 64, 48), (10, 1, 0, 48), (10, 1, 64, 0), (-1, 1, 64, 48)):
+        assert L.psi_raster_workspace_bytes(*args) == 0, args
+
+
 def test_render_refuses_cpu_tensors():
     import torch
     from psi_release_amd import hip, ops, rendering

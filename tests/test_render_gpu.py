@@ -140,11 +140,16 @@ def pixel_to_world(u, v, z, K):
     return np.stack([(u - K[0, 2]) * z / K[0, 0], (v - K[1, 2]) * z / K[1, 1], z], -1)
 
 
-def compare_small(verts, faces, labels, K, size, cam_ext=IDENT):
+def compare_small(verts, faces, labels, K, size, cam_ext=IDENT, max_excluded=1.0, renderer=None):
+    """``renderer``: a SnapshotRenderer of this very mesh (default: a new mesh and renderer)."""
     verts, faces = np.asarray(verts, np.float32), np.asarray(faces, np.int32)
     ref = R.render_views(verts, faces, labels, cam_ext, K, size)
-    depth, seg, tri, stats = render_np(verts, faces, labels, cam_ext, K, size)
-    excluded, derr, serr = check_against_reference(depth, seg, tri, ref, max_excluded=1.0)
+    if renderer is None:
+        depth, seg, tri, stats = render_np(verts, faces, labels, cam_ext, K, size)
+    else:
+        depth, seg, tri = (t.cpu().numpy() for t in renderer.render(cam_ext, K, size))
+        stats = renderer.last_stats
+    excluded, derr, serr = check_against_reference(depth, seg, tri, ref, max_excluded=max_excluded)
     assert derr <= 1e-5 and serr <= 1e-5 * 41
     assert np.array_equal(stats[:, 1], ref['dropped'])
     return depth, seg, tri, stats, ref
@@ -169,6 +174,34 @@ def test_one_triangle_over_the_whole_image():
     verts = pixel_to_world(np.array([-100.0, 300.0, -100.0]), np.array([-100.0, -100.0, 300.0]), np.array([2.0, 3.0, 4.0]), K)
     depth, seg, tri, stats, ref = compare_small(verts, [[0, 1, 2]], np.array([1.0, 20.0, 41.0], np.float32), K, size)
     assert (tri == 0).all() and stats[0, 0] == 12                                   # it sits in each of the 4 x 3 bins
+
+
+def test_bins_beyond_the_workspace():
+    """300 triangles that reach 60 pixels from centres all over a 48 x 64 image: about 1850 (tile, piece) pairs against the 2 * 300 +
+    64 * 12 = 1368 entries of the workspace's bins, so the call takes its bins from the buffer that the mesh handle grows.  Every pixel is
+    hit, by 43 different triangles; 0.065 % of the pixels have two nearest depths within 1e-4 (the cap is the 1 % of the room's images).
+    Then the same handle again (the grown buffer reused: equal bits) and, from 5 cm before the farthest vertex, the tip of one triangle
+    alone beyond z = near: a call that goes back to the workspace's bins."""
+    size, K = (48, 64), K_of((48, 64))
+    verts, faces, labels, estimate = R.triangle_soup(1, 300, 60.0, 1.0, 3.0, K, size)
+    pair_cap = 2 * 300 + 64 * 12
+    assert estimate == 1852 and estimate > pair_cap
+    r = rendering.SnapshotRenderer(rendering.SceneMesh(verts, faces, labels, device=DEV))
+    depth, seg, tri, stats, ref = compare_small(verts, faces, labels, K, size, max_excluded=0.01, renderer=r)
+    print('pairs %d, distinct winners %d' % (stats[0, 0], len(np.unique(tri))))
+    assert stats[0, 0] > pair_cap                                                   # what sends the call down the grow branch
+    assert ref['hit'].all() and len(np.unique(ref['tri'])) == 43
+    again = [t.cpu().numpy() for t in r.render(IDENT, K, size)]
+    assert np.array_equal(again[0], depth) and np.array_equal(again[1], seg) and np.array_equal(again[2], tri)
+    assert np.array_equal(r.last_stats, stats)
+    far = np.sort(verts[:, 2])[::-1]
+    v = int(np.argmax(verts[:, 2]))
+    ext = np.eye(4)
+    ext[:3, 3] = [verts[v, 0], verts[v, 1], float(far[0]) - 0.05 - 0.5 * float(far[0] - far[1])]
+    d1, s1, t1, st1, ref1 = compare_small(verts, faces, labels, K, size, ext[None], renderer=r)
+    assert 0 < st1[0, 0] <= 12 and 0 < (t1 >= 0).sum() < 20 and np.unique(t1[t1 >= 0]).tolist() == [v // 3]
+    back = [t.cpu().numpy() for t in r.render(IDENT, K, size)]                      # and the grown buffer is still good
+    assert np.array_equal(back[0], depth) and np.array_equal(back[1], seg) and np.array_equal(back[2], tri)
 
 
 def test_zero_area_and_behind_the_camera_draw_nothing():

@@ -55,6 +55,33 @@ def test_symbols_declared_exported_and_uncontracted():
     assert L.psi_raster_bodies_workspace_bytes(1 << 27, 8, 1, 64, 48) == 0              # draws_per_pass * F = 2^30
 
 
+def test_workspace_bytes_region_by_region():
+    """psi_raster_bodies_workspace_bytes is the sum of its regions, each rounded up to 256 bytes: the binning's regions as for the snapshots
+    (tests/test_render_cpu.py) with the piece slots of one pass of dpp = min(draws_per_pass, 65535) draws, and the call's own: the pass's
+    pair counts per view, the bad-draw word, the 64-bit key image.  ``pick_draws_per_pass`` is built on differences of these values.
+    Zero for arguments the call refuses."""
+    from psi_release_amd import build, hip
+    build.build()
+    L = hip.lib()
+    r = lambda x: (x + 255) & ~255
+    for F in (1, 300, 20908):
+        for draws in (1, 2, 24, 65535, 65536, 100000):
+            dpp = min(draws, 65535)
+            for n in (1, 4, 65535):
+                for W, H in ((64, 48), (70, 45), (1, 1), (17, 33)):
+                    nt = -(-W // 16) * -(-H // 16)
+                    want = (r(96 * dpp * F) + r(8 * dpp * F) + 3 * r(4 * n * nt) + 2 * r(8 * n) + r(4) + r(8 * n * W * H)
+                            + r(4 * (2 * dpp * F + 64 * n * nt)))
+                    if dpp * F >= 2 ** 30:
+                        want = 0
+                    assert L.psi_raster_bodies_workspace_bytes(F, draws, n, W, H) == want, (F, draws, n, W, H)
+    assert L.psi_raster_bodies_workspace_bytes(300, 2, 1, 4096, 4096) == (r(96 * 600) + r(8 * 600) + 3 * r(4 * 65536) + 2 * r(8) + r(4) + r(8 * 4096 * 4096)
+                                                                          + r(4 * (1200 + 64 * 65536)))
+    for args in ((0, 1, 1, 64, 48), (10, 0, 1, 64, 48), (10, 1, 0, 64, 48), (10, 1, 65536, 64, 48), (10, 1, 1, 0, 48), (10, 1, 1, 64, 0),
+                 (10, 1, 1, 4097, 48), (10, 1, 1, 64, 4097), (1 << 27, 8, 1, 64, 48)):
+        assert L.psi_raster_bodies_workspace_bytes(*args) == 0, args
+
+
 def test_result_renderer_refuses_cpu(tmp_path):
     import torch
     from psi_release_amd import hip, ops, rendering

@@ -1,6 +1,6 @@
 """Result images (csrc/raster_bodies.hip, rendering.ResultRenderer) on the GPU against the NumPy restatement of their contract
 (tests/compose_ref.py): owner, ids, depths, colours and counts; bit identity over reruns, passes, batching and draw order; a streamed
-bin; no scene; empty views; the normals; the refusals; the entry script."""
+bin; passes whose bins outgrow the workspace; no scene; empty views; the normals; the refusals; the entry script."""
 import functools
 import glob
 import json
@@ -134,6 +134,117 @@ def test_many_tiny_body_triangles_in_one_tile_cut_by_a_plane():
     print('covered %d visible %d' % (covered, visible))
     assert 0 < visible < covered
     assert len(np.unique(got['body_id'][got['body_id'] >= 0])) > 100
+
+
+# ---- bins beyond the workspace: a pass whose (tile, piece) pairs exceed 2 * dpp * F + 64 per tile takes its bins from the buffer that the
+# bodies handle grows.  One view (identity camera, 48 x 64: 12 tiles) and a topology of 300 loose triangles:
+#   LARGE  the soup of test_render_gpu.py's overflow test: about 1850 pairs, above the 2 * 300 + 768 = 1368 of a pass of one draw
+#   SMALL  triangles that reach 6 pixels, at depths 0.6 .. 0.9: about 530 pairs, in front of part of LARGE
+#   MOVED  LARGE translated
+LARGE, SMALL, MOVED = 0, 1, 2
+SOUP_SIZE, SOUP_F, SOUP_TILES = (48, 64), 300, 12
+OVERFLOW_CASES = {                               # draws_per_pass, the draws' bodies, with the plate
+    'second_pass_grows': (1, (SMALL, LARGE), False),
+    'first_pass_grows_second_returns': (1, (LARGE, SMALL), False),
+    'second_pass_reuses_the_grown_bins': (1, (LARGE, MOVED), True),
+    'one_pass_of_both': (2, (SMALL, LARGE), False),
+}
+
+
+@functools.lru_cache(None)
+def soups():
+    K = C.K_of(SOUP_SIZE)
+    large, faces, _, n_large = C.R.triangle_soup(1, SOUP_F, 60.0, 1.0, 3.0, K, SOUP_SIZE)
+    small, _, _, n_small = C.R.triangle_soup(2, SOUP_F, 6.0, 0.6, 0.9, K, SOUP_SIZE)
+    assert (n_large, n_small) == (1852, 528)
+    bverts = np.stack([large, small, large + np.array([0.05, -0.04, 0.1], np.float32)])
+    # the plate: two triangles across the whole view at depth 1.2, in front of a good third of what LARGE covers
+    plate = pixel_to_world(np.array([-10.0, 80.0, 80.0, -10.0]), np.array([-10.0, -10.0, 60.0, 60.0]), np.full(4, 1.2), K).astype(np.float32)
+    prgb = np.array([[0.9, 0.2, 0.1], [0.1, 0.8, 0.3], [0.2, 0.3, 0.9], [0.7, 0.7, 0.1]], np.float32)
+    colours = np.array([[0.3, 0.6, 0.9], [0.9, 0.5, 0.2], [0.4, 0.8, 0.3]], np.float32)          # of the bodies
+    return dict(K=K, bverts=bverts, bfaces=faces, plate=(plate, np.array([[0, 1, 2], [0, 2, 3]]), prgb), colours=colours)
+
+
+def render_soups(bodies, draws_per_pass, with_plate):
+    """The draws (body, view 0) of ``bodies`` through a new ResultRenderer (a new bodies handle: nothing grown yet); images and stats."""
+    fx = soups()
+    mesh = rendering.SceneMesh(fx['plate'][0], fx['plate'][1], device=DEV, vertex_rgb=fx['plate'][2]) if with_plate else None
+    r = rendering.ResultRenderer(mesh, fx['bfaces'], device=DEV)
+    res = r.render(torch.tensor(fx['bverts'], device=DEV), np.eye(4)[None], fx['K'], SOUP_SIZE, draw_body=list(bodies), draw_view=[0] * len(bodies),
+                   body_rgb=fx['colours'][list(bodies)], background=C.BACKGROUND, draws_per_pass=draws_per_pass)
+    return to_np(res), r.last_stats
+
+
+@functools.lru_cache(None)
+def soup_pairs():
+    """The (tile, piece) pairs of every body drawn alone."""
+    return [int(render_soups((b,), 1, False)[1][0, 0]) for b in (LARGE, SMALL, MOVED)]
+
+
+@functools.lru_cache(None)
+def overflow_rendered(case):
+    dpp, bodies, with_plate = OVERFLOW_CASES[case]
+    return render_soups(bodies, dpp, with_plate)
+
+
+@functools.lru_cache(None)
+def overflow_reference(bodies, with_plate):
+    fx = soups()
+    ref = C.compose_views(fx['plate'] if with_plate else None, fx['bverts'], fx['bfaces'], list(bodies), [0] * len(bodies), fx['colours'][list(bodies)],
+                          np.eye(4)[None], fx['K'], SOUP_SIZE, background=C.BACKGROUND)
+    for a in ref.values():
+        a.setflags(write=False)
+    return ref
+
+
+@pytest.mark.parametrize('case', list(OVERFLOW_CASES))
+def test_bins_beyond_the_workspace(case):
+    """Every case against the restatement with ``check_images``' own bounds and its 1 % cap (0.065 % .. 0.2 % of the pixels are excluded),
+    and the counts; from the returned stats, the passes that were meant to overflow did, and the others did not: a pass's pairs are those
+    of its draws alone, the call's pairs the passes' sums."""
+    dpp, bodies, with_plate = OVERFLOW_CASES[case]
+    got, stats = overflow_rendered(case)
+    ref = overflow_reference(bodies, with_plate)
+    C.check_images(got, ref, SOUP_F)
+    assert np.array_equal(got['counts'], ref['counts']) and (ref['counts'][:, 0] > 200).all()      # both draws are seen
+    alone = soup_pairs()
+    print('pairs of the bodies alone', alone, 'of the call', stats[0, 0])
+    cap = lambda draws: 2 * draws * SOUP_F + 64 * SOUP_TILES
+    assert alone[LARGE] > cap(1) and alone[MOVED] > cap(1) and alone[SMALL] <= cap(1)
+    assert stats[0, 0] == sum(alone[b] for b in bodies) and stats[0, 1] == 0
+    if dpp == 2:
+        assert stats[0, 0] > cap(2)                                                # the one pass of both draws overflows
+    if with_plate:
+        covered, visible = ref['counts'][0]
+        print('the plate hides %.3f of what the large body covers' % (1.0 - visible / covered))
+        assert 0.2 <= 1.0 - visible / covered <= 0.8
+
+
+def test_bins_beyond_the_workspace_bit_identity():
+    """The pairs of test_bit_identity_over_reruns_passes_batching_and_draw_order among the overflow cases: two passes against one, and the
+    draws in the other order; and a rerun with one renderer, whose second call finds the bins grown."""
+    two, _ = overflow_rendered('second_pass_grows')
+    one, _ = overflow_rendered('one_pass_of_both')
+    for k in FIELDS:
+        assert np.array_equal(two[k], one[k]), k
+    swapped, _ = overflow_rendered('first_pass_grows_second_returns')
+    keep = np.array([1, 0])                                                          # draw i of `swapped` is draw keep[i] of `two`
+    for k in ('depth', 'body_depth'):
+        assert np.array_equal(two[k], swapped[k]), k
+    assert np.array_equal(two['draw'], np.where(swapped['draw'] >= 0, keep[np.maximum(swapped['draw'], 0)], -1))
+    assert np.array_equal(two['counts'][keep], swapped['counts'])
+    sid = np.maximum(swapped['body_id'], 0)
+    ids = np.where(swapped['body_id'] >= 0, keep[sid // SOUP_F] * SOUP_F + sid % SOUP_F, -1)
+    differ = ids != two['body_id']
+    assert differ.mean() <= 0.001                                                   # exact depth ties go to the lower index of each order
+    assert np.array_equal(two['rgb'][~differ], swapped['rgb'][~differ])
+    fx = soups()
+    r = rendering.ResultRenderer(None, fx['bfaces'], device=DEV)
+    args = (torch.tensor(fx['bverts'], device=DEV), np.eye(4)[None], fx['K'], SOUP_SIZE)
+    kw = dict(draw_body=[SMALL, LARGE], draw_view=[0, 0], body_rgb=fx['colours'][[SMALL, LARGE]], background=C.BACKGROUND, draws_per_pass=1)
+    first, again = to_np(r.render(*args, **kw)), to_np(r.render(*args, **kw))
+    for k in FIELDS:
+        assert np.array_equal(first[k], two[k]) and np.array_equal(again[k], two[k]), k
 
 
 def test_no_scene():
